@@ -14,11 +14,15 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the reference's mul
 (strong scaling: `value`), one fp32 gradient sum per step (peer windows over xGMI, or RCCL); the same
 steps with batch 256 and 1M transitions PER replica follow as `weak_scaling_row` (outside `value`).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the library's
-stream (hl_kernel_profile: graph-replayed launches of each kernel of the step; these passes run AFTER the timed region);
-`cpu_baseline` times the
-compiled reference (oracle/_ref, kind "reference") -- or the single-threaded CPU oracle
-(kind "port") when the reference binary is absent -- on a bounded sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the outputs of the
+timed path (--dump-outputs DIR) and prints that line; `ms_per_step` is one timed step in milliseconds.
+
+--full adds what is measured besides the headline figure, all of it after the timed region: `diagnostics` (the same call
+again, a 2000-step sustained rate), `roofline` (measured live with HIP events on the library's stream: hl_kernel_profile,
+graph-replayed launches of each kernel of the step), `other_configs` (us per step of the other BASELINE configurations),
+`cpu_baseline` (the compiled reference, oracle/_ref, kind "reference" -- or the single-threaded CPU oracle, kind "port",
+when the reference binary is absent -- on a bounded sample of the same workload) and, for N > 1, the single-replica
+value and `weak_scaling_row`.  The --no-* options switch single parts of --full off.
 """
 import argparse
 import json
@@ -200,14 +204,27 @@ def other_configs(api, steps=1000, only=None):
     return res
 
 
+def usable_cpus():
+    """CPUs this process may run threads on: its affinity mask, capped by OMP_NUM_THREADS where that is set (os.cpu_count() counts
+    the whole host, and threads beyond the CPUs granted only slow the probes down)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def cpu_baseline(steps_budget_s=20.0):
     ref = os.path.join(ROOT, "oracle", "_ref", "ref_driver_fast")
-    ncpu = os.cpu_count() or 1
+    ncpu = usable_cpus()
     if os.path.exists(ref):
         best = None
         tried = []
         with tempfile.TemporaryDirectory() as td:
-            # (probes up to the box's CPU count -- VERDICT r05: they stopped at 64 of 256; a probe is 400 steps, a few seconds each)
+            # (probes up to the CPUs this process may use -- VERDICT r05: they stopped at 64 of 256; a probe is 400 steps, a few seconds each)
             probes = [t for t in (8, 16, 32, 64, 128, 256) if t <= ncpu] or [ncpu]
             if ncpu > probes[-1] and ncpu <= 512:
                 probes.append(ncpu)
@@ -242,7 +259,7 @@ def cpu_baseline(steps_budget_s=20.0):
                                                  "prototype header would be a stand-in for a file the image lacks -- DESIGN.md section 5)",
                     "march": "x86-64-v3", "flags": "-O3 -ffast-math -fopenmp -DSINGLE_PREC",
                     "sample": "compiled reference (oracle/_ref, -O3 -ffast-math, OpenMP) on a 1M-transition synthetic replay of "
-                              "the same shape and distributions: 400-step probes at threads=%s on %d host CPUs, then %s at the best count"
+                              "the same shape and distributions: 400-step probes at threads=%s on %d usable host CPUs, then %s at the best count"
                               % ([t for t, _ in tried], ncpu, "6000 gradient steps after 100 warm-up" if long_run else "(long run failed) the probe"),
                     "tried": tried}
     # fallback: single-threaded CPU oracle (port)
@@ -261,15 +278,65 @@ def cpu_baseline(steps_budget_s=20.0):
             "sample": "CPU oracle (oracle/port, single thread), same 1M-transition replay, %d steps" % n}
 
 
+DUMP_EPISODES = 64                    # replay fields of this many episodes (a fixed, seeded sample of the 5000) are written
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_arrays(out_dir, arrays):
+    """arrays {name: ndarray} -> out_dir/<name>.npy, float32 kept, every other dtype as float64 (exact for the integers here)."""
+    import numpy as np
+    conv = {k: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("outputs of %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(conv)
+
+
+def step_outputs(L):
+    """What a caller of the timed path receives after its last step: the parameters and Adam moments, the last minibatch's
+    per-sample quantities and summed weight gradient (the library's taps), the replay's per-step fields that the step updates
+    (for a fixed sample of episodes), the learner's scalars and replay statistics."""
+    import numpy as np
+    from smarties_amd import capi
+    w, m1, m2 = L.get_params()
+    out = {"weights": w, "adam_first_moment": m1, "adam_second_moment": m2,
+           "last_step_weight_gradient": L.readback(capi.TAP_GRADSUM),
+           "last_step_sample_index": L.readback(capi.TAP_FLAT),
+           "last_step_outputs": L.readback(capi.TAP_OUTPUT),
+           "last_step_output_gradients": L.readback(capi.TAP_OUTGRAD),
+           "last_step_importance_weights": L.readback(capi.TAP_RHO),
+           "last_step_kl_divergence": L.readback(capi.TAP_DKL),
+           "last_step_delta_q": L.readback(capi.TAP_DELTAQ),
+           "last_step_far_policy": L.readback(capi.TAP_FAR)}
+    n_eps = L.counts()[1]
+    pos = np.sort(np.random.default_rng(2024).choice(n_eps, size=min(DUMP_EPISODES, n_eps), replace=False))
+    fields = {"returns": capi.EP_RETURN, "values": capi.EP_VALUE, "advantages": capi.EP_ADVANTAGE,
+              "importance_weights": capi.EP_IMPW, "kl_divergence": capi.EP_DKL, "delta_q": capi.EP_DELTAQ}
+    for name, f in fields.items():
+        out["replay_" + name] = np.concatenate([L.episode_field(int(p), f) for p in pos])
+    out["replay_sample_episodes"] = pos
+    sc, st = L.scalars(), L.stats()
+    out["scalars"] = np.array([getattr(sc, k) for k, _ in capi.HlScalars._fields_], np.float64)
+    out["replay_stats"] = np.array([getattr(st, k) for k, _ in capi.HlStats._fields_], np.float64)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--warmup", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the us/step of the other BASELINE configurations")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel HIP-event passes (counter-collection runs, which stall under their graph replays)")
-    ap.add_argument("--no-diagnostics", action="store_true", help="skip the repeated call and the 2000-step sustained rate after the timed region (counter-collection runs)")
+    ap.add_argument("--full", action="store_true", help="also the diagnostics, roofline, other configurations and CPU baseline (N > 1: the "
+                    "single-replica value and the weak-scaling row); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed (parameters, the last "
+                    "step's taps, a fixed sample of the replay's fields) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the us/step of the other BASELINE configurations")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the per-kernel HIP-event passes (counter-collection runs, which stall under their graph replays)")
+    ap.add_argument("--no-diagnostics", action="store_true", help="(--full) skip the repeated call and the 2000-step sustained rate after the timed region (counter-collection runs)")
     args = ap.parse_args()
     # the ONE JSON line goes to the real stdout; everything else this process or its libraries print there (RCCL's version banner when
     # a communicator comes up, gloo's connection notes) is sent to stderr
@@ -307,8 +374,10 @@ def main():
                 rank, PROBE_SECONDS), file=sys.stderr, flush=True)
             env = dict(os.environ, SMARTIES_BENCH_EXCHANGE="host", SMARTIES_BENCH_REEXEC="1")
             env.pop("TORCHELASTIC_USE_AGENT_STORE", None)     # (else every rank of the second life is a store client)
-            os.dup2(real_out_fd, 1)      # (the second life prints its line where this one would have)
-            os.execve(sys.executable, [sys.executable] + sys.argv, env)
+            # the second life is a fresh child process (this one has the device open and is not replaced); it prints its line
+            # where this one would have, and its exit status becomes this process's
+            r = subprocess.run([sys.executable] + sys.argv, env=env, stdout=real_out_fd)
+            os._exit(r.returncode if r.returncode >= 0 else 128 - r.returncode)     # (killed by signal s: 128 + s, as a shell reports it)
 
         dog = threading.Timer(PROBE_SECONDS, start_over)
         dog.daemon = True
@@ -417,7 +486,7 @@ def main():
     # N > 1: the single-replica value of THIS box first (rank 0 alone, the N = 1 workload, the same K steps after W warm-up steps), so
     # that the weak-scaling row can state its efficiency against N x that value in the same run; the other ranks wait at the barrier
     single_ref = None
-    if n_ranks > 1 and os.environ.get("SMARTIES_BENCH_SINGLE_REF", "1") != "0":
+    if n_ranks > 1 and args.full and os.environ.get("SMARTIES_BENCH_SINGLE_REF", "1") != "0":
         if rank == 0:
             try:
                 L1 = capi.Learner(api, capi.make_config(device_id=local_rank % ndev, **CFG))
@@ -438,6 +507,8 @@ def main():
 
     L, t_fill, transport = build(CFG, N_EPISODES)
     host_exchange, host_group = state["host_exchange"], state["host_group"]
+    if args.dump_outputs:
+        L.set_tap(True)      # (the C-ABI's order for reading the last step's taps; the HIP library records them always: a no-op there)
     if n_ranks > 1 and host_exchange:
         from smarties_amd import dist_host
 
@@ -552,15 +623,19 @@ def main():
         except Exception as e:  # noqa: BLE001
             transports = transports + ["(gather failed: %s)" % e]
 
-    # diagnostics, after the timed region and outside `value`: the same call once more (what a first call pays on top: page walks,
-    # first launch of the call's graph, clocks) and the sustained rate over 2000 steps
+    # what the timed path computed in its last step, before anything else runs on this learner
+    if args.dump_outputs and rank == 0:
+        write_arrays(args.dump_outputs, step_outputs(L))
+
+    # diagnostics (--full), after the timed region and outside `value`: the same call once more (what a first call pays on top: page
+    # walks, first launch of the call's graph, clocks) and the sustained rate over 2000 steps
     diag = {}
-    if n_ranks == 1 and not args.no_diagnostics:
+    if args.full and n_ranks == 1 and not args.no_diagnostics:
         t1 = time.perf_counter(); run(args.steps); barrier(); diag["same_call_again_ms_per_step"] = (time.perf_counter() - t1) / args.steps * 1e3
         run(400); barrier()
         t1 = time.perf_counter(); run(2000); barrier(); diag["sustained_ms_per_step_2000_steps"] = (time.perf_counter() - t1) / 2000 * 1e3
 
-    if rank == 0 and roof is None and not args.no_roofline:
+    if args.full and rank == 0 and roof is None and not args.no_roofline:
         roof = roofline(L)
 
     out = None
@@ -582,12 +657,12 @@ def main():
             "fill_seconds": t_fill,
             "diagnostics": diag,
         }
-        if not args.no_other_configs and n_ranks == 1:
+        if args.full and not args.no_other_configs and n_ranks == 1:
             try:
                 out["other_configs"] = other_configs(api, steps=1000)
             except Exception as e:  # noqa: BLE001
                 out["other_configs"] = {"error": str(e)}
-        if not args.no_cpu_baseline and n_ranks == 1:
+        if args.full and not args.no_cpu_baseline and n_ranks == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # noqa: BLE001
@@ -596,7 +671,7 @@ def main():
     # N > 1: the same steps with batch 256 and a 1M-transition replay PER REPLICA (weak scaling: what a replica of BASELINE config 3
     # sees -- the global batch grows with the replicas, Settings/HyperParameters.cpp:186-197 splits it back to 256 each), next to
     # the strong-scaling value.  Outside `value`; measured last, under a watchdog that prints the line without it.
-    if n_ranks > 1 and os.environ.get("SMARTIES_BENCH_WEAK", "1") != "0":
+    if n_ranks > 1 and args.full and os.environ.get("SMARTIES_BENCH_WEAK", "1") != "0":
         import threading
 
         def bail():

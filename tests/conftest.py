@@ -2,8 +2,10 @@ import os
 import sys
 
 # several replicas of ONE process that wait for each other inside kernels (test_one_kernel_exchange_among_several_replicas) need a
-# hardware queue each: HIP maps streams onto 4 by default, a fifth stream shares one -- and a waiting kernel then blocks its peer
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# hardware queue each: HIP maps streams onto 4 by default, a fifth stream shares one -- and a waiting kernel then blocks its peer.
+# An environment that already asks for fewer (4, HIP's own default, is often exported) is raised too, not only an unset one.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 # a peer that never shows up: the exchange kernel gives up after this long (the library's own default is one minute)
 os.environ.setdefault("SMARTIES_HIP_XCHG_TIMEOUT_MS", "30000")
 

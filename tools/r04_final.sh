@@ -4,6 +4,6 @@
 cd /root/repo; export PYTHONPATH=.
 O=gpurun_out/r04c; mkdir -p $O
 tools/run_gpu.sh r04c 4000 6 > $O/run_gpu.txt 2>&1; tail -25 $O/run_gpu.txt
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_driver_protocol.json 2>/dev/null; tail -c 400 $O/bench_driver_protocol.json; echo
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_driver_protocol.json 2>/dev/null; tail -c 400 $O/bench_driver_protocol.json; echo
 tools/atari_profile.sh r04c > $O/atari_profile.txt 2>&1; tail -3 $O/atari_profile.txt
 timeout 300 python tools/per_time.py > $O/per_time.txt 2>&1; grep "ms per step" $O/per_time.txt

@@ -4,7 +4,7 @@
 cd /root/repo; export PYTHONPATH=.
 O=gpurun_out/r05f; mkdir -p $O
 tools/run_gpu.sh r05f 4000 6 > $O/run_gpu.txt 2>&1; tail -30 $O/run_gpu.txt
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_driver_protocol.json 2>/dev/null; tail -c 300 $O/bench_driver_protocol.json; echo
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_driver_protocol.json 2>/dev/null; tail -c 300 $O/bench_driver_protocol.json; echo
 bash tools/big_profile.sh 2048 4096 16384 2>&1 | grep -v "simple_timer\|ingest\|rocclr\|moments\|episode_sweep" > $O/big_profile.txt; cat $O/big_profile.txt
 for B in 2048 16384; do cp $(ls gpurun_out/big$B/*/*kernel_stats.csv | head -1) $O/big${B}_kernel_stats.csv; done
 for k in lstm mgu; do for n in 128 256; do

@@ -4,9 +4,9 @@
 cd /root/repo; export PYTHONPATH=.
 O=gpurun_out/r06f; mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py > $O/bench_default.log 2>&1; grep "^{" $O/bench_default.log > $O/bench.json; tail -c 400 $O/bench.json; echo
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_driver_protocol.json 2>/dev/null; tail -c 300 $O/bench_driver_protocol.json; echo
-(cd /tmp && export TMPDIR=/tmp && timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/kt -o r -- python /root/repo/bench.py --steps 4000 --warmup 200 --no-cpu-baseline --no-other-configs --no-diagnostics > /root/repo/$O/bench_rocprof.log 2>&1)
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1; grep "^{" $O/bench_default.log > $O/bench.json; tail -c 400 $O/bench.json; echo
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_driver_protocol.json 2>/dev/null; tail -c 300 $O/bench_driver_protocol.json; echo
+R=$PWD; (cd /tmp && export TMPDIR=/tmp && timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/kt" -o r -- python "$R/bench.py" --full --steps 4000 --warmup 200 --no-cpu-baseline --no-other-configs --no-diagnostics > "$R/$O/bench_rocprof.log" 2>&1)
 grep "^{" $O/bench_rocprof.log > $O/bench_under_rocprof.json; cp $(ls $O/kt/*kernel_stats.csv $O/kt/*/*kernel_stats.csv 2>/dev/null | head -1) $O/kernel_stats.csv; rm -rf $O/kt
 head -8 $O/kernel_stats.csv | cut -c1-160
 timeout 500 bash tools/pmc3.sh 2>&1 | tail -6; cp gpurun_out/pmc3/summary.json $O/pmc.json
