@@ -162,6 +162,14 @@ class RACER_HIP : public Learner
     c.outWeightsPrefac = S.outWeightsPrefac; c.randSeed = D.randSeed;                                       // HyperParameters.cpp:186-197
     c.n_ranks = (int32_t) learn_size; c.rank = (int32_t) learn_rank; c.device_id = -1;                       // rank % device count
     c.ref_threads = (int32_t) D.nThreads;
+    // which sums the replicas' counter / moment reductions deliver (smarties_hip.h: HL_RDX_*): this step's (default) or, with
+    // SMARTIES_HIP_REDUCTION_TIMING=one_behind, the previous step's -- DelayedReductor's other outcome (Utils/DelayedReductor.cpp:34-60).
+    // Peer-window exchange only: with SMARTIES_HIP_RCCL set hl_comm_init refuses it.
+    { const char* t = getenv("SMARTIES_HIP_REDUCTION_TIMING");
+      const std::string timing = t ? t : "current";
+      if (timing == "one_behind") c.reduction_timing = HL_RDX_ONE_BEHIND;
+      else if (timing == "current") c.reduction_timing = HL_RDX_CURRENT;
+      else die("SMARTIES_HIP_REDUCTION_TIMING: current or one_behind"); }
     const int rc = hl_create(&c, &H);
     if (rc) { const std::string msg = H ? hl_last_error(H) : hl_status_string(rc); if (H) hl_destroy(H); H = nullptr; die(msg.c_str()); }
     ck(hl_init_weights(H));

@@ -184,7 +184,26 @@ typedef struct hl_config {
   int32_t encoder_rnn;               /* 1: the encoder layers are plain recurrent layers ("RNN", Builder.cpp:76-81) whatever nn_type says -- what a
                                           partially observable MDP gets for them when nnType is left non-recurrent (Approximator.cpp:264-270),
                                           under the MGU layers of :221-223.  Only with nn_type == HL_NN_MGU. */
+  int32_t reduction_timing;          /* HL_RDX_*: which sums the replicas' counter / moment reductions deliver (below) */
 } hl_config;
+
+/* Timing of the replicas' counter and moment reductions (hl_config::reduction_timing).  The reference reads them through
+ * DelayedReductor (Utils/DelayedReductor.cpp:34-60): update() waits for the previous MPI_Iallreduce and starts the next one, get(false)
+ * polls the new one once -- complete: this step's sums, else the previous step's, which is the intended design ("use result from prev
+ * AllReduce ... we skip an mpi implicit barrier point", ReplayMemory/MemoryProcessing.cpp:46-58; the 1000th step's moments the same
+ * way, :139-150).
+ *   HL_RDX_CURRENT     every step uses its own sums (every poll complete).  The default.
+ *   HL_RDX_ONE_BEHIND  step k's beta, alpha and seen counters come from the counters summed at step k - 1 (step 1: the start-up sums);
+ *                      a 1000th step's reward / state scaling from the last COMPLETED moments sum (at step 1000 the start-up one; its
+ *                      own sum is kept for step 2000).  hl_initialize's start-up reductions stay accurate (Learner.cpp:58-59).
+ * Applies to the peer-window exchange (hl_xchg_connect).  No effect with n_ranks == 1 (DelayedReductor::update returns the current
+ * values when mpisize <= 1) nor in host-exchange mode, where the embedding decides which sums it stores (smarties_amd/dist_host.py).
+ * hl_comm_init (RCCL) refuses HL_RDX_ONE_BEHIND with HL_ERR_UNSUPPORTED.  After hl_restart_memory the first step carries the counters
+ * as restored and the first 1000th step applies its own moments sum (no completed sum is held: the reference seeds its reductions
+ * from the restored buffer, MemoryBuffer.cpp:39-41).
+ * hl_create also takes the layout without this field (struct_size 704): it then reads as HL_RDX_CURRENT. */
+enum { HL_RDX_CURRENT = 0, HL_RDX_ONE_BEHIND = 1 };
+#define HL_CONFIG_SIZE_V1 704   /* sizeof(hl_config) before reduction_timing */
 
 typedef struct hl_learner hl_learner;  /* opaque */
 

@@ -24,6 +24,8 @@ ADV_ZERO, ADV_GAUSSIAN, ADV_DISCRETE = 0, 1, 2
 NN_FFNN, NN_LSTM, NN_MGU, NN_RNN = 0, 1, 2, 3
 RET = {"retrace": 0, "default": 0, "retraceExplore": 1, "GAE": 2, "none": 3}
 ORDER_STABLE, ORDER_REFERENCE = 0, 1
+RDX_CURRENT, RDX_ONE_BEHIND = 0, 1      # hl_config::reduction_timing (include/smarties_hip.h)
+RDX = {"current": RDX_CURRENT, "one_behind": RDX_ONE_BEHIND}
 
 (TAP_FLAT, TAP_EPISODE, TAP_TSTEP, TAP_TAG, TAP_STATE, TAP_OUTPUT, TAP_OUTGRAD, TAP_RHO, TAP_DKL,
  TAP_DELTAQ, TAP_FAR, TAP_GRADSUM) = range(12)
@@ -56,6 +58,7 @@ class HlConfig(C.Structure):
         ("n_options", C.c_int32), ("nn_type", C.c_int32), ("nnBPTTseq", C.c_int32),
         ("nAppendedObs", C.c_int32), ("n_conv", C.c_int32), ("conv", HlConv2d * HL_MAX_CONV), ("ERoldSeqFilter", C.c_int32), ("dataSamplingAlgo", C.c_int32),
         ("returnsEstimator", C.c_int32), ("nnOutputFunc", C.c_int32), ("n_encoder", C.c_int32), ("encoder", C.c_int32 * HL_MAX_HIDDEN), ("encoder_rnn", C.c_int32),
+        ("reduction_timing", C.c_int32),
     ]
 
 
@@ -81,7 +84,7 @@ def make_config(dimS=17, dimA=6, bounded=None, hidden=(256, 256), nnFunc="SoftSi
                 outWeightsPrefac=0.1, randSeed=42, n_ranks=1, rank=0, device_id=-1,
                 episode_order=ORDER_STABLE, ref_threads=1, adv_kind=ADV_ZERO, n_options=0, nn_type=0, nnBPTTseq=0,
                 nAppendedObs=0, conv=(), ERoldSeqFilter="oldest", dataSamplingAlgo="uniform",
-                returnsEstimator="retrace", nnOutputFunc="Linear", encoder=(), encoder_rnn=0):
+                returnsEstimator="retrace", nnOutputFunc="Linear", encoder=(), encoder_rnn=0, reduction_timing="current"):
     """Defaults = the north-star synthetic of BASELINE.md (cfg-NS)."""
     c = HlConfig()
     c.struct_size = C.sizeof(HlConfig)
@@ -104,6 +107,7 @@ def make_config(dimS=17, dimA=6, bounded=None, hidden=(256, 256), nnFunc="SoftSi
     c.nnOutputFunc = FUNC[nnOutputFunc] if isinstance(nnOutputFunc, str) else int(nnOutputFunc)
     c.n_encoder = len(encoder)
     c.encoder_rnn = int(encoder_rnn)
+    c.reduction_timing = RDX[reduction_timing] if isinstance(reduction_timing, str) else int(reduction_timing)
     for i, hsz in enumerate(encoder):
         c.encoder[i] = int(hsz)
     c.nAppendedObs, c.n_conv = nAppendedObs, len(conv)

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
     if (threadIdx.x >= 256) return;            // the tail code is written for 256 threads
     // the sampler runs in block 0; with PH_PUBLISH its gather is spread over blocks 1..7
     if (blockIdx.x == 0) { if (extra.role == 1) { samplePhases(extra.samp, extra.phases, smem); FEND(22); } }      // (the bookkeeping never rides here: its register needs exceed this kernel's 128)
-    else if (blockIdx.x == 1 && a.deferBeta) { farBetaPhase(extra.post, smem); if (threadIdx.x == 0) a.sc->dbgT[23] = wall_clock64(); }      // what the bookkeeping of the step before left over
+    else if (blockIdx.x == 1 && (a.deferBeta || extra.post.mode == POST_ENCODE)) { farBetaPhase(extra.post, smem); if (threadIdx.x == 0) a.sc->dbgT[23] = wall_clock64(); }      // what the bookkeeping of the step before left over
     else if (extra.role == 1 && (extra.phases & PH_PUBLISH)) gatherHelper(extra.samp, blockIdx.x - 1, 7, smem);
     return;
   }

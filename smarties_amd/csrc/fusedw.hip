@@ -83,7 +83,7 @@ __global__ __launch_bounds__(FW_NT, 2) void fused_wide_kernel(FusedArgs a, HeadA
   if (blockIdx.x < 8) {      // riders, as in fused.hip: 8 of them keep blockIdx % 8 == XCD for the panels
     if (threadIdx.x >= 256) return;
     if (blockIdx.x == 0) { if (extra.role == 1) samplePhases(extra.samp, extra.phases, smem); }
-    else if (blockIdx.x == 1 && a.deferBeta) farBetaPhase(extra.post, smem);
+    else if (blockIdx.x == 1 && (a.deferBeta || extra.post.mode == POST_ENCODE)) farBetaPhase(extra.post, smem);      // (POST_ENCODE: one-behind replicas, the heads do not wait)
     return;
   }
   constexpr int NT = FW_NT, NW = NT / 64, HT = H / 16, H4 = H / 4;

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void step_chain_kernel(const GemmProblem* __re
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS0 > HEAD_LDS ? LDS0 : HEAD_LDS];
   if (blockIdx.x < 8) {
     if (blockIdx.x == 0 && extra.role) runExtra(extra, smem);
-    else if (blockIdx.x == 1 && ha.deferBeta) farBetaPhase(extra.post, smem);      // (the count and beta the bookkeeping of the step before left over)
+    else if (blockIdx.x == 1 && (ha.deferBeta || extra.post.mode == POST_ENCODE)) farBetaPhase(extra.post, smem);      // (the count and beta the bookkeeping of the step before left over)
     return;
   }
   const int bid = blockIdx.x - 8, xcd = bid & 7, gi = bid >> 3;

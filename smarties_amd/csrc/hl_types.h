@@ -50,6 +50,8 @@ struct DevScalars {
   unsigned notifySeq;             // exact-size graphs replayed so far (their last node stores it into pinned host memory: hl_sync)
   long long dbgT[32];             // development: wall_clock64() stamps of the tail phases
   long long dbgStep[128];         // development (-DHL_STEP_STAMPS): entry stamps of the two step kernels, by step number mod 64
+  long long cntPrev[4];           // HL_RDX_ONE_BEHIND replicas: this replica's {seenEps, seenSteps, nFar, nStored} as they stood at the end of
+                                  // the last step (after hl_initialize_begin: the start-up ones) -- what the NEXT step's message carries
 };
 
 // ---------------------------------------------------------------------------

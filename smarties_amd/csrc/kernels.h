@@ -183,10 +183,14 @@ struct PostArgs {
   int aggChunk;                      // large batches: 1 = the episode records of 256 samples per workgroup, nothing else; 2 = done by the launch in front (tail_dev.h: postPart)
   float* cntMsg;                     // != nullptr: the four replica counters travel inside the gradient message (16 floats, four
                                      // 16-bit chunks each: exact in fp32 for up to 256 replicas) instead of a collective of their own
+  int behind;                        // 1: HL_RDX_ONE_BEHIND replicas -- the message carries DevScalars::cntPrev (the counters of the step
+                                     // before), POST_BETA stores this step's local counters there
 };
 enum { POST_AGG = 1, POST_BETA = 2, POST_INIT = 4, POST_ENCODE = 8 /* write the counters message only */,
        POST_DEFER = 16 /* with POST_AGG | POST_BETA: leave the far-policy count and the beta / alpha update that hangs off it to
-                          farBetaPhase -- a rider of the NEXT step's fused kernel, whose heads wait for it (tail_dev.h) */ };
+                          farBetaPhase -- a rider of the NEXT step's fused kernel, whose heads wait for it (tail_dev.h) */,
+       POST_KEEPMSG = 32 /* with POST_AGG (one-behind replicas): the counters message of this step was written by the rider of its first
+                            launch (farBetaPhase with POST_ENCODE): leave it */ };
 
 struct AdamArgs {
   const DevScalars* sc; float* W; float* M1; float* M2; const float* G; long long n;

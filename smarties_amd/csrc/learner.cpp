@@ -52,8 +52,18 @@ const char* hl_status_string(int s) {
 }
 const char* hl_last_error(const hl_learner* h) { return h ? h->err.c_str() : "null handle"; }
 
-int hl_create(const hl_config* cfg, hl_learner** out) {
-  if (!cfg || !out || cfg->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
+int hl_create(const hl_config* cfgIn, hl_learner** out) {
+  if (!cfgIn || !out) return HL_ERR_BAD_ARG;
+  // the previous layout (no reduction_timing): copied into a zeroed struct, the missing field reads as HL_RDX_CURRENT
+  hl_config cfgV1;
+  if (cfgIn->struct_size == HL_CONFIG_SIZE_V1) {
+    static_assert(HL_CONFIG_SIZE_V1 <= sizeof(hl_config), "the previous layout is a prefix of this one");
+    std::memset(&cfgV1, 0, sizeof(cfgV1)); std::memcpy(&cfgV1, cfgIn, HL_CONFIG_SIZE_V1); cfgV1.struct_size = sizeof(hl_config);
+    cfgIn = &cfgV1;
+  }
+  const hl_config* cfg = cfgIn;
+  if (cfg->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
+  if (cfg->reduction_timing != HL_RDX_CURRENT && cfg->reduction_timing != HL_RDX_ONE_BEHIND) return HL_ERR_BAD_ARG;
   if (cfg->dimS <= 0 || cfg->dimA <= 0 || cfg->dimA > HL_MAX_DIMA || cfg->n_hidden < 1 ||
       cfg->n_hidden > HL_MAX_HIDDEN || cfg->batchSize <= 0 || cfg->n_ranks < 1) return HL_ERR_BAD_ARG;
   if (cfg->n_ranks > 256) return HL_ERR_UNSUPPORTED;   // the replica counters travel as 16-bit chunks in fp32 (tail_dev.h: encodeCounters)
@@ -352,7 +362,7 @@ int hl_create(const hl_config* cfg, hl_learner** out) {
     HIPCK(devAlloc(&bt.aggIn, (size_t)B * AGG_N));
   }
   HIPCK(devAlloc(&h->dFlatGiven, B));
-  HIPCK(devAlloc(&h->dMoments, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dStatsOut, 16)); HIPCK(devAlloc(&h->dStatsIns, 16));
+  HIPCK(devAlloc(&h->dMoments, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dMomentsPrev, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dStatsOut, 16)); HIPCK(devAlloc(&h->dStatsIns, 16));
   HIPCK(devAlloc(&h->rp.stMean, h->dS)); HIPCK(devAlloc(&h->rp.stScale, h->dS)); HIPCK(devAlloc(&h->rp.stStd, h->dS));
   HIPCK(devAlloc(&h->rp.farStart, 4 * 256));
   {   // ring slack: an eighth of the budget plus room for the episodes in flight (bounded in bytes for image-sized states)
@@ -397,7 +407,7 @@ int hl_destroy(hl_learner* h) {
   if (h->xchg.win) { windowPoolPut(h->dev, h->xchg.winBytes, h->xchg.win); h->xchg.win = nullptr; }      // (never back to the allocator: windowPoolGet)
   for (void* q : {(void*)h->xchg.dPeers, (void*)h->xchg.ctl}) if (q) hipFree(q);
   void* ptrs[] = {h->splitPart, h->widePart, h->wideCtr, h->W, h->M1, h->M2, h->G, h->sc, h->dOut, h->dProbs, h->dFlatGiven, h->dEidList,
-    h->dRedMax, h->dRedErr, h->dMomPartial, h->dMoments, h->dStatsOut, h->dStatsIns,
+    h->dRedMax, h->dRedErr, h->dMomPartial, h->dMoments, h->dMomentsPrev, h->dStatsOut, h->dStatsIns,
     h->rp.S, h->rp.A, h->rp.MU, h->rp.R, h->rp.V, h->rp.ADV, h->rp.RET, h->rp.DQ, h->rp.IMPW, h->rp.DKL,
     h->rp.epOff, h->rp.epN, h->rp.epTerm, h->rp.epAgg, h->rp.posEid, h->rp.posPrefix, h->rp.stMean, h->rp.stScale,
     h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->dActS, h->dActO};
@@ -686,6 +696,8 @@ int hl_get_episode_field(hl_learner* h, int64_t pos, int32_t field, float* dst, 
 static int initializeBegin(hl_learner* h) {
   if (h->order.empty()) return fail(h, HL_ERR_TOO_FEW_DATA, "empty replay");
   int rc = flushPending(h); if (rc) return rc;
+  // (one-behind replicas: the local start-up counters are what the first step's message carries -- they make up the start-up sums)
+  HIPCK(hipMemcpyAsync(h->sc->cntPrev, h->sc->cnt, sizeof(h->sc->cnt), hipMemcpyDeviceToDevice, h->stream));
   rc = launchMoments(h); if (rc) return rc;                          // updateRewardsStats(bInit): the local sums
   h->momentsPending = true; h->initPending = true;
   return HL_OK;
@@ -694,6 +706,9 @@ static int initializeEnd(hl_learner* h) {
   if (!h->initPending) return fail(h, HL_ERR_STATE, "hl_initialize_end without hl_initialize_begin");
   int rc = launchPost(h, 0, POST_INIT, h->stream); if (rc) return rc;     // updateCounters(bInit)
   rc = launchMomentsApply(h, true, 1); if (rc) return rc;
+  // (one-behind replicas: the start-up sum is the last completed one until the 1000th step's completes)
+  HIPCK(hipMemcpyAsync(h->dMomentsPrev, h->dMoments, (size_t)(2 * h->dS + 3) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  h->momPrevValid = true;
   h->momentsPending = false; h->initPending = false;
   h->nGatheredB4Startup = h->minObsLocal;
   rc = runSweep(h, nullptr, (int)h->order.size(), 0); if (rc) return rc;   // rescaleAllReturnEstimator

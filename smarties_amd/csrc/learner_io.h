@@ -301,6 +301,9 @@ int hl_restart_memory(hl_learner* h, const char* base, int32_t rank) {
   sc.Cmax = Cmax; sc.Cinv = 1 / Cmax; sc.beta = beta; sc.nGradSteps = doneGrad;
   HIPCK(hipMemcpy(h->sc, &sc, sizeof(DevScalars), hipMemcpyHostToDevice));
   rc = runSweep(h, nullptr, (int)h->order.size(), 1, /*skipRetrace*/1); if (rc) return rc;
+  // (one-behind replicas: the first step's message carries the counters as restored; no completed moments sum is held)
+  HIPCK(hipMemcpyAsync(h->sc->cntPrev, h->sc->cnt, sizeof(h->sc->cnt), hipMemcpyDeviceToDevice, h->stream));
+  h->momPrevValid = false;
   HIPCK(hipStreamSynchronize(h->stream));
   if ((unsigned long)h->nTransitions != nObs) return fail(h, HL_ERR_IO, "nStoredObs of the status file does not match the data file");
   h->initialized = true;      // Learner::initializeLearner is skipped for a restarted learner (Learner.cpp:51-54)

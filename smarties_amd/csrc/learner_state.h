@@ -121,6 +121,7 @@ struct hl_learner {
   bool noDeferBeta = false;             // (SMARTIES_HIP_GENERIC & 2) the whole bookkeeping stays in the dW launch
   float* dRedMax = nullptr; double* dRedErr = nullptr; int redCap = 0;
   double* dMomPartial = nullptr; double* dMoments = nullptr; int momBlocksCap = 0;
+  double* dMomentsPrev = nullptr; bool momPrevValid = false;      // HL_RDX_ONE_BEHIND: the last completed moments sum (step_exec.h: applyMomentsOneBehind)
   double* dStatsOut = nullptr;
   // replayed graphs: one per entry of GRAPH_SIZES and starting minibatch buffer (step_exec.h)
   GraphSlot graphs[16][2]; bool graphsStale = false, useGraph = true;

@@ -13,6 +13,8 @@ int hl_comm_unique_id(uint8_t id[128]) {
 int hl_comm_init(hl_learner* h, const uint8_t id[128]) {
   if (!h || !id) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
+  if (h->cfg.reduction_timing == HL_RDX_ONE_BEHIND)
+    return fail(h, HL_ERR_UNSUPPORTED, "hl_comm_init: the one-behind reduction timing is implemented for the peer-window exchange (hl_xchg_connect) only");
   ncclUniqueId u; std::memcpy(&u, id, sizeof(u));
   HIPCK(hipSetDevice(h->dev));
   NCCLCK(ncclCommInitRank(&h->comm, h->cfg.n_ranks, u, h->cfg.rank));

@@ -260,12 +260,16 @@ SampleArgs sampleArgs(hl_learner* h, int parity, const long long* dFlat, bool co
 // single one (hl_comm_init with n_ranks == 1 runs the N > 1 sequence over a 1-rank RCCL communicator)
 bool exchanging(const hl_learner* h) { return h->cfg.n_ranks > 1 || h->comm != nullptr; }
 bool wired(const hl_learner* h) { return h->comm != nullptr || h->xchg.on; }      // the library itself exchanges (RCCL or xchg.hip)
+// replicas over peer windows in the reference's other reduction timing (HL_RDX_ONE_BEHIND): step k's message carries the counters of step
+// k - 1, a 1000th step applies the last completed moments sum
+bool oneBehind(const hl_learner* h) { return h->xchg.on && h->cfg.n_ranks > 1 && h->cfg.reduction_timing == HL_RDX_ONE_BEHIND; }
 PostArgs postArgs(hl_learner* h, int parity, int mode) {
   PostArgs pa{}; pa.sc = h->sc; pa.rp = h->rp; pa.bt = h->buf[parity].bt; pa.B = h->B; pa.mode = mode;
   pa.clipImpWeight = h->cfg.clipImpWeight; pa.epsAnneal = h->cfg.epsAnneal; pa.penalTol = h->cfg.penalTol;
   pa.maxObsGlobal = (double)h->maxObsGlobal; pa.batchGlobal = (double)h->Bglobal; pa.nRanks = exchanging(h) ? 2 : 1;   // > 1: use the exchanged counters
   pa.parity = parity; pa.eta0 = (float)h->cfg.learnrate; pa.aggStaged = h->fusedOk ? 1 : 0; pa.hasAdv = h->nAdv > 0 ? 1 : 0;
   pa.cntMsg = wired(h) ? h->G + h->nParams + CNT_MSG_OFFSET : nullptr;
+  pa.behind = oneBehind(h) ? 1 : 0;
   return pa;
 }
 HeadArgs headArgs(hl_learner* h, int parity) {
@@ -343,31 +347,35 @@ FusedArgs fusedArgs(hl_learner* h, int parity) {
 // forward + head + dX of the whole minibatch as one kernel (fused.hip); `nextSample`: sampler phases
 // A and B of the NEXT step ride along
 // `deferBeta`: the step before ran its bookkeeping with POST_DEFER: block 1 finishes it (farBetaPhase), the heads wait for beta
-int launchFused(hl_learner* h, int parity, hipStream_t s, bool nextSample = false, bool deferBeta = false) {
+// `encodeCnt`: one-behind replicas, the step before deferred its far-policy count: block 1 takes it and writes this step's counters
+// message (farBetaPhase, POST_ENCODE); beta is the exchange's, the heads do not wait
+int launchFused(hl_learner* h, int parity, hipStream_t s, bool nextSample = false, bool deferBeta = false, bool encodeCnt = false) {
   FusedArgs fa = fusedArgs(h, parity);
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   // (draws, sort, redraws of the next minibatch here; its search and gather ride along the dW kernel: launchWeightGrad)
   if (nextSample) { ex = extraSample(h, parity ^ 1, PH_A | PH_B); pex = &ex; }
   if (deferBeta) { fa.deferBeta = 1; ex.post = postArgs(h, parity ^ 1, POST_BETA); pex = &ex; }
+  if (encodeCnt) { ex.post = postArgs(h, parity ^ 1, POST_ENCODE); pex = &ex; }
   HIPCK(timed(h, "fused_fwd_head_dx", s, [&] { return launch_fused(fa, h->Mmax, pex, s); }));
   return HL_OK;
 }
 HeadArgs headArgs(hl_learner* h, int parity);
 // the wide variant (fusedw.hip): the same launch with the head's description next to the fused kernel's
-int launchFusedWide(hl_learner* h, int parity, hipStream_t s, bool nextSample = false, bool deferBeta = false) {
+int launchFusedWide(hl_learner* h, int parity, hipStream_t s, bool nextSample = false, bool deferBeta = false, bool encodeCnt = false) {
   FusedArgs fa = fusedArgs(h, parity);
   const HeadArgs ha = headArgs(h, parity);
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   if (nextSample) { ex = extraSample(h, parity ^ 1, PH_A | PH_B); pex = &ex; }
   if (deferBeta) { fa.deferBeta = 1; ex.post = postArgs(h, parity ^ 1, POST_BETA); pex = &ex; }
+  if (encodeCnt) { ex.post = postArgs(h, parity ^ 1, POST_ENCODE); pex = &ex; }
   HIPCK(timed(h, "fused_wide", s, [&] { return launch_fused_wide(fa, ha, h->Mmax, pex, s); }));
   return HL_OK;
 }
 int launchFront(hl_learner* h, int parity, hipStream_t s, bool gather);
 // dense networks off the fused kernels: forward chain, head and input-gradient chain as one launch (gemm16.hip: step_chain_kernel)
 // `wholeSampler`: the rider draws, sorts, searches and gathers the next minibatch (a few state components: no gather helpers needed)
-// `deferBeta`: as launchFused
-int launchStepChain(hl_learner* h, int parity, hipStream_t s, bool nextSample = false, bool wholeSampler = false, bool deferBeta = false) {
+// `deferBeta`, `encodeCnt`: as launchFused
+int launchStepChain(hl_learner* h, int parity, hipStream_t s, bool nextSample = false, bool wholeSampler = false, bool deferBeta = false, bool encodeCnt = false) {
   const AdamHyper hyp = adamHyper(h, parity);
   const StepBuf& sb = h->buf[parity];
   { const int rc = launchFront(h, parity, s, true); if (rc) return rc; }
@@ -375,6 +383,7 @@ int launchStepChain(hl_learner* h, int parity, hipStream_t s, bool nextSample = 
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   if (nextSample) { ex = extraSample(h, parity ^ 1, wholeSampler ? PH_ALL : (PH_A | PH_B)); pex = &ex; }
   if (deferBeta) { ha.deferBeta = 1; ex.post = postArgs(h, parity ^ 1, POST_BETA); pex = &ex; }
+  if (encodeCnt) { ex.post = postArgs(h, parity ^ 1, POST_ENCODE); pex = &ex; }
   int fIdx[HL_MAX_HIDDEN], xIdx[HL_MAX_HIDDEN];
   for (int j = 0; j < h->nHidden; ++j) fIdx[j] = sb.fwdIdx[j];
   const int nX = (int)sb.dxIdx.size();
@@ -686,10 +695,20 @@ int launchMoments(hl_learner* h) {
   HIPCK(timed(h, "moments_kernel", h->stream, [&] { return launch_moments(ma, h->stream); }));
   return HL_OK;
 }
-int launchMomentsApply(hl_learner* h, bool bInit, double rRateFac) {
-  MomentsArgs ma{}; ma.sc = h->sc; ma.rp = h->rp; ma.dS = h->dS; ma.moments = h->dMoments;
+int launchMomentsApply(hl_learner* h, bool bInit, double rRateFac, double* moments = nullptr) {
+  MomentsArgs ma{}; ma.sc = h->sc; ma.rp = h->rp; ma.dS = h->dS; ma.moments = moments ? moments : h->dMoments;
   ma.bInit = bInit ? 1 : 0; ma.learnrate = h->cfg.learnrate; ma.epsAnneal = h->cfg.epsAnneal; ma.rRateFac = rRateFac;
   HIPCK(launch_moments_apply(ma, h->stream));
+  return HL_OK;
+}
+// one-behind replicas, a 1000th step: the statistics update takes the last COMPLETED moments sum (MemoryProcessing.cpp:139-150 with
+// DelayedReductor::get(false) finding the new reduction pending), this step's sum -- in dMoments -- is kept for the next 1000th step.
+// None held (after hl_restart_memory): this step's own sum.
+int applyMomentsOneBehind(hl_learner* h) {
+  const size_t bytes = (size_t)(2 * h->dS + 3) * sizeof(double);
+  int rc = launchMomentsApply(h, false, 10, h->momPrevValid ? h->dMomentsPrev : h->dMoments); if (rc) return rc;
+  HIPCK(hipMemcpyAsync(h->dMomentsPrev, h->dMoments, bytes, hipMemcpyDeviceToDevice, h->stream));
+  h->momPrevValid = true;
   return HL_OK;
 }
 
@@ -915,7 +934,8 @@ int stepEager(hl_learner* h, const long long* dFlat) {
     rc = launchPeriodicSweep(h); if (rc) return rc;
     rc = launchMoments(h); if (rc) return rc;
     rc = allreduceMoments(h); if (rc) return rc;
-    rc = launchMomentsApply(h, false, 10); if (rc) return rc;
+    if (oneBehind(h)) { rc = applyMomentsOneBehind(h); if (rc) return rc; }
+    else { rc = launchMomentsApply(h, false, 10); if (rc) return rc; }
   }
   if (evict) { rc = applyRemoval(h); if (rc) return rc; rc = flushPending(h); if (rc) return rc; }
   if (exch) {
@@ -973,10 +993,15 @@ int captureSteps(hl_learner* h, int U, int p0, GraphSlot* slot, bool notify = fa
       // one replica: the far-policy count and the beta update of every step but the last are taken out of the dW launch's
       // bookkeeping rider, where they sat at the end of the kernel's longest workgroup, into a rider of the next fused kernel
       const bool single = !exchanging(h) && !h->noDeferBeta;
+      // one-behind replicas: every step but the last leaves its far-policy count to a rider of the next step's first launch, which writes
+      // that step's counters message with it (the count of the step before is what the message carries); the last step counts in its
+      // own weight-gradient launch, so that the scalars are complete when the call returns
+      const bool behind = oneBehind(h) && !h->noDeferBeta;
       // (the chained step with a few state components: the whole sampler of the next minibatch as its rider -- a 10 us chain beside a 30 us
       //  launch --, the bookkeeping alone on the dW launch of the generic steps; wider states keep the gather helpers of launchWeightGrad)
       const bool chainNarrow = h->stepChainOk && !exchanging(h) && !h->preproc && 2ll * h->B * h->dS <= 16384;
-      rc = h->fusedOk ? launchFused(h, p, s0, true, single && j > 0) : (h->fusedWideOk ? launchFusedWide(h, p, s0, true, single && j > 0) : launchStepChain(h, p, s0, true, chainNarrow, single && j > 0)); if (rc) break;
+      const bool enc = behind && j > 0;
+      rc = h->fusedOk ? launchFused(h, p, s0, true, single && j > 0, enc) : (h->fusedWideOk ? launchFusedWide(h, p, s0, true, single && j > 0, enc) : launchStepChain(h, p, s0, true, chainNarrow, single && j > 0, enc)); if (rc) break;
       if (chainNarrow) {
         rc = launchBackward(h, p, true, s0, true, POST_AGG | POST_BETA | (single && j + 1 < U ? POST_DEFER : 0), false, true); if (rc) break;
         continue;
@@ -988,7 +1013,7 @@ int captureSteps(hl_learner* h, int U, int p0, GraphSlot* slot, bool notify = fa
       // replicas: the exchange is part of the replayed graph (RCCL calls are captured like kernels).  ONE collective per
       // step: the bookkeeping rider of the dW launch appends the four counters to the gradient buffer (four exact 16-bit
       // chunks each), the pass after Adam decodes their sums.
-      rc = launchWeightGrad(h, p, false, s0, true, true, POST_AGG);
+      rc = launchWeightGrad(h, p, false, s0, true, true, POST_AGG | (behind && j + 1 < U ? POST_DEFER : 0) | (enc ? POST_KEEPMSG : 0));
       if (!rc && h->xchg.on) { rc = xchgAllreduce(h, h->G, (size_t)h->nParams + CNT_MSG_OFFSET + CNT_MSG_FLOATS, 0, p); if (rc) break; continue; }
       if (!rc) rc = allreduceGrad(h);
       if (!rc) rc = launchAdam(h, p);

@@ -219,15 +219,21 @@ __device__ __forceinline__ void postPart(const PostArgs& a, long long* sFarDelta
       sc->maxAbsErrAll = maxAll; sc->maxAbsErrStep = maxAll; sc->Cmax = Cm; sc->Cinv = 1 / Cm; sc->cnt[3] = nTrans;
       if (!defer) { sc->nFarTotal = nFarTot; sc->nFarStat = nFarStat; sc->cnt[2] = nFarStat; }
       if (a.nRanks > 1) { sc->cnt[0] = sc->seenLocal[0]; sc->cnt[1] = sc->seenLocal[1]; }   // undo the last all-reduce
-      if (a.cntMsg) {       // counters ride in the tail of the gradient buffer: one all-reduce per step instead of two
+      if (a.cntMsg && !(mode & POST_KEEPMSG)) {       // counters ride in the tail of the gradient buffer: one all-reduce per step instead of two
+        if (a.behind) { const long long c4[4] = {sc->cntPrev[0], sc->cntPrev[1], sc->cntPrev[2], sc->cntPrev[3]}; encodeCounters(a.cntMsg, c4); }      // (one behind: the step before's)
+        else {
         const long long c4[4] = {sc->seenLocal[0], sc->seenLocal[1], nFarStat, nTrans};
         encodeCounters(a.cntMsg, c4);
+        }
       }
     }
   }
   if ((mode & POST_ENCODE) && a.cntMsg && tid == 0) {   // eager steps: the counters as they stand after the removal pass
+    if (a.behind) { const long long c4[4] = {sc->cntPrev[0], sc->cntPrev[1], sc->cntPrev[2], sc->cntPrev[3]}; encodeCounters(a.cntMsg, c4); }      // (one behind: the step before's)
+    else {
     const long long c4[4] = {sc->seenLocal[0], sc->seenLocal[1], sc->cnt[2], sc->cnt[3]};
     encodeCounters(a.cntMsg, c4);
+    }
   }
   if ((mode & (POST_BETA | POST_INIT)) && tid == 0) {
     // updateCounters (:46-92); with several replicas cnt[] holds the all-reduced counters
@@ -258,6 +264,9 @@ __device__ __forceinline__ void postPart(const PostArgs& a, long long* sFarDelta
       sc->nGradSteps = nGrad0 + 1;
       // Adam step size of the NEXT step (read by its dW epilogue from the other buffer slot)
       sc->etaEff[a.parity ^ 1] = adamEtaEff(nStep0 + 1, nb1, nb2, a.eta0, a.epsAnneal);
+      // one-behind replicas: this step's local counters -- as the step's own message would have carried them -- for the next step's message
+      // (a step whose far-policy count is still deferred stores a stale count here: the next step's first launch encodes that one itself)
+      if (a.behind) { sc->cntPrev[0] = sc->seenLocal[0]; sc->cntPrev[1] = sc->seenLocal[1]; sc->cntPrev[2] = nFarStat; sc->cntPrev[3] = nTrans; }
     }
   }
   PSTAMP(sc, 20);
@@ -711,7 +720,8 @@ __device__ __forceinline__ void postPhase(const PostArgs& a, unsigned char* smem
 }
 
 // What a POST_DEFER bookkeeping pass left over, as a rider (block 1) of the NEXT step's fused kernel: the far-policy count over
-// the fractions that pass patched (dev_common.h) and the beta / alpha update that needs it.  The heads of this kernel read
+// the fractions that pass patched (dev_common.h) and the beta / alpha update that needs it (mode POST_BETA) or -- one-behind replicas,
+// mode POST_ENCODE -- the counters message of the step the rider's launch belongs to.  The heads of this kernel read
 // beta late (fused.hip): they wait for betaSeq, published here with agent-scope stores (the first acknowledged before the second
 // is issued; no cache-wide release, which costs tens of microseconds).  256 threads.
 __device__ __forceinline__ void farBetaPhase(const PostArgs& a, unsigned char* smem) {
@@ -742,6 +752,13 @@ __device__ __forceinline__ void farBetaPhase(const PostArgs& a, unsigned char* s
   if (tid != 0) return;
   const long long nFar = Cmax <= 1 ? 0 : (long long)tot;
   sc->nFarTotal = nFar; sc->nFarStat = nFar; sc->cnt[2] = nFar;
+  if (a.mode & POST_ENCODE) {
+    // one-behind replicas (POST_ENCODE): the count of the step before goes into THIS step's message with the other three counters as
+    // that step left them (nothing between two steps of a replayed call changes them); beta comes from the exchange, nobody waits here
+    const long long c4[4] = {sc->seenLocal[0], sc->seenLocal[1], nFar, nTrans};
+    encodeCounters(a.cntMsg, c4);
+    return;
+  }
   const double fracOffPol = (double)nFar / (double)(nTrans > 1 ? nTrans : 1);
   const double learnRefer = 0.1 * a.batchGlobal / fmax(a.maxObsGlobal, (double)nTrans);
   refEerPenal(sc, fracOffPol, learnRefer, a.penalTol, beta0, alpha0, true);
