@@ -1,0 +1,63 @@
+/*
+ * include/smarties_hip_act.h -- batched acting: the network evaluated for MANY agents' windows in one call.
+ *
+ * An addition to the C-ABI of include/smarties_hip.h (same library, same conventions: plain C, an int status per call).
+ * It lives in a header of its own because the CPU oracle (oracle/port) mirrors smarties_hip.h declaration by declaration
+ * and needs no twin of this call: ol_forward_sequence, called once per agent, defines the result.
+ *
+ * What it replaces in the reference (paths relative to source/smarties/): what every agent's Learner::select does for its
+ * action -- MemoryBuffer::agentToMinibatch (ReplayMemory/MemoryBuffer.cpp:440-467: the agent's last min(nnBPTTseq, t) + 1
+ * steps become a one-sample minibatch) followed by Approximator::forward(agent) (every step of that window forwarded from a
+ * zero recurrent state; the last step's output feeds the policy) -- for n agents at once instead of one at a time.
+ *
+ * Which call when:
+ *   hl_forward            dense nets, n raw states (rows): one kernel for up to 64 agents.
+ *   hl_forward_sequence   ONE agent's window, any net.  The cheapest call for a single agent of a recurrent net.
+ *   hl_forward_sequences  n agents' windows, any net.  One launch per HL_ACT_SEQ_CHUNK agents for the shapes listed below.
+ */
+#ifndef SMARTIES_HIP_ACT_H
+#define SMARTIES_HIP_ACT_H
+
+#include "smarties_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* agents per launch: the pinned staging of the library (states, window offsets, outputs, completion stamps) is sized once,
+ * at the first acting call, for this many windows of nnBPTTseq + 1 + nAppendedObs states; a call with more agents is cut
+ * into ceil(n / HL_ACT_SEQ_CHUNK) launches */
+#define HL_ACT_SEQ_CHUNK 512
+
+/* n agents.  n_steps[i] = min(nnBPTTseq, t_i) + 1 (+ up to nAppendedObs states in front), as for hl_forward_sequence.
+ * states: the windows back to back, oldest state first in each (sum of n_steps[i] rows of dimS raw floats).
+ * outputs[i * nOutputs .. ]: nOutputs doubles, those of agent i's last state.
+ *
+ * Agent i's result is what hl_forward_sequence(h, n_steps[i], window_i, outputs_i) defines: the window forwarded from a
+ * zero recurrent state, appended observations filled from the leading context states, steps before the first given state
+ * repeating it (Episode::standardizedState, Episode.h:172-183); output layer, nnOutputFunc and the ParamLayer values.
+ *
+ * Status: HL_ERR_STATE between hl_step_begin and hl_step_end.  HL_ERR_BAD_ARG if any n_steps[i] < 1 or, for a net with
+ * recurrent layers, n_steps[i] > nnBPTTseq + 1 + nAppendedObs (dense nets read the last 1 + nAppendedObs states of a window
+ * of any length, as hl_forward_sequence does): nothing is launched and `outputs` is not written.  n == 0: HL_OK, the device
+ * is not touched.  n has no upper limit.
+ *
+ * Batched (one kernel per chunk: a workgroup per agent up to the number of compute units, further agents walked by the same
+ * workgroups, which stage the weights once; states and outputs through pinned host memory, completion by per-agent stamps;
+ * the minibatch buffers are not touched and a minibatch drawn ahead stays as it is):
+ *     nnType LSTM, MGU or RNN without convolutional layers and without encoder_rnn, every layer <= 256 cells with
+ *     <= 1024 inputs, any nAppendedObs, (nnBPTTseq + 1 + nAppendedObs) x dimS floats of window within 64 KB.
+ *     The gate sums are formed in another order than by hl_forward_sequence's kernels: the two agree to rounding
+ *     (both within 1e-5 of the CPU oracle), not bit for bit.
+ * Dense nets: the [n][dimS (1 + nAppendedObs)] rows are built on the host and go through ONE hl_forward(n) call.
+ * Looped, agent by agent through hl_forward_sequence's own route (bit-identical to it): layers wider than 256 cells
+ * (time-step-major launches), recurrent layers behind convolutions, RNN encoder layers under MGU layers (encoder_rnn).
+ *
+ * For a single agent the call costs more than hl_forward_sequence (which runs the window with the weights in registers
+ * where the shape allows): hl_forward_sequence stays the call for one agent. */
+HL_API int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* n_steps, const float* states, double* outputs);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -25,6 +25,7 @@ NN_FFNN, NN_LSTM, NN_MGU, NN_RNN = 0, 1, 2, 3
 RET = {"retrace": 0, "default": 0, "retraceExplore": 1, "GAE": 2, "none": 3}
 ORDER_STABLE, ORDER_REFERENCE = 0, 1
 RDX_CURRENT, RDX_ONE_BEHIND = 0, 1      # hl_config::reduction_timing (include/smarties_hip.h)
+ACT_SEQ_CHUNK = 512                     # HL_ACT_SEQ_CHUNK (include/smarties_hip_act.h): agents per launch of hl_forward_sequences
 RDX = {"current": RDX_CURRENT, "one_behind": RDX_ONE_BEHIND}
 
 (TAP_FLAT, TAP_EPISODE, TAP_TSTEP, TAP_TAG, TAP_STATE, TAP_OUTPUT, TAP_OUTGRAD, TAP_RHO, TAP_DKL,
@@ -210,6 +211,7 @@ class CApi:
             "kernel_profile": (C.c_int, [P, I32, I32, pd]),
             "forward": (C.c_int, [P, I32, pf, pd]),
             "forward_sequence": (C.c_int, [P, I32, pf, pd]),
+            "forward_sequences": (C.c_int, [P, I32, pi32, pf, pd]),      # include/smarties_hip_act.h (product library only)
             "save": (C.c_int, [P, C.c_char_p]),
             "metrics": (C.c_int, [P, C.c_char_p, I32, C.c_char_p, I32]),
             "grad_stats": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -417,6 +419,22 @@ class Learner:
         states = _f32(states).reshape(-1, self.dS)
         out = np.zeros(self.nOut, np.float64)
         self._ck(self.api.fn("forward_sequence")(self.h, states.shape[0], _ptr(states, C.c_float), _ptr(out, C.c_double)))
+        return out
+
+    def forward_sequences(self, windows, out=None):
+        """network outputs [n][nOut] (float64) for n agents' windows (each: consecutive raw states, oldest first), one call
+        (hl_forward_sequences, include/smarties_hip_act.h); a library without that entry point (the CPU oracle) is asked
+        window by window.  `out`: array to fill instead of a new one."""
+        wins = [_f32(w).reshape(-1, self.dS) for w in windows]
+        if out is None:
+            out = np.zeros((len(wins), self.nOut), np.float64)
+        if not self.api.has("forward_sequences"):
+            for i, w in enumerate(wins):
+                out[i] = self.forward_sequence(w)
+            return out
+        n_steps = np.ascontiguousarray([w.shape[0] for w in wins], dtype=np.int32)
+        states = np.ascontiguousarray(np.concatenate(wins, axis=0) if wins else np.zeros((0, self.dS)), dtype=np.float32)
+        self._ck(self.api.fn("forward_sequences")(self.h, len(wins), _ptr(n_steps, C.c_int32), _ptr(states, C.c_float), _ptr(out, C.c_double)))
         return out
 
     def metrics(self):

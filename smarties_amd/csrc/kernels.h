@@ -353,6 +353,21 @@ struct ActArgs {
   ActLayer L[HL_MAX_HIDDEN];
 };
 hipError_t launch_act_forward(const ActArgs& a, int n, hipStream_t s);
+// rollout inference of recurrent nets for many agents (actseq.hip: act_seq_kernel): a workgroup stages the recurrent stack once and
+// walks its agents' windows; states, window offsets, outputs and per-agent stamps in pinned host memory
+constexpr int ACT_SEQ_CHUNK = 512;      // agents per launch (HL_ACT_SEQ_CHUNK of include/smarties_hip_act.h)
+struct ActSeqLayer { int nIn, nC, hasRes, resW; long long indW, indB, indWr, indBr; int wOff, pOff; /* LDS offsets (act_seq_plan) */ };
+struct ActSeqArgs {
+  const float* W; const float* stMean; const float* stScale;
+  const float* states; const int* offset;      // the windows back to back, raw; offset[i] = first state of agent i, offset[n] = their number
+  double* out; volatile unsigned* done; unsigned tag;
+  int n, dS, nApp, recWin, nL, gates, func;     // gates / func as RecArgs
+  int nDense, nSig, nOut, ldWo; long long indWo, indBo, indBp; int outFunc;
+  int ldsW, parOff, stOff; size_t ldsBytes;     // act_seq_plan: weights in LDS, offsets (floats) of the parameters / the window, dynamic LDS
+  ActSeqLayer L[HL_MAX_HIDDEN];
+};
+bool act_seq_plan(ActSeqArgs* a);             // the kernel serves this net (<= 256 cells and <= 1024 inputs per layer, window within the LDS): LDS layout filled in
+hipError_t launch_act_seq(const ActSeqArgs& a, int nBlocks, hipStream_t s);
 hipError_t launch_episode_sweep(const EpisodeSweepArgs& a, int nBlocks, hipStream_t s);
 hipError_t launch_far_build(DevReplay rp, int nEpisodes, hipStream_t s);    // after the table or all fractions changed
 hipError_t launch_sweep_finish(DevScalars* sc, DevReplay rp, const float* redMaxAbs, const double* redErr, int countRet, int nBlocks, hipStream_t s);

@@ -1,10 +1,36 @@
-// smarties_amd/csrc/learner_act.h -- part of learner.cpp's ONE translation unit (included there, like step_exec.h): rollout inference (Learner::select's network evaluation): hl_forward, hl_forward_sequence
+// smarties_amd/csrc/learner_act.h -- part of learner.cpp's ONE translation unit (included there, like step_exec.h): rollout inference (Learner::select's network evaluation): hl_forward, hl_forward_sequence, hl_forward_sequences
 #pragma once
+#include "../../include/smarties_hip_act.h"
+static_assert(ACT_SEQ_CHUNK == HL_ACT_SEQ_CHUNK, "the chunk capacity the header states");
 
 static size_t actPinFloats(const hl_learner* h) { return std::max((size_t)ACT_MAXROWS * h->dIn, (size_t)(std::max(h->recWin, 1) + h->nApp) * h->dS); }
+// the batched window kernel (actseq.hip) serves this net: one recurrent layer type, no convolutions in front, layers within its bounds
+static bool actSeqOk(hl_learner* h) {
+  if (h->actSeqState) return h->actSeqState > 0;
+  h->actSeqState = -1;
+  if (!h->recurrent || h->nConv > 0 || h->recSplit) return false;
+  const RecArgs ra = recArgs(h, 0);
+  ActSeqArgs& a = h->actSeq; a = ActSeqArgs{};
+  a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
+  a.dS = h->dS; a.nApp = h->nApp; a.recWin = h->recWin; a.nL = ra.nL; a.gates = ra.gates; a.func = ra.func;
+  a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo; a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp;
+  a.outFunc = h->cfg.nnOutputFunc;
+  for (int j = 0; j < ra.nL; ++j) { const RecLayer& L = ra.L[j]; a.L[j] = ActSeqLayer{L.nIn, L.nC, L.hasRes, L.resW, L.indW, L.indB, L.indWr, L.indBr, 0, 0}; }
+  if (!act_seq_plan(&a)) return false;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return false;
+  h->actSeqCus = cus; h->actSeqState = 1;
+  return true;
+}
+// one pinned block: [outputs of ACT_MAXROWS rows | their states | their stamps] of hl_forward / hl_forward_sequence, then (nets the
+// batched window kernel serves) [outputs | stamps | window offsets | states] of a chunk of ACT_SEQ_CHUNK agents
+static size_t actSeqStateFloats(const hl_learner* h) { return (size_t)ACT_SEQ_CHUNK * (h->recWin + h->nApp) * h->dS; }
 static int actPinEnsure(hl_learner* h) {
   if (h->actPin) return HL_OK;
-  const size_t bytes = (size_t)ACT_MAXROWS * (h->nOut * sizeof(double) + sizeof(unsigned)) + actPinFloats(h) * sizeof(float) + 256;
+  size_t bytes = (size_t)ACT_MAXROWS * (h->nOut * sizeof(double) + sizeof(unsigned)) + actPinFloats(h) * sizeof(float) + 256;
+  bytes = (bytes + 255) & ~(size_t)255;
+  h->actSeqPinOff = bytes;
+  if (actSeqOk(h)) bytes += (size_t)ACT_SEQ_CHUNK * (h->nOut * sizeof(double) + sizeof(unsigned)) + ((size_t)ACT_SEQ_CHUNK + 2) * sizeof(int) + actSeqStateFloats(h) * sizeof(float);
   HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actPin), bytes, hipHostMallocMapped));
   std::memset(h->actPin, 0, bytes);
   return HL_OK;
@@ -122,5 +148,61 @@ int hl_forward_sequence(hl_learner* h, int32_t nSteps, const float* states, doub
                           pOut, h->stream, const_cast<unsigned*>(pDone), tag, h->cfg.nnOutputFunc));
   { int rc = actWait(h, pDone, 1, tag); if (rc) return rc; }
   std::memcpy(outputs, pOut, (size_t)h->nOut * sizeof(double));
+  return HL_OK;
+}
+
+// n agents' windows (include/smarties_hip_act.h)
+int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const float* states, double* outputs) {
+  if (!h || n < 0 || (n > 0 && (!nSteps || !states || !outputs))) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  if (h->inStep) return fail(h, HL_ERR_STATE, "hl_forward_sequences between hl_step_begin and hl_step_end");
+  if (n == 0) return HL_OK;
+  const int maxSteps = h->recWin + h->nApp;
+  for (int i = 0; i < n; ++i) {
+    if (nSteps[i] < 1) return fail(h, HL_ERR_BAD_ARG, "hl_forward_sequences: a window without a state");
+    if (h->recurrent && nSteps[i] > maxSteps) return fail(h, HL_ERR_BAD_ARG, "more steps than nnBPTTseq + 1 (+ nAppendedObs)");
+  }
+  if (!h->recurrent) {
+    // dense net: the rows hl_forward reads -- the state of the last step followed by those of the steps before it (Episode::standardizedState,
+    // Episode.h:172-183; steps before the first given one repeat it) -- then ONE call for all agents
+    std::vector<float> rows((size_t)n * h->dIn);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+      for (int j = 0; j <= h->nApp; ++j) { const int tt = std::max(nSteps[i] - 1 - j, 0);
+        std::memcpy(rows.data() + (size_t)i * h->dIn + (size_t)j * h->dS, states + (off + tt) * h->dS, (size_t)h->dS * sizeof(float)); }
+      off += nSteps[i];
+    }
+    return hl_forward(h, n, rows.data(), outputs);
+  }
+  if (!actSeqOk(h)) {      // layers beyond the batched kernel, convolutions in front, two layer types: hl_forward_sequence's routes, agent by agent
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+      const int rc = hl_forward_sequence(h, nSteps[i], states + off * h->dS, outputs + (size_t)i * h->nOut); if (rc) return rc;
+      off += nSteps[i];
+    }
+    return HL_OK;
+  }
+  { int rc = actPinEnsure(h); if (rc) return rc; }
+  double* pOut = reinterpret_cast<double*>(h->actPin + h->actSeqPinOff);
+  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pOut + (size_t)ACT_SEQ_CHUNK * h->nOut);
+  int* pOff = reinterpret_cast<int*>(const_cast<unsigned*>(pDone) + ACT_SEQ_CHUNK);
+  float* pIn = reinterpret_cast<float*>(pOff + ACT_SEQ_CHUNK + 2);
+  size_t first = 0;      // states in front of the chunk
+  for (int i0 = 0; i0 < n; i0 += ACT_SEQ_CHUNK) {
+    const int m = std::min(ACT_SEQ_CHUNK, n - i0);
+    int sum = 0;
+    for (int i = 0; i < m; ++i) { pOff[i] = sum; sum += nSteps[i0 + i]; }
+    pOff[m] = sum;
+    std::memcpy(pIn, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
+    ActSeqArgs a = h->actSeq;
+    a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
+    a.states = pIn; a.offset = pOff; a.out = pOut; a.done = pDone; a.n = m;
+    a.tag = ++h->actTag; if (a.tag == 0) a.tag = ++h->actTag;
+    const int blocks = std::min(m, h->actSeqCus);
+    HIPCK(timed(h, "act_seq", h->stream, [&] { return launch_act_seq(a, blocks, h->stream); }));
+    { int rc = actWait(h, pDone, m, a.tag); if (rc) return rc; }
+    std::memcpy(outputs + (size_t)i0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
+    first += sum;
+  }
   return HL_OK;
 }
