@@ -81,7 +81,9 @@ enum { HL_FUNC_LINEAR = 0, HL_FUNC_TANH = 1, HL_FUNC_SOFTSIGN = 2, HL_FUNC_RELU 
  * HL_NN_LSTM: rec.hip (a workgroup -- two wavefronts for the shipped 2 x 32 shape -- per sample walks the BPTT window; cells <= 256 per layer). */
 enum { HL_NN_FFNN = 0, HL_NN_LSTM = 1, HL_NN_MGU = 2 /* Layer_GRU.h: what a partially observable MDP gets when nnType is left FFNN (Approximator.cpp:221-223) */,
        HL_NN_RNN = 3 /* "RNN" / "Recurrent" (Builder.cpp:76-81): dense layers with a recurrent term, y_t = f(W x_t + W_rec y_{t-1} + b)
-                        (BaseLayer with bRecurrent, Layer_Base.h:64-113) */ };
+                        (BaseLayer with bRecurrent, Layer_Base.h:64-113).  Up to 256 cells per layer: the per-sample kernels of rec.hip; up to
+                        1024 where every layer is a multiple of 16 cells and no encoder layers or convolutions lie in front: nets with a
+                        layer above 256 cells run time-step-major on the MFMA, as wide LSTM / MGU layers do (rectm.hip) */ };
 
 /* settings key returnsEstimator (Settings/HyperParameters.cpp:135; MemoryProcessing::createReturnEstimator,
  * ReplayMemory/MemoryProcessing.cpp:391-450): how the per-step return estimates are swept backwards over an episode */

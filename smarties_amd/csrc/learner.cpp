@@ -78,9 +78,9 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   if (cfg->nn_type != HL_NN_FFNN) {   // rec.hip: 256-thread workgroups looping over gates and cells (REC_GENC, REC_GENIN)
     if (cfg->n_conv <= 0 && (cfg->dimS > 256 || (long long)cfg->dimS * (1 + std::max(cfg->nAppendedObs, 0)) > 1024)) return HL_ERR_UNSUPPORTED;
     // (encoder layers are hidden layers of the same network, Learner_approximator.cpp:149-166: the same limits hold for them)
-    // (LSTM / MGU layers of up to 1024 cells, all multiples of 16, without encoder layers or convolutions in front: the time-step-major
+    // (LSTM / MGU / RNN layers of up to 1024 cells, all multiples of 16, without encoder layers or convolutions in front: the time-step-major
     //  launches -- rectm.hip -- serve their training windows and their acting windows; checked again where recTm is decided)
-    const bool tmKind = (cfg->nn_type == HL_NN_LSTM || cfg->nn_type == HL_NN_MGU) && cfg->n_encoder == 0 && cfg->n_conv <= 0;
+    const bool tmKind = cfg->n_encoder == 0 && cfg->n_conv <= 0;      // (every recurrent type)
     for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] > (tmKind && cfg->hidden[j] % 16 == 0 ? 1024 : 256)) return HL_ERR_UNSUPPORTED;
     for (int j = 0; j < cfg->n_encoder; ++j) if (cfg->encoder[j] > 256) return HL_ERR_UNSUPPORTED;
   }
@@ -153,11 +153,13 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   if (h->recurrent) h->recK = h->recWin = (cfg->nnBPTTseq > 0 ? cfg->nnBPTTseq : 16) + 1;
   // LSTM / MGU layers wider than 64 cells: time-step-major launches (rectm.hip); the windows then carry the next state's step as a row
   // of their own (one row more per sample)
-  if (h->recurrent && (cfg->nn_type == HL_NN_LSTM || cfg->nn_type == HL_NN_MGU) && !(h->generic & 4) && cfg->n_encoder == 0 && cfg->n_conv == 0) {
+  // Plain RNN layers take them only where a layer is wider than the 256 cells the per-sample kernels hold (rnn_tm_fwd_kernel): below that
+  // the crossover is not measured, and those nets keep their kernels and their results
+  if (h->recurrent && !(h->generic & 4) && cfg->n_encoder == 0 && cfg->n_conv == 0) {
     bool wide = false, ok = true;
     // (measured again with a launch per diagonal, batch 128, 17 steps: LSTM 2 x 64 cells 314 us per-sample against 284 time-step-major, 2 x 48: 204 / 282;
     //  MGU 2 x 64: 238 / 488 -- the time-step-major chain has a floor of 37 (LSTM) / 74 (MGU) dependent launches)
-    h->tmMinCells = cfg->nn_type == HL_NN_LSTM ? 48 : 64;
+    h->tmMinCells = cfg->nn_type == HL_NN_LSTM ? 48 : (cfg->nn_type == HL_NN_MGU ? 64 : 256);      // (RNN: 256 = REC_GENC, the per-sample kernels' limit, not a crossover)
     for (int j = 0; j < h->cfg.n_hidden; ++j) { wide = wide || h->cfg.hidden[j] > h->tmMinCells; ok = ok && h->cfg.hidden[j] % 16 == 0; }
     // (the crossover, measured at batch 128 and 17 steps: 2 x 64 cells 325 us with the per-sample kernels against 452 time-step-major, 2 x 96: 631 against 499)
     h->recTm = wide && ok;
@@ -168,7 +170,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     if (h->recTm && !(h->generic & 128)) h->bigMm |= 2;
   }
   if (h->recurrent && !h->recTm)
-    for (int j = 0; j < h->cfg.n_hidden; ++j) if (h->cfg.hidden[j] > 256) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer wider than 256 cells: every layer must be a multiple of 16 cells (time-step-major launches)");
+    for (int j = 0; j < h->cfg.n_hidden; ++j) if (h->cfg.hidden[j] > 256) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer wider than 256 cells: every LSTM / MGU / RNN layer must be a multiple of 16 cells, without encoder layers or convolutions in front (time-step-major launches)");
   h->convB = B; h->convMmax = h->Mmax;
   if (h->recurrent && h->nConv > 0) {
     if (h->nHidden < 2) return fail(h, HL_ERR_UNSUPPORTED, "recurrent network type behind convolutions without a recurrent layer (nnLayerSizes is empty)");
@@ -252,7 +254,8 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       HIPCK(devAlloc(&L.D, R * g * d.size + 16));
       if (d.hasRes) HIPCK(devAlloc(&L.Rd, R * L.ldR));
       if (d.lstm == 2) HIPCK(devAlloc(&L.A2, R * L.ldA2 + 16));
-      if (h->recTm) { HIPCK(devAlloc(&h->tmER[j], (size_t)B * d.size)); HIPCK(devAlloc(&h->tmSD[j], (size_t)B * d.size)); HIPCK(devAlloc(&h->tmFP[j], (size_t)B * d.size)); HIPCK(devAlloc(&h->tmET[j], (size_t)B * d.size)); }
+      if (h->recTm) { HIPCK(devAlloc(&h->tmER[j], (size_t)B * d.size)); HIPCK(devAlloc(&h->tmET[j], (size_t)B * d.size)); }
+      if (h->recTm && d.lstm >= 2) { HIPCK(devAlloc(&h->tmSD[j], (size_t)B * d.size)); HIPCK(devAlloc(&h->tmFP[j], (size_t)B * d.size)); }      // (the RNN kernels carry no state between steps but the error itself)
     }
     if (h->recTm) {
       HIPCK(devAlloc(&h->tmT, (size_t)B)); HIPCK(devAlloc(&h->tmSteps, (size_t)B)); HIPCK(devAlloc(&h->tmNext, (size_t)B));

@@ -1,4 +1,4 @@
-// smarties_amd/csrc/rectm.hip -- LSTM layers wider than 64 cells, TIME-STEP-MAJOR: one launch per (layer, window step) over the whole
+// smarties_amd/csrc/rectm.hip -- LSTM / MGU layers wider than 64 cells and plain RNN layers wider than 256, TIME-STEP-MAJOR: one launch per (layer, window step) over the whole
 // minibatch, the step's gate sums as ONE product on the MFMA (round 5; VERDICT r04: "rec.hip contains no MFMA").
 //
 //   reference: Network/Layers/Layer_LSTM.h:77-166 (forward / backward of one step), Network/Network.h:155-193 (back-propagation over
@@ -525,16 +525,203 @@ __global__ __launch_bounds__(256) void mgu_tm_bwd_kernel(RecArgs a, int j0, int 
   if (live) tmMguOpen(a, J, Kc, b, c, T, below ? v : o, below ? o : v);
 }
 
+// ---- plain RNN layers (nnType "RNN": BaseLayer with bRecurrent, Network/Layers/Layer_Base.h:64-113), the same arrangement ----------
+//   y_t = f(b + W_in x_t + W_rec y_{t-1}):  one gate, the epilogue is the activation.  W is [nIn + nC][nC]; rows kept per (sample,
+//   step): X = pre-activation, Y = output, D = delta -- the rows rec.hip's rnn_forward_kernel keeps, so the taps, the head and the dW
+//   launch see nothing new.
+// Tile shape of the forward kernel: a workgroup = 16 samples x TWO 16-cell tiles, its eight wavefronts = tile (w & 1) x quarter (w >> 1)
+// of the reduction over [W_in; W_rec].  With one gate the LSTM kernel's "wavefront = gate" has no meaning; what a workgroup pays before
+// its first MFMA is the staging of the A tile (16 rows x (nIn + nC) floats -- as many bytes as ONE tile's W columns), so the staged tile
+// serves two cell tiles (half as many workgroups restage it), and the reduction is split four ways so that a wavefront's chain of
+// dependent W batches stays short ((nIn + nC) / 64 loads of 16 rows: 3 at 2 x 272 cells, 8 at 2 x 1024).  Four tiles x two halves -- the
+// LSTM kernel's 64 columns per workgroup -- would leave 5 x 8 workgroups per (layer, step) at 272 cells and batch 128 for 256 CUs and double
+// that chain; one tile x eight eighths (the MGU kernel) restages A per 16 cells.  A layer with an odd number of tiles (272 = 17 x 16) has
+// one workgroup whose second tile does not exist: its wavefronts run on clamped columns and write nothing.
+// Measured with this shape (profiles/rnn_tm_timing.json): the forward chain of 2 x 272 cells, batch 128, 18 steps takes 186 us,
+// of 2 x 512 cells 239 us -- 3.5 x the operations for 28 % more time, so at these sizes the dependent launches set the time and not the
+// product.  The other two shapes were not built: the choice between them rests on the arithmetic above.
+constexpr int RNN_TM_TILES = 2;
+__global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, int k0) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;      // (a diagonal per launch: lstm_tm_fwd_kernel)
+  const RecLayer& L = a.L[j];
+  if ((int)blockIdx.x * 16 * RNN_TM_TILES >= L.nC) return;           // (the grid is as wide as the diagonal's widest layer)
+  const int nIn = L.nIn, nC = L.nC, Kt = nIn + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
+  float* sA = sm;                        // [16][lds]
+  float* sG = sA + 16 * lds;             // [8][16][17]
+  __shared__ int sAct[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
+  const int b0 = blockIdx.y * 16, cBase = blockIdx.x * 16 * RNN_TM_TILES;
+  if (tid < 16) sAct[tid] = (b0 + tid < a.B && a.tmSteps[b0 + tid] > k) ? 1 : 0;
+  // this wavefront's W column (tile, cell li) over its quarter of the rows [W_in; W_rec]: the first batch is requested in front of the A tile
+  const int tile = wave & 1, quarter = wave >> 1;
+  const int nS = Kt4 >> 2, nSq = (nS + 3) >> 2, sBeg = quarter * nSq, sEnd = min(nS, sBeg + nSq);
+  const float* Wg = a.W + L.indW + min(cBase + 16 * tile, nC - 16) + li;      // (W's row pitch is nC: a multiple of 16)
+  constexpr int UN = 16;
+  float bv[UN];
+#pragma unroll
+  for (int u = 0; u < UN; ++u) { const int i = min(4 * (sBeg + u) + lc, Kt - 1); bv[u] = Wg[(size_t)i * nC]; }      // (rows behind Kt: a valid row, the A element is zero)
+  // what the epilogue reads from memory: requested here, used behind the products (lstm_tm_fwd_kernel)
+  const int eTile = tid >> 8, eRow = (tid >> 4) & 15, eC = cBase + 16 * eTile + (tid & 15), eB = min(b0 + eRow, a.B - 1);
+  const bool eOk = eC < nC;
+  const float biE = eOk ? a.W[L.indB + eC] : 0.f;
+  const int stepsE = a.tmSteps[eB], TE = a.tmT[eB];
+  float wrE = 0.f, brE = 0.f;
+  if (L.hasRes && eC < L.resW) { wrE = a.W[L.indWr + eC]; brE = a.W[L.indBr + eC]; }
+  {      // the A tile: rows r = b K + k, Kt floats each, 16-byte pieces; zeros behind Kt
+    const int q4 = Kt4 >> 2;
+    for (int i = tid; i < 16 * q4; i += TM_FNT) {
+      const int row = i / q4, q = i - row * q4, b = min(b0 + row, a.B - 1);
+      f32x4 v = *reinterpret_cast<const f32x4*>(L.A + ((size_t)b * a.K + k) * L.ldA + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) if (4 * q + e >= Kt) v[e] = 0.f;
+      *reinterpret_cast<f32x4*>(sA + row * lds + 4 * q) = v;
+    }
+  }
+  __syncthreads();
+  bool any = false;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) any = any || sAct[i] != 0;
+  if (!any) return;
+  // acc[q] = sample 4 lc + q, cell li
+  const float* ar = sA + li * lds + lc;
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  for (int s0 = sBeg; s0 < sEnd; s0 += UN) {
+    float bn[UN];
+    const bool more = s0 + UN < sEnd;
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < UN; ++u) { const int i = min(4 * (s0 + UN + u) + lc, Kt - 1); bn[u] = Wg[(size_t)i * nC]; }      // the next batch flies during this one's MFMAs
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const float av = s0 + u < sEnd ? ar[4 * (s0 + u)] : 0.f;
+      if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc1, 0, 0, 0);
+      else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc0, 0, 0, 0);
+    }
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < UN; ++u) bv[u] = bn[u];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sG[(wave * 16 + 4 * lc + q) * 17 + li] = acc0[q] + acc1[q];
+  __syncthreads();
+  // BaseLayer::forward of (sample row, cell c): thread = (tile, row, cell)
+  const int row = eRow, cc = tid & 15, b = b0 + row, c = eC;
+  if (!eOk || !sAct[row]) return;
+  const long long r = (long long)b * a.K + k;
+  auto part = [&](int q) { return sG[((RNN_TM_TILES * q + eTile) * 16 + row) * 17 + cc]; };
+  const float x = biE + ((part(0) + part(1)) + (part(2) + part(3)));
+  const float out = actEval(a.func, x);
+  L.X[r * nC + c] = x; L.Y[r * nC + c] = out;
+  float blk = out;                                       // ParametricResidualLayer::forward (Layers.h:347-361)
+  if (L.hasRes && c < L.resW) blk += sA[row * lds + c] * wrE + brE;
+  const int steps = stepsE, T = TE;
+  if (k + 1 < steps) L.A[(r + 1) * L.ldA + nIn + c] = out;          // the next step's recurrent input
+  if (j + 1 < a.nL) { const RecLayer& U = a.L[j + 1]; U.A[r * U.ldA + c] = blk; }      // the layer above, same step
+  else {
+    if (k == T) a.Yout[(size_t)b * a.ldY + c] = blk;
+    else if (k == T + 1) a.Yout[(size_t)a.tmNext[b] * a.ldY + c] = blk;
+  }
+}
+// the delta of (layer j, step k, sample b, cell c), BaseLayer::backward (Layer_Base.h:97-113): eTop = error from the block above (same step),
+// eRec = error handed back by step k + 1 (zero at the sample's last step) -- as rnn_backward_kernel forms it
+__device__ __forceinline__ void tmRnnDelta(const RecArgs& a, int j, int k, int b, int c, int T, float eTop, float eRec) {
+  const RecLayer& L = a.L[j];
+  const int nC = L.nC;
+  const long long r = (long long)b * a.K + k;
+  if (L.hasRes) L.Rd[r * L.ldR + c] = eTop;
+  const float D = eTop + (k < T ? eRec : 0.f);
+  L.D[r * nC + c] = D * actDiff(a.func, L.X[r * nC + c], L.Y[r * nC + c]);
+}
+// Layer::backward of layer j at step k (Layers.h:123-188): [error to the block below | error to step k - 1] = D[r] W^T, a launch per
+// anti-diagonal, the two producers of a tile of deltas meeting at the arrival counter -- lstm_tm_bwd_kernel with one gate.  The four
+// wavefronts split the reduction over the nC deltas into quarters (nC / 4 is a multiple of 4, not of 16: whole groups of 16 as 16-byte
+// loads, the rest four per lane group as in mgu_tm_bwd_kernel).
+__global__ __launch_bounds__(256) void rnn_tm_bwd_kernel(RecArgs a, int j0, int k0) {
+  __shared__ float sR[4 * 256];
+  __shared__ int sT[16];
+  __shared__ unsigned sArr;
+  const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;
+  const int top = a.nL - 1;
+  if (k == a.nBPTT + 1 && j != top) return;      // (only the last layer has a launch at the step behind the windows)
+  const RecLayer& L = a.L[j];
+  const int nIn = L.nIn, nC = L.nC;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
+  const int row0 = j > 0 ? 0 : nIn;      // (no error below the first layer)
+  const int nRowW = nIn + nC;
+  const int b0 = blockIdx.y * 16, i0 = row0 + blockIdx.x * 16;
+  if (i0 >= nIn + (k > 0 ? nC : 0)) return;      // (the grid is as wide as the diagonal's widest member; no error to a step in front of the first)
+  if (tid < 16) sT[tid] = b0 + tid < a.B ? a.tmT[b0 + tid] : -2;
+  const int iw = min(i0 + li, nRowW - 1), bl = min(b0 + li, a.B - 1);
+  const int q = nC >> 2;                 // deltas per wavefront
+  const float* wq = a.W + L.indW + (size_t)iw * nC + wave * q;
+  const float* dq = L.D + ((size_t)bl * a.K + k) * nC + wave * q;
+  const f32x4* wr = reinterpret_cast<const f32x4*>(wq) + lc;
+  const f32x4* dr = reinterpret_cast<const f32x4*>(dq) + lc;
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  const int nG = q >> 4, rem = q & 15;
+  constexpr int UG = 8;
+  for (int g0 = 0; g0 < nG; g0 += UG) {
+    f32x4 wv[UG], dv[UG];
+#pragma unroll
+    for (int u = 0; u < UG; ++u) { const int G = min(g0 + u, nG - 1); wv[u] = wr[4 * G]; dv[u] = dr[4 * G]; }
+#pragma unroll
+    for (int u = 0; u < UG; ++u) {
+      if (g0 + u < nG) {      // A = deltas (rows = samples), B = W rows (columns = rows i of W)
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][0], wv[u][0], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][1], wv[u][1], acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][2], wv[u][2], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][3], wv[u][3], acc1, 0, 0, 0);
+      }
+    }
+  }
+  for (int e = 0; 4 * e < rem; ++e) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dq[16 * nG + 4 * e + lc], wq[16 * nG + 4 * e + lc], acc0, 0, 0, 0);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) sR[wave * 256 + (4 * lc + p) * 16 + li] = acc0[p] + acc1[p];
+  __syncthreads();
+  const int row = tid >> 4, ii = tid & 15, b = b0 + row, i = i0 + ii, T = sT[row];
+  const float e = (sR[tid] + sR[256 + tid]) + (sR[512 + tid] + sR[768 + tid]);      // (zero for a sample without step k)
+  // the tile's cells: (J, Kc), the same for the whole workgroup (layer inputs and cells come in multiples of 16)
+  const bool below = i0 < nIn;
+  const int J = below ? j - 1 : j, Kc = below ? k : k - 1, c = below ? i : i - nIn;
+  const int nCJ = a.L[J].nC;
+  const bool live = b < a.B && c < nCJ && T >= Kc;      // (this sample has step Kc: its rows of deltas exist)
+  float v = e;
+  if (below && L.hasRes && i < L.resW && b < a.B) v += L.Rd[((size_t)b * a.K + k) * L.ldR + i] * a.W[L.indWr + i];
+  if (!below && j == top) {      // the last layer's deltas of the previous step: nothing else feeds them
+    if (live) tmRnnDelta(a, j, Kc, b, c, T, Kc == T ? a.Dres[(size_t)b * a.ldD + c] : 0.f, v);
+    return;
+  }
+  if (below && k + 1 > a.nBPTT) {      // (no launch of the layer below behind the windows: these deltas have one producer)
+    if (live) tmRnnDelta(a, J, Kc, b, c, T, v, 0.f);
+    return;
+  }
+  // the two producers meet at the arrival counter: values as agent-scope stores, acknowledged before the arrival is counted (lstm_tm_bwd_kernel)
+  float* mine = below ? a.tmET[J] : a.tmER[J];
+  const float* other = below ? a.tmER[J] : a.tmET[J];
+  const size_t at = (size_t)min(b, a.B - 1) * nCJ + min(c, nCJ - 1);
+  if (b < a.B && c < nCJ) __hip_atomic_store(mine + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __builtin_amdgcn_s_waitcnt(0);          // vmcnt(0): this tile's values are at the coherence point
+  __syncthreads();
+  if (tid == 0) sArr = __hip_atomic_fetch_add(a.tmCtr + a.tmCtrOff[J] + c0tile(i0, nIn, below) * (int)gridDim.y + (int)blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if ((sArr & 1u) == 0u) return;          // the first of the two
+  const float o = __hip_atomic_load(other + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (live) tmRnnDelta(a, J, Kc, b, c, T, below ? v : o, below ? o : v);
+}
+
 static bool tmLayersOk(const RecArgs& a);
 // acting (one window of a.actSteps given states) through the same launches: used where a layer is wider than the per-sample kernels hold
 bool rec_tm_act_ok(const RecArgs& a) {
-  if ((a.gates != 4 && a.gates != 2) || a.actStates == nullptr || a.B != 1 || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
+  if ((a.gates != 4 && a.gates != 2 && a.gates != 1) || a.actStates == nullptr || a.B != 1 || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
   bool wide = false;
   for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > 256;
   return wide && tmLayersOk(a);
 }
 bool rec_tm_ok(const RecArgs& a) {
-  if ((a.gates != 4 && a.gates != 2) || a.actStates != nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.DresRows != nullptr || a.K < a.nBPTT + 2) return false;
+  if ((a.gates != 4 && a.gates != 2 && a.gates != 1) || a.actStates != nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.DresRows != nullptr || a.K < a.nBPTT + 2) return false;
   return tmLayersOk(a);
 }
 static bool tmLayersOk(const RecArgs& a) {
@@ -566,6 +753,14 @@ hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s) {
       int jLo, nz, gx; size_t lds; diag(d, &jLo, &nz, &gx, &lds);
       for (int ph = 0; ph < 2; ++ph)
         hipLaunchKernelGGL(mgu_tm_fwd_kernel, dim3(gx, (a.B + 15) / 16, nz), dim3(TM_FNT), lds, s, a, jLo, d - jLo, ph);
+    }
+    return hipGetLastError();
+  }
+  if (a.gates == 1) {      // (a workgroup covers RNN_TM_TILES tiles of 16 cells)
+    hipError_t e1 = ensureDynLds(reinterpret_cast<const void*>(rnn_tm_fwd_kernel), ldsMax); if (e1 != hipSuccess) return e1;
+    for (int d = 0; d <= kLast + a.nL - 1; ++d) {
+      int jLo, nz, gx; size_t lds; diag(d, &jLo, &nz, &gx, &lds);
+      hipLaunchKernelGGL(rnn_tm_fwd_kernel, dim3((gx + RNN_TM_TILES - 1) / RNN_TM_TILES, (a.B + 15) / 16, nz), dim3(TM_FNT), lds, s, a, jLo, d - jLo);
     }
     return hipGetLastError();
   }
@@ -605,7 +800,8 @@ hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s) {
       gx = std::max(gx, (nOut + 15) / 16);
     }
     if (gx <= 0) continue;
-    hipLaunchKernelGGL(lstm_tm_bwd_kernel, dim3(gx, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo);
+    if (a.gates == 1) hipLaunchKernelGGL(rnn_tm_bwd_kernel, dim3(gx, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo);
+    else hipLaunchKernelGGL(lstm_tm_bwd_kernel, dim3(gx, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo);
   }
   return hipGetLastError();
 }
