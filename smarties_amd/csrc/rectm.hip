@@ -21,6 +21,12 @@
 //             whose inputs the product completes
 // The windows carry one row more per sample than nnBPTTseq + 1 (RecArgs::K): a truncated episode's next state is step T + 1 of its
 // window like any other (forward only; its deltas are zero).  Weight gradients: the common dW launch over all rows, as before.
+// The LSTM, MGU and plain RNN kernels are built from the same pieces, each written once:
+//   forward   tmActiveMask / tmAnyActive (samples that have the step), tmLoadW + tmColumnProduct (a wavefront's W column x the A tile),
+//             tmStageA (the A tile into LDS), tmStorePartial, tmHandOn (next step's recurrent slot, the layer above's row or Yout)
+//   backward  tmDeltaProduct (a wavefront's part of D W^T), tmJoinPartials, tmFinishTile (whose cell deltas the tile completes, and the
+//             hand-off between the two producers of a tile at the arrival counter -- the protocol and its reasoning stand there)
+// A kernel keeps what is its own: how its wavefronts split columns and reduction, the loads it requests early, its cell.
 #include "rec_dev.h"
 
 namespace hl {
@@ -76,8 +82,190 @@ __global__ __launch_bounds__(256) void lstm_tm_prepare_act_kernel(RecArgs a) {
   }
 }
 
-// forward of layer j at window step k: samples with tmSteps[b] > k.  512 threads: wavefront w = gate (w & 3) x half (w >> 2) of the reduction
+// ---- what the three forward kernels share --------------------------------------------------------------------------------------------
+// 512 threads: eight wavefronts that split a 16-cell tile's gate columns and the reduction over [W_in; W_rec] between them (per kernel)
 constexpr int TM_FNT = 512;
+constexpr int TM_UN = 16;      // rows of a W column a wavefront has in flight (one batch of the forward product)
+constexpr int TM_UG = 8;       // groups of 16 deltas a wavefront has in flight in the backward product
+
+// which of the workgroup's 16 samples have window step k; read back behind the staging barrier (tmAnyActive, the epilogues)
+__device__ __forceinline__ void tmActiveMask(int* sAct, const RecArgs& a, int b0, int k, int tid) {
+  if (tid < 16) sAct[tid] = (b0 + tid < a.B && a.tmSteps[b0 + tid] > k) ? 1 : 0;
+}
+__device__ __forceinline__ bool tmAnyActive(const int* sAct) {
+  bool any = false;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) any = any || sAct[i] != 0;
+  return any;
+}
+// the A tile: rows r = b K + k of 16 samples, Kt floats each, into sA[16][lds] in 16-byte pieces; zeros behind Kt.
+//   REC_ELSEWHERE = false   the row is [input | previous output] of L.A (its pitch is a multiple of 16 floats): 16-byte loads
+//   REC_ELSEWHERE = true    the recurrent part comes from rec[r ldRec + .] (MGU phase 1: A2; no alignment of its pitch is asked
+//                           for by tmLayersOk): element by element
+template <bool REC_ELSEWHERE>
+__device__ __forceinline__ void tmStageA(float* sA, int lds, const RecArgs& a, const RecLayer& L, const float* rec, int ldRec, int Kt, int Kt4, int b0, int k, int tid) {
+  const int q4 = Kt4 >> 2;
+  for (int i = tid; i < 16 * q4; i += TM_FNT) {
+    const int row = i / q4, q = i - row * q4, b = min(b0 + row, a.B - 1);
+    f32x4 v;
+    if constexpr (REC_ELSEWHERE) {
+      const long long r = (long long)b * a.K + k;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int x = 4 * q + e;
+        v[e] = x < L.nIn ? L.A[r * L.ldA + x] : (x < Kt ? rec[r * ldRec + (x - L.nIn)] : 0.f);
+      }
+    } else {
+      v = *reinterpret_cast<const f32x4*>(L.A + ((size_t)b * a.K + k) * L.ldA + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) if (4 * q + e >= Kt) v[e] = 0.f;
+    }
+    *reinterpret_cast<f32x4*>(sA + row * lds + 4 * q) = v;
+  }
+}
+// a batch of a wavefront's W column Wg (row pitch `pitch`): rows 4 (s + u) + lc (rows behind Kt: a valid row, the A element is zero).
+// The kernels request the first batch in front of the A tile.
+__device__ __forceinline__ void tmLoadW(float (&bv)[TM_UN], const float* Wg, int pitch, int s, int lc, int Kt) {
+#pragma unroll
+  for (int u = 0; u < TM_UN; ++u) { const int i = min(4 * (s + u) + lc, Kt - 1); bv[u] = Wg[(size_t)i * pitch]; }
+}
+// sum over the wavefront's slices [sBeg, sEnd) of the reduction (four rows each) of A tile x W column, on v_mfma_f32_16x16x4_f32; bv = the
+// first batch; ar = sA + li lds + lc.  Element q of the result = sample 4 lc + q, cell li.  PREFETCH: the next batch flies during this
+// one's MFMAs (LSTM, RNN); else it is requested in front of its own (MGU: an eighth of the reduction per wavefront, seldom a second batch)
+template <bool PREFETCH>
+__device__ __forceinline__ f32x4 tmColumnProduct(float (&bv)[TM_UN], const float* Wg, int pitch, const float* ar, int sBeg, int sEnd, int lc, int Kt) {
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  for (int s0 = sBeg; s0 < sEnd; s0 += TM_UN) {
+    float bn[TM_UN];
+    const bool more = PREFETCH && s0 + TM_UN < sEnd;
+    if (more) tmLoadW(bn, Wg, pitch, s0 + TM_UN, lc, Kt);
+    if (!PREFETCH && s0 > sBeg) tmLoadW(bv, Wg, pitch, s0, lc, Kt);
+#pragma unroll
+    for (int u = 0; u < TM_UN; ++u) {
+      const float av = s0 + u < sEnd ? ar[4 * (s0 + u)] : 0.f;
+      if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc1, 0, 0, 0);
+      else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc0, 0, 0, 0);
+    }
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < TM_UN; ++u) bv[u] = bn[u];
+    }
+  }
+  return acc0 + acc1;
+}
+// the wavefront's partial tile into sG[8][16][17]
+__device__ __forceinline__ void tmStorePartial(float* sG, const f32x4& p, int wave, int lc, int li) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sG[(wave * 16 + 4 * lc + q) * 17 + li] = p[q];
+}
+// where the output of (layer j, step k, sample b, cell c) goes, r = b K + k: the next step's recurrent slot; with the parametric residual
+// (ParametricResidualLayer::forward, Layers.h:347-361; the layer's input from the staged row sArow) the layer above's input row of the
+// same step, or Yout at the sample's last step T / at the next state's step T + 1.  wr, br = the residual's parameters of cell c (zero without)
+__device__ __forceinline__ void tmHandOn(const RecArgs& a, const RecLayer& L, int j, int k, int b, int c, long long r, float out, const float* sArow, float wr, float br, int steps, int T) {
+  float blk = out;
+  if (L.hasRes && c < L.resW) blk += sArow[c] * wr + br;
+  if (k + 1 < steps) L.A[(r + 1) * L.ldA + L.nIn + c] = out;          // the next step's recurrent input
+  if (j + 1 < a.nL) { const RecLayer& U = a.L[j + 1]; U.A[r * U.ldA + c] = blk; }      // the layer above, same step
+  else {
+    if (k == T) a.Yout[(size_t)b * a.ldY + c] = blk;
+    else if (k == T + 1) a.Yout[(size_t)a.tmNext[b] * a.ldY + c] = blk;
+  }
+}
+
+// ---- what the three backward kernels share -------------------------------------------------------------------------------------------
+// A launch is one ANTI-DIAGONAL of the (layer, step) grid -- blockIdx.z picks (j0 + z, k0 - z) -- and a workgroup forms, for 16 samples and 16
+// rows i of [W_in; W_rec], e[b][i] = sum_o D[r][o] W[i][o] (Layer::backward, Layers.h:123-188); the deltas of a step a sample does not have
+// are zero rows (lstm_tm_prepare_kernel).  Each of the four wavefronts reduces over its own range of n deltas (tmDeltaProduct), the four
+// partial tiles meet in LDS (tmJoinPartials), and the epilogue forms the cell deltas whose inputs the product completes (tmFinishTile).
+
+// this wavefront's part of D W^T: dq = its n deltas of sample row li, wq = the same columns of W row li (n a multiple of 4).  Both operands
+// come straight from memory: whole groups of 16 as 16-byte loads, the reduction index permuted inside a group (lane group lc takes
+// o = 16 G + 4 lc + e in sub-step e), TM_UG groups in flight; the rest four per lane group (element 16 nG + 4 e + lc in sub-step e).
+// KEEP: the W operand times `keep` (MGU phase 1: recurrent rows take the forget deltas only)
+template <bool KEEP>
+__device__ __forceinline__ f32x4 tmDeltaProduct(const float* wq, const float* dq, int n, int lc, float keep = 1.f) {
+  auto w = [&](float x) { if constexpr (KEEP) return x * keep; else return x; };
+  const f32x4* wr = reinterpret_cast<const f32x4*>(wq) + lc;
+  const f32x4* dr = reinterpret_cast<const f32x4*>(dq) + lc;
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  const int nG = n >> 4, rem = n & 15;
+  for (int g0 = 0; g0 < nG; g0 += TM_UG) {
+    f32x4 wv[TM_UG], dv[TM_UG];
+#pragma unroll
+    for (int u = 0; u < TM_UG; ++u) { const int G = min(g0 + u, nG - 1); wv[u] = wr[4 * G]; dv[u] = dr[4 * G]; }
+#pragma unroll
+    for (int u = 0; u < TM_UG; ++u) {
+      if (g0 + u < nG) {      // A = deltas (rows = samples), B = W rows (columns = rows i of W)
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][0], w(wv[u][0]), acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][1], w(wv[u][1]), acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][2], w(wv[u][2]), acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][3], w(wv[u][3]), acc1, 0, 0, 0);
+      }
+    }
+  }
+  for (int e = 0; 4 * e < rem; ++e) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dq[16 * nG + 4 * e + lc], w(wq[16 * nG + 4 * e + lc]), acc0, 0, 0, 0);
+  return acc0 + acc1;
+}
+// the four wavefronts' partial tiles through sR[4][256]: thread tid's element (sample row tid >> 4, W row tid & 15)
+__device__ __forceinline__ float tmJoinPartials(float* sR, const f32x4& p, int wave, int lc, int li, int tid) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sR[wave * 256 + (4 * lc + q) * 16 + li] = p[q];
+  __syncthreads();
+  return (sR[tid] + sR[256 + tid]) + (sR[512 + tid] + sR[768 + tid]);
+}
+// The end of a backward workgroup of (layer j, step k) whose 16 rows of W start at i0.  Its tile of errors -- thread = (sample b with last
+// step T, row i = i0 + tid % 16) -- is one of the two inputs of the deltas of a tile of cells (J, Kc), the same for the whole workgroup
+// (layer inputs and cells come in multiples of 16):
+//   rows i <  nIn (j > 0)   eBelow + residual path = the error of the block below at THIS step: the error from above of the deltas of (j - 1, k)
+//   rows i >= nIn           eRec = the error handed to step k - 1: the last layer forms its deltas of (j, k - 1) at once (its error from above
+//                           is the head's gradient at the sample's last step, else zero); for the other layers it is the second input of
+//                           the deltas of (j, k - 1), whose first one comes from the launch (j + 1, k - 1) -- a member of the SAME diagonal.
+// Delta(a, J, Kc, b, c, T, eTop, eRec) forms and stores the deltas of one cell.  Deltas formed on diagonal e are the operands of diagonal
+// e - 1: 18 launches instead of 34 at two layers and 17 steps.  Launch (nL - 1, nBPTT + 1) -- a step no sample has -- starts the chain with
+// the last layer's deltas of step nBPTT.
+template <void (*Delta)(const RecArgs&, int, int, int, int, int, float, float)>
+__device__ __forceinline__ void tmFinishTile(const RecArgs& a, int j, int k, int i0, int b, int i, int T, float eBelow, float eRec, unsigned& sArr) {
+  const RecLayer& L = a.L[j];
+  const int nIn = L.nIn;
+  const bool below = i0 < nIn;
+  const int J = below ? j - 1 : j, Kc = below ? k : k - 1, c = below ? i : i - nIn;
+  const int nCJ = a.L[J].nC;
+  const bool live = b < a.B && c < nCJ && T >= Kc;      // (this sample has step Kc: its rows of deltas exist)
+  float v = below ? eBelow : eRec;
+  if (below && L.hasRes && i < L.resW && b < a.B) v += L.Rd[((size_t)b * a.K + k) * L.ldR + i] * a.W[L.indWr + i];
+  if (!below && j == a.nL - 1) {      // the last layer's deltas of the previous step: nothing else feeds them
+    if (live) Delta(a, j, Kc, b, c, T, Kc == T ? a.Dres[(size_t)b * a.ldD + c] : 0.f, v);
+    return;
+  }
+  // the other producer of these deltas -- (j - 1, k + 1) for a tile below, (j + 1, k - 1) else -- is a member of this diagonal, unless it
+  // would lie behind the windows: no launch of the layer below there, these deltas have one producer
+  if (below && k + 1 > a.nBPTT) {
+    if (live) Delta(a, J, Kc, b, c, T, v, 0.f);
+    return;
+  }
+  // The two producers meet at an arrival counter per (layer, 16 cells, 16 samples): the first leaves its values, the second reads them
+  // and forms the deltas (the pattern of dw_wide_kernel's row quarters); the result does not depend on who arrives first.
+  // Hand-off without a release / acquire pair, on purpose: the ONLY data that changes hands are these values, written by agent-scope
+  // atomic stores -- which go to the coherence point themselves -- and acknowledged (vmcnt(0)) BEFORE the arrival is counted; the second
+  // producer reads them back with agent-scope atomic loads.  A release here would write back this XCD's whole L2: ~15 us.  First and
+  // second are told apart by the counter's parity: every counter gets exactly two arrivals per step, and lstm_tm_prepare_kernel zeroes
+  // them in front of every window, so a launch that never completed cannot leave a parity behind.
+  float* mine = below ? a.tmET[J] : a.tmER[J];
+  const float* other = below ? a.tmER[J] : a.tmET[J];
+  const size_t at = (size_t)min(b, a.B - 1) * nCJ + min(c, nCJ - 1);
+  if (b < a.B && c < nCJ) __hip_atomic_store(mine + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __builtin_amdgcn_s_waitcnt(0);          // vmcnt(0): this tile's values are at the coherence point
+  __syncthreads();
+  const int cTile = (below ? i0 : i0 - nIn) >> 4;
+  if (threadIdx.x == 0) sArr = __hip_atomic_fetch_add(a.tmCtr + a.tmCtrOff[J] + cTile * (int)gridDim.y + (int)blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if ((sArr & 1u) == 0u) return;          // the first of the two
+  const float o = __hip_atomic_load(other + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (live) Delta(a, J, Kc, b, c, T, below ? v : o, below ? o : v);
+}
+
+// ---- LSTM layers (Network/Layers/Layer_LSTM.h:77-166) -------------------------------------------------------------------------------
+// forward of layer j at window step k: samples with tmSteps[b] > k.  Wavefront w = gate (w & 3) x half (w >> 2) of the reduction.
 // One launch = one DIAGONAL of the (layer, step) grid: blockIdx.z picks (j0 + z, k0 - z) -- layer j at step k needs layer j - 1 at step k
 // and its own step k - 1, both on the diagonal in front, so a window of K steps through nL layers is K + nL - 1 launches instead of K nL
 // (what they write into a shared row -- the block output of the layer below, the recurrent input of the step before -- are different columns)
@@ -99,15 +287,13 @@ __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, 
   __shared__ int sAct[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int b0 = blockIdx.y * 16, c0 = blockIdx.x * 16;
-  if (tid < 16) sAct[tid] = (b0 + tid < a.B && a.tmSteps[b0 + tid] > k) ? 1 : 0;
+  tmActiveMask(sAct, a, b0, k, tid);
   // this wavefront's W column (gate, cell li) over its half of the rows [W_in; W_rec]: the first batch is requested in front of the A tile
   const int gate = wave & 3, half = wave >> 2;
   const int nS = Kt4 >> 2, nSh = (nS + 1) >> 1, sBeg = half * nSh, sEnd = min(nS, sBeg + nSh);
   const float* Wg = a.W + L.indW + (size_t)gate * nC + c0 + li;
-  constexpr int UN = 16;
-  float bv[UN];
-#pragma unroll
-  for (int u = 0; u < UN; ++u) { const int i = min(4 * (sBeg + u) + lc, Kt - 1); bv[u] = Wg[(size_t)i * NO]; }      // (rows behind Kt: a valid row, the A element is zero)
+  float bv[TM_UN];
+  tmLoadW(bv, Wg, NO, sBeg, lc, Kt);
   // what the cell's epilogue reads from memory -- the four biases, the state of the step before, the window's length: requested here, used
   // behind the products (a load issued there is a round trip of its own at the end of every launch of the chain)
   const int eRow = (tid >> 4) & 15, eC = c0 + (tid & 15), eB = min(b0 + eRow, a.B - 1);
@@ -118,48 +304,13 @@ __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, 
   const int stepsE = a.tmSteps[eB], TE = a.tmT[eB];
   float wrE = 0.f, brE = 0.f;
   if (L.hasRes && eC < L.resW) { wrE = a.W[L.indWr + eC]; brE = a.W[L.indBr + eC]; }
-  // the A tile: rows r = b K + k, Kt floats each, 16-byte pieces (the row pitch is a multiple of 16 floats); zeros behind Kt
-  {
-    const int q4 = Kt4 >> 2;
-    for (int i = tid; i < 16 * q4; i += TM_FNT) {
-      const int row = i / q4, q = i - row * q4, b = min(b0 + row, a.B - 1);
-      f32x4 v = *reinterpret_cast<const f32x4*>(L.A + ((size_t)b * a.K + k) * L.ldA + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (4 * q + e >= Kt) v[e] = 0.f;
-      *reinterpret_cast<f32x4*>(sA + row * lds + 4 * q) = v;
-    }
-  }
+  tmStageA<false>(sA, lds, a, L, nullptr, 0, Kt, Kt4, b0, k, tid);
   TMSTMP(1);
   __syncthreads();
   TMSTMP(2);
-  bool any = false;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) any = any || sAct[i] != 0;
-  if (!any) return;
-  // acc[q] = sample 4 lc + q, cell li
-  const float* ar = sA + li * lds + lc;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  for (int s0 = sBeg; s0 < sEnd; s0 += UN) {
-    float bn[UN];
-    const bool more = s0 + UN < sEnd;
-    if (more) {
-#pragma unroll
-      for (int u = 0; u < UN; ++u) { const int i = min(4 * (s0 + UN + u) + lc, Kt - 1); bn[u] = Wg[(size_t)i * NO]; }      // the next batch flies during this one's MFMAs
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const float av = s0 + u < sEnd ? ar[4 * (s0 + u)] : 0.f;
-      if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc1, 0, 0, 0);
-      else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc0, 0, 0, 0);
-    }
-    if (more) {
-#pragma unroll
-      for (int u = 0; u < UN; ++u) bv[u] = bn[u];
-    }
-  }
+  if (!tmAnyActive(sAct)) return;
+  tmStorePartial(sG, tmColumnProduct<true>(bv, Wg, NO, sA + li * lds + lc, sBeg, sEnd, lc, Kt), wave, lc, li);
   TMSTMP(3);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sG[(wave * 16 + 4 * lc + q) * 17 + li] = acc0[q] + acc1[q];
   __syncthreads();
   TMSTMP(4);
   // the cell of (sample row, cell c): Layer_LSTM.h:77-125
@@ -172,24 +323,14 @@ __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, 
   const float ig = recSigm(gsum(1) + bi1);
   const float fg = recSigm(gsum(2) + bi2);
   const float og = recSigm(gsum(3) + bi3);
-  const float prevSt = prevStE;
-  const float st = ci * ig + prevSt * fg;
+  const float st = ci * ig + prevStE * fg;
   const float co = actEval(HL_FUNC_TANH, st);
   const float out = og * co;
   L.X[r * NO + c] = ci; L.X[r * NO + nC + c] = ig; L.X[r * NO + 2 * nC + c] = fg; L.X[r * NO + 3 * nC + c] = og;
   L.Y[r * NO + c] = out; L.Y[r * NO + nC + c] = st; L.Y[r * NO + 2 * nC + c] = co;
-  float blk = out;                                       // ParametricResidualLayer::forward (Layers.h:347-361)
-  if (L.hasRes && c < L.resW) blk += sA[row * lds + c] * wrE + brE;
-  const int steps = stepsE, T = TE;
-  if (k + 1 < steps) L.A[(r + 1) * L.ldA + nIn + c] = out;          // the next step's recurrent input
-  if (j + 1 < a.nL) { const RecLayer& U = a.L[j + 1]; U.A[r * U.ldA + c] = blk; }      // the layer above, same step
-  else {
-    if (k == T) a.Yout[(size_t)b * a.ldY + c] = blk;
-    else if (k == T + 1) a.Yout[(size_t)a.tmNext[b] * a.ldY + c] = blk;
-  }
+  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wrE, brE, stepsE, TE);
   TMSTMP(5);
 }
-
 // the cell's deltas of (layer j, step k, sample b, cell c), Layer_LSTM.h:127-165: eTop = error from the block above (same step), eRec = error
 // handed back by step k + 1 (zero at the sample's last step)
 __device__ __forceinline__ void tmDelta(const RecArgs& a, int j, int k, int b, int c, int T, float eTop, float eRec) {
@@ -209,91 +350,25 @@ __device__ __forceinline__ void tmDelta(const RecArgs& a, int j, int k, int b, i
   L.D[r * NO + 3 * nC + c] = og * (1.f - og) * D * co;
   a.tmSD[j][(size_t)b * nC + c] = sd;
 }
-__device__ __forceinline__ int c0tile(int i0, int nIn, bool below) { return (below ? i0 : i0 - nIn) >> 4; }
-// Layer::backward of layer j at step k (Layers.h:123-188): e[b][i] = sum_o W[i][o] D[r][o] for rows i of [W_in; W_rec], samples with T >= k - 1
-// (the deltas of a step a sample does not have are zero rows: lstm_tm_prepare_kernel).  The epilogues also form the cell deltas whose inputs
-// the products complete, and a launch is one ANTI-DIAGONAL of the (layer, step) grid -- blockIdx.z picks (j0 + z, k0 - z):
-//   tiles i <  nIn (j > 0)   e + residual path = the error of the block below at THIS step: one of the two inputs of the deltas of (j - 1, k)
-//   tiles i >= nIn           the error handed to step k - 1: the last layer forms its deltas of (j, k - 1) at once (its error from above is
-//                            the head's gradient at the sample's last step, else zero); for the other layers it is the second input of the
-//                            deltas of (j, k - 1), whose first one comes from the launch (j + 1, k - 1) -- a member of the SAME diagonal.
-// The two producers of a (layer, 16 cells, 16 samples) tile of deltas meet at an arrival counter: the first leaves its values (agent-scope
-// stores, acknowledged before the arrival), the second reads them and forms the deltas (the pattern of dw_wide_kernel's row quarters).
-// Deltas formed on diagonal e are the operands of diagonal e - 1: 18 launches instead of 34 at two layers and 17 steps.
-// Launch (nL - 1, nBPTT + 1) -- a step no sample has -- starts the chain with the last layer's deltas of step nBPTT.
-// Both operands come straight from memory as 16-byte loads (the reduction index permuted inside groups of 16: lane group lc takes
-// o = 16 G + 4 lc + e in sub-step e); wavefront w reduces over gate w's deltas, the four partial tiles meet in LDS.
+// backward of layer j at step k, samples with T >= k - 1: wavefront w reduces over gate w's nC deltas
 __global__ __launch_bounds__(256) void lstm_tm_bwd_kernel(RecArgs a, int j0, int k0) {
   __shared__ float sR[4 * 256];
   __shared__ int sT[16];
   __shared__ unsigned sArr;
   const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;
-  const int top = a.nL - 1;
-  if (k == a.nBPTT + 1 && j != top) return;      // (only the last layer has a launch at the step behind the windows)
+  if (k == a.nBPTT + 1 && j != a.nL - 1) return;      // (only the last layer has a launch at the step behind the windows)
   const RecLayer& L = a.L[j];
   const int nIn = L.nIn, nC = L.nC, NO = 4 * nC;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int row0 = j > 0 ? 0 : nIn;      // (no error below the first layer)
-  const int nRowW = nIn + nC;
   const int b0 = blockIdx.y * 16, i0 = row0 + blockIdx.x * 16;
   if (i0 >= nIn + (k > 0 ? nC : 0)) return;      // (the grid is as wide as the diagonal's widest member; no error to a step in front of the first)
   if (tid < 16) sT[tid] = b0 + tid < a.B ? a.tmT[b0 + tid] : -2;
-  const int iw = min(i0 + li, nRowW - 1), bl = min(b0 + li, a.B - 1);
-  const f32x4* wr = reinterpret_cast<const f32x4*>(a.W + L.indW + (size_t)iw * NO + wave * nC) + lc;
-  const f32x4* dr = reinterpret_cast<const f32x4*>(L.D + ((size_t)bl * a.K + k) * NO + wave * nC) + lc;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const int nG = nC >> 4;
-  constexpr int UG = 8;
-  for (int g0 = 0; g0 < nG; g0 += UG) {
-    f32x4 wv[UG], dv[UG];
-#pragma unroll
-    for (int u = 0; u < UG; ++u) { const int G = min(g0 + u, nG - 1); wv[u] = wr[4 * G]; dv[u] = dr[4 * G]; }
-#pragma unroll
-    for (int u = 0; u < UG; ++u) {
-      if (g0 + u < nG) {      // A = deltas (rows = samples), B = W rows (columns = rows i of W)
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][0], wv[u][0], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][1], wv[u][1], acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][2], wv[u][2], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][3], wv[u][3], acc1, 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sR[wave * 256 + (4 * lc + q) * 16 + li] = acc0[q] + acc1[q];
-  __syncthreads();
-  const int row = tid >> 4, ii = tid & 15, b = b0 + row, i = i0 + ii, T = sT[row];
-  const float e = (sR[tid] + sR[256 + tid]) + (sR[512 + tid] + sR[768 + tid]);      // (zero for a sample without step k)
-  // the tile's cells: (J, Kc), the same for the whole workgroup (layer inputs and cells come in multiples of 16)
-  const bool below = i0 < nIn;
-  const int J = below ? j - 1 : j, Kc = below ? k : k - 1, c = below ? i : i - nIn;
-  const int nCJ = a.L[J].nC;
-  const bool live = b < a.B && c < nCJ && T >= Kc;      // (this sample has step Kc: its rows of deltas exist)
-  float v = e;
-  if (below && L.hasRes && i < L.resW && b < a.B) v += L.Rd[((size_t)b * a.K + k) * L.ldR + i] * a.W[L.indWr + i];
-  if (!below && j == top) {      // the last layer's deltas of the previous step: nothing else feeds them
-    if (live) tmDelta(a, j, Kc, b, c, T, Kc == T ? a.Dres[(size_t)b * a.ldD + c] : 0.f, v);
-    return;
-  }
-  // the other producer of these deltas -- (j - 1, k + 1) for a tile below, (j + 1, k - 1) else -- is a member of this diagonal, unless it
-  // would lie behind the windows
-  if (below && k + 1 > a.nBPTT) {
-    if (live) tmDelta(a, J, Kc, b, c, T, v, 0.f);
-    return;
-  }
-  float* mine = below ? a.tmET[J] : a.tmER[J];
-  const float* other = below ? a.tmER[J] : a.tmET[J];
-  const size_t at = (size_t)min(b, a.B - 1) * nCJ + min(c, nCJ - 1);
-  // (hand-off without a release / acquire pair, on purpose: the ONLY data that changes hands are these values, written by agent-scope
-  //  atomic stores -- which go to the coherence point themselves -- and acknowledged (vmcnt(0)) before the arrival is counted; the
-  //  second producer reads them back with agent-scope atomic loads.  A release here would write back this XCD's whole L2: ~15 us.)
-  if (b < a.B && c < nCJ) __hip_atomic_store(mine + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __builtin_amdgcn_s_waitcnt(0);          // vmcnt(0): this tile's values are at the coherence point
-  __syncthreads();
-  if (tid == 0) sArr = __hip_atomic_fetch_add(a.tmCtr + a.tmCtrOff[J] + (c0tile(i0, nIn, below)) * (int)gridDim.y + (int)blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if ((sArr & 1u) == 0u) return;          // the first of the two
-  const float o = __hip_atomic_load(other + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (live) tmDelta(a, J, Kc, b, c, T, below ? v : o, below ? o : v);
+  const int iw = min(i0 + li, nIn + nC - 1), bl = min(b0 + li, a.B - 1);
+  __builtin_assume((nC & 15) == 0);      // (tmLayersOk: a gate's deltas are whole groups of 16, tmDeltaProduct's rest is empty)
+  const f32x4 p = tmDeltaProduct<false>(a.W + L.indW + (size_t)iw * NO + wave * nC, L.D + ((size_t)bl * a.K + k) * NO + wave * nC, nC, lc);
+  const float e = tmJoinPartials(sR, p, wave, lc, li, tid);      // (zero for a sample without step k)
+  tmFinishTile<tmDelta>(a, j, k, i0, b0 + (tid >> 4), i0 + (tid & 15), sT[tid >> 4], e, e, sArr);
 }
 
 // ---- MGU layers (Network/Layers/Layer_GRU.h:64-231), the same arrangement ------------------------------------------------------------
@@ -317,49 +392,17 @@ __global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, i
   __shared__ int sAct[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int b0 = blockIdx.y * 16, c0 = blockIdx.x * 16;
-  if (tid < 16) sAct[tid] = (b0 + tid < a.B && a.tmSteps[b0 + tid] > k) ? 1 : 0;
+  tmActiveMask(sAct, a, b0, k, tid);
   // wavefront w: an eighth of the rows [W_in; W_rec] of column (phase, cell li)
   const int nS = Kt4 >> 2, nSe = (nS + 7) >> 3, sBeg = wave * nSe, sEnd = min(nS, sBeg + nSe);
   const float* Wg = a.W + L.indW + (size_t)phase * nC + c0 + li;
-  constexpr int UN = 16;
-  float bv[UN];
-#pragma unroll
-  for (int u = 0; u < UN; ++u) { const int i = min(4 * (sBeg + u) + lc, Kt - 1); bv[u] = Wg[(size_t)i * NO]; }
-  {      // A tile: [in | prevOut] (phase 0) or [in | f * prevOut] (phase 1), zeros behind Kt
-    const int q4 = Kt4 >> 2;
-    for (int i = tid; i < 16 * q4; i += TM_FNT) {
-      const int row = i / q4, q = i - row * q4, b = min(b0 + row, a.B - 1);
-      const long long r = (long long)b * a.K + k;
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int x = 4 * q + e;
-        v[e] = x < nIn ? L.A[r * L.ldA + x] : (x < Kt ? (phase ? L.A2[r * L.ldA2 + (x - nIn)] : L.A[r * L.ldA + x]) : 0.f);
-      }
-      *reinterpret_cast<f32x4*>(sA + row * lds + 4 * q) = v;
-    }
-  }
+  float bv[TM_UN];
+  tmLoadW(bv, Wg, NO, sBeg, lc, Kt);
+  // A tile: [in | prevOut] (phase 0) or [in | f * prevOut] (phase 1)
+  tmStageA<true>(sA, lds, a, L, phase ? L.A2 : L.A + nIn, phase ? L.ldA2 : L.ldA, Kt, Kt4, b0, k, tid);
   __syncthreads();
-  bool any = false;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) any = any || sAct[i] != 0;
-  if (!any) return;
-  const float* ar = sA + li * lds + lc;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  for (int s0 = sBeg; s0 < sEnd; s0 += UN) {
-    if (s0 > sBeg) {
-#pragma unroll
-      for (int u = 0; u < UN; ++u) { const int i = min(4 * (s0 + u) + lc, Kt - 1); bv[u] = Wg[(size_t)i * NO]; }
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const float av = s0 + u < sEnd ? ar[4 * (s0 + u)] : 0.f;
-      if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc1, 0, 0, 0);
-      else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc0, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sG[(wave * 16 + 4 * lc + q) * 17 + li] = acc0[q] + acc1[q];
+  if (!tmAnyActive(sAct)) return;
+  tmStorePartial(sG, tmColumnProduct<false>(bv, Wg, NO, sA + li * lds + lc, sBeg, sEnd, lc, Kt), wave, lc, li);
   __syncthreads();
   if (tid >= 256) return;
   const int row = tid >> 4, cc = tid & 15, b = b0 + row, c = c0 + cc;
@@ -380,15 +423,9 @@ __global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, i
   const float f = L.X[r * NO + c], prev = L.A[r * L.ldA + nIn + c];
   const float out = k > 0 ? f * st + (1.f - f) * prev : f * st;
   L.Y[r * NO + c] = out;
-  float blk = out;
-  if (L.hasRes && c < L.resW) blk += sA[row * lds + c] * a.W[L.indWr + c] + a.W[L.indBr + c];
-  const int steps = a.tmSteps[b], T = a.tmT[b];
-  if (k + 1 < steps) L.A[(r + 1) * L.ldA + nIn + c] = out;
-  if (j + 1 < a.nL) { const RecLayer& U = a.L[j + 1]; U.A[r * U.ldA + c] = blk; }
-  else {
-    if (k == T) a.Yout[(size_t)b * a.ldY + c] = blk;
-    else if (k == T + 1) a.Yout[(size_t)a.tmNext[b] * a.ldY + c] = blk;
-  }
+  float wr = 0.f, br = 0.f;
+  if (L.hasRes && c < L.resW) { wr = a.W[L.indWr + c]; br = a.W[L.indBr + c]; }
+  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wr, br, a.tmSteps[b], a.tmT[b]);
 }
 // dLdO and the state delta of (layer j, step k, sample b, cell c): eTop = error from the block above, eRec = error handed back by step k + 1
 __device__ __forceinline__ void tmMguOpen(const RecArgs& a, int j, int k, int b, int c, int T, float eTop, float eRec) {
@@ -401,7 +438,7 @@ __device__ __forceinline__ void tmMguOpen(const RecArgs& a, int j, int k, int b,
   a.tmSD[j][(size_t)b * nC + c] = dLdO;
   L.D[r * NO + nC + c] = dLdO * f * (1.f - st * st);
 }
-// (a launch is one anti-diagonal of the (layer, step) grid and one phase, blockIdx.z picks (j0 + z, k0 - z): lstm_tm_bwd_kernel)
+// (a launch is one anti-diagonal of the (layer, step) grid and one phase)
 __global__ __launch_bounds__(256) void mgu_tm_bwd_kernel(RecArgs a, int j0, int k0, int phase) {
   __shared__ float sR[4 * 256];
   __shared__ int sT[16];
@@ -412,117 +449,41 @@ __global__ __launch_bounds__(256) void mgu_tm_bwd_kernel(RecArgs a, int j0, int 
   const int nIn = L.nIn, nC = L.nC, NO = 2 * nC;
   if (phase == 0 ? (int)blockIdx.x * 16 >= nC : (j > 0 ? 0 : nIn) + (int)blockIdx.x * 16 >= nIn + (k > 0 ? nC : 0)) return;      // (the grid is as wide as the diagonal's widest member)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
-  const int b0 = blockIdx.y * 16;
+  const int b0 = blockIdx.y * 16, row = tid >> 4, b = b0 + row;
   if (tid < 16) sT[tid] = b0 + tid < a.B ? a.tmT[b0 + tid] : -2;
   const int bl = min(b0 + li, a.B - 1);
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  constexpr int UG = 8;
+  const float* dRow = L.D + ((size_t)bl * a.K + k) * NO;
   if (phase == 0) {
-    // fp[b][c] = sum_o dS[b][o] W[nIn + c][nC + o]: the four wavefronts split the nC state deltas (k == 0: no recurrent input, fp = 0)
-    const int c0 = blockIdx.x * 16;
-    if (k > 0) {
-      const int q = nC >> 2;      // deltas per wavefront (nC is a multiple of 16)
-      const f32x4* wr = reinterpret_cast<const f32x4*>(a.W + L.indW + (size_t)(nIn + c0 + li) * NO + nC + wave * q) + lc;
-      const f32x4* dr = reinterpret_cast<const f32x4*>(L.D + ((size_t)bl * a.K + k) * NO + nC + wave * q) + lc;
-      const int nG = q >> 4, rem = q & 15;      // whole groups of 16; nC % 64 != 0 leaves a group of `rem` (a multiple of 4)
-      for (int g0 = 0; g0 < nG; g0 += UG) {
-        f32x4 wv[UG], dv[UG];
-#pragma unroll
-        for (int u = 0; u < UG; ++u) { const int G = min(g0 + u, nG - 1); wv[u] = wr[4 * G]; dv[u] = dr[4 * G]; }
-#pragma unroll
-        for (int u = 0; u < UG; ++u) if (g0 + u < nG) {
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][0], wv[u][0], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][1], wv[u][1], acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][2], wv[u][2], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][3], wv[u][3], acc1, 0, 0, 0);
-        }
-      }
-      if (rem) {      // the last `rem` deltas of the wavefront's range, four per lane group: lane group lc takes element 16 nG + 4 e + lc in sub-step e < rem / 4
-        const float* wq = a.W + L.indW + (size_t)(nIn + c0 + li) * NO + nC + wave * q + 16 * nG;
-        const float* dq = L.D + ((size_t)bl * a.K + k) * NO + nC + wave * q + 16 * nG;
-        for (int e = 0; 4 * e < rem; ++e) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dq[4 * e + lc], wq[4 * e + lc], acc0, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sR[wave * 256 + (4 * lc + q) * 16 + li] = acc0[q] + acc1[q];
-    __syncthreads();
-    const int row = tid >> 4, cc = tid & 15, b = b0 + row, c = c0 + cc, T = sT[row];
+    // fp[b][c] = sum_o dS[b][o] W[nIn + c][nC + o]: the four wavefronts a quarter of the nC state deltas each (k == 0: no recurrent input, fp = 0)
+    const int c0 = blockIdx.x * 16, q = nC >> 2;
+    f32x4 p = {0.f, 0.f, 0.f, 0.f};
+    if (k > 0) p = tmDeltaProduct<false>(a.W + L.indW + (size_t)(nIn + c0 + li) * NO + nC + wave * q, dRow + nC + wave * q, q, lc);
+    const float sum = tmJoinPartials(sR, p, wave, lc, li, tid);
+    const int c = c0 + (tid & 15), T = sT[row];
     if (T < k) return;
-    const float fp = k > 0 ? (sR[tid] + sR[256 + tid]) + (sR[512 + tid] + sR[768 + tid]) : 0.f;
+    const float fp = k > 0 ? sum : 0.f;
     const long long r = (long long)b * a.K + k;
-    const float f = L.X[r * NO + c], st = L.X[r * NO + nC + c], p = k > 0 ? L.Y[(r - 1) * NO + c] : 0.f;
+    const float f = L.X[r * NO + c], st = L.X[r * NO + nC + c], pO = k > 0 ? L.Y[(r - 1) * NO + c] : 0.f;
     const float dLdO = a.tmSD[j][(size_t)b * nC + c];
     a.tmFP[j][(size_t)b * nC + c] = fp;
-    L.D[r * NO + c] = ((st - p) * dLdO + fp * p) * f * (1.f - f);
+    L.D[r * NO + c] = ((st - pO) * dLdO + fp * pO) * f * (1.f - f);
     return;
   }
   // phase 1: rows i of [W_in; W_rec]: i < nIn reduce over [dF | dS] (wavefronts 0, 1 the forget half, 2, 3 the state half), i >= nIn over dF only
-  const int row0 = j > 0 ? 0 : nIn, i0 = row0 + blockIdx.x * 16, nRowW = nIn + nC;
-  const int iw = min(i0 + li, nRowW - 1);
+  const int i0 = (j > 0 ? 0 : nIn) + blockIdx.x * 16, iw = min(i0 + li, nIn + nC - 1);
   const int h = nC >> 1;                                      // deltas per wavefront: half of a gate's
-  const bool stateHalf = wave >= 2;
-  const f32x4* wr = reinterpret_cast<const f32x4*>(a.W + L.indW + (size_t)iw * NO + wave * h) + lc;
-  const f32x4* dr = reinterpret_cast<const f32x4*>(L.D + ((size_t)bl * a.K + k) * NO + wave * h) + lc;
-  const float keep = (stateHalf && i0 + li >= nIn) ? 0.f : 1.f;      // (recurrent rows take the forget deltas only)
-  {
-    const int nG = h >> 4, rem = h & 15;
-    for (int g0 = 0; g0 < nG; g0 += UG) {
-      f32x4 wv[UG], dv[UG];
-#pragma unroll
-      for (int u = 0; u < UG; ++u) { const int G = min(g0 + u, nG - 1); wv[u] = wr[4 * G]; dv[u] = dr[4 * G]; }
-#pragma unroll
-      for (int u = 0; u < UG; ++u) if (g0 + u < nG) {
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][0], wv[u][0] * keep, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][1], wv[u][1] * keep, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][2], wv[u][2] * keep, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][3], wv[u][3] * keep, acc1, 0, 0, 0);
-      }
-    }
-    if (rem) {
-      const float* wq = a.W + L.indW + (size_t)iw * NO + wave * h + 16 * nG;
-      const float* dq = L.D + ((size_t)bl * a.K + k) * NO + wave * h + 16 * nG;
-      for (int e = 0; 4 * e < rem; ++e) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dq[4 * e + lc], wq[4 * e + lc] * keep, acc0, 0, 0, 0);
-    }
+  const float keep = (wave >= 2 && i0 + li >= nIn) ? 0.f : 1.f;      // (recurrent rows take the forget deltas only)
+  const f32x4 p = tmDeltaProduct<true>(a.W + L.indW + (size_t)iw * NO + wave * h, dRow + wave * h, h, lc, keep);
+  const float e = tmJoinPartials(sR, p, wave, lc, li, tid);      // (zero for a sample without step k)
+  const int i = i0 + (tid & 15), T = sT[row];
+  float eRec = 0.f;      // the error handed to step k - 1 by a recurrent tile
+  if (i0 >= nIn && b < a.B && i - nIn < nC && T >= k) {
+    const long long r = (long long)b * a.K + k;
+    const int c = i - nIn;
+    const float f = L.X[r * NO + c];
+    eRec = (1.f - f) * a.tmSD[j][(size_t)b * nC + c] + f * a.tmFP[j][(size_t)b * nC + c] + e;
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sR[wave * 256 + (4 * lc + q) * 16 + li] = acc0[q] + acc1[q];
-  __syncthreads();
-  const int row = tid >> 4, ii = tid & 15, b = b0 + row, i = i0 + ii, T = sT[row];
-  const float e = (sR[tid] + sR[256 + tid]) + (sR[512 + tid] + sR[768 + tid]);      // (zero for a sample without step k)
-  // the tile's cells (J, Kc) and their two producers: as in lstm_tm_bwd_kernel
-  const bool below = i0 < nIn;
-  const int J = below ? j - 1 : j, Kc = below ? k : k - 1, c = below ? i : i - nIn;
-  const int nCJ = a.L[J].nC;
-  const bool live = b < a.B && c < nCJ && T >= Kc;
-  float v = e;
-  if (below) { if (L.hasRes && i < L.resW && b < a.B) v += L.Rd[((size_t)b * a.K + k) * L.ldR + i] * a.W[L.indWr + i]; }
-  else {
-    v = 0.f;
-    if (b < a.B && c < nC && T >= k) {
-      const long long r = (long long)b * a.K + k;
-      const float f = L.X[r * NO + c];
-      v = (1.f - f) * a.tmSD[j][(size_t)b * nC + c] + f * a.tmFP[j][(size_t)b * nC + c] + e;
-    }
-  }
-  if (!below && j == top) {
-    if (live) tmMguOpen(a, j, Kc, b, c, T, Kc == T ? a.Dres[(size_t)b * a.ldD + c] : 0.f, v);
-    return;
-  }
-  if (below && k + 1 > a.nBPTT) {      // (no launch of the layer below behind the windows: these deltas have one producer)
-    if (live) tmMguOpen(a, J, Kc, b, c, T, v, 0.f);
-    return;
-  }
-  float* mine = below ? a.tmET[J] : a.tmER[J];
-  const float* other = below ? a.tmER[J] : a.tmET[J];
-  const size_t at = (size_t)min(b, a.B - 1) * nCJ + min(c, nCJ - 1);
-  if (b < a.B && c < nCJ) __hip_atomic_store(mine + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (tid == 0) sArr = __hip_atomic_fetch_add(a.tmCtr + a.tmCtrOff[J] + c0tile(i0, nIn, below) * (int)gridDim.y + (int)blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if ((sArr & 1u) == 0u) return;          // the first of the two
-  const float o = __hip_atomic_load(other + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (live) tmMguOpen(a, J, Kc, b, c, T, below ? v : o, below ? o : v);
+  tmFinishTile<tmMguOpen>(a, j, k, i0, b, i, T, e, eRec, sArr);
 }
 
 // ---- plain RNN layers (nnType "RNN": BaseLayer with bRecurrent, Network/Layers/Layer_Base.h:64-113), the same arrangement ----------
@@ -552,15 +513,13 @@ __global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, i
   __shared__ int sAct[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int b0 = blockIdx.y * 16, cBase = blockIdx.x * 16 * RNN_TM_TILES;
-  if (tid < 16) sAct[tid] = (b0 + tid < a.B && a.tmSteps[b0 + tid] > k) ? 1 : 0;
+  tmActiveMask(sAct, a, b0, k, tid);
   // this wavefront's W column (tile, cell li) over its quarter of the rows [W_in; W_rec]: the first batch is requested in front of the A tile
   const int tile = wave & 1, quarter = wave >> 1;
   const int nS = Kt4 >> 2, nSq = (nS + 3) >> 2, sBeg = quarter * nSq, sEnd = min(nS, sBeg + nSq);
   const float* Wg = a.W + L.indW + min(cBase + 16 * tile, nC - 16) + li;      // (W's row pitch is nC: a multiple of 16)
-  constexpr int UN = 16;
-  float bv[UN];
-#pragma unroll
-  for (int u = 0; u < UN; ++u) { const int i = min(4 * (sBeg + u) + lc, Kt - 1); bv[u] = Wg[(size_t)i * nC]; }      // (rows behind Kt: a valid row, the A element is zero)
+  float bv[TM_UN];
+  tmLoadW(bv, Wg, nC, sBeg, lc, Kt);
   // what the epilogue reads from memory: requested here, used behind the products (lstm_tm_fwd_kernel)
   const int eTile = tid >> 8, eRow = (tid >> 4) & 15, eC = cBase + 16 * eTile + (tid & 15), eB = min(b0 + eRow, a.B - 1);
   const bool eOk = eC < nC;
@@ -568,44 +527,10 @@ __global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, i
   const int stepsE = a.tmSteps[eB], TE = a.tmT[eB];
   float wrE = 0.f, brE = 0.f;
   if (L.hasRes && eC < L.resW) { wrE = a.W[L.indWr + eC]; brE = a.W[L.indBr + eC]; }
-  {      // the A tile: rows r = b K + k, Kt floats each, 16-byte pieces; zeros behind Kt
-    const int q4 = Kt4 >> 2;
-    for (int i = tid; i < 16 * q4; i += TM_FNT) {
-      const int row = i / q4, q = i - row * q4, b = min(b0 + row, a.B - 1);
-      f32x4 v = *reinterpret_cast<const f32x4*>(L.A + ((size_t)b * a.K + k) * L.ldA + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (4 * q + e >= Kt) v[e] = 0.f;
-      *reinterpret_cast<f32x4*>(sA + row * lds + 4 * q) = v;
-    }
-  }
+  tmStageA<false>(sA, lds, a, L, nullptr, 0, Kt, Kt4, b0, k, tid);
   __syncthreads();
-  bool any = false;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) any = any || sAct[i] != 0;
-  if (!any) return;
-  // acc[q] = sample 4 lc + q, cell li
-  const float* ar = sA + li * lds + lc;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  for (int s0 = sBeg; s0 < sEnd; s0 += UN) {
-    float bn[UN];
-    const bool more = s0 + UN < sEnd;
-    if (more) {
-#pragma unroll
-      for (int u = 0; u < UN; ++u) { const int i = min(4 * (s0 + UN + u) + lc, Kt - 1); bn[u] = Wg[(size_t)i * nC]; }      // the next batch flies during this one's MFMAs
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const float av = s0 + u < sEnd ? ar[4 * (s0 + u)] : 0.f;
-      if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc1, 0, 0, 0);
-      else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], acc0, 0, 0, 0);
-    }
-    if (more) {
-#pragma unroll
-      for (int u = 0; u < UN; ++u) bv[u] = bn[u];
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sG[(wave * 16 + 4 * lc + q) * 17 + li] = acc0[q] + acc1[q];
+  if (!tmAnyActive(sAct)) return;
+  tmStorePartial(sG, tmColumnProduct<true>(bv, Wg, nC, sA + li * lds + lc, sBeg, sEnd, lc, Kt), wave, lc, li);
   __syncthreads();
   // BaseLayer::forward of (sample row, cell c): thread = (tile, row, cell)
   const int row = eRow, cc = tid & 15, b = b0 + row, c = eC;
@@ -615,15 +540,7 @@ __global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, i
   const float x = biE + ((part(0) + part(1)) + (part(2) + part(3)));
   const float out = actEval(a.func, x);
   L.X[r * nC + c] = x; L.Y[r * nC + c] = out;
-  float blk = out;                                       // ParametricResidualLayer::forward (Layers.h:347-361)
-  if (L.hasRes && c < L.resW) blk += sA[row * lds + c] * wrE + brE;
-  const int steps = stepsE, T = TE;
-  if (k + 1 < steps) L.A[(r + 1) * L.ldA + nIn + c] = out;          // the next step's recurrent input
-  if (j + 1 < a.nL) { const RecLayer& U = a.L[j + 1]; U.A[r * U.ldA + c] = blk; }      // the layer above, same step
-  else {
-    if (k == T) a.Yout[(size_t)b * a.ldY + c] = blk;
-    else if (k == T + 1) a.Yout[(size_t)a.tmNext[b] * a.ldY + c] = blk;
-  }
+  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wrE, brE, stepsE, TE);
 }
 // the delta of (layer j, step k, sample b, cell c), BaseLayer::backward (Layer_Base.h:97-113): eTop = error from the block above (same step),
 // eRec = error handed back by step k + 1 (zero at the sample's last step) -- as rnn_backward_kernel forms it
@@ -635,173 +552,106 @@ __device__ __forceinline__ void tmRnnDelta(const RecArgs& a, int j, int k, int b
   const float D = eTop + (k < T ? eRec : 0.f);
   L.D[r * nC + c] = D * actDiff(a.func, L.X[r * nC + c], L.Y[r * nC + c]);
 }
-// Layer::backward of layer j at step k (Layers.h:123-188): [error to the block below | error to step k - 1] = D[r] W^T, a launch per
-// anti-diagonal, the two producers of a tile of deltas meeting at the arrival counter -- lstm_tm_bwd_kernel with one gate.  The four
-// wavefronts split the reduction over the nC deltas into quarters (nC / 4 is a multiple of 4, not of 16: whole groups of 16 as 16-byte
-// loads, the rest four per lane group as in mgu_tm_bwd_kernel).
+// lstm_tm_bwd_kernel with one gate: the four wavefronts split the reduction over the nC deltas into quarters (nC / 4 is a multiple of 4,
+// not of 16: tmDeltaProduct's rest)
 __global__ __launch_bounds__(256) void rnn_tm_bwd_kernel(RecArgs a, int j0, int k0) {
   __shared__ float sR[4 * 256];
   __shared__ int sT[16];
   __shared__ unsigned sArr;
   const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;
-  const int top = a.nL - 1;
-  if (k == a.nBPTT + 1 && j != top) return;      // (only the last layer has a launch at the step behind the windows)
+  if (k == a.nBPTT + 1 && j != a.nL - 1) return;      // (only the last layer has a launch at the step behind the windows)
   const RecLayer& L = a.L[j];
   const int nIn = L.nIn, nC = L.nC;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int row0 = j > 0 ? 0 : nIn;      // (no error below the first layer)
-  const int nRowW = nIn + nC;
   const int b0 = blockIdx.y * 16, i0 = row0 + blockIdx.x * 16;
   if (i0 >= nIn + (k > 0 ? nC : 0)) return;      // (the grid is as wide as the diagonal's widest member; no error to a step in front of the first)
   if (tid < 16) sT[tid] = b0 + tid < a.B ? a.tmT[b0 + tid] : -2;
-  const int iw = min(i0 + li, nRowW - 1), bl = min(b0 + li, a.B - 1);
+  const int iw = min(i0 + li, nIn + nC - 1), bl = min(b0 + li, a.B - 1);
   const int q = nC >> 2;                 // deltas per wavefront
-  const float* wq = a.W + L.indW + (size_t)iw * nC + wave * q;
-  const float* dq = L.D + ((size_t)bl * a.K + k) * nC + wave * q;
-  const f32x4* wr = reinterpret_cast<const f32x4*>(wq) + lc;
-  const f32x4* dr = reinterpret_cast<const f32x4*>(dq) + lc;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const int nG = q >> 4, rem = q & 15;
-  constexpr int UG = 8;
-  for (int g0 = 0; g0 < nG; g0 += UG) {
-    f32x4 wv[UG], dv[UG];
-#pragma unroll
-    for (int u = 0; u < UG; ++u) { const int G = min(g0 + u, nG - 1); wv[u] = wr[4 * G]; dv[u] = dr[4 * G]; }
-#pragma unroll
-    for (int u = 0; u < UG; ++u) {
-      if (g0 + u < nG) {      // A = deltas (rows = samples), B = W rows (columns = rows i of W)
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][0], wv[u][0], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][1], wv[u][1], acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][2], wv[u][2], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u][3], wv[u][3], acc1, 0, 0, 0);
-      }
-    }
-  }
-  for (int e = 0; 4 * e < rem; ++e) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dq[16 * nG + 4 * e + lc], wq[16 * nG + 4 * e + lc], acc0, 0, 0, 0);
-#pragma unroll
-  for (int p = 0; p < 4; ++p) sR[wave * 256 + (4 * lc + p) * 16 + li] = acc0[p] + acc1[p];
-  __syncthreads();
-  const int row = tid >> 4, ii = tid & 15, b = b0 + row, i = i0 + ii, T = sT[row];
-  const float e = (sR[tid] + sR[256 + tid]) + (sR[512 + tid] + sR[768 + tid]);      // (zero for a sample without step k)
-  // the tile's cells: (J, Kc), the same for the whole workgroup (layer inputs and cells come in multiples of 16)
-  const bool below = i0 < nIn;
-  const int J = below ? j - 1 : j, Kc = below ? k : k - 1, c = below ? i : i - nIn;
-  const int nCJ = a.L[J].nC;
-  const bool live = b < a.B && c < nCJ && T >= Kc;      // (this sample has step Kc: its rows of deltas exist)
-  float v = e;
-  if (below && L.hasRes && i < L.resW && b < a.B) v += L.Rd[((size_t)b * a.K + k) * L.ldR + i] * a.W[L.indWr + i];
-  if (!below && j == top) {      // the last layer's deltas of the previous step: nothing else feeds them
-    if (live) tmRnnDelta(a, j, Kc, b, c, T, Kc == T ? a.Dres[(size_t)b * a.ldD + c] : 0.f, v);
-    return;
-  }
-  if (below && k + 1 > a.nBPTT) {      // (no launch of the layer below behind the windows: these deltas have one producer)
-    if (live) tmRnnDelta(a, J, Kc, b, c, T, v, 0.f);
-    return;
-  }
-  // the two producers meet at the arrival counter: values as agent-scope stores, acknowledged before the arrival is counted (lstm_tm_bwd_kernel)
-  float* mine = below ? a.tmET[J] : a.tmER[J];
-  const float* other = below ? a.tmER[J] : a.tmET[J];
-  const size_t at = (size_t)min(b, a.B - 1) * nCJ + min(c, nCJ - 1);
-  if (b < a.B && c < nCJ) __hip_atomic_store(mine + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __builtin_amdgcn_s_waitcnt(0);          // vmcnt(0): this tile's values are at the coherence point
-  __syncthreads();
-  if (tid == 0) sArr = __hip_atomic_fetch_add(a.tmCtr + a.tmCtrOff[J] + c0tile(i0, nIn, below) * (int)gridDim.y + (int)blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if ((sArr & 1u) == 0u) return;          // the first of the two
-  const float o = __hip_atomic_load(other + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (live) tmRnnDelta(a, J, Kc, b, c, T, below ? v : o, below ? o : v);
+  const f32x4 p = tmDeltaProduct<false>(a.W + L.indW + (size_t)iw * nC + wave * q, L.D + ((size_t)bl * a.K + k) * nC + wave * q, q, lc);
+  const float e = tmJoinPartials(sR, p, wave, lc, li, tid);      // (zero for a sample without step k)
+  tmFinishTile<tmRnnDelta>(a, j, k, i0, b0 + (tid >> 4), i0 + (tid & 15), sT[tid >> 4], e, e, sArr);
 }
 
-static bool tmLayersOk(const RecArgs& a);
-// acting (one window of a.actSteps given states) through the same launches: used where a layer is wider than the per-sample kernels hold
-bool rec_tm_act_ok(const RecArgs& a) {
-  if ((a.gates != 4 && a.gates != 2 && a.gates != 1) || a.actStates == nullptr || a.B != 1 || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
-  bool wide = false;
-  for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > 256;
-  return wide && tmLayersOk(a);
-}
-bool rec_tm_ok(const RecArgs& a) {
-  if ((a.gates != 4 && a.gates != 2 && a.gates != 1) || a.actStates != nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.DresRows != nullptr || a.K < a.nBPTT + 2) return false;
-  return tmLayersOk(a);
-}
+// ---- host side -----------------------------------------------------------------------------------------------------------------------
+static bool tmGatesOk(const RecArgs& a) { return a.gates == 4 || a.gates == 2 || a.gates == 1; }
+static size_t tmFwdLds(const RecLayer& L) { return (size_t)(16 * (((L.nIn + L.nC + 3) & ~3) + TM_LDA) + 8 * 16 * 17) * 4; }
 static bool tmLayersOk(const RecArgs& a) {
   for (int j = 0; j < a.nL; ++j) {
     const RecLayer& L = a.L[j];
     if (L.nC % 16 || L.indW % 4 || (L.ldA & 3) || (j > 0 && L.nIn != a.L[j - 1].nC)) return false;
     if (a.gates == 2 && a.tmFP[j] == nullptr) return false;
-    if ((size_t)(16 * (((L.nIn + L.nC + 3) & ~3) + TM_LDA) + 8 * 16 * 17) * 4 > 150 * 1024) return false;
+    if (tmFwdLds(L) > 150 * 1024) return false;
   }
   return true;
 }
-static size_t tmFwdLds(const RecLayer& L) { return (size_t)(16 * (((L.nIn + L.nC + 3) & ~3) + TM_LDA) + 8 * 16 * 17) * 4; }
-hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s) {
-  const bool acting = a.actStates != nullptr;
-  const int kLast = acting ? a.actSteps - 1 : a.nBPTT + 1;      // the last window step any sample can have
-  if (acting) hipLaunchKernelGGL(lstm_tm_prepare_act_kernel, dim3(1), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(lstm_tm_prepare_kernel, dim3(a.B, a.K), dim3(256), 0, s, a);
+// acting (one window of a.actSteps given states) through the same launches: used where a layer is wider than the per-sample kernels hold
+bool rec_tm_act_ok(const RecArgs& a) {
+  if (!tmGatesOk(a) || a.actStates == nullptr || a.B != 1 || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
+  bool wide = false;
+  for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > 256;
+  return wide && tmLayersOk(a);
+}
+bool rec_tm_ok(const RecArgs& a) {
+  if (!tmGatesOk(a) || a.actStates != nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.DresRows != nullptr || a.K < a.nBPTT + 2) return false;
+  return tmLayersOk(a);
+}
+// the forward chain: diagonal d of the (layer, step) grid = layers jLo .. jLo + nz - 1 at steps d - j, kLast = the last window step any
+// sample can have; a workgroup covers `tiles` tiles of 16 cells; launch(grid, dynamic LDS bytes, jLo, k of jLo) enqueues a diagonal
+template <class Launch>
+static hipError_t tmForwardDiagonals(const RecArgs& a, int kLast, const void* kernel, int tiles, Launch launch) {
   size_t ldsMax = 0;
   for (int j = 0; j < a.nL; ++j) ldsMax = std::max(ldsMax, tmFwdLds(a.L[j]));
-  // diagonal d of the (layer, step) grid: layers jLo .. jLo + nz - 1 at steps d - j
-  auto diag = [&](int d, int* jLo, int* nz, int* gx, size_t* lds) {
-    *jLo = std::max(0, d - kLast); const int jHi = std::min(a.nL - 1, d);
-    *nz = jHi - *jLo + 1; *gx = 0; *lds = 0;
-    for (int j = *jLo; j <= jHi; ++j) { *gx = std::max(*gx, a.L[j].nC / 16); *lds = std::max(*lds, tmFwdLds(a.L[j])); }
-  };
-  if (a.gates == 2) {
-    hipError_t e2 = ensureDynLds(reinterpret_cast<const void*>(mgu_tm_fwd_kernel), ldsMax); if (e2 != hipSuccess) return e2;
-    for (int d = 0; d <= kLast + a.nL - 1; ++d) {
-      int jLo, nz, gx; size_t lds; diag(d, &jLo, &nz, &gx, &lds);
-      for (int ph = 0; ph < 2; ++ph)
-        hipLaunchKernelGGL(mgu_tm_fwd_kernel, dim3(gx, (a.B + 15) / 16, nz), dim3(TM_FNT), lds, s, a, jLo, d - jLo, ph);
-    }
-    return hipGetLastError();
-  }
-  if (a.gates == 1) {      // (a workgroup covers RNN_TM_TILES tiles of 16 cells)
-    hipError_t e1 = ensureDynLds(reinterpret_cast<const void*>(rnn_tm_fwd_kernel), ldsMax); if (e1 != hipSuccess) return e1;
-    for (int d = 0; d <= kLast + a.nL - 1; ++d) {
-      int jLo, nz, gx; size_t lds; diag(d, &jLo, &nz, &gx, &lds);
-      hipLaunchKernelGGL(rnn_tm_fwd_kernel, dim3((gx + RNN_TM_TILES - 1) / RNN_TM_TILES, (a.B + 15) / 16, nz), dim3(TM_FNT), lds, s, a, jLo, d - jLo);
-    }
-    return hipGetLastError();
-  }
-  hipError_t e = ensureDynLds(reinterpret_cast<const void*>(lstm_tm_fwd_kernel), ldsMax); if (e != hipSuccess) return e;
+  hipError_t e = ensureDynLds(kernel, ldsMax); if (e != hipSuccess) return e;
   for (int d = 0; d <= kLast + a.nL - 1; ++d) {
-    int jLo, nz, gx; size_t lds; diag(d, &jLo, &nz, &gx, &lds);
-    hipLaunchKernelGGL(lstm_tm_fwd_kernel, dim3(gx, (a.B + 15) / 16, nz), dim3(TM_FNT), lds, s, a, jLo, d - jLo);
+    const int jLo = std::max(0, d - kLast), jHi = std::min(a.nL - 1, d);
+    int gx = 0; size_t lds = 0;
+    for (int j = jLo; j <= jHi; ++j) { gx = std::max(gx, a.L[j].nC / 16); lds = std::max(lds, tmFwdLds(a.L[j])); }
+    launch(dim3((gx + tiles - 1) / tiles, (a.B + 15) / 16, jHi - jLo + 1), lds, jLo, d - jLo);
   }
   return hipGetLastError();
 }
-hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s) {
-  if (a.gates == 2) {
-    for (int e = a.nL - 1 + a.nBPTT + 1; e >= 0; --e) {      // anti-diagonals j + k = e: phase 0 of every member, then phase 1 of every member
-      const int jLo = std::max(0, e - (a.nBPTT + 1)), jHi = std::min(a.nL - 1, e);
-      int gx0 = 0, gx1 = 0;
-      for (int j = jLo; j <= jHi; ++j) {
-        const int k = e - j;
-        if (k == a.nBPTT + 1 && j != a.nL - 1) continue;
-        const RecLayer& L = a.L[j];
-        const int row0 = j > 0 ? 0 : L.nIn, nOut = L.nIn + (k > 0 ? L.nC : 0) - row0;
-        if (k != a.nBPTT + 1) gx0 = std::max(gx0, L.nC / 16);
-        gx1 = std::max(gx1, (nOut + 15) / 16);
-      }
-      if (gx0 > 0) hipLaunchKernelGGL(mgu_tm_bwd_kernel, dim3(gx0, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo, 0);
-      if (gx1 > 0) hipLaunchKernelGGL(mgu_tm_bwd_kernel, dim3(gx1, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo, 1);
-    }
-    return hipGetLastError();
+hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s) {
+  const bool acting = a.actStates != nullptr;
+  const int kLast = acting ? a.actSteps - 1 : a.nBPTT + 1;
+  if (acting) hipLaunchKernelGGL(lstm_tm_prepare_act_kernel, dim3(1), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(lstm_tm_prepare_kernel, dim3(a.B, a.K), dim3(256), 0, s, a);
+  if (a.gates == 2) return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(mgu_tm_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
+    for (int ph = 0; ph < 2; ++ph) hipLaunchKernelGGL(mgu_tm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0, ph);
+  });
+  if (a.gates == 1) return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(rnn_tm_fwd_kernel), RNN_TM_TILES, [&](dim3 g, size_t lds, int jLo, int k0) {
+    hipLaunchKernelGGL(rnn_tm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0);
+  });
+  return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(lstm_tm_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
+    hipLaunchKernelGGL(lstm_tm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0);
+  });
+}
+// anti-diagonal j + k = e of the backward chain: its members are layers jLo .. jLo + nz - 1 at steps e - j (behind the windows, k = nBPTT + 1,
+// the last layer only); gx1 = grid width of the D W^T launches over the members' rows of W, gx0 = that of MGU's phase 0 over their cells
+struct TmAntiDiagonal { int jLo, nz, gx0, gx1; };
+static TmAntiDiagonal tmAntiDiagonal(const RecArgs& a, int e) {
+  const int jLo = std::max(0, e - (a.nBPTT + 1)), jHi = std::min(a.nL - 1, e);
+  TmAntiDiagonal d = {jLo, jHi - jLo + 1, 0, 0};
+  for (int j = jLo; j <= jHi; ++j) {
+    const int k = e - j;
+    if (k == a.nBPTT + 1 && j != a.nL - 1) continue;
+    const RecLayer& L = a.L[j];
+    const int row0 = j > 0 ? 0 : L.nIn, nOut = L.nIn + (k > 0 ? L.nC : 0) - row0;
+    if (k != a.nBPTT + 1) d.gx0 = std::max(d.gx0, L.nC / 16);
+    d.gx1 = std::max(d.gx1, (nOut + 15) / 16);
   }
-  for (int e = a.nL - 1 + a.nBPTT + 1; e >= 0; --e) {      // anti-diagonals j + k = e; the members: layers jLo .. jHi at steps e - j
-    const int jLo = std::max(0, e - (a.nBPTT + 1)), jHi = std::min(a.nL - 1, e);
-    int gx = 0;
-    for (int j = jLo; j <= jHi; ++j) {
-      const int k = e - j;
-      if (k == a.nBPTT + 1 && j != a.nL - 1) continue;
-      const RecLayer& L = a.L[j];
-      const int row0 = j > 0 ? 0 : L.nIn, nOut = L.nIn + (k > 0 ? L.nC : 0) - row0;
-      gx = std::max(gx, (nOut + 15) / 16);
-    }
-    if (gx <= 0) continue;
-    if (a.gates == 1) hipLaunchKernelGGL(rnn_tm_bwd_kernel, dim3(gx, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo);
-    else hipLaunchKernelGGL(lstm_tm_bwd_kernel, dim3(gx, (a.B + 15) / 16, jHi - jLo + 1), dim3(256), 0, s, a, jLo, e - jLo);
+  return d;
+}
+hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s) {
+  for (int e = a.nL - 1 + a.nBPTT + 1; e >= 0; --e) {      // (MGU: phase 0 of every member, then phase 1 of every member)
+    const TmAntiDiagonal d = tmAntiDiagonal(a, e);
+    const dim3 g0(d.gx0, (a.B + 15) / 16, d.nz), g1(d.gx1, (a.B + 15) / 16, d.nz);
+    if (a.gates == 2 && d.gx0 > 0) hipLaunchKernelGGL(mgu_tm_bwd_kernel, g0, dim3(256), 0, s, a, d.jLo, e - d.jLo, 0);
+    if (d.gx1 <= 0) continue;
+    if (a.gates == 2) hipLaunchKernelGGL(mgu_tm_bwd_kernel, g1, dim3(256), 0, s, a, d.jLo, e - d.jLo, 1);
+    else if (a.gates == 1) hipLaunchKernelGGL(rnn_tm_bwd_kernel, g1, dim3(256), 0, s, a, d.jLo, e - d.jLo);
+    else hipLaunchKernelGGL(lstm_tm_bwd_kernel, g1, dim3(256), 0, s, a, d.jLo, e - d.jLo);
   }
   return hipGetLastError();
 }
