@@ -10,11 +10,14 @@
 // is needed:
 //
 //   every WG:  h1 = f(S W0 + b0) for the whole panel (17x256 weights: recomputed, not exchanged)
-//              its tile of x2 = h1 W1 + b1, y3 = f(x2) + w*h1 + b and f'(x2)
-//              -> global (agent-scope write-through stores)
-//   -- group barrier: a counter per panel, one atomic arrive per WG, no L2 flush / invalidate --
-//   every WG:  reads the panel's y3 and f'(x2) back (L2 hits), output layer + V-RACER head for the
-//              16 samples (fp64, one (sample, action dim) per lane), delta_y3 = delta_out Wout^T,
+//              its tile of x2 = h1 W1 + b1, y3 = f(x2) + w*h1 + b and f'(x2), and its SHARE of the output layer,
+//              the 16 x 8 partial y3[:, tile] Wout[rows of the tile] (the layer is linear in the columns)
+//              -> global (plain stores through the XCD's L2; agent-scope write-through stores if the probe says so)
+//   -- group barrier: a counter per panel, one arrive per WG (no returned value: the target comes from a read of the
+//      counter issued with the first loads), no L2 flush / invalidate --
+//   every WG:  sums the HT partials of the panel's outputs in one fixed association (one round trip of small L2 hits; y3 is
+//              not read back), V-RACER head for the 16 samples (fp64, one (sample, action dim) per lane) while the waves
+//              that have no part in the head stage f'(x2) of the panel, delta_y3 = delta_out Wout^T,
 //              delta_x2 = delta_y3 f'(x2) for the whole panel, its tile of
 //              delta_h1 = delta_x2 W1^T (+ residual path), delta_x1 = delta_h1 f'(x1)
 //
@@ -62,9 +65,8 @@ namespace hl {
 #endif
 
 // LDS carve-up (floats).  R1: h1 panel, later the W1 row tile of the dX contraction.  R2: W0
-// (k-major, leading dimension H+16), later the y3 panel.  R3: W1 column tile, later f'(x2) ->
-// delta_x2 panel.
-__host__ __device__ inline int fusedR2Floats(int dSp, int H) { const int a = dSp * (H + 16), b = 16 * FLDR; return a > b ? a : b; }
+// (k-major, leading dimension H+16).  R3: W1 column tile, later f'(x2) -> delta_x2 panel.
+__host__ __device__ inline int fusedR2Floats(int dSp, int H) { return dSp * (H + 16); }
 __host__ __device__ inline int fusedR3Floats(int H) { const int a = H * 16, b = 16 * FLDR; return a > b ? a : b; }
 __host__ __device__ inline size_t fusedLdsBytes(int dS, int H) {
   const int dSp = (dS + 3) & ~3;
@@ -96,6 +98,12 @@ __device__ __forceinline__ f32x4 waveMma(FA fa, FB fb) {
 template <int NP> __device__ __forceinline__ float redSum(const float* red, int tid) {
   if constexpr (NP == 8) return ((red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid])) + ((red[1024 + tid] + red[1280 + tid]) + (red[1536 + tid] + red[1792 + tid]));
   else return (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
+}
+
+// sum of N values held in registers, same association as redSum (pairs, then pairs of pairs, ...)
+template <int N> __device__ __forceinline__ float treeSum(const float* v) {
+  if constexpr (N == 1) return v[0];
+  else return treeSum<N / 2>(v) + treeSum<N / 2>(v + N / 2);
 }
 
 template <int H, int CF, int NT>
@@ -208,6 +216,10 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   const float bov = tid < nDense ? W[a.indBo + tid] : 0.f, bpv = tid < dA ? W[a.indBp + tid] : 0.f;
   double beta = sc->beta; const double Cmax = sc->Cmax, Cinv = sc->Cinv;
   const long long betaWant = sc->nGradSteps;      // (deferBeta: the rider in block 1 publishes beta under this number)
+  // the panel's arrive counter as it stands before this workgroup's own arrival: it advances by HT per launch (the whole group of a
+  // panel runs or leaves), so any such value lies in [base, base + HT - 1] and gives the barrier's target without a returning atomic
+  unsigned ctr0 = 0;
+  if constexpr (HT > 1) ctr0 = __hip_atomic_load(a.panelCtr + panel * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // ---- stage: states, W0 (k-major), W1 column tile (k-major), Wout, vectors ------------------------
 #pragma unroll
   for (int q = 0; q < QS; ++q) { const int idx = tid + NT * q, r = idx >> 5, c = idx & 31; sS[r * FLDS + c] = sv[q]; }
@@ -339,12 +351,13 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   }
   __syncthreads();
   FSTAMP(3);
+  float y3 = 0.f;      // (padding rows: zero, they add nothing to the partial outputs)
   if (rowValid) {
     const float v = redSum<XW>(red, tid);
     const float x2 = v + b1e;
     float y2 = 0.f, f2 = 0.f;
     dispatchFunc<CF>(func, [&](auto F) { constexpr int FN = decltype(F)::value; y2 = actEvalT<FN>(x2); f2 = actDiffT<FN>(x2, y2); });
-    const float y3 = (n0 + en < resN) ? resOut(y2, y1o, sWr[n0 + en], sBr[n0 + en]) : y2;
+    y3 = (n0 + en < resN) ? resOut(y2, y1o, sWr[n0 + en], sBr[n0 + en]) : y2;
     // plain stores: the consumers are the workgroups of this panel, which share this XCD's L2 (the vector L1 is
     // write-through); other XCDs see y3 after the kernel boundary.  Agent-scope (write-through) stores made the
     // acknowledgement wait below ~1 us longer.
@@ -354,6 +367,24 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
     } else {
       gR2[(size_t)row * ldA1 + n0 + en] = y3;                // also the A operand of dWout
       gX2[(size_t)row * ldA1 + n0 + en] = f2;                // f'(x2)
+    }
+  }
+  // ---- this tile's share of the output layer, O[16][8] += y3[:, tile n] Wout[rows of tile n]: the layer is linear in the
+  // columns, so the 16 x 8 partial travels with the exchange and nobody reads the y3 panel back.  Lane en multiplies its y3 with
+  // row n0 + en of Wout; the sum over the 16 lanes of a sample is the rotation butterfly of sum16 (every lane gets it) ----
+  float pOwn = 0.f;     // lane en < 8: partial O[em][en] of this tile
+  if (wave < 4) {
+    const f32x4 wa = *reinterpret_cast<const f32x4*>(sWo + (n0 + en) * 8), wb = *reinterpret_cast<const f32x4*>(sWo + (n0 + en) * 8 + 4);
+    float p[8] = {y3 * wa[0], y3 * wa[1], y3 * wa[2], y3 * wa[3], y3 * wb[0], y3 * wb[1], y3 * wb[2], y3 * wb[3]};
+#pragma unroll
+    for (int o = 0; o < 8; ++o) { p[o] += rowRorF<8>(p[o]); p[o] += rowRorF<4>(p[o]); p[o] += rowRorF<2>(p[o]); p[o] += rowRorF<1>(p[o]); }
+    pOwn = p[0];
+#pragma unroll
+    for (int o = 1; o < 8; ++o) pOwn = (en & 7) == o ? p[o] : pOwn;
+    if (HT > 1 && rowValid && en < 8) {      // same kind of store as y3 / f'(x2)
+      float* po = a.Opart + ((size_t)panel * HT + n) * 128 + em * 8 + en;
+      if (a.xcdSafe) __hip_atomic_store(po, pOwn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else *po = pOwn;
     }
   }
   FSTAMP(4);
@@ -366,10 +397,23 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   FSTAMP(6);
   // (safe mode: the agent-scope stores above are write-through and acknowledged -- vmcnt(0) -- before the arrival below; the
   // agent-scope loads behind the barrier bypass this XCD's L2: no cache-wide release / acquire, which costs ~20 us each here)
+  // (one L2 round trip: the target comes from the early read `ctr0`, the arrival returns nothing, polling starts at once; the
+  // counter wraps soundly: HT is a power of two and the comparison is a signed difference)
+  if (HT > 1 && tid == 0) __hip_atomic_fetch_add(a.panelCtr + panel * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // h1 is dead (own tile kept in registers): R1 takes the W1 row tile of the dX contraction while the peers arrive
+  float* sF2 = sR3; float* sBx = sY1;
+#pragma unroll
+  for (int q = 0; q < QP; ++q) {
+    const int f = tid + NT * q;
+    if (f < 16 * H4) {
+      const int r = f / H4, c = 4 * (f % H4);
+      float2* d = reinterpret_cast<float2*>(sBx + r * FLDR + c);
+      d[0] = make_float2(w1r[q][0], w1r[q][1]); d[1] = make_float2(w1r[q][2], w1r[q][3]);
+    }
+  }
   if (HT > 1 && tid == 0) {
     unsigned* ctr = a.panelCtr + panel * 32;
-    const unsigned old = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned barTarget = (old / (unsigned)HT + 1u) * (unsigned)HT;
+    const unsigned barTarget = (ctr0 / (unsigned)HT + 1u) * (unsigned)HT;
     int spins = 0;
     while ((int)(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - barTarget) < 0) {
       __builtin_amdgcn_s_sleep(1);
@@ -377,8 +421,8 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
     }
   }
   // beta of this step may still be on its way (POST_DEFER: the count it hangs off is taken by the rider in block 1 while the
-  // panels run): one look now, so that the load's latency is hidden behind the output contraction; the wait proper sits in
-  // front of the head
+  // panels run): one look now, so that the load's latency is hidden behind the loads of the partial outputs; the wait proper sits
+  // in front of the head
   if (a.deferBeta && tid == 0) {
     double got = 0; double ok = 0;
     if (__hip_atomic_load(&a.sc->betaSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == betaWant) {
@@ -389,81 +433,89 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   __syncthreads();
 
   FSTAMP(7);
-  // ---- read the panel's y3 and f'(x2) back -----------------------------------------------------------------
   FVARIANT_STOP(4);
-  float* sY3 = sR2; float* sF2 = sR3; float* sBx = sY1;
-  f32x4 yv[QP], fv[QP];
-  {
+  // ---- the HT partials of O[em][en]: one round trip of HT small loads per element thread (lanes en >= 8 repeat the addresses of
+  // en - 8: no guard, no extra lines) ----------------------------------------------------------------------------------------
+  float pv[HT];
+  if constexpr (HT > 1) {
 #pragma unroll
-    for (int q = 0; q < QP; ++q) {
-      const int f = tid + NT * q; yv[q] = z4; fv[q] = z4;
-      if (f < 16 * H4) {
-        const int r = f / H4, c4 = f % H4;
-        if (m0 + r < nRows) {
-          if (a.xcdSafe) {
-            const float* py = gR2 + (size_t)(m0 + r) * ldA1 + 4 * c4; const float* pf = gX2 + (size_t)(m0 + r) * ldA1 + 4 * c4;
+    for (int t = 0; t < HT; ++t) pv[t] = 0.f;
+    if (wave < 4) {
+      const float* pp = a.Opart + (size_t)panel * HT * 128 + em * 8 + (en & 7);
+      if (a.xcdSafe) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { yv[q][u] = __hip_atomic_load(py + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); fv[q][u] = __hip_atomic_load(pf + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-          } else {
-            yv[q] = *reinterpret_cast<const f32x4*>(gR2 + (size_t)(m0 + r) * ldA1 + 4 * c4);
-            fv[q] = *reinterpret_cast<const f32x4*>(gX2 + (size_t)(m0 + r) * ldA1 + 4 * c4);
-          }
+        for (int t = 0; t < HT; ++t) pv[t] = __hip_atomic_load(pp + t * 128, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+#pragma unroll
+        for (int t = 0; t < HT; ++t) pv[t] = pp[t * 128];
+      }
+    }
+  } else pv[0] = pOwn;      // no peers: the one partial never leaves its registers
+  // ---- f'(x2) of the panel is needed by the dX contraction only: loaded behind the partials and staged by the waves that have
+  // no part in the head (waves 4-7 of 8; with 4 waves, by all of them after the head) ------------------------------------------
+  constexpr int SNT = NW == 8 ? 256 : NT;           // staging threads
+  constexpr int QF = (16 * H4 + SNT - 1) / SNT;     // float4 per staging thread of a 16 x H panel
+  const int stid = NW == 8 ? tid - 256 : tid;
+  f32x4 fv[QF];
+#pragma unroll
+  for (int q = 0; q < QF; ++q) fv[q] = z4;
+  if (stid >= 0) {
+    if (a.xcdSafe) {
+#pragma unroll
+      for (int q = 0; q < QF; ++q) {
+        const int f = stid + SNT * q, r = f / H4, c4 = f % H4;
+        if (f < 16 * H4 && m0 + r < nRows) {
+          const float* pf = gX2 + (size_t)(m0 + r) * ldA1 + 4 * c4;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) fv[q][u] = __hip_atomic_load(pf + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-    }
-    // only y3 is needed by the next contraction: f'(x2) and the W1 row tile are staged after it
+    } else {
 #pragma unroll
-    for (int q = 0; q < QP; ++q) {
-      const int f = tid + NT * q;
-      if (f < 16 * H4) {
-        const int r = f / H4, c = 4 * (f % H4);
-        float2* dy = reinterpret_cast<float2*>(sY3 + r * FLDR + c);
-        dy[0] = make_float2(yv[q][0], yv[q][1]); dy[1] = make_float2(yv[q][2], yv[q][3]);
+      for (int q = 0; q < QF; ++q) {
+        const int f = stid + SNT * q, r = f / H4, c4 = f % H4;
+        if (f < 16 * H4 && m0 + r < nRows) fv[q] = *reinterpret_cast<const f32x4*>(gX2 + (size_t)(m0 + r) * ldA1 + 4 * c4);
       }
     }
   }
-  __syncthreads();
-  FSTAMP(8);
-  FVARIANT_STOP(5);
-
-  // ---- output layer: O[16][nDense] = y3 Wout + bo (MFMA, columns >= 8 are zero) -----------------------
-  if (wave < KWAVES) {
-    const int k0 = wave * KW + lc;
-    const f32x4 acc = waveMma<NK>([&](int s) { return sY3[li * FLDR + k0 + 4 * s]; },
-                                  [&](int s) { return li < 8 ? sWo[(k0 + 4 * s) * 8 + li] : 0.f; });
+  auto stageF2 = [&]() {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave * 256 + (lc * 4 + r) * 16 + li] = acc[r];
-  }
-  // h1 is dead (own tile kept in registers): R1 takes the W1 row tile of the dX contraction, R3 f'(x2)
-#pragma unroll
-  for (int q = 0; q < QP; ++q) {
-    const int f = tid + NT * q;
-    if (f < 16 * H4) {
-      const int r = f / H4, c = 4 * (f % H4);
-      float2* d = reinterpret_cast<float2*>(sBx + r * FLDR + c);
-      d[0] = make_float2(w1r[q][0], w1r[q][1]); d[1] = make_float2(w1r[q][2], w1r[q][3]);
-      float2* df = reinterpret_cast<float2*>(sF2 + r * FLDR + c);
-      df[0] = make_float2(fv[q][0], fv[q][1]); df[1] = make_float2(fv[q][2], fv[q][3]);
+    for (int q = 0; q < QF; ++q) {
+      const int f = stid + SNT * q;
+      if (f < 16 * H4) {
+        const int r = f / H4, c = 4 * (f % H4);
+        float2* df = reinterpret_cast<float2*>(sF2 + r * FLDR + c);
+        df[0] = make_float2(fv[q][0], fv[q][1]); df[1] = make_float2(fv[q][2], fv[q][3]);
+      }
     }
-  }
-  if (a.deferBeta && tid == 0 && sBeta[1] == 0) {
-    int spins = 0;
-    while (__hip_atomic_load(&a.sc->betaSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != betaWant) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > (1 << 22)) { a.sc->errFlag = 79; break; }
+  };
+  if (a.deferBeta) {
+    if (sBeta[1] == 0) {      // (the same value in every thread: written before the barrier above, not after it)
+      if (tid == 0) {
+        int spins = 0;
+        while (__hip_atomic_load(&a.sc->betaSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != betaWant) {
+          __builtin_amdgcn_s_sleep(1);
+          if (++spins > (1 << 22)) { a.sc->errFlag = 79; break; }
+        }
+        sBeta[0] = __hip_atomic_load(&a.sc->beta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      __syncthreads();
     }
-    sBeta[0] = __hip_atomic_load(&a.sc->beta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    beta = sBeta[0];
   }
-  __syncthreads();
-  if (a.deferBeta) beta = sBeta[0];
 #ifdef HL_TAIL_STAMPS
   if (tid == 0 && blockIdx.x == 8 + 8) { a.sc->dbgT[13] = wall_clock64(); a.sc->dbgT[3] = sBeta[1] != 0 ? 1 : 0; }      // beta in hand; was it there at the first look
 #endif
-  FSTAMP(9);
+  FSTAMP(8);
+  FVARIANT_STOP(5);
+  if (NW == 8 && stid >= 0) stageF2();      // (waves 4-7, while waves 0-3 run the head; the barrier that closes the head covers it)
   // network outputs of sample em stay in registers: lane en holds O[em][en] (dense part); the
   // ParamLayer part (Linear) is its bias
-  const int base = lane & ~15;
-  const float Oen = eth ? redSum<KWAVES>(red, tid) + sBo[en] : 0.f;
+  const float Oen = eth ? ((rowValid && en < 8) ? treeSum<HT>(pv) : 0.f) + sBo[en] : 0.f;
+#if defined(HL_FSTAMPS)
+  asm volatile("" :: "v"(Oen));
+#endif
+  FSTAMP(9);
   const double O0 = (double)bcast0F(Oen, en);
   const double mean = (double)rowRorF<15>(Oen);                           // O[em][1 + en]: lane i reads lane i+1
 
@@ -554,6 +606,7 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
       if (en < dA) a.bt.O[(size_t)row * a.nOut + nDense + en] = (double)sBp[en];
     }
   }
+  if (NW != 8) stageF2();
   __syncthreads();
   FSTAMP(10);
   FVARIANT_STOP(7);

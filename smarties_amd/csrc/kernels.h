@@ -241,6 +241,7 @@ struct FusedArgs {
   float* X3; float* R3; float* D3; float* Dres3; int ldA2;
   float* dOut; int ldDo;                  // output-layer deltas [B][ldDo]
   unsigned* panelCtr;                     // [panels][32] arrive counters of the panel barrier (monotonic)
+  float* Opart;                           // [panels][H/16][16][8] partial outputs y3[:, tile] Wout[tile rows] of the panel exchange (fused.hip)
   int variant;                            // development: stop after phase `variant` (0 = run everything)
   int deferBeta;                          // 1: beta of this step is still being computed by the rider in block 1 (POST_DEFER): the heads wait for DevScalars::betaSeq
   int xcdSafe;                            // 1: the workgroups of a panel may sit on different XCDs (probe at hl_create): the panel exchange

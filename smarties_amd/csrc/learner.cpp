@@ -288,6 +288,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       const size_t nCtr = (size_t)roundUp((h->Mmax + 15) / 16, 8) * 32;
       HIPCK(devAlloc(&h->panelCtr, nCtr));
       HIPCK(hipMemset(h->panelCtr, 0, nCtr * sizeof(unsigned)));
+      HIPCK(devAlloc(&h->panelOpart, (nCtr / 32) * (size_t)HT * 128));
       HIPCK(hipStreamSynchronize(nullptr));
     }
   }
@@ -413,7 +414,7 @@ int hl_destroy(hl_learner* h) {
     h->dRedMax, h->dRedErr, h->dMomPartial, h->dMoments, h->dMomentsPrev, h->dStatsOut, h->dStatsIns,
     h->rp.S, h->rp.A, h->rp.MU, h->rp.R, h->rp.V, h->rp.ADV, h->rp.RET, h->rp.DQ, h->rp.IMPW, h->rp.DKL,
     h->rp.epOff, h->rp.epN, h->rp.epTerm, h->rp.epAgg, h->rp.posEid, h->rp.posPrefix, h->rp.stMean, h->rp.stScale,
-    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->dActS, h->dActO};
+    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->dActS, h->dActO};
   for (int pb = 0; pb < 2; ++pb) {
     DevBatch& bt = h->buf[pb].bt;
     void* bp[] = {h->buf[pb].X0, bt.sVals, bt.tag, bt.pEid, bt.pNextOf, bt.flat, bt.pos, bt.eid, bt.t, bt.slot, bt.nextOf, bt.nextSrc,

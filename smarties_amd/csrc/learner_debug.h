@@ -127,6 +127,21 @@ extern "C" HL_API int64_t hl_debug_graph_kernels(hl_learner* h, int32_t steps) {
   }
   return -1;
 }
+// sets every arrive counter of the in-kernel panel barriers to `value` (tests: the counters are monotonic and wrap; the barrier's
+// target arithmetic must survive that).  A barrier's group adds HT per launch to its counter, so only multiples of HT are states
+// the kernels can meet: anything else is refused.
+extern "C" HL_API int hl_debug_set_panel_counters(hl_learner* h, uint32_t value) {
+  if (!h) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  if (!h->panelCtr) return HL_ERR_STATE;
+  const unsigned HT = h->fusedOk || h->fusedWideOk ? (unsigned)(h->hid[1].size / 16) : (unsigned)h->chainHT;
+  if (HT == 0 || value % HT != 0) return HL_ERR_BAD_ARG;
+  const size_t nCtr = (size_t)roundUp((h->Mmax + 15) / 16, 8) * 32;
+  std::vector<unsigned> v(nCtr, (unsigned)value);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return HL_ERR_HIP;
+  if (hipMemcpy(h->panelCtr, v.data(), nCtr * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) return HL_ERR_HIP;
+  return HL_OK;
+}
 // fused kernel: -1 not in use, 0 panel exchange through the shared L2 (probe: workgroup b on XCD b % 8), 1 through agent-scope accesses
 extern "C" HL_API int hl_debug_panel_mode(const hl_learner* h) { return !h || !h->fusedOk ? -1 : (h->xcdSafe ? 1 : 0); }
 

@@ -340,7 +340,7 @@ FusedArgs fusedArgs(hl_learner* h, int parity) {
     fa.nLH = 3; fa.indW2 = d2.indW; fa.indB2 = d2.indB; fa.indWr2 = d2.indWr; fa.indBr2 = d2.indBr; fa.ldW2 = d2.ldW; fa.resN2 = d2.resW;
     fa.X3 = d2.X; fa.R3 = d2.Rr; fa.D3 = d2.D; fa.Dres3 = d2.Dres; fa.ldA2 = d2.ldA;
   }
-  fa.dOut = h->dOut; fa.ldDo = h->ldDo; fa.panelCtr = h->panelCtr; fa.variant = h->dbgVariant; fa.xcdSafe = h->xcdSafe ? 1 : 0;
+  fa.dOut = h->dOut; fa.ldDo = h->ldDo; fa.panelCtr = h->panelCtr; fa.Opart = h->panelOpart; fa.variant = h->dbgVariant; fa.xcdSafe = h->xcdSafe ? 1 : 0;
   for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) fa.boundedMask |= 1ull << i;
   return fa;
 }

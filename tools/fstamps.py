@@ -1,5 +1,6 @@
-import sys, ctypes as C
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, ctypes as C
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import bench, numpy as np
 from smarties_amd import capi, load_hip
 api = load_hip()
@@ -16,7 +17,7 @@ for it in range(40):
     acc.append(np.array(list(out), dtype=np.int64))
 a = np.array(acc[5:])
 d = np.diff(a[:, 0:14], axis=1) * 10   # ns
-names = ['loads+stage', 'h1', 'x2 mma+red', 'epi+st issue', 'precompute', 'waitcnt', 'barrier', 'readback+stage', 'out mma+red', 'head', 'dx2', 'dx mma+red', 'final store']
+names = ['loads+stage', 'h1', 'x2 mma+red', 'epi+st issue', 'precompute', 'waitcnt', 'barrier', 'partials issue', 'partials sum', 'head', 'dx2', 'dx mma+red', 'final store']
 med = np.median(d, axis=0)
 for nm, v in zip(names, med): print('%-16s %7.0f ns' % (nm, v))
 print('total', med.sum())
