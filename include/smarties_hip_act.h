@@ -13,7 +13,8 @@
  * Which call when:
  *   hl_forward            dense nets, n raw states (rows): one kernel for up to 64 agents.
  *   hl_forward_sequence   ONE agent's window, any net.  The cheapest call for a single agent of a recurrent net.
- *   hl_forward_sequences  n agents' windows, any net.  One launch per HL_ACT_SEQ_CHUNK agents for the shapes listed below.
+ *   hl_forward_sequences  n agents' windows, any net.  One launch (layers wider than 256 cells: one chain of launches) per chunk
+ *                         of agents for the shapes listed below.
  */
 #ifndef SMARTIES_HIP_ACT_H
 #define SMARTIES_HIP_ACT_H
@@ -26,7 +27,7 @@ extern "C" {
 
 /* agents per launch: the pinned staging of the library (states, window offsets, outputs, completion stamps) is sized once,
  * at the first acting call, for this many windows of nnBPTTseq + 1 + nAppendedObs states; a call with more agents is cut
- * into ceil(n / HL_ACT_SEQ_CHUNK) launches */
+ * into ceil(n / HL_ACT_SEQ_CHUNK) launches (layers wider than 256 cells: chunks of min(local batch size, HL_ACT_SEQ_CHUNK)) */
 #define HL_ACT_SEQ_CHUNK 512
 
 /* n agents.  n_steps[i] = min(nnBPTTseq, t_i) + 1 (+ up to nAppendedObs states in front), as for hl_forward_sequence.
@@ -49,9 +50,17 @@ extern "C" {
  *     <= 1024 inputs, any nAppendedObs, (nnBPTTseq + 1 + nAppendedObs) x dimS floats of window within 64 KB.
  *     The gate sums are formed in another order than by hl_forward_sequence's kernels: the two agree to rounding
  *     (both within 1e-5 of the CPU oracle), not bit for bit.
+ * Batched, layers wider than 256 cells (the nets whose single window hl_forward_sequence runs through the time-step-major
+ * launches: LSTM, MGU or RNN without convolutional layers and without encoder_rnn, a layer above 256 cells, every layer a
+ * multiple of 16 cells up to 1024): agent i of a chunk is sample row i of ONE chain of those launches -- a prepare kernel over
+ * (agent, window step), the forward diagonals up to the chunk's longest window, the output layer on the chunk's rows --
+ * instead of one chain per agent.  A chunk holds min(local batch size, HL_ACT_SEQ_CHUNK) agents: the chain borrows the
+ * training rows of that many samples between steps (as hl_forward_sequence borrows those of one); the minibatch index
+ * buffers and a minibatch drawn ahead stay as they are.  The kernels and their order of summation are those of the
+ * single-agent call, an agent's row of a tile does not see the other rows: bit-identical to hl_forward_sequence.
  * Dense nets: the [n][dimS (1 + nAppendedObs)] rows are built on the host and go through ONE hl_forward(n) call.
- * Looped, agent by agent through hl_forward_sequence's own route (bit-identical to it): layers wider than 256 cells
- * (time-step-major launches), recurrent layers behind convolutions, RNN encoder layers under MGU layers (encoder_rnn).
+ * Looped, agent by agent through hl_forward_sequence's own route (bit-identical to it): recurrent layers behind
+ * convolutions, RNN encoder layers under MGU layers (encoder_rnn).
  *
  * For a single agent the call costs more than hl_forward_sequence (which runs the window with the weights in registers
  * where the shape allows): hl_forward_sequence stays the call for one agent. */

@@ -22,15 +22,32 @@ static bool actSeqOk(hl_learner* h) {
   h->actSeqCus = cus; h->actSeqState = 1;
   return true;
 }
+// the time-step-major launches (rectm.hip) serve this net's acting window -- hl_forward_sequence's route where a layer is wider than 256
+// cells --: many agents' windows then run as the samples of one chain of those launches
+static bool actTmOk(hl_learner* h) {
+  if (h->actTmState) return h->actTmState > 0;
+  h->actTmState = -1;
+  if (!h->recurrent || h->nConv > 0 || h->recSplit) return false;
+  static const float one = 0.f;      // (the predicate asks for given states, it does not read them)
+  RecArgs ra = recArgs(h, 0); ra.B = 1; ra.actStates = &one; ra.actSteps = 1; ra.actCtx = 0;
+  if (!rec_tm_act_ok(ra)) return false;
+  h->actTmState = 1;
+  return true;
+}
+// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the time-step-major chain borrows the
+// training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples
+static int actChunkCap(hl_learner* h) { return actSeqOk(h) ? ACT_SEQ_CHUNK : (actTmOk(h) ? std::min(h->B, ACT_SEQ_CHUNK) : 0); }
 // one pinned block: [outputs of ACT_MAXROWS rows | their states | their stamps] of hl_forward / hl_forward_sequence, then (nets the
-// batched window kernel serves) [outputs | stamps | window offsets | states] of a chunk of ACT_SEQ_CHUNK agents
-static size_t actSeqStateFloats(const hl_learner* h) { return (size_t)ACT_SEQ_CHUNK * (h->recWin + h->nApp) * h->dS; }
+// batched window kernel or the time-step-major chain serves) [outputs | stamps | window offsets | state counts | states] of a chunk of
+// actChunkCap agents
+static size_t actSeqStateFloats(const hl_learner* h, int cap) { return (size_t)cap * (h->recWin + h->nApp) * h->dS; }
 static int actPinEnsure(hl_learner* h) {
   if (h->actPin) return HL_OK;
   size_t bytes = (size_t)ACT_MAXROWS * (h->nOut * sizeof(double) + sizeof(unsigned)) + actPinFloats(h) * sizeof(float) + 256;
   bytes = (bytes + 255) & ~(size_t)255;
   h->actSeqPinOff = bytes;
-  if (actSeqOk(h)) bytes += (size_t)ACT_SEQ_CHUNK * (h->nOut * sizeof(double) + sizeof(unsigned)) + ((size_t)ACT_SEQ_CHUNK + 2) * sizeof(int) + actSeqStateFloats(h) * sizeof(float);
+  const size_t cap = (size_t)actChunkCap(h);
+  if (cap) bytes += cap * (h->nOut * sizeof(double) + sizeof(unsigned)) + (2 * cap + 2) * sizeof(int) + actSeqStateFloats(h, (int)cap) * sizeof(float);
   HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actPin), bytes, hipHostMallocMapped));
   std::memset(h->actPin, 0, bytes);
   return HL_OK;
@@ -151,6 +168,39 @@ int hl_forward_sequence(hl_learner* h, int32_t nSteps, const float* states, doub
   return HL_OK;
 }
 
+// n checked windows of a net whose layers run time-step-major (actTmOk): agent i of a chunk is sample row i of ONE chain of launches --
+// prepare, the forward diagonals up to the chunk's longest window, the output layer on the chunk's rows of Yout.  The chain borrows rows
+// 0 .. m - 1 of the training buffers between steps, as hl_forward_sequence borrows row 0: every training step writes its rows anew
+static int actTmForward(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
+  { int rc = actPinEnsure(h); if (rc) return rc; }
+  const int cap = actChunkCap(h);
+  double* pOut = reinterpret_cast<double*>(h->actPin + h->actSeqPinOff);
+  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pOut + (size_t)cap * h->nOut);
+  int* pOff = reinterpret_cast<int*>(const_cast<unsigned*>(pDone) + cap);
+  int* pCnt = pOff + cap + 2;
+  float* pIn = reinterpret_cast<float*>(pCnt + cap);
+  const DevHidden& q = h->hid[h->nHidden - 1];
+  size_t first = 0;      // states in front of the chunk
+  for (int i0 = 0; i0 < n; i0 += cap) {
+    const int m = std::min(cap, n - i0);
+    int sum = 0, winMax = 0;
+    for (int i = 0; i < m; ++i) { pOff[i] = sum; pCnt[i] = nSteps[i0 + i]; sum += nSteps[i0 + i]; winMax = std::max(winMax, std::min((int)nSteps[i0 + i], h->recWin)); }
+    std::memcpy(pIn, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
+    RecArgs ra = recArgs(h, 0); ra.B = m; ra.actStates = pIn; ra.actOff = pOff; ra.actCnt = pCnt; ra.actSteps = winMax; ra.actCtx = 0;
+    if (!rec_tm_act_ok(ra)) return fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the time-step-major launches refuse the chunk");
+    unsigned tag = ++h->actTag; if (tag == 0) tag = ++h->actTag;
+    HIPCK(timed(h, "act_tm_chain", h->stream, [&] {
+      const hipError_t e = launch_rec_tm_forward(ra, h->stream); if (e != hipSuccess) return e;
+      return launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, m,
+                               pOut, h->stream, const_cast<unsigned*>(pDone), tag, h->cfg.nnOutputFunc);
+    }));
+    { int rc = actWait(h, pDone, m, tag); if (rc) return rc; }
+    std::memcpy(outputs + (size_t)i0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
+    first += sum;
+  }
+  return HL_OK;
+}
+
 // n agents' windows (include/smarties_hip_act.h)
 int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const float* states, double* outputs) {
   if (!h || n < 0 || (n > 0 && (!nSteps || !states || !outputs))) return HL_ERR_BAD_ARG;
@@ -174,7 +224,8 @@ int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const 
     }
     return hl_forward(h, n, rows.data(), outputs);
   }
-  if (!actSeqOk(h)) {      // layers beyond the batched kernel, convolutions in front, two layer types: hl_forward_sequence's routes, agent by agent
+  if (!actSeqOk(h) && actTmOk(h)) return actTmForward(h, n, nSteps, states, outputs);      // layers wider than 256 cells
+  if (!actSeqOk(h)) {      // convolutions in front, two layer types, a window beyond the batched kernel's LDS: hl_forward_sequence's routes, agent by agent
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
       const int rc = hl_forward_sequence(h, nSteps[i], states + off * h->dS, outputs + (size_t)i * h->nOut); if (rc) return rc;

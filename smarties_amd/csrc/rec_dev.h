@@ -27,6 +27,11 @@ __device__ __forceinline__ float recInputAt(const RecArgs& a, bool acting, int b
   else { const int tt = t - T + k, back = j < tt ? j : tt; raw = a.rp.S[(size_t)(slot - T + k - back) * a.dS + i]; }
   return (raw - a.rp.stMean[i]) * a.rp.stScale[i];
 }
+// its acting form for one of many agents: `states` = the agent's own states, oldest first, `ctx` of them in front of its window
+__device__ __forceinline__ float recActInputAt(const RecArgs& a, const float* states, int ctx, int k, int e) {
+  const int j = e / a.dS, i = e - j * a.dS, g = ctx + k - j;
+  return (states[(size_t)(g > 0 ? g : 0) * a.dS + i] - a.rp.stMean[i]) * a.rp.stScale[i];
+}
 
 
 }  // namespace hl

@@ -9,7 +9,8 @@
 // are aligned at their first step; at global step k the rows r = b K + k of all samples that have that step form the operand of
 //     gates[b][o] = bias[o] + sum_i A[r][i] W[i][o],        A[r] = [input of the step | previous output]   (the dW operand row itself)
 // a [B x (nIn + nC)] x [(nIn + nC) x 4 nC] product per layer and step: the weights are read once per step, not once per sample.
-//   forward   lstm_tm_prepare_kernel (window geometry per sample, the first layer's input rows), then per step and layer
+//   forward   lstm_tm_prepare_kernel (window geometry per sample, the first layer's input rows; acting: lstm_tm_prepare_act_kernel for one
+//             agent's window, lstm_tm_prepare_acts_kernel for many agents as the samples), then per step and layer
 //             lstm_tm_fwd_kernel: workgroup = 16 samples x 16 cells, its four wavefronts the four gates (16 x 16 x K on
 //             v_mfma_f32_16x16x4_f32: A tile staged in LDS with 16-byte loads, W columns as 64-byte runs from the L2); epilogue =
 //             the cell (Layer_LSTM.h:77-125), the rows kept for the backward pass and the dW launch, this step's block output into the
@@ -79,6 +80,30 @@ __global__ __launch_bounds__(256) void lstm_tm_prepare_act_kernel(RecArgs a) {
   for (int j = 0; j < a.nL; ++j) {
     const RecLayer& L = a.L[j];
     for (int c = tid; c < L.nC; c += 256) L.A[L.nIn + c] = 0.f;
+  }
+}
+
+// ... and the windows of a.B agents as the a.B samples of ONE chain of launches (hl_forward_sequences): a workgroup per (agent, window
+// step), as lstm_tm_prepare_kernel.  Agent b's actCnt[b] states start at state actOff[b] of actStates (both tables and the states in mapped
+// pinned memory); the last nBPTT + 1 of them are its window, those in front only feed appended observations.  The forward kernels leave
+// out an agent whose window has ended (tmActiveMask) and hand its last step's block output to Yout row b (tmHandOn); a row of a longer
+// window of the chunk before is never read: rows k >= tmSteps[b] feed no sum of agent b, and every row k < tmSteps[b] is written here
+// (inputs) or by step k - 1 (recurrent slot) first.
+__global__ __launch_bounds__(256) void lstm_tm_prepare_acts_kernel(RecArgs a) {
+  const int b = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+  const int steps = a.actCnt[b], win = min(steps, a.nBPTT + 1), ctx = steps - win;
+  const long long r = (long long)b * a.K + k;
+  if (k == 0) {
+    if (tid == 0) { a.tmT[b] = win - 1; a.tmSteps[b] = win; a.tmNext[b] = -1; }
+    for (int j = 0; j < a.nL; ++j) {
+      const RecLayer& L = a.L[j];
+      for (int c = tid; c < L.nC; c += 256) L.A[r * L.ldA + L.nIn + c] = 0.f;
+    }
+  }
+  if (k < win) {
+    const RecLayer& L0 = a.L[0];
+    const float* states = a.actStates + (size_t)a.actOff[b] * a.dS;
+    for (int i = tid; i < L0.nIn; i += 256) L0.A[r * L0.ldA + i] = recActInputAt(a, states, ctx, k, i);
   }
 }
 
@@ -586,9 +611,12 @@ static bool tmLayersOk(const RecArgs& a) {
   }
   return true;
 }
-// acting (one window of a.actSteps given states) through the same launches: used where a layer is wider than the per-sample kernels hold
+// acting (one window of a.actSteps given states, or with the per-agent tables a.B windows of up to a.actSteps) through the same launches:
+// used where a layer is wider than the per-sample kernels hold
 bool rec_tm_act_ok(const RecArgs& a) {
-  if (!tmGatesOk(a) || a.actStates == nullptr || a.B != 1 || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
+  const bool many = a.actOff != nullptr && a.actCnt != nullptr;
+  if ((a.actOff != nullptr) != (a.actCnt != nullptr) || (many ? a.B < 1 || a.actSteps > a.nBPTT + 1 : a.B != 1)) return false;
+  if (!tmGatesOk(a) || a.actStates == nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
   bool wide = false;
   for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > 256;
   return wide && tmLayersOk(a);
@@ -615,7 +643,8 @@ static hipError_t tmForwardDiagonals(const RecArgs& a, int kLast, const void* ke
 hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s) {
   const bool acting = a.actStates != nullptr;
   const int kLast = acting ? a.actSteps - 1 : a.nBPTT + 1;
-  if (acting) hipLaunchKernelGGL(lstm_tm_prepare_act_kernel, dim3(1), dim3(256), 0, s, a);
+  if (acting && a.actOff) hipLaunchKernelGGL(lstm_tm_prepare_acts_kernel, dim3(a.B, a.actSteps), dim3(256), 0, s, a);
+  else if (acting) hipLaunchKernelGGL(lstm_tm_prepare_act_kernel, dim3(1), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(lstm_tm_prepare_kernel, dim3(a.B, a.K), dim3(256), 0, s, a);
   if (a.gates == 2) return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(mgu_tm_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
     for (int ph = 0; ph < 2; ++ph) hipLaunchKernelGGL(mgu_tm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0, ph);
