@@ -61,14 +61,11 @@ __device__ __forceinline__ int recLdsOffset(const RecArgs& a, int j) {
 
 #ifdef REC_STAMPS
 __device__ unsigned long long recStamps[256];
-#define RSTAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && (i) < 256) recStamps[i] = wall_clock64(); } while (0)
-// (the one-launch step: first sample's workgroup -- block 1 behind a rider --, wavefront 0 / wavefront 1)
-#define SSTAMP(i) do { if (b == 0 && threadIdx.x == 0 && (i) < 256) recStamps[i] = wall_clock64(); } while (0)
-#define SSTAMP1(i) do { if (b == 0 && threadIdx.x == 64 && (i) < 256) recStamps[i] = wall_clock64(); } while (0)
+// stamp i, taken by thread `thread` of the first sample's workgroup (the one-launch step: block 1 behind a rider; thread 0 / 64: its
+// wavefront 0 / 1)
+#define REC_STAMP(sample, thread, i) do { if ((sample) == 0 && threadIdx.x == (thread) && (i) < 256) recStamps[i] = wall_clock64(); } while (0)
 #else
-#define RSTAMP(i) do {} while (0)
-#define SSTAMP(i) do {} while (0)
-#define SSTAMP1(i) do {} while (0)
+#define REC_STAMP(sample, thread, i) do {} while (0)
 #endif
 template <bool LDSW>
 __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
@@ -77,7 +74,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   __shared__ float sPrevOut[HL_MAX_HIDDEN][REC_GENC], sPrevSt[HL_MAX_HIDDEN][REC_GENC];
   __shared__ float sX[4 * REC_GENC];
   const int b = blockIdx.x, tid = threadIdx.x;
-  RSTAMP(0);
+  REC_STAMP(blockIdx.x, 0, 0);
   // acting (MemoryBuffer::agentToMinibatch, MemoryBuffer.cpp:440-467): the agent's last steps, from a zero recurrent state
   const bool acting = a.actStates != nullptr;
   const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
@@ -90,9 +87,9 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   RecLayer LL[HL_MAX_HIDDEN];
 #pragma unroll
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) LL[j] = a.L[j];
-  RSTAMP(1);
+  REC_STAMP(blockIdx.x, 0, 1);
   if constexpr (LDSW) recStageWeights(a, sW, tid);
-  RSTAMP(2);
+  REC_STAMP(blockIdx.x, 0, 2);
   float bias[HL_MAX_HIDDEN], wr[HL_MAX_HIDDEN], br[HL_MAX_HIDDEN];      // this thread's gate bias / residual parameters per layer
 #pragma unroll
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) {
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   }
   const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
   vmDrain(); ldsBarrier();
-  RSTAMP(3);
+  REC_STAMP(blockIdx.x, 0, 3);
   for (int k = 0; k < nSteps; ++k) {
     const bool store = !acting && k <= T;
     const long long r = (long long)b * a.K + k;
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
       else { const float raw = acting ? a.actStates[(size_t)k * a.dS + tid] : a.rp.S[(size_t)sl * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
     }
     ldsBarrier();
-    RSTAMP(4 + k * 5);
+    REC_STAMP(blockIdx.x, 0, 4 + k * 5);
     int cur = 0;
 #pragma unroll
     for (int j = 0; j < HL_MAX_HIDDEN; ++j) if (j < a.nL) {
@@ -155,7 +152,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
         if (store) L.X[r * NO + o] = acc;
       }
       ldsBarrier();
-      if (j < 2) RSTAMP(4 + k * 5 + 1 + 2 * j);
+      if (j < 2) REC_STAMP(blockIdx.x, 0, 4 + k * 5 + 1 + 2 * j);
       float out = 0.f, st = 0.f;
       if (tid < nC) {
         st = sX[tid] * sX[nC + tid] + (k > 0 ? sPrevSt[j][tid] * sX[2 * nC + tid] : 0.f);
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
         sBuf[cur ^ 1][tid] = blk;
       }
       ldsBarrier();
-      if (j < 2) RSTAMP(4 + k * 5 + 2 + 2 * j);
+      if (j < 2) REC_STAMP(blockIdx.x, 0, 4 + k * 5 + 2 + 2 * j);
       if (tid < nC) { sPrevOut[j][tid] = out; sPrevSt[j][tid] = st; }
       cur ^= 1;
     }
@@ -176,7 +173,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
     if (k == T + 1 && tid < nCl) a.Yout[(size_t)nextRow * a.ldY + tid] = sBuf[cur][tid];
     ldsBarrier();
   }
-  RSTAMP(250);
+  REC_STAMP(blockIdx.x, 0, 250);
 }
 
 // ---- LSTM forward, weights resident in LDS: the version the step uses whenever they fit --------------------------------
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   __shared__ __attribute__((aligned(16))) float sA[HL_MAX_HIDDEN][2][LSTM_VEC];
   __shared__ float sStates[REC_STATES];
   const int b = blockIdx.x, tid = threadIdx.x;
-  RSTAMP(0);
+  REC_STAMP(blockIdx.x, 0, 0);
   const bool acting = a.actStates != nullptr;
   const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
   const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   RecLayer LL[MAXL];
 #pragma unroll
   for (int j = 0; j < MAXL; ++j) LL[j] = a.L[j];
-  RSTAMP(1);
+  REC_STAMP(blockIdx.x, 0, 1);
   // weights, transposed (coalesced 16-byte global reads along the gates of one input row, scattered LDS writes)
   {
     int off = 0;
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
       off += NO * g.ld;
     }
   }
-  RSTAMP(2);
+  REC_STAMP(blockIdx.x, 0, 2);
   // this thread's role per layer: cell, gate, part; the parameters of its cell
   float wr[MAXL], br[MAXL], prevSt[MAXL];
 #pragma unroll
@@ -284,13 +281,13 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   vmDrain(); ldsBarrier();
   if (tid < a.dS) sA[0][0][tid] = stateOf(0);
   ldsBarrier();
-  RSTAMP(3);
+  REC_STAMP(blockIdx.x, 0, 3);
   for (int k = 0; k < nSteps; ++k) {
     const bool store = !acting && k <= T;
     const long long r = (long long)b * a.K + k;
     const int cb = k & 1;
     if (k + 1 < nSteps && tid < a.dS) sA[0][cb ^ 1][tid] = stateOf(k + 1);             // (that copy was last read a step ago)
-    RSTAMP(4 + k * 5);
+    REC_STAMP(blockIdx.x, 0, 4 + k * 5);
     int off = 0;
 #pragma unroll
     for (int j = 0; j < MAXL; ++j) if (j < nL) {
@@ -348,11 +345,11 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
         }
       }
       ldsBarrier();
-      if (j < 2) RSTAMP(4 + k * 5 + 2 + 2 * j);
+      if (j < 2) REC_STAMP(blockIdx.x, 0, 4 + k * 5 + 2 + 2 * j);
       off += NO * g.ld;
     }
   }
-  RSTAMP(250);
+  REC_STAMP(blockIdx.x, 0, 250);
 }
 
 template <bool LDSW>
@@ -835,7 +832,6 @@ __device__ __forceinline__ float fromUpperHalf(float x) {
   return __uint_as_float(r[1]);
 }
 __device__ __forceinline__ void waveLdsSync() { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_wave_barrier(); }
-__device__ __forceinline__ void pairBarrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ float fastRcp(float d) { float r = __builtin_amdgcn_rcpf(d); return fmaf(fmaf(-d, r, 1.0f), r, r); }
 __device__ __forceinline__ float fastSigm(float in) {      // Sigm::_eval with safeExp cut at 8, one exponential for both branches
   const float ex = __expf(fmaxf(-8.f, -fabsf(in))), r = fastRcp(1.f + ex);
@@ -888,82 +884,225 @@ __device__ __forceinline__ void lstm32LayerStep(const RecLayer& L, const f32x2 (
   }
 }
 
-template <int IN0>     // inputs of the first layer, padded to a multiple of 4 (<= 32)
-__global__ __launch_bounds__(128) void lstm32_forward_wave_kernel(RecArgs a) {
-  constexpr int NC = 32, NO = 128;
-  constexpr int NTMAX = (IN0 + NC) > 2 * NC ? (IN0 + NC) : 2 * NC;    // terms per gate as the unrolled loop walks them (zero weights behind the layer's own)
-  __shared__ __attribute__((aligned(16))) float sV0[2][NTMAX];         // layer 0 operand [x_k | h0_{k-1} | 0 ...], double-buffered over the steps
-  __shared__ __attribute__((aligned(16))) float sV1[2][2 * NC];        // layer 1 operand [block-0 output of step k | h1_{k-1}]
-  __shared__ float sStates[18 * 32];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  RSTAMP(0);
-  const int layer = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform
-  const bool acting = a.actStates != nullptr;                          // rollout inference: the agent's last states, nothing stored
-  const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
-  const int nextRow = acting ? -1 : a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
-  const float* W = a.W;
-  const RecLayer L = a.L[layer];
-  const int nIn = a.L[0].nIn, dS = a.dS;
-  // this lane's gate columns of its layer: o = lane (cell input | input gate) and lane + 64 (forget | output gate)
-  f32x2 w[NTMAX];
-  {
-    const float* Wl = W + L.indW;
-#pragma unroll
-    for (int i = 0; i < NTMAX; ++i) {
-      int row;
-      if (layer == 0) row = i < IN0 ? (i < nIn ? i : -1) : (i < IN0 + NC ? nIn + (i - IN0) : -1);
-      else row = i < 2 * NC ? i : -1;
-      w[i] = row >= 0 ? f32x2{Wl[(size_t)row * NO + lane], Wl[(size_t)row * NO + lane + 64]} : f32x2{0.f, 0.f};
-    }
-  }
-  const f32x2 bias = {W[L.indB + lane], W[L.indB + lane + 64]};
+// ---- pieces of the wave kernels.  Each stands once: the stand-alone forward / backward kernels and the one-launch step kernels below
+// are these calls in a row, with what is their own (the acting form, the head, where rows come from and go to) between them.
+// wave32*: LSTM and MGU alike (NO = gate columns of a layer, 128 / 64); lstm32* / mgu32*: the cell type's own. ----
+// sample b's window: steps t - T .. t and, behind a truncated episode end, step t + 1 (output row nextRow); `acting`: the agent's last states
+struct WaveWin { int b, T, nextRow, nSteps; long long slot; };
+__device__ __forceinline__ WaveWin wave32Window(const RecArgs& a, int b, bool acting) {
+  WaveWin win; win.b = b;
+  const int t = acting ? 0 : a.bt.t[b]; win.slot = acting ? 0 : a.bt.slot[b];
+  win.T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
+  win.nextRow = acting ? -1 : a.bt.nextOf[b];
+  win.nSteps = win.T + 1 + (win.nextRow >= 0 ? 1 : 0);
+  return win;
+}
+// residual scalars of this lane's cell (forward)
+__device__ __forceinline__ void wave32ResScalars(const RecLayer& L, const float* W, int lane, float& wr, float& br) {
   const int c = lane & 31;
-  float wr = 0.f, br = 0.f;
+  wr = 0.f; br = 0.f;
   if (L.hasRes && c < L.resW) { wr = W[L.indWr + c]; br = W[L.indBr + c]; }
-  for (int e = tid; e < nSteps * dS; e += 128) {
+}
+// staging of a window forward (both wavefronts): the window's standardised states, zeroed operands of both layers (V0LEN floats / 128)
+template <int V0LEN>
+__device__ __forceinline__ void wave32StageWindow(const RecArgs& a, const WaveWin& win, bool acting, int tid, float* sStates, float* sV0, float* sV1) {
+  const int dS = a.dS;
+  for (int e = tid; e < win.nSteps * dS; e += 128) {
     const int kk = e / dS, i = e - kk * dS;
-    const float raw = acting ? a.actStates[e] : a.rp.S[(size_t)(slot - T + kk) * dS + i];
+    const float raw = acting ? a.actStates[e] : a.rp.S[(size_t)(win.slot - win.T + kk) * dS + i];
     sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
   }
-  for (int i = tid; i < 2 * NTMAX; i += 128) (&sV0[0][0])[i] = 0.f;
-  for (int i = tid; i < 4 * NC; i += 128) (&sV1[0][0])[i] = 0.f;
-  RSTAMP(1);
-  vmDrain(); pairBarrier();
-  RSTAMP(2);
-  if (layer == 0 && lane < dS) sV0[0][lane] = sStates[lane];
-  pairBarrier();
+  for (int i = tid; i < V0LEN; i += 128) sV0[i] = 0.f;
+  for (int i = tid; i < 4 * 32; i += 128) sV1[i] = 0.f;
+}
+// staging done, layer 0's operand of step 0 in place (stamps 1 and 2 on either side of the first barrier)
+__device__ __forceinline__ void wave32FirstOperand(const WaveWin& win, int layer, int lane, int dS, const float* sStates, float* sV0) {
+  REC_STAMP(win.b, 0, 1);
+  vmDrain(); ldsBarrier();
+  REC_STAMP(win.b, 0, 2);
+  if (layer == 0 && lane < dS) sV0[lane] = sStates[lane];
+  ldsBarrier();
+}
+// backward: this lane's row of [W_in; W_rec] -- top layer row `lane` (0..31 input, 32..63 recurrent); layer 0 row nIn + lane (recurrent
+// part only: nothing is propagated to the network input) -- and, requested behind the row, its residual weight
+template <int NO>
+__device__ __forceinline__ const f32x4* wave32WeightRow(const RecArgs& a, const RecLayer& L, int j, int lane) {
+  return reinterpret_cast<const f32x4*>(a.W + L.indW + (size_t)(j == 1 ? lane : a.L[0].nIn + (lane & 31)) * NO);
+}
+__device__ __forceinline__ float wave32ResRowWeight(const RecArgs& a, const RecLayer& L, int lane) {
+  return (L.hasRes && lane < L.resW) ? a.W[L.indWr + lane] : 0.f;
+}
+// rows of the steps this sample does not have: zero deltas
+template <int NO>
+__device__ __forceinline__ void wave32ZeroRows(const RecArgs& a, const RecLayer& L, int b, int T, int lane) {
+  for (int k = T + 1; k < a.K; ++k) {
+    const long long r = (long long)b * a.K + k;
+#pragma unroll
+    for (int o = 0; o < NO; o += 64) L.D[r * NO + lane + o] = 0.f;
+    if (L.hasRes && lane < 32) L.Rd[r * L.ldR + lane] = 0.f;
+  }
+}
+// error w.r.t. the output of layer-step (j, k) on lanes 0..31: from above (the top layer: the head's error at step T; layer 0: sTop) plus what
+// step k + 1 handed back (sRec); the residual path's row goes to memory, its share of the error below into `res`
+__device__ __forceinline__ float wave32OutputError(const RecLayer& L, int j, int k, int T, long long r, int lane, float dres, float wr,
+                                                   const float (*sTop)[32], const float (*sRec)[32], float& res) {
+  const float eTop = j == 1 ? (k == T ? dres : 0.f) : sTop[k & 1][lane];
+  if (L.hasRes) { L.Rd[r * L.ldR + lane] = eTop; res = lane < L.resW ? eTop * wr : 0.f; }
+  return eTop + (k < T ? sRec[j][lane] : 0.f);
+}
+
+// ---- LSTM ----
+constexpr int lstm32Terms(int in0) { return (in0 + 32) > 2 * 32 ? (in0 + 32) : 2 * 32; }      // terms per gate as the unrolled loop walks them (zero weights behind the layer's own)
+// this lane's gate columns of its layer: o = lane (cell input | input gate) and lane + 64 (forget | output gate); bias, residual scalars
+template <int IN0, int NT>
+__device__ __forceinline__ void lstm32LoadColumns(const RecArgs& a, const RecLayer& L, int layer, int lane, f32x2 (&w)[NT], f32x2& bias, float& wr, float& br) {
+  constexpr int NC = 32, NO = 128;
+  const float* W = a.W;
+  const float* Wl = W + L.indW;
+  const int nIn = a.L[0].nIn;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    int row;
+    if (layer == 0) row = i < IN0 ? (i < nIn ? i : -1) : (i < IN0 + NC ? nIn + (i - IN0) : -1);
+    else row = i < 2 * NC ? i : -1;
+    w[i] = row >= 0 ? f32x2{Wl[(size_t)row * NO + lane], Wl[(size_t)row * NO + lane + 64]} : f32x2{0.f, 0.f};
+  }
+  bias = f32x2{W[L.indB + lane], W[L.indB + lane + 64]};
+  wave32ResScalars(L, W, lane, wr, br);
+}
+// the window forward: wavefront 0 = layer 0 at step k = it, wavefront 1 = layer 1 one step behind.  `store`: a training window (rows
+// of steps <= T kept); LDSACT: their gates and states go to sAct [2][17][ACT].  idle(): wavefront 1 at it = 0, no layer-step yet;
+// top(k, blk): the top layer's block output of step k, lanes 0..31 (the caller keeps steps T and T + 1).
+template <int IN0, int NT, bool LDSACT, class Idle, class Top>
+__device__ __forceinline__ void lstm32ForwardWindow(const RecArgs& a, const RecLayer& L, const WaveWin& win, int layer, int lane, bool store, const f32x2 (&w)[NT], f32x2 bias,
+                                                    float wr, float br, float (*sV0)[NT], float (*sV1)[64], const float* sStates, float* sAct, Idle idle, Top top) {
+  constexpr int NC = 32, ACT = 6 * NC;
+  const int nIn = a.L[0].nIn, dS = a.dS, T = win.T, nSteps = win.nSteps;
   float prevSt = 0.f;
   for (int it = 0; it <= nSteps; ++it) {
-    RSTAMP(4 + it);
+    REC_STAMP(win.b, 0, 4 + it);
     if (layer == 0) {
       const int k = it;
       if (k < nSteps) {
         const int cb = k & 1;
         if (k + 1 < nSteps && lane < dS) sV0[cb ^ 1][lane] = sStates[(k + 1) * dS + lane];       // (that copy was last read a step ago)
         float blk = 0.f;
-        lstm32LayerStep<NTMAX>(L, w, bias, sV0[cb], IN0, nIn, prevSt, wr, br, &sV0[cb ^ 1][IN0], blk, !acting && k <= T, (long long)b * a.K + k, lane);
+        lstm32LayerStep<NT, LDSACT>(L, w, bias, sV0[cb], IN0, nIn, prevSt, wr, br, &sV0[cb ^ 1][IN0], blk, store && k <= T, (long long)win.b * a.K + k, lane,
+                                    LDSACT ? sAct + (0 * 17 + (k <= T ? k : 0)) * ACT : nullptr);
         if (lane < NC) sV1[cb][lane] = blk;
       }
     } else {
       const int k = it - 1;
-      if (k >= 0) {
+      if (k < 0) idle();
+      else {
         const int cb = k & 1;
         float blk = 0.f;
-        lstm32LayerStep<NTMAX>(L, w, bias, sV1[cb], NC, NC, prevSt, wr, br, &sV1[cb ^ 1][NC], blk, !acting && k <= T, (long long)b * a.K + k, lane);
-        if (lane < NC) {
-          if (k == T) a.Yout[(size_t)b * a.ldY + lane] = blk;
-          if (k == T + 1) a.Yout[(size_t)nextRow * a.ldY + lane] = blk;
-        }
+        lstm32LayerStep<NT, LDSACT>(L, w, bias, sV1[cb], NC, NC, prevSt, wr, br, &sV1[cb ^ 1][NC], blk, store && k <= T, (long long)win.b * a.K + k, lane,
+                                    LDSACT ? sAct + (1 * 17 + (k <= T ? k : 0)) * ACT : nullptr);
+        if (lane < NC) top(k, blk);
       }
     }
-    pairBarrier();
+    ldsBarrier();
   }
-  RSTAMP(250);
+}
+// this lane's row (see wave32WeightRow) as 32 four-column pieces
+__device__ __forceinline__ void lstm32LoadRow(const RecArgs& a, const RecLayer& L, int j, int lane, f32x4 (&wq)[32], float& wr) {
+  const f32x4* rw = wave32WeightRow<128>(a, L, j, lane);
+#pragma unroll
+  for (int q = 0; q < 32; ++q) wq[q] = rw[q];
+  wr = wave32ResRowWeight(a, L, lane);
+}
+// gate deltas of one layer-step on lanes 0..31 (LSTMLayer::backward, Layer_LSTM.h:127-165) into sDj [cell input | I | F | O]; D: error w.r.t.
+// the step's output; nxtSt / nxtF: state error / forget gate of step k + 1, replaced by this step's
+__device__ __forceinline__ void lstm32GateDeltas(const float* act, int k, int T, float D, float& nxtSt, float& nxtF, float* sDj, int lane) {
+  constexpr int NC = 32, ACT = 6 * NC;
+  const float cellInpt = act[lane], IG = act[NC + lane], FG = act[2 * NC + lane], OG = act[3 * NC + lane], co = act[5 * NC + lane];
+  const float prevSt = k > 0 ? (act - ACT)[4 * NC + lane] : 0.f;
+  const float diff = (1.f - co * co) * D;
+  const float sd = diff * OG + (k < T ? nxtSt * nxtF : 0.f);
+  const float d0 = IG * sd;
+  const float d1 = IG * (1.f - IG) * cellInpt * sd;
+  const float d2 = k > 0 ? FG * (1.f - FG) * prevSt * sd : 0.f;
+  const float d3 = OG * (1.f - OG) * D * co;
+  sDj[lane] = d0; sDj[NC + lane] = d1; sDj[2 * NC + lane] = d2; sDj[3 * NC + lane] = d3;
+  nxtSt = sd; nxtF = FG;
+}
+// e_i = sum_o W[i][o] delta[o] for this lane's row (Layer::backward, Layers.h:123-188)
+__device__ __forceinline__ float lstm32RowProduct(const f32x4 (&wq)[32], const float* sDj) {
+  constexpr int NO = 128;
+  const f32x4* d4 = reinterpret_cast<const f32x4*>(sDj);
+  f32x2 p0 = {0.f, 0.f}, p1 = {0.f, 0.f}, p2 = {0.f, 0.f}, p3 = {0.f, 0.f};
+  // (the reads of half the deltas before the first FMA of that half -- see lstm32LayerStep; all 32 pieces at once would
+  //  take the step kernel past 256 VGPRs)
+#pragma unroll
+  for (int h0 = 0; h0 < NO / 4; h0 += NO / 8) {
+    f32x4 dq[NO / 8];
+#pragma unroll
+    for (int q = 0; q < NO / 8; ++q) dq[q] = d4[h0 + q];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NO / 8; q += 2) {
+      const f32x4 da = dq[q], db = dq[q + 1];
+      p0 += f32x2{wq[h0 + q][0], wq[h0 + q][1]} * f32x2{da[0], da[1]}; p1 += f32x2{wq[h0 + q][2], wq[h0 + q][3]} * f32x2{da[2], da[3]};
+      p2 += f32x2{wq[h0 + q + 1][0], wq[h0 + q + 1][1]} * f32x2{db[0], db[1]}; p3 += f32x2{wq[h0 + q + 1][2], wq[h0 + q + 1][3]} * f32x2{db[2], db[3]};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const f32x2 ps = (p0 + p1) + (p2 + p3);
+  return ps[0] + ps[1];
+}
+// back-propagation through time: wavefront 0 = the top layer (j = 1) at step k = T - it, wavefront 1 = layer 0 one step behind.  sAct
+// [2][17][ACT]: per (layer, step) [cell input | I | F | O | state | tanh(state)]; dres: error w.r.t. the top block's output at step T.
+__device__ __forceinline__ void lstm32BackwardWindow(const RecArgs& a, const RecLayer& L, int j, int b, int T, int lane, const f32x4 (&wq)[32], float wr, float dres,
+                                                     const float* sAct, float (*sD)[128], float (*sTop)[32], float (*sRec)[32]) {
+  constexpr int NC = 32, NO = 128, ACT = 6 * NC;
+  float nxtSt = 0.f, nxtF = 0.f;                           // state error / forget gate of step k + 1 (lanes 0..31)
+  for (int it = 0; it <= T + 1; ++it) {
+    const int k = T - it + (j == 1 ? 0 : 1);               // the top layer is one step ahead
+    if (k >= 0 && k <= T) {
+      const long long r = (long long)b * a.K + k;
+      float res = 0.f;
+      if (lane < NC) {
+        const float D = wave32OutputError(L, j, k, T, r, lane, dres, wr, sTop, sRec, res);
+        lstm32GateDeltas(sAct + (j * 17 + k) * ACT, k, T, D, nxtSt, nxtF, sD[j], lane);
+      }
+      waveLdsSync();                                       // this wavefront's deltas are in LDS
+      { const float u0 = sD[j][lane], u1 = sD[j][64 + lane]; L.D[r * NO + lane] = u0; L.D[r * NO + 64 + lane] = u1; }      // the row for the weight gradients: two whole-wavefront stores
+      if (j == 1 || k > 0) {
+        const float e = lstm32RowProduct(wq, sD[j]);
+        if (j == 1) {   // rows 0..31: error of block 0's output (+ the residual path of this layer); rows 32..63: handed to step k - 1
+          if (lane < NC) sTop[k & 1][lane] = res + e; else sRec[1][lane - NC] = e;
+        } else if (lane < NC) sRec[0][lane] = e;
+      }
+    }
+    ldsBarrier();
+  }
 }
 
-template <int IN0>
+template <int IN0>     // inputs of the first layer, padded to a multiple of 4 (<= 32)
+__global__ __launch_bounds__(128) void lstm32_forward_wave_kernel(RecArgs a) {
+  constexpr int NC = 32, NTMAX = lstm32Terms(IN0);
+  __shared__ __attribute__((aligned(16))) float sV0[2][NTMAX];         // layer 0 operand [x_k | h0_{k-1} | 0 ...], double-buffered over the steps
+  __shared__ __attribute__((aligned(16))) float sV1[2][2 * NC];        // layer 1 operand [block-0 output of step k | h1_{k-1}]
+  __shared__ float sStates[18 * 32];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  REC_STAMP(b, 0, 0);
+  const int layer = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform
+  const bool acting = a.actStates != nullptr;                          // rollout inference: the agent's last states, nothing stored
+  const WaveWin win = wave32Window(a, b, acting);
+  const RecLayer L = a.L[layer];
+  f32x2 w[NTMAX], bias; float wr, br;
+  lstm32LoadColumns<IN0>(a, L, layer, lane, w, bias, wr, br);
+  wave32StageWindow<2 * NTMAX>(a, win, acting, tid, sStates, &sV0[0][0], &sV1[0][0]);
+  wave32FirstOperand(win, layer, lane, a.dS, sStates, sV0[0]);
+  lstm32ForwardWindow<IN0, NTMAX, false>(a, L, win, layer, lane, !acting, w, bias, wr, br, sV0, sV1, sStates, nullptr, [] {},
+    [&](int k, float blk) {
+      if (k == win.T) a.Yout[(size_t)b * a.ldY + lane] = blk;
+      if (k == win.T + 1) a.Yout[(size_t)win.nextRow * a.ldY + lane] = blk;
+    });
+  REC_STAMP(b, 0, 250);
+}
+
 __global__ __launch_bounds__(128) void lstm32_backward_wave_kernel(RecArgs a) {
   constexpr int NC = 32, NO = 128, ACT = 6 * NC;           // per (step, layer): [cell input | I | F | O | state | tanh(state)]
   __shared__ __attribute__((aligned(16))) float sD[2][NO]; // gate deltas of the layer-step, per layer
@@ -973,19 +1112,10 @@ __global__ __launch_bounds__(128) void lstm32_backward_wave_kernel(RecArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = 1 - wv;                                    // wavefront 0 = the top layer (one step ahead), wavefront 1 = layer 0
-  const int t = a.bt.t[b];
-  const int T = min(a.nBPTT, t);
-  const float* W = a.W;
+  const int T = min(a.nBPTT, a.bt.t[b]);
   const RecLayer L = a.L[j];
-  const int nIn0 = a.L[0].nIn;
-  // this lane's row of [W_in; W_rec]: top layer row `lane` (0..31 input, 32..63 recurrent); layer 0 row nIn + lane (recurrent
-  // part only: nothing is propagated to the network input)
-  f32x4 wq[NO / 4];
-  {
-    const f32x4* rw = reinterpret_cast<const f32x4*>(W + L.indW + (size_t)(j == 1 ? lane : nIn0 + (lane & 31)) * NO);
-#pragma unroll
-    for (int q = 0; q < NO / 4; ++q) wq[q] = rw[q];
-  }
+  f32x4 wq[NO / 4]; float wr;
+  lstm32LoadRow(a, L, j, lane, wq, wr);
   {   // stored activations of this layer over the window
     const int total = (T + 1) * ACT;
     for (int e = lane; e < total; e += 64) {
@@ -994,69 +1124,10 @@ __global__ __launch_bounds__(128) void lstm32_backward_wave_kernel(RecArgs a) {
       sAct[j][e] = x < 4 * NC ? L.X[r * NO + x] : L.Y[r * NO + NC + (x - 4 * NC)];
     }
   }
-  const float wr = (L.hasRes && lane < L.resW) ? W[L.indWr + lane] : 0.f;
   const float dres = (j == 1 && lane < NC) ? a.Dres[(size_t)b * a.ldD + lane] : 0.f;
-  // rows of the steps this sample does not have: zero deltas
-  for (int k = T + 1; k < a.K; ++k) {
-    const long long r = (long long)b * a.K + k;
-    L.D[r * NO + lane] = 0.f; L.D[r * NO + lane + 64] = 0.f;
-    if (L.hasRes && lane < NC) L.Rd[r * L.ldR + lane] = 0.f;
-  }
-  vmDrain(); pairBarrier();
-  float nxtSt = 0.f, nxtF = 0.f;                           // state error / forget gate of step k + 1 (lanes 0..31)
-  for (int it = 0; it <= T + 1; ++it) {
-    const int k = T - it + (j == 1 ? 0 : 1);               // the top layer is one step ahead
-    if (k >= 0 && k <= T) {
-      const long long r = (long long)b * a.K + k;
-      // gate deltas on lanes 0..31 (LSTMLayer::backward, Layer_LSTM.h:127-165)
-      float res = 0.f;
-      if (lane < NC) {
-        const float eTop = j == 1 ? (k == T ? dres : 0.f) : sTop[k & 1][lane];
-        const float* act = sAct[j] + k * ACT;
-        if (L.hasRes) { L.Rd[r * L.ldR + lane] = eTop; res = lane < L.resW ? eTop * wr : 0.f; }
-        const float D = eTop + (k < T ? sRec[j][lane] : 0.f);
-        const float cellInpt = act[lane], IG = act[NC + lane], FG = act[2 * NC + lane], OG = act[3 * NC + lane], co = act[5 * NC + lane];
-        const float prevSt = k > 0 ? (act - ACT)[4 * NC + lane] : 0.f;
-        const float diff = (1.f - co * co) * D;
-        const float sd = diff * OG + (k < T ? nxtSt * nxtF : 0.f);
-        const float d0 = IG * sd;
-        const float d1 = IG * (1.f - IG) * cellInpt * sd;
-        const float d2 = k > 0 ? FG * (1.f - FG) * prevSt * sd : 0.f;
-        const float d3 = OG * (1.f - OG) * D * co;
-        sD[j][lane] = d0; sD[j][NC + lane] = d1; sD[j][2 * NC + lane] = d2; sD[j][3 * NC + lane] = d3;
-        L.D[r * NO + lane] = d0; L.D[r * NO + NC + lane] = d1; L.D[r * NO + 2 * NC + lane] = d2; L.D[r * NO + 3 * NC + lane] = d3;
-        nxtSt = sd; nxtF = FG;
-      }
-      __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_wave_barrier();    // this wavefront's deltas are in LDS
-      if (j == 1 || k > 0) {
-        // e_i = sum_o W[i][o] delta[o] for this lane's row (Layer::backward, Layers.h:123-188)
-        const f32x4* d4 = reinterpret_cast<const f32x4*>(sD[j]);
-        f32x2 p0 = {0.f, 0.f}, p1 = {0.f, 0.f}, p2 = {0.f, 0.f}, p3 = {0.f, 0.f};
-        // (the reads of half the deltas before the first FMA of that half -- see lstm32LayerStep; all 32 pieces at once would
-        //  take the kernel past 256 VGPRs)
-#pragma unroll
-        for (int h0 = 0; h0 < NO / 4; h0 += NO / 8) {
-          f32x4 dq[NO / 8];
-#pragma unroll
-          for (int q = 0; q < NO / 8; ++q) dq[q] = d4[h0 + q];
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int q = 0; q < NO / 8; q += 2) {
-            const f32x4 da = dq[q], db = dq[q + 1];
-            p0 += f32x2{wq[h0 + q][0], wq[h0 + q][1]} * f32x2{da[0], da[1]}; p1 += f32x2{wq[h0 + q][2], wq[h0 + q][3]} * f32x2{da[2], da[3]};
-            p2 += f32x2{wq[h0 + q + 1][0], wq[h0 + q + 1][1]} * f32x2{db[0], db[1]}; p3 += f32x2{wq[h0 + q + 1][2], wq[h0 + q + 1][3]} * f32x2{db[2], db[3]};
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        const f32x2 ps = (p0 + p1) + (p2 + p3);
-        const float e = ps[0] + ps[1];
-        if (j == 1) {   // rows 0..31: error of block 0's output (+ the residual path of this layer); rows 32..63: handed to step k - 1
-          if (lane < NC) sTop[k & 1][lane] = res + e; else sRec[1][lane - NC] = e;
-        } else if (lane < NC) sRec[0][lane] = e;
-      }
-    }
-    pairBarrier();
-  }
+  wave32ZeroRows<NO>(a, L, b, T, lane);
+  vmDrain(); ldsBarrier();
+  lstm32BackwardWindow(a, L, j, b, T, lane, wq, wr, dres, &sAct[0][0], sD, sTop, sRec);
 }
 
 // ---- the whole sample in ONE launch: window forward, output layer + RACER head, back-propagation through time ---------------------
@@ -1137,8 +1208,7 @@ __device__ __forceinline__ void stepHeadRun(StepHeadRegs& R, const HeadArgs& ha,
 
 template <int IN0>
 __global__ __launch_bounds__(256) void lstm32_step_wave_kernel(RecArgs a, HeadArgs ha, unsigned long long boundedMask, ExtraArgs extra) {
-  constexpr int NC = 32, NO = 128, ACT = 6 * NC;
-  constexpr int NTMAX = (IN0 + NC) > 2 * NC ? (IN0 + NC) : 2 * NC;
+  constexpr int NC = 32, NO = 128, ACT = 6 * NC, NTMAX = lstm32Terms(IN0);
   constexpr int O_V0 = 2 * 17 * ACT * 4, O_V1 = O_V0 + 2 * NTMAX * 4, O_ST = O_V1 + 2 * 64 * 4, O_D = O_ST + 18 * 32 * 4, O_TOP = O_D + 2 * NO * 4,
                 O_REC = O_TOP + 2 * NC * 4, O_HEAD = O_REC + 2 * NC * 4, TOTAL = O_HEAD + STEP_HEAD_LDS;
   static_assert(O_HEAD % 16 == 0, "alignment of the head rows");
@@ -1155,153 +1225,44 @@ __global__ __launch_bounds__(256) void lstm32_step_wave_kernel(RecArgs a, HeadAr
 
   const int b = blockIdx.x - (extra.role ? 1 : 0), tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = a.bt.t[b]; const long long slot = a.bt.slot[b];
-  const int T = min(a.nBPTT, t);
-  const int nextRow = a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
-  const float* W = a.W;
-  const int nIn = a.L[0].nIn, dS = a.dS;
-  SSTAMP(0);
+  const WaveWin win = wave32Window(a, b, false);
+  const int T = win.T;
+  REC_STAMP(b, 0, 0);
   StepHeadRegs R;
-  stepHeadLoad(R, ha, a.sc, wv, lane, slot, nextRow);
+  stepHeadLoad(R, ha, a.sc, wv, lane, win.slot, win.nextRow);
   {
     // ================================================ forward over the window ==================================================
     const int layer = wv;
     const RecLayer L = a.L[layer];
-    f32x2 w[NTMAX];
-    {
-      const float* Wl = W + L.indW;
-#pragma unroll
-      for (int i = 0; i < NTMAX; ++i) {
-        int row;
-        if (layer == 0) row = i < IN0 ? (i < nIn ? i : -1) : (i < IN0 + NC ? nIn + (i - IN0) : -1);
-        else row = i < 2 * NC ? i : -1;
-        w[i] = row >= 0 ? f32x2{Wl[(size_t)row * NO + lane], Wl[(size_t)row * NO + lane + 64]} : f32x2{0.f, 0.f};
-      }
-    }
-    const f32x2 bias = {W[L.indB + lane], W[L.indB + lane + 64]};
-    const int c = lane & 31;
-    float wr = 0.f, br = 0.f;
-    if (L.hasRes && c < L.resW) { wr = W[L.indWr + c]; br = W[L.indBr + c]; }
-    for (int e = tid; e < nSteps * dS; e += 128) {
-      const int kk = e / dS, i = e - kk * dS;
-      sStates[e] = (a.rp.S[(size_t)(slot - T + kk) * dS + i] - a.rp.stMean[i]) * a.rp.stScale[i];
-    }
+    f32x2 w[NTMAX], bias; float wr, br;
+    lstm32LoadColumns<IN0>(a, L, layer, lane, w, bias, wr, br);
+    wave32StageWindow<2 * NTMAX>(a, win, false, tid, sStates, &sV0[0][0], &sV1[0][0]);
     for (int e = tid; e < NC * ha.ldWo; e += 128) S.sWo[e] = ha.params[ha.indWo + e];
-    for (int i = tid; i < 2 * NTMAX; i += 128) (&sV0[0][0])[i] = 0.f;
-    for (int i = tid; i < 4 * NC; i += 128) (&sV1[0][0])[i] = 0.f;
     if (wv == 1 && lane < 32) { if (R.en < 8) S.sMisc[R.em][R.en] = R.hr.misc; if (R.en == 0) S.sActMsg[R.em] = R.hr.actMsg; }
-    SSTAMP(1);
-    vmDrain(); pairBarrier();
-    SSTAMP(2);
-    if (layer == 0 && lane < dS) sV0[0][lane] = sStates[lane];
-    pairBarrier();
-    float prevSt = 0.f;
-    for (int it = 0; it <= nSteps; ++it) {
-      SSTAMP(4 + it);
-      if (layer == 0) {
-        const int k = it;
-        if (k < nSteps) {
-          const int cb = k & 1;
-          if (k + 1 < nSteps && lane < dS) sV0[cb ^ 1][lane] = sStates[(k + 1) * dS + lane];
-          float blk = 0.f;
-          lstm32LayerStep<NTMAX, true>(L, w, bias, sV0[cb], IN0, nIn, prevSt, wr, br, &sV0[cb ^ 1][IN0], blk, k <= T, (long long)b * a.K + k, lane,
-                                       sAct + (0 * 17 + (k <= T ? k : 0)) * ACT);
-          if (lane < NC) sV1[cb][lane] = blk;
-        }
-      } else {
-        const int k = it - 1;
-        if (k < 0) R.hr.hoist(ha, boundedMask, R.bpv, R.live, R.en);       // (this wavefront has no layer-step yet)
-        else {
-          const int cb = k & 1;
-          float blk = 0.f;
-          lstm32LayerStep<NTMAX, true>(L, w, bias, sV1[cb], NC, NC, prevSt, wr, br, &sV1[cb ^ 1][NC], blk, k <= T, (long long)b * a.K + k, lane,
-                                       sAct + (1 * 17 + (k <= T ? k : 0)) * ACT);
-          if (lane < NC) {
-            if (k == T) { a.Yout[(size_t)b * a.ldY + lane] = blk; S.sYo[0][lane] = blk; }       // (memory: A operand of the output layer's weight gradient)
-            if (k == T + 1) S.sYo[1][lane] = blk;
-          }
-        }
-      }
-      pairBarrier();
-    }
+    wave32FirstOperand(win, layer, lane, a.dS, sStates, sV0[0]);
+    lstm32ForwardWindow<IN0, NTMAX, true>(a, L, win, layer, lane, true, w, bias, wr, br, sV0, sV1, sStates, sAct,
+      [&] { R.hr.hoist(ha, boundedMask, R.bpv, R.live, R.en); },
+      [&](int k, float blk) {
+        if (k == T) { a.Yout[(size_t)b * a.ldY + lane] = blk; S.sYo[0][lane] = blk; }       // (memory: A operand of the output layer's weight gradient)
+        if (k == T + 1) S.sYo[1][lane] = blk;
+      });
   }
-  SSTAMP(30);
+  REC_STAMP(b, 0, 30);
   // ======================================================= backward: weight rows requested now ==================================
   const int j = 1 - wv;                                    // wavefront 0 = the top layer (one step ahead), wavefront 1 = layer 0
   const RecLayer L = a.L[j];
-  f32x4 wq[NO / 4];
-  {
-    const f32x4* rw = reinterpret_cast<const f32x4*>(W + L.indW + (size_t)(j == 1 ? lane : nIn + (lane & 31)) * NO);
-#pragma unroll
-    for (int q = 0; q < NO / 4; ++q) wq[q] = rw[q];
-  }
-  const float wrB = (L.hasRes && lane < L.resW) ? W[L.indWr + lane] : 0.f;
-  for (int k = T + 1; k < a.K; ++k) {      // rows of the steps this sample does not have: zero deltas
-    const long long r = (long long)b * a.K + k;
-    L.D[r * NO + lane] = 0.f; L.D[r * NO + lane + 64] = 0.f;
-    if (L.hasRes && lane < NC) L.Rd[r * L.ldR + lane] = 0.f;
-  }
+  f32x4 wq[NO / 4]; float wrB;
+  lstm32LoadRow(a, L, j, lane, wq, wrB);
+  wave32ZeroRows<NO>(a, L, b, T, lane);
   // ======================================================= output layer + head (wavefront 1) ====================================
-  SSTAMP(31);
-  if (wv == 1) stepHeadRun(R, ha, S, lane, b, slot, nextRow);
-  if (wv == 1) SSTAMP1(32);
-  vmDrain(); pairBarrier();
-  SSTAMP(33);
+  REC_STAMP(b, 0, 31);
+  if (wv == 1) stepHeadRun(R, ha, S, lane, b, win.slot, win.nextRow);
+  if (wv == 1) REC_STAMP(b, 64, 32);
+  vmDrain(); ldsBarrier();
+  REC_STAMP(b, 0, 33);
   // ======================================================= back-propagation through time ========================================
-  {
-    const float dres = (j == 1 && lane < NC) ? S.sDres[lane] : 0.f;
-    float nxtSt = 0.f, nxtF = 0.f;
-    for (int it = 0; it <= T + 1; ++it) {
-      const int k = T - it + (j == 1 ? 0 : 1);
-      if (k >= 0 && k <= T) {
-        const long long r = (long long)b * a.K + k;
-        float res = 0.f;
-        if (lane < NC) {
-          const float eTop = j == 1 ? (k == T ? dres : 0.f) : sTop[k & 1][lane];
-          const float* act = sAct + (j * 17 + k) * ACT;
-          if (L.hasRes) { L.Rd[r * L.ldR + lane] = eTop; res = lane < L.resW ? eTop * wrB : 0.f; }
-          const float D = eTop + (k < T ? sRec[j][lane] : 0.f);
-          const float cellInpt = act[lane], IG = act[NC + lane], FG = act[2 * NC + lane], OG = act[3 * NC + lane], co = act[5 * NC + lane];
-          const float prevSt = k > 0 ? (act - ACT)[4 * NC + lane] : 0.f;
-          const float diff = (1.f - co * co) * D;
-          const float sd = diff * OG + (k < T ? nxtSt * nxtF : 0.f);
-          const float d0 = IG * sd;
-          const float d1 = IG * (1.f - IG) * cellInpt * sd;
-          const float d2 = k > 0 ? FG * (1.f - FG) * prevSt * sd : 0.f;
-          const float d3 = OG * (1.f - OG) * D * co;
-          sD[j][lane] = d0; sD[j][NC + lane] = d1; sD[j][2 * NC + lane] = d2; sD[j][3 * NC + lane] = d3;
-          nxtSt = sd; nxtF = FG;
-        }
-        waveLdsSync();
-        { const float u0 = sD[j][lane], u1 = sD[j][64 + lane]; L.D[r * NO + lane] = u0; L.D[r * NO + 64 + lane] = u1; }      // the row for the weight gradients: two whole-wavefront stores
-        if (j == 1 || k > 0) {
-          const f32x4* d4 = reinterpret_cast<const f32x4*>(sD[j]);
-          f32x2 p0 = {0.f, 0.f}, p1 = {0.f, 0.f}, p2 = {0.f, 0.f}, p3 = {0.f, 0.f};
-#pragma unroll
-          for (int h0 = 0; h0 < NO / 4; h0 += NO / 8) {
-            f32x4 dq[NO / 8];
-#pragma unroll
-            for (int q = 0; q < NO / 8; ++q) dq[q] = d4[h0 + q];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < NO / 8; q += 2) {
-              const f32x4 da = dq[q], db = dq[q + 1];
-              p0 += f32x2{wq[h0 + q][0], wq[h0 + q][1]} * f32x2{da[0], da[1]}; p1 += f32x2{wq[h0 + q][2], wq[h0 + q][3]} * f32x2{da[2], da[3]};
-              p2 += f32x2{wq[h0 + q + 1][0], wq[h0 + q + 1][1]} * f32x2{db[0], db[1]}; p3 += f32x2{wq[h0 + q + 1][2], wq[h0 + q + 1][3]} * f32x2{db[2], db[3]};
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          const f32x2 ps = (p0 + p1) + (p2 + p3);
-          const float e = ps[0] + ps[1];
-          if (j == 1) { if (lane < NC) sTop[k & 1][lane] = res + e; else sRec[1][lane - NC] = e; }
-          else if (lane < NC) sRec[0][lane] = e;
-        }
-      }
-      pairBarrier();
-    }
-  }
-  SSTAMP(250);
+  lstm32BackwardWindow(a, L, j, b, T, lane, wq, wrB, (j == 1 && lane < NC) ? S.sDres[lane] : 0.f, sAct, sD, sTop, sRec);
+  REC_STAMP(b, 0, 250);
 }
 
 // ---- MGU, two layers of 32 cells: the same arrangement ---------------------------------------------------------------------
@@ -1350,47 +1311,27 @@ __device__ __forceinline__ void mgu32LayerStep(const RecLayer& L, const float (&
   }
 }
 
-template <int IN0>
-__global__ __launch_bounds__(128) void mgu32_forward_wave_kernel(RecArgs a) {
+// this lane's gate column of its layer, input part (zeros behind the layer's own inputs) and recurrent part; bias, residual scalars
+__device__ __forceinline__ void mgu32LoadColumns(const RecArgs& a, const RecLayer& L, int layer, int lane, float (&win)[32], float (&wrec)[32], float& bias, float& wr, float& br) {
   constexpr int NC = 32, NO = 64;
-  __shared__ __attribute__((aligned(16))) float sV0[2][IN0 + NC];      // layer 0 operand [x_k | h0_{k-1}], double-buffered over the steps
-  __shared__ __attribute__((aligned(16))) float sV1[2][2 * NC];        // layer 1 operand [block-0 output of step k | h1_{k-1}]
-  __shared__ __attribute__((aligned(16))) float sHF[2][NC];            // prevOut * forget, per layer
-  __shared__ float sStates[18 * 32];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int layer = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool acting = a.actStates != nullptr;                          // rollout inference: the agent's last states, nothing stored
-  const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
-  const int nextRow = acting ? -1 : a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
   const float* W = a.W;
-  const RecLayer L = a.L[layer];
-  const int nIn = a.L[0].nIn, dS = a.dS;
-  float win[32], wrec[32];
-  {
-    const float* Wl = W + L.indW;
-    const int nInL = layer == 0 ? nIn : NC;
+  const float* Wl = W + L.indW;
+  const int nInL = layer == 0 ? a.L[0].nIn : NC;
 #pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      win[i] = i < nInL ? Wl[(size_t)i * NO + lane] : 0.f;
-      wrec[i] = Wl[(size_t)(nInL + i) * NO + lane];
-    }
+  for (int i = 0; i < 32; ++i) {
+    win[i] = i < nInL ? Wl[(size_t)i * NO + lane] : 0.f;
+    wrec[i] = Wl[(size_t)(nInL + i) * NO + lane];
   }
-  const float bias = W[L.indB + lane];
-  const int c = lane & 31;
-  float wr = 0.f, br = 0.f;
-  if (L.hasRes && c < L.resW) { wr = W[L.indWr + c]; br = W[L.indBr + c]; }
-  for (int e = tid; e < nSteps * dS; e += 128) {
-    const int kk = e / dS, i = e - kk * dS;
-    const float raw = acting ? a.actStates[e] : a.rp.S[(size_t)(slot - T + kk) * dS + i];
-    sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
-  }
-  for (int i = tid; i < 2 * (IN0 + NC); i += 128) (&sV0[0][0])[i] = 0.f;
-  for (int i = tid; i < 4 * NC; i += 128) (&sV1[0][0])[i] = 0.f;
-  vmDrain(); pairBarrier();
-  if (layer == 0 && lane < dS) sV0[0][lane] = sStates[lane];
-  pairBarrier();
+  bias = W[L.indB + lane];
+  wave32ResScalars(L, W, lane, wr, br);
+}
+// the window forward (see lstm32ForwardWindow: the same skew, `store`, LDSACT into sAct [2][17][ACT], idle() and top(k, blk)); sHF: prevOut * forget, per layer
+template <int IN0, bool LDSACT, class Idle, class Top>
+__device__ __forceinline__ void mgu32ForwardWindow(const RecArgs& a, const RecLayer& L, const WaveWin& win, int layer, int lane, bool store, const float (&wIn)[32],
+                                                   const float (&wrec)[32], float bias, float wr, float br, float (*sV0)[IN0 + 32], float (*sV1)[64], float (*sHF)[32],
+                                                   const float* sStates, float* sAct, Idle idle, Top top) {
+  constexpr int NC = 32, ACT = 3 * NC;
+  const int nIn = a.L[0].nIn, dS = a.dS, T = win.T, nSteps = win.nSteps;
   for (int it = 0; it <= nSteps; ++it) {
     if (layer == 0) {
       const int k = it;
@@ -1398,28 +1339,94 @@ __global__ __launch_bounds__(128) void mgu32_forward_wave_kernel(RecArgs a) {
         const int cb = k & 1;
         if (k + 1 < nSteps && lane < dS) sV0[cb ^ 1][lane] = sStates[(k + 1) * dS + lane];
         float blk = 0.f;
-        mgu32LayerStep<IN0>(L, win, wrec, bias, sV0[cb], sHF[0], nIn, wr, br, &sV0[cb ^ 1][IN0], blk, !acting && k <= T, (long long)b * a.K + k, lane);
+        mgu32LayerStep<IN0, LDSACT>(L, wIn, wrec, bias, sV0[cb], sHF[0], nIn, wr, br, &sV0[cb ^ 1][IN0], blk, store && k <= T, (long long)win.b * a.K + k, lane,
+                                    LDSACT ? sAct + (0 * 17 + (k <= T ? k : 0)) * ACT : nullptr);
         if (lane < NC) sV1[cb][lane] = blk;
       }
     } else {
       const int k = it - 1;
-      if (k >= 0) {
+      if (k < 0) idle();
+      else {
         const int cb = k & 1;
         float blk = 0.f;
-        mgu32LayerStep<NC>(L, win, wrec, bias, sV1[cb], sHF[1], NC, wr, br, &sV1[cb ^ 1][NC], blk, !acting && k <= T, (long long)b * a.K + k, lane);
-        if (lane < NC) {
-          if (k == T) a.Yout[(size_t)b * a.ldY + lane] = blk;
-          if (k == T + 1) a.Yout[(size_t)nextRow * a.ldY + lane] = blk;
-        }
+        mgu32LayerStep<NC, LDSACT>(L, wIn, wrec, bias, sV1[cb], sHF[1], NC, wr, br, &sV1[cb ^ 1][NC], blk, store && k <= T, (long long)win.b * a.K + k, lane,
+                                   LDSACT ? sAct + (1 * 17 + (k <= T ? k : 0)) * ACT : nullptr);
+        if (lane < NC) top(k, blk);
       }
     }
-    pairBarrier();
+    ldsBarrier();
+  }
+}
+// backward (MGULayer::backward, Layer_GRU.h:126-231): lane i holds ROW i of [W_in; W_rec] (32 forget + 32 candidate columns); the
+// top layer's lanes 0..31 are its input rows, 32..63 its recurrent rows; layer 0 needs its recurrent rows only (lanes 0..31)
+__device__ __forceinline__ void mgu32LoadRow(const RecArgs& a, const RecLayer& L, int j, int lane, float (&wf)[32], float (&ws)[32], float& wr) {
+  const f32x4* rw = wave32WeightRow<64>(a, L, j, lane);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { const f32x4 u = rw[q], v = rw[8 + q]; wf[4 * q] = u[0]; wf[4 * q + 1] = u[1]; wf[4 * q + 2] = u[2]; wf[4 * q + 3] = u[3];
+                                ws[4 * q] = v[0]; ws[4 * q + 1] = v[1]; ws[4 * q + 2] = v[2]; ws[4 * q + 3] = v[3]; }
+  wr = wave32ResRowWeight(a, L, lane);
+}
+// back-propagation through time (the skew of lstm32BackwardWindow).  sAct [2][17][ACT]: per (layer, step) [forget | candidate | output];
+// wf / ws: this lane's row, forget / candidate columns; sDS / sDF: the deltas of the layer-step, per layer
+__device__ __forceinline__ void mgu32BackwardWindow(const RecArgs& a, const RecLayer& L, int j, int b, int T, int lane, const float (&wf)[32], const float (&ws)[32], float wr,
+                                                    float dres, const float* sAct, float (*sDS)[32], float (*sDF)[32], float (*sTop)[32], float (*sRec)[32]) {
+  constexpr int NC = 32, NO = 64, ACT = 3 * NC;
+  for (int it = 0; it <= T + 1; ++it) {
+    const int k = T - it + (j == 1 ? 0 : 1);
+    if (k >= 0 && k <= T) {
+      const long long r = (long long)b * a.K + k;
+      float res = 0.f, dLdO = 0.f, f = 0.f, sc = 0.f, po = 0.f, dS_ = 0.f;
+      if (lane < NC) {
+        const float* act = sAct + (j * 17 + k) * ACT;
+        dLdO = wave32OutputError(L, j, k, T, r, lane, dres, wr, sTop, sRec, res);
+        f = act[lane]; sc = act[NC + lane]; po = k > 0 ? (act - ACT)[2 * NC + lane] : 0.f;
+        dS_ = dLdO * f * (1.f - sc * sc);                                         // 1) dLdS
+        sDS[j][lane] = dS_;
+      }
+      waveLdsSync();
+      const float viaS = dotIn<NC>(ws, sDS[j]);                                    // row i: sum_o W[i][nC + o] dLdS[o]
+      float fp = j == 1 ? fromUpperHalf(viaS) : viaS;                              // 2) dLdFprevOut of cell c = the recurrent row nIn + c
+      if (k == 0) fp = 0.f;
+      if (lane < NC) {
+        const float dF = ((sc - po) * dLdO + fp * po) * f * (1.f - f);             // 3) dLdF
+        sDF[j][lane] = dF;
+      }
+      waveLdsSync();
+      L.D[r * NO + lane] = lane < NC ? sDF[j][lane] : sDS[j][lane - NC];          // the row for the weight gradients [dLdF | dLdS]: one whole-wavefront store
+      const float viaF = dotIn<NC>(wf, sDF[j]);                                    // row i: sum_o W[i][o] dLdF[o]
+      const float g = j == 1 ? fromUpperHalf(viaF) : viaF;
+      if (lane < NC) {
+        if (j == 1) sTop[k & 1][lane] = (res + viaF) + viaS;                       // error of block 0's output (+ the residual path)
+        if (k > 0) sRec[j][lane] = ((1.f - f) * dLdO + f * fp) + g;                // 4) dLdprevOut
+      }
+    }
+    ldsBarrier();
   }
 }
 
-// backward (MGULayer::backward, Layer_GRU.h:126-231): lane i holds ROW i of [W_in; W_rec] (32 forget + 32 candidate columns); the
-// top layer's lanes 0..31 are its input rows, 32..63 its recurrent rows; layer 0 needs its recurrent rows only (lanes 0..31)
 template <int IN0>
+__global__ __launch_bounds__(128) void mgu32_forward_wave_kernel(RecArgs a) {
+  constexpr int NC = 32;
+  __shared__ __attribute__((aligned(16))) float sV0[2][IN0 + NC];      // layer 0 operand [x_k | h0_{k-1}], double-buffered over the steps
+  __shared__ __attribute__((aligned(16))) float sV1[2][2 * NC];        // layer 1 operand [block-0 output of step k | h1_{k-1}]
+  __shared__ __attribute__((aligned(16))) float sHF[2][NC];            // prevOut * forget, per layer
+  __shared__ float sStates[18 * 32];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int layer = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool acting = a.actStates != nullptr;                          // rollout inference: the agent's last states, nothing stored
+  const WaveWin win = wave32Window(a, b, acting);
+  const RecLayer L = a.L[layer];
+  float wIn[32], wrec[32], bias, wr, br;
+  mgu32LoadColumns(a, L, layer, lane, wIn, wrec, bias, wr, br);
+  wave32StageWindow<2 * (IN0 + NC)>(a, win, acting, tid, sStates, &sV0[0][0], &sV1[0][0]);
+  wave32FirstOperand(win, layer, lane, a.dS, sStates, sV0[0]);
+  mgu32ForwardWindow<IN0, false>(a, L, win, layer, lane, !acting, wIn, wrec, bias, wr, br, sV0, sV1, sHF, sStates, nullptr, [] {},
+    [&](int k, float blk) {
+      if (k == win.T) a.Yout[(size_t)b * a.ldY + lane] = blk;
+      if (k == win.T + 1) a.Yout[(size_t)win.nextRow * a.ldY + lane] = blk;
+    });
+}
+
 __global__ __launch_bounds__(128) void mgu32_backward_wave_kernel(RecArgs a) {
   constexpr int NC = 32, NO = 64, ACT = 3 * NC;            // per (step, layer): [forget | candidate | output]
   __shared__ __attribute__((aligned(16))) float sDS[2][NC], sDF[2][NC];
@@ -1429,18 +1436,10 @@ __global__ __launch_bounds__(128) void mgu32_backward_wave_kernel(RecArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = 1 - wv;                                    // wavefront 0 = the top layer (one step ahead), wavefront 1 = layer 0
-  const int t = a.bt.t[b];
-  const int T = min(a.nBPTT, t);
-  const float* W = a.W;
+  const int T = min(a.nBPTT, a.bt.t[b]);
   const RecLayer L = a.L[j];
-  const int nIn0 = a.L[0].nIn;
-  float wf[32], ws[32];                                    // this lane's row: forget columns, candidate columns
-  {
-    const f32x4* rw = reinterpret_cast<const f32x4*>(W + L.indW + (size_t)(j == 1 ? lane : nIn0 + (lane & 31)) * NO);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { const f32x4 u = rw[q], v = rw[8 + q]; wf[4 * q] = u[0]; wf[4 * q + 1] = u[1]; wf[4 * q + 2] = u[2]; wf[4 * q + 3] = u[3];
-                                  ws[4 * q] = v[0]; ws[4 * q + 1] = v[1]; ws[4 * q + 2] = v[2]; ws[4 * q + 3] = v[3]; }
-  }
+  float wf[32], ws[32], wr;                                // this lane's row: forget columns, candidate columns
+  mgu32LoadRow(a, L, j, lane, wf, ws, wr);
   {
     const int total = (T + 1) * ACT;
     for (int e = lane; e < total; e += 64) {
@@ -1449,55 +1448,17 @@ __global__ __launch_bounds__(128) void mgu32_backward_wave_kernel(RecArgs a) {
       sAct[j][e] = x < NO ? L.X[r * NO + x] : L.Y[r * NO + (x - NO)];
     }
   }
-  const float wr = (L.hasRes && lane < L.resW) ? W[L.indWr + lane] : 0.f;
   const float dres = (j == 1 && lane < NC) ? a.Dres[(size_t)b * a.ldD + lane] : 0.f;
-  for (int k = T + 1; k < a.K; ++k) {
-    const long long r = (long long)b * a.K + k;
-    L.D[r * NO + lane] = 0.f;
-    if (L.hasRes && lane < NC) L.Rd[r * L.ldR + lane] = 0.f;
-  }
-  vmDrain(); pairBarrier();
-  for (int it = 0; it <= T + 1; ++it) {
-    const int k = T - it + (j == 1 ? 0 : 1);
-    if (k >= 0 && k <= T) {
-      const long long r = (long long)b * a.K + k;
-      float res = 0.f, dLdO = 0.f, f = 0.f, sc = 0.f, po = 0.f, dS_ = 0.f;
-      if (lane < NC) {
-        const float eTop = j == 1 ? (k == T ? dres : 0.f) : sTop[k & 1][lane];
-        const float* act = sAct[j] + k * ACT;
-        if (L.hasRes) { L.Rd[r * L.ldR + lane] = eTop; res = lane < L.resW ? eTop * wr : 0.f; }
-        dLdO = eTop + (k < T ? sRec[j][lane] : 0.f);
-        f = act[lane]; sc = act[NC + lane]; po = k > 0 ? (act - ACT)[2 * NC + lane] : 0.f;
-        dS_ = dLdO * f * (1.f - sc * sc);                                         // 1) dLdS
-        sDS[j][lane] = dS_;
-      }
-      waveLdsSync();
-      const float viaS = dotIn<NC>(ws, sDS[j]);                                    // row i: sum_o W[i][nC + o] dLdS[o]
-      // 2) dLdFprevOut of cell c = the recurrent row nIn + c
-      float fp = j == 1 ? fromUpperHalf(viaS) : viaS;
-      if (k == 0) fp = 0.f;
-      if (lane < NC) {
-        const float dF = ((sc - po) * dLdO + fp * po) * f * (1.f - f);             // 3) dLdF
-        sDF[j][lane] = dF;
-        L.D[r * NO + lane] = dF; L.D[r * NO + NC + lane] = dS_;
-      }
-      waveLdsSync();
-      const float viaF = dotIn<NC>(wf, sDF[j]);                                    // row i: sum_o W[i][o] dLdF[o]
-      const float g = j == 1 ? fromUpperHalf(viaF) : viaF;
-      if (lane < NC) {
-        if (j == 1) sTop[k & 1][lane] = (res + viaF) + viaS;                       // error of block 0's output (+ the residual path)
-        if (k > 0) sRec[j][lane] = ((1.f - f) * dLdO + f * fp) + g;                // 4) dLdprevOut
-      }
-    }
-    pairBarrier();
-  }
+  wave32ZeroRows<NO>(a, L, b, T, lane);
+  vmDrain(); ldsBarrier();
+  mgu32BackwardWindow(a, L, j, b, T, lane, wf, ws, wr, dres, &sAct[0][0], sDS, sDF, sTop, sRec);
 }
 
 // ---- the MGU form of the one-launch step (see lstm32_step_wave_kernel): window forward, output layer + head, back-propagation through
 // time of a sample in one workgroup; forget gates, candidates and outputs of the window stay in LDS ---------------------------------
 template <int IN0>
 __global__ __launch_bounds__(256) void mgu32_step_wave_kernel(RecArgs a, HeadArgs ha, unsigned long long boundedMask, ExtraArgs extra) {
-  constexpr int NC = 32, NO = 64, ACT = 3 * NC;            // per (step, layer): [forget | candidate | output]
+  constexpr int NC = 32, ACT = 3 * NC;                     // per (step, layer): [forget | candidate | output]
   constexpr int O_V0 = 2 * 17 * ACT * 4, O_V1 = O_V0 + 2 * (IN0 + NC) * 4, O_HF = O_V1 + 2 * 64 * 4, O_ST = O_HF + 2 * NC * 4, O_DS = O_ST + 18 * 32 * 4,
                 O_DF = O_DS + 2 * NC * 4, O_TOP = O_DF + 2 * NC * 4, O_REC = O_TOP + 2 * NC * 4, O_HEAD = O_REC + 2 * NC * 4, TOTAL = O_HEAD + STEP_HEAD_LDS;
   static_assert(O_HEAD % 16 == 0 && O_V0 % 16 == 0 && O_V1 % 16 == 0 && O_HF % 16 == 0 && O_DS % 16 == 0 && O_DF % 16 == 0, "alignment of the 16-byte reads");
@@ -1516,127 +1477,38 @@ __global__ __launch_bounds__(256) void mgu32_step_wave_kernel(RecArgs a, HeadArg
 
   const int b = blockIdx.x - (extra.role ? 1 : 0), tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = a.bt.t[b]; const long long slot = a.bt.slot[b];
-  const int T = min(a.nBPTT, t);
-  const int nextRow = a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
-  const float* W = a.W;
-  const int nIn = a.L[0].nIn, dS = a.dS;
+  const WaveWin win = wave32Window(a, b, false);
+  const int T = win.T;
   StepHeadRegs R;
-  stepHeadLoad(R, ha, a.sc, wv, lane, slot, nextRow);
+  stepHeadLoad(R, ha, a.sc, wv, lane, win.slot, win.nextRow);
   {
     // ================================================ forward over the window ==================================================
     const int layer = wv;
     const RecLayer L = a.L[layer];
-    float win[32], wrec[32];
-    {
-      const float* Wl = W + L.indW;
-      const int nInL = layer == 0 ? nIn : NC;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        win[i] = i < nInL ? Wl[(size_t)i * NO + lane] : 0.f;
-        wrec[i] = Wl[(size_t)(nInL + i) * NO + lane];
-      }
-    }
-    const float bias = W[L.indB + lane];
-    const int c = lane & 31;
-    float wr = 0.f, br = 0.f;
-    if (L.hasRes && c < L.resW) { wr = W[L.indWr + c]; br = W[L.indBr + c]; }
-    for (int e = tid; e < nSteps * dS; e += 128) {
-      const int kk = e / dS, i = e - kk * dS;
-      sStates[e] = (a.rp.S[(size_t)(slot - T + kk) * dS + i] - a.rp.stMean[i]) * a.rp.stScale[i];
-    }
+    float wIn[32], wrec[32], bias, wr, br;
+    mgu32LoadColumns(a, L, layer, lane, wIn, wrec, bias, wr, br);
+    wave32StageWindow<2 * (IN0 + NC)>(a, win, false, tid, sStates, &sV0[0][0], &sV1[0][0]);
     for (int e = tid; e < NC * ha.ldWo; e += 128) S.sWo[e] = ha.params[ha.indWo + e];
-    for (int i = tid; i < 2 * (IN0 + NC); i += 128) (&sV0[0][0])[i] = 0.f;
-    for (int i = tid; i < 4 * NC; i += 128) (&sV1[0][0])[i] = 0.f;
     if (wv == 1 && lane < 32) { if (R.en < 8) S.sMisc[R.em][R.en] = R.hr.misc; if (R.en == 0) S.sActMsg[R.em] = R.hr.actMsg; }
-    vmDrain(); pairBarrier();
-    if (layer == 0 && lane < dS) sV0[0][lane] = sStates[lane];
-    pairBarrier();
-    for (int it = 0; it <= nSteps; ++it) {
-      if (layer == 0) {
-        const int k = it;
-        if (k < nSteps) {
-          const int cb = k & 1;
-          if (k + 1 < nSteps && lane < dS) sV0[cb ^ 1][lane] = sStates[(k + 1) * dS + lane];
-          float blk = 0.f;
-          mgu32LayerStep<IN0, true>(L, win, wrec, bias, sV0[cb], sHF[0], nIn, wr, br, &sV0[cb ^ 1][IN0], blk, k <= T, (long long)b * a.K + k, lane,
-                                    sAct + (0 * 17 + (k <= T ? k : 0)) * ACT);
-          if (lane < NC) sV1[cb][lane] = blk;
-        }
-      } else {
-        const int k = it - 1;
-        if (k < 0) R.hr.hoist(ha, boundedMask, R.bpv, R.live, R.en);       // (this wavefront has no layer-step yet)
-        else {
-          const int cb = k & 1;
-          float blk = 0.f;
-          mgu32LayerStep<NC, true>(L, win, wrec, bias, sV1[cb], sHF[1], NC, wr, br, &sV1[cb ^ 1][NC], blk, k <= T, (long long)b * a.K + k, lane,
-                                   sAct + (1 * 17 + (k <= T ? k : 0)) * ACT);
-          if (lane < NC) {
-            if (k == T) { a.Yout[(size_t)b * a.ldY + lane] = blk; S.sYo[0][lane] = blk; }
-            if (k == T + 1) S.sYo[1][lane] = blk;
-          }
-        }
-      }
-      pairBarrier();
-    }
+    wave32FirstOperand(win, layer, lane, a.dS, sStates, sV0[0]);
+    mgu32ForwardWindow<IN0, true>(a, L, win, layer, lane, true, wIn, wrec, bias, wr, br, sV0, sV1, sHF, sStates, sAct,
+      [&] { R.hr.hoist(ha, boundedMask, R.bpv, R.live, R.en); },
+      [&](int k, float blk) {
+        if (k == T) { a.Yout[(size_t)b * a.ldY + lane] = blk; S.sYo[0][lane] = blk; }
+        if (k == T + 1) S.sYo[1][lane] = blk;
+      });
   }
   // ======================================================= backward: weight rows requested now ==================================
   const int j = 1 - wv;                                    // wavefront 0 = the top layer (one step ahead), wavefront 1 = layer 0
   const RecLayer L = a.L[j];
-  float wf[32], ws[32];                                    // this lane's row: forget columns, candidate columns
-  {
-    const f32x4* rw = reinterpret_cast<const f32x4*>(W + L.indW + (size_t)(j == 1 ? lane : nIn + (lane & 31)) * NO);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { const f32x4 u = rw[q], v = rw[8 + q]; wf[4 * q] = u[0]; wf[4 * q + 1] = u[1]; wf[4 * q + 2] = u[2]; wf[4 * q + 3] = u[3];
-                                  ws[4 * q] = v[0]; ws[4 * q + 1] = v[1]; ws[4 * q + 2] = v[2]; ws[4 * q + 3] = v[3]; }
-  }
-  const float wrB = (L.hasRes && lane < L.resW) ? W[L.indWr + lane] : 0.f;
-  for (int k = T + 1; k < a.K; ++k) {
-    const long long r = (long long)b * a.K + k;
-    L.D[r * NO + lane] = 0.f;
-    if (L.hasRes && lane < NC) L.Rd[r * L.ldR + lane] = 0.f;
-  }
+  float wf[32], ws[32], wrB;                               // this lane's row: forget columns, candidate columns
+  mgu32LoadRow(a, L, j, lane, wf, ws, wrB);
+  wave32ZeroRows<64>(a, L, b, T, lane);
   // ======================================================= output layer + head (wavefront 1) ====================================
-  if (wv == 1) stepHeadRun(R, ha, S, lane, b, slot, nextRow);
-  vmDrain(); pairBarrier();
+  if (wv == 1) stepHeadRun(R, ha, S, lane, b, win.slot, win.nextRow);
+  vmDrain(); ldsBarrier();
   // ======================================================= back-propagation through time ========================================
-  {
-    const float dres = (j == 1 && lane < NC) ? S.sDres[lane] : 0.f;
-    for (int it = 0; it <= T + 1; ++it) {
-      const int k = T - it + (j == 1 ? 0 : 1);
-      if (k >= 0 && k <= T) {
-        const long long r = (long long)b * a.K + k;
-        float res = 0.f, dLdO = 0.f, f = 0.f, sc = 0.f, po = 0.f, dS_ = 0.f;
-        if (lane < NC) {
-          const float eTop = j == 1 ? (k == T ? dres : 0.f) : sTop[k & 1][lane];
-          const float* act = sAct + (j * 17 + k) * ACT;
-          if (L.hasRes) { L.Rd[r * L.ldR + lane] = eTop; res = lane < L.resW ? eTop * wrB : 0.f; }
-          dLdO = eTop + (k < T ? sRec[j][lane] : 0.f);
-          f = act[lane]; sc = act[NC + lane]; po = k > 0 ? (act - ACT)[2 * NC + lane] : 0.f;
-          dS_ = dLdO * f * (1.f - sc * sc);                                         // 1) dLdS
-          sDS[j][lane] = dS_;
-        }
-        waveLdsSync();
-        const float viaS = dotIn<NC>(ws, sDS[j]);                                    // row i: sum_o W[i][nC + o] dLdS[o]
-        float fp = j == 1 ? fromUpperHalf(viaS) : viaS;                              // 2) dLdFprevOut of cell c = the recurrent row nIn + c
-        if (k == 0) fp = 0.f;
-        if (lane < NC) {
-          const float dF = ((sc - po) * dLdO + fp * po) * f * (1.f - f);             // 3) dLdF
-          sDF[j][lane] = dF;
-        }
-        waveLdsSync();
-        L.D[r * NO + lane] = lane < NC ? sDF[j][lane] : sDS[j][lane - NC];          // the row for the weight gradients [dLdF | dLdS]: one whole-wavefront store
-        const float viaF = dotIn<NC>(wf, sDF[j]);                                    // row i: sum_o W[i][o] dLdF[o]
-        const float g = j == 1 ? fromUpperHalf(viaF) : viaF;
-        if (lane < NC) {
-          if (j == 1) sTop[k & 1][lane] = (res + viaF) + viaS;                       // error of block 0's output (+ the residual path)
-          if (k > 0) sRec[j][lane] = ((1.f - f) * dLdO + f * fp) + g;                // 4) dLdprevOut
-        }
-      }
-      pairBarrier();
-    }
-  }
+  mgu32BackwardWindow(a, L, j, b, T, lane, wf, ws, wrB, (j == 1 && lane < NC) ? S.sDres[lane] : 0.f, sAct, sDS, sDF, sTop, sRec);
 }
 
 // ---- nnType "RNN": dense layers with a recurrent term (BaseLayer with bRecurrent; Network/Builder.cpp:76-81,
@@ -1840,14 +1712,20 @@ static size_t rnnLdsBytes(const RecArgs& a) {
   return fl * sizeof(float);
 }
 
-static bool mgu32Wave(const RecArgs& a) {
-  return a.gates == 2 && (a.actStates == nullptr || a.actSteps <= 17) && a.nL == 2 && a.L[0].nC == 32 && a.L[1].nC == 32 && a.L[1].nIn == 32 &&
+// the wave-per-(sample, layer) kernels serve two LSTM (gates = 4) or MGU (2) layers of 32 cells each over up to 32 inputs and 17 steps
+static bool wave32(const RecArgs& a, int gates) {      // (forward: training windows and rollout inference; backward: training only)
+  return a.gates == gates && (a.actStates == nullptr || a.actSteps <= 17) && a.nL == 2 && a.L[0].nC == 32 && a.L[1].nC == 32 && a.L[1].nIn == 32 &&
          a.L[0].nIn <= 32 && a.dS == a.L[0].nIn && a.K <= 17 && a.L[0].indW % 4 == 0 && a.L[1].indW % 4 == 0 && !a.L[0].hasRes;
 }
-// the wave-per-sample kernels serve the training pass of two LSTM layers of 32 cells each over up to 32 inputs and 17 steps
-static bool lstm32Wave(const RecArgs& a) {      // (forward: training windows and rollout inference; backward: training only)
-  return a.gates == 4 && (a.actStates == nullptr || a.actSteps <= 17) && a.nL == 2 && a.L[0].nC == 32 && a.L[1].nC == 32 && a.L[1].nIn == 32 &&
-         a.L[0].nIn <= 32 && a.dS == a.L[0].nIn && a.K <= 17 && a.L[0].indW % 4 == 0 && a.L[1].indW % 4 == 0 && !a.L[0].hasRes;
+// ... their forward and step kernels are instantiated for first-layer inputs padded to 4, 8, 16 and 32: launch(in0) with in0 a
+// std::integral_constant launches the kernel of the family for that width
+template <class Launch> static hipError_t launchWave32(const RecArgs& a, Launch launch) {
+  const int in0 = (a.L[0].nIn + 3) & ~3;
+  if (in0 <= 4) launch(std::integral_constant<int, 4>{});
+  else if (in0 <= 8) launch(std::integral_constant<int, 8>{});
+  else if (in0 <= 16) launch(std::integral_constant<int, 16>{});
+  else launch(std::integral_constant<int, 32>{});
+  return hipGetLastError();
 }
 // shapes only the one-gate-per-thread kernels serve: inputs other than the step's own observed state, layers wider than 64 cells
 static bool recGeneral(const RecArgs& a) {
@@ -1876,28 +1754,16 @@ hipError_t launch_rec_forward(const RecArgs& a, hipStream_t s) {
     if (a.gates == 2) return fit ? recLaunch(mgu_forward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_forward_kernel<false, 0>, a, 0, &attr[1], s);
     return fit ? recLaunch(rec_forward_kernel<true>, a, lds, &attr[2], s) : recLaunch(rec_forward_kernel<false>, a, 0, &attr[3], s);
   }
-  if (mgu32Wave(a)) {        // two layers of 32 cells, training pass: one wavefront per (sample, layer), weights in registers
-    const int in0 = (a.L[0].nIn + 3) & ~3;
-    if (in0 <= 4) hipLaunchKernelGGL(mgu32_forward_wave_kernel<4>, dim3(a.B), dim3(128), 0, s, a);
-    else if (in0 <= 8) hipLaunchKernelGGL(mgu32_forward_wave_kernel<8>, dim3(a.B), dim3(128), 0, s, a);
-    else if (in0 <= 16) hipLaunchKernelGGL(mgu32_forward_wave_kernel<16>, dim3(a.B), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(mgu32_forward_wave_kernel<32>, dim3(a.B), dim3(128), 0, s, a);
-    return hipGetLastError();
-  }
+  if (wave32(a, 2))          // two layers of 32 cells, training pass: one wavefront per (sample, layer), weights in registers
+    return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(mgu32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
   if (a.gates == 2) {
     static size_t attrM[4] = {0, 0, 0, 0};
     if (fit && a.nL == 1) return recLaunch(mgu_forward_kernel<true, 1>, a, lds, &attrM[1], s);
     if (fit && a.nL == 2) return recLaunch(mgu_forward_kernel<true, 2>, a, lds, &attrM[2], s);
     return fit ? recLaunch(mgu_forward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_forward_kernel<false, 0>, a, 0, &attr[1], s);
   }
-  if (lstm32Wave(a)) {      // two layers of 32 cells, training pass: one wavefront per sample, weights in registers
-    const int in0 = (a.L[0].nIn + 3) & ~3;
-    if (in0 <= 4) hipLaunchKernelGGL(lstm32_forward_wave_kernel<4>, dim3(a.B), dim3(128), 0, s, a);
-    else if (in0 <= 8) hipLaunchKernelGGL(lstm32_forward_wave_kernel<8>, dim3(a.B), dim3(128), 0, s, a);
-    else if (in0 <= 16) hipLaunchKernelGGL(lstm32_forward_wave_kernel<16>, dim3(a.B), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(lstm32_forward_wave_kernel<32>, dim3(a.B), dim3(128), 0, s, a);
-    return hipGetLastError();
-  }
+  if (wave32(a, 4))          // the same arrangement for LSTM layers
+    return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(lstm32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
   size_t fl = 0; bool al = true;
   for (int j = 0; j < a.nL; ++j) { fl += (size_t)4 * a.L[j].nC * lstmGeo(a.L[j].nIn, a.L[j].nC).ld; al = al && a.L[j].indW % 4 == 0 && a.L[j].nIn <= REC_MAXIN; }
   if (al && fl * sizeof(float) <= 120 * 1024) {
@@ -1917,7 +1783,7 @@ hipError_t launch_rec_forward(const RecArgs& a, hipStream_t s) {
 // dense outputs and 16 action components / options
 bool rec_step_fused_ok(const RecArgs& a, const HeadArgs& ha) {
   const int comps = ha.nOpt ? ha.nOpt : ha.dA;
-  return !recGeneral(a) && (lstm32Wave(a) || mgu32Wave(a)) && a.actStates == nullptr && a.YoutRows == nullptr && a.DresRows == nullptr && a.K <= 17 &&
+  return !recGeneral(a) && (wave32(a, 4) || wave32(a, 2)) && a.actStates == nullptr && a.YoutRows == nullptr && a.DresRows == nullptr && a.K <= 17 &&
          ha.H == 32 && ha.nDense <= 32 && ha.nOut <= 48 && comps <= 16 && ha.ldWo <= 40;
 }
 hipError_t launch_rec_step_fused(const RecArgs& a, const HeadArgs& ha, const ExtraArgs* extra, hipStream_t s) {
@@ -1925,19 +1791,8 @@ hipError_t launch_rec_step_fused(const RecArgs& a, const HeadArgs& ha, const Ext
   ExtraArgs ex{}; if (extra) ex = *extra;
   unsigned long long mask = 0; for (int c = 0; c < HL_MAX_DIMA && c < 64; ++c) if (ha.bounded[c]) mask |= 1ull << c;
   const dim3 grid(a.B + (ex.role ? 1 : 0)), block(ex.role ? 256 : 128);
-  const int in0 = (a.L[0].nIn + 3) & ~3;
-  if (a.gates == 2) {
-    if (in0 <= 4) hipLaunchKernelGGL(mgu32_step_wave_kernel<4>, grid, block, 0, s, a, ha, mask, ex);
-    else if (in0 <= 8) hipLaunchKernelGGL(mgu32_step_wave_kernel<8>, grid, block, 0, s, a, ha, mask, ex);
-    else if (in0 <= 16) hipLaunchKernelGGL(mgu32_step_wave_kernel<16>, grid, block, 0, s, a, ha, mask, ex);
-    else hipLaunchKernelGGL(mgu32_step_wave_kernel<32>, grid, block, 0, s, a, ha, mask, ex);
-    return hipGetLastError();
-  }
-  if (in0 <= 4) hipLaunchKernelGGL(lstm32_step_wave_kernel<4>, grid, block, 0, s, a, ha, mask, ex);
-  else if (in0 <= 8) hipLaunchKernelGGL(lstm32_step_wave_kernel<8>, grid, block, 0, s, a, ha, mask, ex);
-  else if (in0 <= 16) hipLaunchKernelGGL(lstm32_step_wave_kernel<16>, grid, block, 0, s, a, ha, mask, ex);
-  else hipLaunchKernelGGL(lstm32_step_wave_kernel<32>, grid, block, 0, s, a, ha, mask, ex);
-  return hipGetLastError();
+  if (a.gates == 2) return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(mgu32_step_wave_kernel<decltype(in0)::value>, grid, block, 0, s, a, ha, mask, ex); });
+  return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(lstm32_step_wave_kernel<decltype(in0)::value>, grid, block, 0, s, a, ha, mask, ex); });
 }
 hipError_t launch_rec_backward(const RecArgs& a, hipStream_t s) {
   if (rec_tm_ok(a)) return launch_rec_tm_backward(a, s);
@@ -1949,19 +1804,12 @@ hipError_t launch_rec_backward(const RecArgs& a, hipStream_t s) {
   }
   if (a.gates == 2) {
     static size_t attrM[4] = {0, 0, 0, 0};
-    if (mgu32Wave(a)) { hipLaunchKernelGGL(mgu32_backward_wave_kernel<32>, dim3(a.B), dim3(128), 0, s, a); return hipGetLastError(); }
+    if (wave32(a, 2)) { hipLaunchKernelGGL(mgu32_backward_wave_kernel, dim3(a.B), dim3(128), 0, s, a); return hipGetLastError(); }
     if (fit && a.nL == 1) return recLaunch(mgu_backward_kernel<true, 1>, a, lds, &attrM[1], s);
     if (fit && a.nL == 2) return recLaunch(mgu_backward_kernel<true, 2>, a, lds, &attrM[2], s);
     return fit ? recLaunch(mgu_backward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_backward_kernel<false, 0>, a, 0, &attr[1], s);
   }
-  if (lstm32Wave(a)) {
-    const int in0 = (a.L[0].nIn + 3) & ~3;
-    if (in0 <= 4) hipLaunchKernelGGL(lstm32_backward_wave_kernel<4>, dim3(a.B), dim3(128), 0, s, a);
-    else if (in0 <= 8) hipLaunchKernelGGL(lstm32_backward_wave_kernel<8>, dim3(a.B), dim3(128), 0, s, a);
-    else if (in0 <= 16) hipLaunchKernelGGL(lstm32_backward_wave_kernel<16>, dim3(a.B), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(lstm32_backward_wave_kernel<32>, dim3(a.B), dim3(128), 0, s, a);
-    return hipGetLastError();
-  }
+  if (wave32(a, 4)) { hipLaunchKernelGGL(lstm32_backward_wave_kernel, dim3(a.B), dim3(128), 0, s, a); return hipGetLastError(); }
   size_t fl = 0; bool al = true;
   for (int j = 0; j < a.nL; ++j) {
     fl += (size_t)(a.L[j].nIn + a.L[j].nC) * lstmBwdPitch(4 * a.L[j].nC) + (size_t)a.K * 6 * a.L[j].nC;

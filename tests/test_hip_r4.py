@@ -358,7 +358,33 @@ def test_one_launch_recurrent_step_random_shapes_match_oracle(hip_api, seed, mon
     assert G.scalars().nFarPolicySteps == T.scalars().nFarPolicySteps
 
 
-ATARI_KW = dict(dimS=7056, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=6, nAppendedObs=3,
+@pytest.mark.parametrize("dS", [4, 5, 8, 9, 16, 17])
+@pytest.mark.parametrize("nn_type", [capi.NN_LSTM, capi.NN_MGU], ids=["lstm", "mgu"])
+def test_recurrent_wave_kernels_at_every_input_width_rung(hip_api, nn_type, dS, monkeypatch):
+    """The wave kernels of two 32-cell layers are instantiated for first-layer inputs padded to 4, 8, 16 and 32 (rec.hip:
+    launchWave32); the seeds of the random test above leave the MGU kernels of the 8 rung unlaunched and test no rung at both of its
+    edges.  The last width of each rung and the first of the next, LSTM and MGU, short windows with truncated and terminated ends:
+    the one-launch step against the oracle, then the three-launch form (SMARTIES_HIP_GENERIC=4: the stand-alone forward and backward
+    kernels) against the one-launch form."""
+    kw = dict(dimS=dS, dimA=1, hidden=(32, 32), nnFunc="Tanh", batchSize=3, maxTotObsNum=8000, randSeed=17, nn_type=nn_type, nnBPTTseq=2,
+              adv_kind=capi.ADV_GAUSSIAN)
+    sc = synth_cfg(seed=23, dimS=dS, dimA=1, lenMin=2, lenMax=8, pTerm=0.5)
+    G, O = _pair(hip_api, kw, sc, 30)
+    for _ in range(3):
+        G.step(1); O.step(1)
+        _compare_step(G, O)
+    assert relinf(G.get_params()[0], O.get_params()[0]) < 2 * TOL32
+    monkeypatch.setenv("SMARTIES_HIP_GENERIC", "4")
+    T = capi.Learner(hip_api, capi.make_config(**kw))
+    T.init_weights(); fill_synth(T, sc, 30); T.initialize(); T.set_tap(True)
+    T.step(1); T.step(1); T.step(1)
+    assert np.array_equal(G.readback(capi.TAP_FLAT), T.readback(capi.TAP_FLAT))
+    assert np.array_equal(G.get_rng_state(), T.get_rng_state())
+    assert relinf(G.get_params()[0], T.get_params()[0]) < TOL32
+    assert G.scalars().nFarPolicySteps == T.scalars().nFarPolicySteps
+
+
+ATARI_KW =dict(dimS=7056, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=6, nAppendedObs=3,
                 conv=[(84, 84, 4, 8, 8, 4), (20, 20, 8, 16, 6, 2), (8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)],
                 hidden=(512,), nnFunc="Tanh", batchSize=16, maxTotObsNum=600, randSeed=11)
 ATARI_SC = dict(seed=9, dimS=7056, dimA=1, lenMin=4, lenMax=12, pTerm=0.5)
