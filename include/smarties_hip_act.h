@@ -13,8 +13,9 @@
  * Which call when:
  *   hl_forward            dense nets, n raw states (rows): one kernel for up to 64 agents.
  *   hl_forward_sequence   ONE agent's window, any net.  The cheapest call for a single agent of a recurrent net.
- *   hl_forward_sequences  n agents' windows, any net.  One launch (layers wider than 256 cells: one chain of launches) per chunk
- *                         of agents for the shapes listed below.
+ *   hl_forward_sequences  n agents' windows, any net.  Per chunk of agents one launch, or -- layers wider than 256 cells, recurrent
+ *                         layers behind convolutions, RNN encoder layers under MGU layers, nets of at most 256 cells whose window
+ *                         is beyond the one launch's 64 KB -- one chain of hl_forward_sequence's own launches (listed below).
  */
 #ifndef SMARTIES_HIP_ACT_H
 #define SMARTIES_HIP_ACT_H
@@ -27,8 +28,13 @@ extern "C" {
 
 /* agents per launch: the pinned staging of the library (states, window offsets, outputs, completion stamps) is sized once,
  * at the first acting call, for this many windows of nnBPTTseq + 1 + nAppendedObs states; a call with more agents is cut
- * into ceil(n / HL_ACT_SEQ_CHUNK) launches (layers wider than 256 cells: chunks of min(local batch size, HL_ACT_SEQ_CHUNK)) */
+ * into ceil(n / HL_ACT_SEQ_CHUNK) launches (the nets served by a chain of launches: chunks of min(local batch size,
+ * HL_ACT_SEQ_CHUNK)) */
 #define HL_ACT_SEQ_CHUNK 512
+/* recurrent layers behind convolutions: the stacked window rows of a chunk's agents (nnBPTTseq + 1 rows of
+ * dimS (1 + nAppendedObs) floats each) are staged in pinned host memory, and a chunk holds no more agents than fit this many
+ * bytes (512 agents of an 84 x 84 x 4 image window would pin hundreds of megabytes), though never fewer than one */
+#define HL_ACT_WIN_STAGE_BYTES (32u << 20)
 
 /* n agents.  n_steps[i] = min(nnBPTTseq, t_i) + 1 (+ up to nAppendedObs states in front), as for hl_forward_sequence.
  * states: the windows back to back, oldest state first in each (sum of n_steps[i] rows of dimS raw floats).
@@ -59,8 +65,19 @@ extern "C" {
  * buffers and a minibatch drawn ahead stay as they are.  The kernels and their order of summation are those of the
  * single-agent call, an agent's row of a tile does not see the other rows: bit-identical to hl_forward_sequence.
  * Dense nets: the [n][dimS (1 + nAppendedObs)] rows are built on the host and go through ONE hl_forward(n) call.
- * Looped, agent by agent through hl_forward_sequence's own route (bit-identical to it): recurrent layers behind
- * convolutions, RNN encoder layers under MGU layers (encoder_rnn).
+ * Batched, every other recurrent net -- recurrent layers behind convolutions, RNN encoder layers under MGU layers (encoder_rnn),
+ * nets of at most 256 cells whose window exceeds the 64 KB above; every layer <= 256 cells with <= 1024 inputs --: agent i of a
+ * chunk is sample i of ONE chain of hl_forward_sequence's own launches.  Its window kernels run a workgroup per sample; here
+ * workgroup i takes agent i's window from a per-agent table of offsets and lengths and walks that window alone (no padding to
+ * the chunk's longest), the two launches of an encoder_rnn stack and the output layer follow on the chunk's rows.  Behind
+ * convolutions the host stacks the rows of all agents of the chunk (agent i's window step k at row i (nnBPTTseq + 1) + k, the
+ * rows of steps a window lacks repeating its last one) and they pass the convolutional front as one set of launches.  A chunk
+ * holds min(local batch size, HL_ACT_SEQ_CHUNK) agents -- the chain borrows the training rows of that many samples -- and behind
+ * convolutions no more than HL_ACT_WIN_STAGE_BYTES of staged rows allow.  The same kernels on the same rows in the same order
+ * of summation: bit-identical to hl_forward_sequence.  Behind convolutions a minibatch drawn ahead is dropped and drawn again
+ * with the same generator state, as by hl_forward_sequence.
+ * Looped, agent by agent through hl_forward_sequence's own route: only a net beyond those bounds (more than 1024 inputs to the
+ * first recurrent layer) which the time-step-major launches do not take either.
  *
  * For a single agent the call costs more than hl_forward_sequence (which runs the window with the weights in registers
  * where the shape allows): hl_forward_sequence stays the call for one agent. */

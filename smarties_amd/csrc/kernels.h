@@ -79,8 +79,9 @@ struct RecArgs {
   const float* Dres; int ldD;      // head: gradient w.r.t. Yout, rows < B
   const float* actStates; int actSteps;   // acting (hl_forward_sequence): raw states of the agent's last steps instead of a minibatch
   int actCtx;                      // ... of which the first actCtx lie in front of the window (they only feed appended observations)
-  const int* actOff; const int* actCnt;   // != nullptr: acting for B agents (hl_forward_sequences, rectm.hip): agent b's actCnt[b] states start at state actOff[b] of
-                                          // actStates; its window and context follow from its count, actSteps = the longest window of the B
+  const int* actOff; const int* actCnt;   // != nullptr: acting for B agents (hl_forward_sequences; rectm.hip and the workgroup-per-sample forward kernels of rec.hip):
+                                          // agent b's actCnt[b] states start at state actOff[b] of actStates; its window and context follow from its count,
+                                          // actSteps = the longest window of the B
   int nApp;                        // appended observations: the first layer's input is the step's state followed by the nApp before it
   const float* Xin; int ldXin;     // != nullptr: the first layer's input rows, written by launches in front (conv stack): row b K + k, next rows behind B K
   // a stack of two layer types runs as two launches (lower segment: the rnn kernels):
@@ -99,6 +100,7 @@ hipError_t launch_rec_forward(const RecArgs& a, hipStream_t s);
 hipError_t launch_rec_backward(const RecArgs& a, hipStream_t s);
 bool rec_tm_ok(const RecArgs& a);                                     // rectm.hip serves this net: a launch per (layer, window step) over the whole minibatch
 bool rec_tm_act_ok(const RecArgs& a);                                 // ... and this acting window, or these B agents' windows (layers beyond 256 cells)
+bool rec_win_act_ok(const RecArgs& a);                                // rec.hip's workgroup-per-sample kernels serve this acting window, or these B agents' windows (one workgroup each)
 hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s);
 hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s);
 // window forward + output layer + head + back-propagation through time of a sample as ONE launch (rec.hip: lstm32_step_wave_kernel)

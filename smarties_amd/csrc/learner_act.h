@@ -34,13 +34,36 @@ static bool actTmOk(hl_learner* h) {
   h->actTmState = 1;
   return true;
 }
-// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the time-step-major chain borrows the
-// training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples
-static int actChunkCap(hl_learner* h) { return actSeqOk(h) ? ACT_SEQ_CHUNK : (actTmOk(h) ? std::min(h->B, ACT_SEQ_CHUNK) : 0); }
-// one pinned block: [outputs of ACT_MAXROWS rows | their states | their stamps] of hl_forward / hl_forward_sequence, then (nets the
-// batched window kernel or the time-step-major chain serves) [outputs | stamps | window offsets | state counts | states] of a chunk of
-// actChunkCap agents
-static size_t actSeqStateFloats(const hl_learner* h, int cap) { return (size_t)cap * (h->recWin + h->nApp) * h->dS; }
+// the workgroup-per-sample window kernels (rec.hip) serve this net's acting window -- hl_forward_sequence's route for every net the two
+// predicates above leave: convolutions in front, RNN encoder layers under MGU layers, a window beyond the batched kernel's LDS --: many
+// agents' windows then run as the samples of hl_forward_sequence's own launches, workgroup b on agent b's window
+static bool actWinOk(hl_learner* h) {
+  if (h->actWinState) return h->actWinState > 0;
+  h->actWinState = -1;
+  if (!h->recurrent) return false;
+  static const float one = 0.f;      // (the predicate asks for given states, it does not read them)
+  for (int seg = h->recSplit ? 0 : -1; seg < (h->recSplit ? 2 : 0); ++seg) {
+    RecArgs ra = recArgs(h, 0, seg); ra.B = 1; ra.actStates = &one; ra.actSteps = 1; ra.actCtx = 0;
+    if (!rec_win_act_ok(ra)) return false;
+  }
+  h->actWinState = 1;
+  return true;
+}
+// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the chains of the other two routes borrow
+// the training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples -- and, behind
+// convolutions, no more than whose stacked window rows fit HL_ACT_WIN_STAGE_BYTES of pinned staging (never fewer than one)
+static int actWinCap(const hl_learner* h) {
+  size_t cap = (size_t)std::min(h->B, ACT_SEQ_CHUNK);
+  if (h->nConv > 0) cap = std::min(cap, (size_t)HL_ACT_WIN_STAGE_BYTES / ((size_t)h->recK * h->dIn * sizeof(float)));
+  return (int)std::max(cap, (size_t)1);
+}
+static int actChunkCap(hl_learner* h) { return actSeqOk(h) ? ACT_SEQ_CHUNK : (actTmOk(h) ? std::min(h->B, ACT_SEQ_CHUNK) : (actWinOk(h) ? actWinCap(h) : 0)); }
+// one pinned block: [outputs of ACT_MAXROWS rows | their states | their stamps] of hl_forward / hl_forward_sequence, then (recurrent nets)
+// [outputs | stamps | window offsets | state counts | states] of a chunk of actChunkCap agents; behind convolutions the states are the
+// agents' stacked window rows, recK rows of dIn floats each
+static size_t actSeqStateFloats(const hl_learner* h, int cap) {
+  return h->nConv > 0 ? (size_t)cap * h->recK * h->dIn : (size_t)cap * (h->recWin + h->nApp) * h->dS;
+}
 static int actPinEnsure(hl_learner* h) {
   if (h->actPin) return HL_OK;
   size_t bytes = (size_t)ACT_MAXROWS * (h->nOut * sizeof(double) + sizeof(unsigned)) + actPinFloats(h) * sizeof(float) + 256;
@@ -201,6 +224,68 @@ static int actTmForward(hl_learner* h, int n, const int32_t* nSteps, const float
   return HL_OK;
 }
 
+// n checked windows of a net whose windows the workgroup-per-sample kernels run (actWinOk): agent i of a chunk is sample i of ONE chain of
+// hl_forward_sequence's own launches -- behind convolutions the chunk's stacked rows through the front; the window launch (two for a
+// stack of two layer types) with the per-agent tables, workgroup i walking agent i's window alone; the output layer on the chunk's rows
+// of Yout.  The chain borrows the training rows of the first m samples between steps, as hl_forward_sequence borrows those of the first
+static int actWinForward(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
+  { int rc = actPinEnsure(h); if (rc) return rc; }
+  const int cap = actChunkCap(h), K = h->recK;
+  double* pOut = reinterpret_cast<double*>(h->actPin + h->actSeqPinOff);
+  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pOut + (size_t)cap * h->nOut);
+  int* pOff = reinterpret_cast<int*>(const_cast<unsigned*>(pDone) + cap);
+  int* pCnt = pOff + cap + 2;
+  float* pIn = reinterpret_cast<float*>(pCnt + cap);
+  const DevHidden& q = h->hid[h->nHidden - 1];
+  const bool conv = h->nConv > 0;
+  if (conv) {      // (as hl_forward_sequence: the front borrows minibatch buffer 0)
+    int rc = dropPresample(h); if (rc) return rc;
+    if (!h->dActS) { HIPCK(devAlloc(&h->dActS, (size_t)h->convMmax * h->dIn)); HIPCK(devAlloc(&h->dActO, (size_t)h->Mmax * h->nOut)); }
+    rc = ensureConvPrep(h); if (rc) return rc;
+  }
+  size_t first = 0;      // states in front of the chunk
+  for (int i0 = 0; i0 < n; i0 += cap) {
+    const int m = std::min(cap, n - i0);
+    int sum = 0, winMax = 0;
+    for (int i = 0; i < m; ++i) {
+      const int steps = nSteps[i0 + i], win = std::min(steps, h->recWin), ctx = steps - win;
+      winMax = std::max(winMax, win);
+      if (!conv) { pOff[i] = sum; pCnt[i] = steps; sum += steps; continue; }
+      // the agent's stacked rows, window step k at row i K + k (the state of the step followed by the nApp before it); rows of steps its
+      // window lacks repeat its last one
+      const float* st = states + (first + sum) * h->dS;
+      float* rows = pIn + (size_t)i * K * h->dIn;
+      for (int k = 0; k < win; ++k) for (int j = 0; j <= h->nApp; ++j) { const int g = std::max(ctx + k - j, 0);
+        std::memcpy(rows + (size_t)k * h->dIn + (size_t)j * h->dS, st + (size_t)g * h->dS, (size_t)h->dS * sizeof(float)); }
+      for (int k = win; k < K; ++k) std::memcpy(rows + (size_t)k * h->dIn, rows + (size_t)(win - 1) * h->dIn, (size_t)h->dIn * sizeof(float));
+      pOff[i] = i * K * (1 + h->nApp); pCnt[i] = win; sum += steps;      // (the window kernel reads its rows from Xin; the tables give it the window's length)
+    }
+    if (!conv) std::memcpy(pIn, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
+    const float* actStates = conv ? h->dActS : pIn;
+    auto table = [&](RecArgs ra) { ra.B = m; ra.actStates = actStates; ra.actOff = pOff; ra.actCnt = pCnt; ra.actSteps = winMax; ra.actCtx = 0; return ra; };
+    const RecArgs lo = table(recArgs(h, 0, h->recSplit ? 0 : -1)), up = table(recArgs(h, 0, h->recSplit ? 1 : -1));
+    if (!rec_win_act_ok(lo) || !rec_win_act_ok(up)) return fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the window kernels refuse the chunk");
+    unsigned tag = ++h->actTag; if (tag == 0) tag = ++h->actTag;
+    int rcFront = HL_OK;
+    HIPCK(timed(h, "act_win_chain", h->stream, [&] {
+      if (conv) {
+        hipError_t e = hipMemcpyAsync(h->dActS, pIn, (size_t)m * K * h->dIn * sizeof(float), hipMemcpyHostToDevice, h->stream); if (e != hipSuccess) return e;
+        e = launch_act_standardize(h->sc, h->rp, h->dActS, m * K, h->dS, h->dIn, h->buf[0].X0, h->ldX0, h->stream); if (e != hipSuccess) return e;
+        rcFront = launchFront(h, 0, h->stream, /*gather*/false); if (rcFront) return hipSuccess;
+      }
+      hipError_t e = launch_rec_forward(lo, h->stream); if (e != hipSuccess) return e;
+      if (h->recSplit) { e = launch_rec_forward(up, h->stream); if (e != hipSuccess) return e; }
+      return launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, m,
+                               pOut, h->stream, const_cast<unsigned*>(pDone), tag, h->cfg.nnOutputFunc);
+    }));
+    if (rcFront) return rcFront;
+    { int rc = actWait(h, pDone, m, tag); if (rc) return rc; }
+    std::memcpy(outputs + (size_t)i0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
+    first += sum;
+  }
+  return HL_OK;
+}
+
 // n agents' windows (include/smarties_hip_act.h)
 int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const float* states, double* outputs) {
   if (!h || n < 0 || (n > 0 && (!nSteps || !states || !outputs))) return HL_ERR_BAD_ARG;
@@ -224,8 +309,11 @@ int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const 
     }
     return hl_forward(h, n, rows.data(), outputs);
   }
-  if (!actSeqOk(h) && actTmOk(h)) return actTmForward(h, n, nSteps, states, outputs);      // layers wider than 256 cells
-  if (!actSeqOk(h)) {      // convolutions in front, two layer types, a window beyond the batched kernel's LDS: hl_forward_sequence's routes, agent by agent
+  if (!actSeqOk(h)) {
+    if (actTmOk(h)) return actTmForward(h, n, nSteps, states, outputs);       // layers wider than 256 cells
+    if (actWinOk(h)) return actWinForward(h, n, nSteps, states, outputs);     // convolutions in front, two layer types, a window beyond the batched kernel's LDS
+    // a net all three predicates refuse -- layers or inputs beyond the bounds the window kernels state (256 cells, 1024 inputs) that the
+    // time-step-major launches do not take either --: hl_forward_sequence's own route, agent by agent, as before
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
       const int rc = hl_forward_sequence(h, nSteps[i], states + off * h->dS, outputs + (size_t)i * h->nOut); if (rc) return rc;

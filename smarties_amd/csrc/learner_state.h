@@ -108,6 +108,7 @@ struct hl_learner {
   double* dStatsIns = nullptr; bool statsFresh = false, anyStep = false;
   unsigned char* actPin = nullptr; unsigned actTag = 0; bool actFastOk = false;     // rollout inference of a few agents (hl_forward)
   int actTmState = 0;      // ... of a net whose layers run time-step-major (rectm.hip): 0 not looked at yet / 1 its acting windows go through those launches, many agents as one chain / -1 not
+  int actWinState = 0;     // ... of every other recurrent net (rec.hip's workgroup-per-sample kernels, agent b = workgroup b): 0 not looked at yet / 1 many agents as one chain / -1 not
   int actSeqState = 0, actSeqCus = 0; size_t actSeqPinOff = 0; ActSeqArgs actSeq{};      // many agents of a recurrent net (hl_forward_sequences): 0 not looked at yet / 1 the batched kernel serves the net / -1 not; compute units; its part of actPin; the launch arguments
   // prioritised samplers (per.hip): probabilities / cumulative table of the stored transitions, rebuilt before every minibatch
   float *perProb = nullptr, *perKey = nullptr, *perKeyS = nullptr; double* perCp = nullptr; unsigned *perIdx = nullptr, *perIdxS = nullptr; void* perScan = nullptr; size_t perScanBytes = 0;

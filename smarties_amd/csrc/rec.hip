@@ -67,7 +67,7 @@ __device__ unsigned long long recStamps[256];
 #else
 #define REC_STAMP(sample, thread, i) do {} while (0)
 #endif
-template <bool LDSW>
+template <bool LDSW, bool MANY>
 __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sW[];
   __shared__ float sBuf[2][REC_GENIN];                    // input of the current layer / output of the current block
@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   // acting (MemoryBuffer::agentToMinibatch, MemoryBuffer.cpp:440-467): the agent's last steps, from a zero recurrent state
   const bool acting = a.actStates != nullptr;
   const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
+  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
+  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
   const int nextRow = acting ? -1 : a.bt.nextOf[b];
   const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
   const float* W = a.W;
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   const bool preload = plain && nSteps * a.dS <= REC_STATES;
   if (preload) for (int e = tid; e < nSteps * a.dS; e += 256) {
     const int kk = e / a.dS, i = e - kk * a.dS;
-    const float raw = acting ? a.actStates[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
+    const float raw = acting ? aw.states(a)[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
     sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
   }
   const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
@@ -117,10 +118,10 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
     const bool store = !acting && k <= T;
     const long long r = (long long)b * a.K + k;
     const long long sl = slot - T + k;
-    if (!plain) { for (int e = tid; e < dIn; e += 256) sBuf[0][e] = recInputAt(a, acting, b, slot, t, T, nextRow, k, e); }
+    if (!plain) { for (int e = tid; e < dIn; e += 256) sBuf[0][e] = recInputAtWin<MANY>(a, acting, aw, b, slot, t, T, nextRow, k, e); }
     else if (tid < a.dS) {
       if (preload) sBuf[0][tid] = sStates[k * a.dS + tid];
-      else { const float raw = acting ? a.actStates[(size_t)k * a.dS + tid] : a.rp.S[(size_t)sl * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
+      else { const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)sl * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
     }
     ldsBarrier();
     REC_STAMP(blockIdx.x, 0, 4 + k * 5);
@@ -198,7 +199,7 @@ __host__ __device__ __forceinline__ LstmGeo lstmGeo(int nIn, int nC) {
 #define LSTM_VEC (REC_MAXIN + REC_MAXC + 8)
 // NL / NC: number of layers / cells of every layer known at compile time (0: read from the arguments) -- with the general
 // eight-layer body the loop invariants alone are 450 spilled scalars and each layer-step some 600 instructions
-template <int NL, int NC>
+template <int NL, int NC, bool MANY>
 __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   constexpr int MAXL = NL ? NL : HL_MAX_HIDDEN;
   const int nL = NL ? NL : a.nL;
@@ -209,7 +210,8 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   REC_STAMP(blockIdx.x, 0, 0);
   const bool acting = a.actStates != nullptr;
   const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
+  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
+  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
   const int nextRow = acting ? -1 : a.bt.nextOf[b];
   const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
   const float* W = a.W;
@@ -269,13 +271,13 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   const bool preload = nSteps * a.dS <= REC_STATES;
   if (preload) for (int e = tid; e < nSteps * a.dS; e += 256) {
     const int kk = e / a.dS, i = e - kk * a.dS;
-    const float raw = acting ? a.actStates[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
+    const float raw = acting ? aw.states(a)[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
     sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
   }
   const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
   auto stateOf = [&](int k) -> float {     // standardised state component `tid` of step k (Episode::standardizedState, Episode.h:172-183)
     if (preload) return sStates[k * a.dS + tid];
-    const float raw = acting ? a.actStates[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(slot - T + k) * a.dS + tid];
+    const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(slot - T + k) * a.dS + tid];
     return (raw - sMean) * sScale;
   };
   vmDrain(); ldsBarrier();
@@ -604,7 +606,7 @@ __global__ __launch_bounds__(256) void lstm_backward_lds_kernel(RecArgs a) {
   }
 }
 
-template <bool LDSW, int NL>
+template <bool LDSW, int NL, bool MANY>
 __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
   constexpr int MAXL = NL ? NL : HL_MAX_HIDDEN;
   const int nL = NL ? NL : a.nL;
@@ -616,7 +618,8 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool acting = a.actStates != nullptr;
   const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
+  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
+  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
   const int nextRow = acting ? -1 : a.bt.nextOf[b];
   const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
   const float* W = a.W;
@@ -641,7 +644,7 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
   const bool preload = plain && nSteps * a.dS <= REC_STATES;
   if (preload) for (int e = tid; e < nSteps * a.dS; e += 256) {
     const int kk = e / a.dS, i = e - kk * a.dS;
-    const float raw = acting ? a.actStates[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
+    const float raw = acting ? aw.states(a)[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
     sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
   }
   const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
@@ -649,10 +652,10 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
   for (int k = 0; k < nSteps; ++k) {
     const bool store = !acting && k <= T;
     const long long r = (long long)b * a.K + k;
-    if (!plain) { for (int e = tid; e < dIn; e += 256) sBuf[0][e] = recInputAt(a, acting, b, slot, t, T, nextRow, k, e); }
+    if (!plain) { for (int e = tid; e < dIn; e += 256) sBuf[0][e] = recInputAtWin<MANY>(a, acting, aw, b, slot, t, T, nextRow, k, e); }
     else if (tid < a.dS) {
       if (preload) sBuf[0][tid] = sStates[k * a.dS + tid];
-      else { const float raw = acting ? a.actStates[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(slot - T + k) * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
+      else { const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(slot - T + k) * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
     }
     ldsBarrier();
     int cur = 0;
@@ -1540,7 +1543,7 @@ __device__ __forceinline__ int rnnLdsOffset(const RecArgs& a, int j) {
   for (int q = 0; q < j; ++q) off += (a.L[q].nIn + a.L[q].nC) * rnnPitch(a.L[q].nC);
   return off;
 }
-template <bool LDSW>
+template <bool LDSW, bool MANY>
 __global__ __launch_bounds__(256) void rnn_forward_kernel(RecArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sW[];
   __shared__ float sBuf[2][REC_GENIN];
@@ -1549,7 +1552,8 @@ __global__ __launch_bounds__(256) void rnn_forward_kernel(RecArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, c0 = tid & 63, part = tid >> 6;
   const bool acting = a.actStates != nullptr;
   const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const int T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
+  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
+  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
   const int nextRow = acting ? -1 : a.bt.nextOf[b];
   const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
   const float* W = a.W;
@@ -1570,8 +1574,8 @@ __global__ __launch_bounds__(256) void rnn_forward_kernel(RecArgs a) {
     const bool store = !acting && k <= T;
     const long long r = (long long)b * a.K + k;
     const long long sl = slot - T + k;
-    if (a.Xin != nullptr || a.nApp > 0) { for (int e = tid; e < a.L[0].nIn; e += 256) sBuf[0][e] = recInputAt(a, acting, b, slot, t, T, nextRow, k, e); }
-    else if (tid < a.dS) { const float raw = acting ? a.actStates[(size_t)k * a.dS + tid] : a.rp.S[(size_t)sl * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
+    if (a.Xin != nullptr || a.nApp > 0) { for (int e = tid; e < a.L[0].nIn; e += 256) sBuf[0][e] = recInputAtWin<MANY>(a, acting, aw, b, slot, t, T, nextRow, k, e); }
+    else if (tid < a.dS) { const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)sl * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
     ldsBarrier();
     int cur = 0;
     for (int j = 0; j < a.nL; ++j) {
@@ -1743,24 +1747,42 @@ template <class K> static hipError_t recLaunch(K kernel, const RecArgs& a, size_
   hipLaunchKernelGGL(kernel, dim3(a.B), dim3(256), lds, s, a);
   return hipGetLastError();
 }
+// launch_rec_forward takes one of the wave-per-(sample, layer) kernels for this net
+static bool recWaveForward(const RecArgs& a) { return a.gates != 1 && !recGeneral(a) && (wave32(a, 2) || wave32(a, 4)); }
+// Acting through the workgroup-per-sample kernels whose acting form knows the per-agent tables (rnn_forward_kernel, mgu_forward_kernel,
+// rec_forward_kernel, lstm_forward_lds_kernel): one window of a.actSteps given states (B = 1) or, with actOff / actCnt, the windows of a.B
+// agents, workgroup b walking agent b's.  True exactly where launch_rec_forward picks one of the four: its choice follows from the layers,
+// the input form and K alone -- the two time-step-major predicates are asked for the single-agent call, the only rule among them that
+// reads B or the tables.
+bool rec_win_act_ok(const RecArgs& a) {
+  const bool many = a.actOff != nullptr && a.actCnt != nullptr;
+  if (a.actStates == nullptr || (a.actOff != nullptr) != (a.actCnt != nullptr) || (many ? a.B < 1 : a.B != 1)) return false;
+  if (a.actSteps < 1 || a.actSteps > a.nBPTT + 1 || a.actSteps > a.K || a.nL < 1) return false;
+  if (a.gates != 1 && a.YoutRows != nullptr) return false;      // (every step's output as a row: the plain recurrent kernel alone)
+  for (int j = 0; j < a.nL; ++j) if (a.L[j].nC > REC_GENC || a.L[j].nIn > REC_GENIN) return false;
+  RecArgs one = a; one.B = 1; one.actOff = nullptr; one.actCnt = nullptr;
+  return !rec_tm_ok(one) && !rec_tm_act_ok(one) && !recWaveForward(one);
+}
 // (static LDS of the kernels comes on top of the weights; 160 KB per workgroup)
+// one of the four workgroup-per-sample forward kernels: its form for the per-agent tables where they are given, else the form it had
+#define REC_FWD(lds, kernel, ...) (many ? recLaunch(kernel<__VA_ARGS__, true>, a, lds, nullptr, s) : recLaunch(kernel<__VA_ARGS__, false>, a, lds, nullptr, s))
 hipError_t launch_rec_forward(const RecArgs& a, hipStream_t s) {
   if (rec_tm_ok(a)) return launch_rec_tm_forward(a, s);      // wide LSTM layers, training windows: time-step-major on the MFMA (rectm.hip)
   if (rec_tm_act_ok(a)) return launch_rec_tm_forward(a, s);  // ... and the acting window of nets wider than the kernels below hold
   // (static LDS of the general kernels: up to 46 KB)
-  static size_t attr[4] = {0, 0, 0, 0}; const size_t lds = recLdsBytes(a); const bool fit = lds <= 100 * 1024; const bool general = recGeneral(a);
-  if (a.gates == 1) { const size_t l1 = rnnLdsBytes(a); return l1 <= 100 * 1024 ? recLaunch(rnn_forward_kernel<true>, a, l1, &attr[0], s) : recLaunch(rnn_forward_kernel<false>, a, 0, &attr[1], s); }
+  const bool many = a.actStates != nullptr && a.actCnt != nullptr;
+  const size_t lds = recLdsBytes(a); const bool fit = lds <= 100 * 1024; const bool general = recGeneral(a);
+  if (a.gates == 1) { const size_t l1 = rnnLdsBytes(a); return l1 <= 100 * 1024 ? REC_FWD(l1, rnn_forward_kernel, true) : REC_FWD(0, rnn_forward_kernel, false); }
   if (general) {
-    if (a.gates == 2) return fit ? recLaunch(mgu_forward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_forward_kernel<false, 0>, a, 0, &attr[1], s);
-    return fit ? recLaunch(rec_forward_kernel<true>, a, lds, &attr[2], s) : recLaunch(rec_forward_kernel<false>, a, 0, &attr[3], s);
+    if (a.gates == 2) return fit ? REC_FWD(lds, mgu_forward_kernel, true, 0) : REC_FWD(0, mgu_forward_kernel, false, 0);
+    return fit ? REC_FWD(lds, rec_forward_kernel, true) : REC_FWD(0, rec_forward_kernel, false);
   }
   if (wave32(a, 2))          // two layers of 32 cells, training pass: one wavefront per (sample, layer), weights in registers
     return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(mgu32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
   if (a.gates == 2) {
-    static size_t attrM[4] = {0, 0, 0, 0};
-    if (fit && a.nL == 1) return recLaunch(mgu_forward_kernel<true, 1>, a, lds, &attrM[1], s);
-    if (fit && a.nL == 2) return recLaunch(mgu_forward_kernel<true, 2>, a, lds, &attrM[2], s);
-    return fit ? recLaunch(mgu_forward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_forward_kernel<false, 0>, a, 0, &attr[1], s);
+    if (fit && a.nL == 1) return REC_FWD(lds, mgu_forward_kernel, true, 1);
+    if (fit && a.nL == 2) return REC_FWD(lds, mgu_forward_kernel, true, 2);
+    return fit ? REC_FWD(lds, mgu_forward_kernel, true, 0) : REC_FWD(0, mgu_forward_kernel, false, 0);
   }
   if (wave32(a, 4))          // the same arrangement for LSTM layers
     return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(lstm32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
@@ -1770,15 +1792,15 @@ hipError_t launch_rec_forward(const RecArgs& a, hipStream_t s) {
     // (hidden layers above the first take the block below as input; the specialised bodies rely on nIn == cells there)
     bool same = true;
     for (int j = 0; j < a.nL; ++j) same = same && a.L[j].nC == a.L[0].nC && (j == 0 || a.L[j].nIn == a.L[0].nC);
-    static size_t attrS[4] = {0, 0, 0, 0};
-    if (same && a.nL == 2 && a.L[0].nC == 32) return recLaunch(lstm_forward_lds_kernel<2, 32>, a, fl * sizeof(float), &attrS[0], s);   // RACER_RNN.json
-    if (a.nL == 1) return recLaunch(lstm_forward_lds_kernel<1, 0>, a, fl * sizeof(float), &attrS[1], s);
-    if (a.nL == 2) return recLaunch(lstm_forward_lds_kernel<2, 0>, a, fl * sizeof(float), &attrS[2], s);
-    if (a.nL == 3) return recLaunch(lstm_forward_lds_kernel<3, 0>, a, fl * sizeof(float), &attrS[3], s);
-    return recLaunch(lstm_forward_lds_kernel<0, 0>, a, fl * sizeof(float), &attr[2], s);
+    if (same && a.nL == 2 && a.L[0].nC == 32) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 2, 32);   // RACER_RNN.json
+    if (a.nL == 1) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 1, 0);
+    if (a.nL == 2) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 2, 0);
+    if (a.nL == 3) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 3, 0);
+    return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 0, 0);
   }
-  return recLaunch(rec_forward_kernel<false>, a, 0, &attr[3], s);
+  return REC_FWD(0, rec_forward_kernel, false);
 }
+#undef REC_FWD
 // the one-launch step (lstm32_step_wave_kernel): the shapes of the wave-per-(sample, layer) LSTM kernels with a head of up to 32
 // dense outputs and 16 action components / options
 bool rec_step_fused_ok(const RecArgs& a, const HeadArgs& ha) {

@@ -32,6 +32,25 @@ __device__ __forceinline__ float recActInputAt(const RecArgs& a, const float* st
   const int j = e / a.dS, i = e - j * a.dS, g = ctx + k - j;
   return (states[(size_t)(g > 0 ? g : 0) * a.dS + i] - a.rp.stMean[i]) * a.rp.stScale[i];
 }
-
+// The acting window of workgroup b of the per-sample kernels (rec.hip): the one agent's of the arguments (actSteps states behind actCtx
+// context states) or -- MANY, the kernels' form for the per-agent tables -- agent b's own: the last nBPTT + 1 of its actCnt[b] states,
+// those in front as context.  win() = its window steps; states() = its first given state.  MANY is a flag of the kernel, not a test of
+// the tables at run time, and without it the accessors are the arguments' fields read where they are used: the training form stays the
+// code it was, register for register.
+template <bool MANY>
+struct RecActWin {
+  const float* st; int w, c;
+  __device__ __forceinline__ RecActWin(const RecArgs& a, int b) : st(nullptr), w(0), c(0) {
+    if constexpr (MANY) { const int steps = a.actCnt[b]; w = min(steps, a.nBPTT + 1); c = steps - w; st = a.actStates + (size_t)a.actOff[b] * a.dS; }
+  }
+  __device__ __forceinline__ const float* states(const RecArgs& a) const { if constexpr (MANY) return st; else return a.actStates; }
+  __device__ __forceinline__ int win(const RecArgs& a) const { if constexpr (MANY) return w; else return a.actSteps; }
+};
+// element e of the first layer's input at step k: recInputAt or, MANY, its form for agent b's own window `aw`
+template <bool MANY>
+__device__ __forceinline__ float recInputAtWin(const RecArgs& a, bool acting, const RecActWin<MANY>& aw, int b, long long slot, int t, int T, int nextRow, int k, int e) {
+  if constexpr (MANY) { if (a.Xin == nullptr) return recActInputAt(a, aw.st, aw.c, k, e); }
+  return recInputAt(a, acting, b, slot, t, T, nextRow, k, e);
+}
 
 }  // namespace hl
