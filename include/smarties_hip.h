@@ -330,7 +330,15 @@ HL_API int hl_prepare_steps(hl_learner* h, int32_t n_steps);
  * (Learners/RACER.cpp:30-59; Network/Approximator.h:300-330): outputs[i] = [V_net, mean[dA],
  * sigma_param[dA]] as doubles, nOut per state.  The caller builds the policy, draws the action
  * with the agent's generator and applies scaleNet2V exactly as the reference does.  Call between
- * steps, from the thread that owns the learner. */
+ * steps, from the thread that owns the learner.  n has no upper limit: up to 64 rows run as one
+ * kernel, more rows (and dense nets with a layer or input row of 1025 - 2048) as one launch per
+ * 1024 rows, neither touching the minibatch buffers.  Exception: a dense net of more than
+ * HL_ACT_ROWS_SMALL_NET (192 K) weights that the one kernel does not serve -- a single row of a
+ * 2 x 2048 net, 70 rows of a 3 x 1024 net -- runs the training forward launches on minibatch
+ * buffer 0 (a minibatch drawn ahead is dropped and drawn again) until n reaches 1024 rows and
+ * 4 x batchSize rows; so do nets with convolutions and input rows beyond 2048.  Which route
+ * when, the measurements behind the switch and how closely the routes agree:
+ * include/smarties_hip_act.h.  n == 0: HL_OK, the device is not touched. */
 HL_API int hl_forward(hl_learner* h, int32_t n, const float* states /*[n][dimS]*/, double* outputs /*[n][nOut]*/);
 
 /* ---- episodes in the reference's wire format (second row) --------------------

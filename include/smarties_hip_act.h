@@ -11,7 +11,15 @@
  * zero recurrent state; the last step's output feeds the policy) -- for n agents at once instead of one at a time.
  *
  * Which call when:
- *   hl_forward            dense nets, n raw states (rows): one kernel for up to 64 agents.
+ *   hl_forward            dense nets, n raw states (rows).  Up to 64 rows of a net whose layers and input rows are at most 1024 wide: one
+ *                         kernel, a workgroup per row.  More rows, or a wider layer or input row (up to 2048): the many-row route -- per
+ *                         chunk of HL_ACT_ROWS_CHUNK rows ONE launch in which a workgroup runs the whole net for a block of 16 rows on
+ *                         the MFMA, rows and outputs through pinned host memory; the minibatch buffers are not touched and a minibatch
+ *                         drawn ahead stays as it is.  Nets beyond HL_ACT_ROWS_SMALL_NET weights take it only from HL_ACT_ROWS_WIDE_MIN_N
+ *                         rows and 4 x batchSize rows on (below).  Everything else (convolutions in front, input rows beyond 2048, SMARTIES_HIP_GENERIC bit 2): the
+ *                         training forward launches over minibatch buffer 0, a minibatch drawn ahead dropped and drawn again.  The two
+ *                         dense routes form their sums in different orders: they agree to rounding (both within 1e-5 of the CPU
+ *                         oracle), not bit for bit; a row's result on the many-row route depends neither on n nor on its place.
  *   hl_forward_sequence   ONE agent's window, any net.  The cheapest call for a single agent of a recurrent net.
  *   hl_forward_sequences  n agents' windows, any net.  Per chunk of agents one launch, or -- layers wider than 256 cells, recurrent
  *                         layers behind convolutions, RNN encoder layers under MGU layers, nets of at most 256 cells whose window
@@ -31,6 +39,25 @@ extern "C" {
  * into ceil(n / HL_ACT_SEQ_CHUNK) launches (the nets served by a chain of launches: chunks of min(local batch size,
  * HL_ACT_SEQ_CHUNK)) */
 #define HL_ACT_SEQ_CHUNK 512
+/* rows per launch of hl_forward's many-row route (dense nets): its pinned staging (raw rows, outputs, one completion stamp per
+ * block of 16 rows) is sized for this many rows at the first call that takes the route; a call with more rows is cut into
+ * ceil(n / HL_ACT_ROWS_CHUNK) launches */
+#define HL_ACT_ROWS_CHUNK 1024
+/* where hl_forward switches to the many-row route (measured on an MI355X at batchSize 256, profiles/act_rows_timing.json; us per
+ * call, many-row route against the launches over the training buffers).  A workgroup streams all weights of the net for its 16
+ * rows, so the call costs about 24 us + 0.146 us per 1024 weights whatever n is up to 4096, the training launches about
+ * 43 us + 0.067 us per 1024 weights per round of 2 x batchSize rows:
+ *     2 x 256 (74 K weights)   34 against 48 at 65 rows, 43 against 106 at 1024        -- the route wins everywhere
+ *     2 x 512 (275 K weights)  64 against 62 at 65 rows, 72 against 134 at 1024         -- loses the bare call below one round
+ *     3 x 1024 (2.1 M weights) 338 against 91 at 65 rows, 353 against 384 at 1024       -- wins only against two rounds
+ * (The 65-row figures of 2 x 512 and 3 x 1024 are the route's with the switch held open; the profile holds what the library does:
+ * the training launches there.)
+ * A dense net of up to HL_ACT_ROWS_SMALL_NET weights (floats, all layers; the two lines cross at 248 K, the constant keeps a
+ * margin below that) takes the route whenever the one-kernel route does not apply.  A larger net takes it only for
+ * n >= HL_ACT_ROWS_WIDE_MIN_N and n >= 4 x batchSize (two rounds of the training launches; 1024 rows is the measured point, at
+ * batchSize 256), and runs the training launches below that -- also for a single row of a net with a 1025 - 2048 wide layer. */
+#define HL_ACT_ROWS_SMALL_NET (192 * 1024)
+#define HL_ACT_ROWS_WIDE_MIN_N 1024
 /* recurrent layers behind convolutions: the stacked window rows of a chunk's agents (nnBPTTseq + 1 rows of
  * dimS (1 + nAppendedObs) floats each) are staged in pinned host memory, and a chunk holds no more agents than fit this many
  * bytes (512 agents of an 84 x 84 x 4 image window would pin hundreds of megabytes), though never fewer than one */

@@ -358,6 +358,27 @@ struct ActArgs {
   ActLayer L[HL_MAX_HIDDEN];
 };
 hipError_t launch_act_forward(const ActArgs& a, int n, hipStream_t s);
+// rollout inference of dense nets for many rows (actrows.hip: act_rows_kernel): the whole net for a block of 16 rows per workgroup on the
+// MFMA, activations in LDS from layer to layer; raw rows, outputs and one stamp per row block in pinned host memory
+constexpr int ACT_ROWS_MAXW = 2048;       // widest layer / input row
+constexpr int ACT_ROWS_CHUNK = 1024;      // rows per launch (HL_ACT_ROWS_CHUNK of include/smarties_hip_act.h)
+// a workgroup streams ALL weights of the net for its 16 rows, so below a device's worth of row blocks the launch lasts as long as one
+// compute unit needs for them: nets up to ACT_ROWS_SMALL_NET weights (floats) take the route for any row count; larger ones only where
+// the launches over the training buffers need at least two rounds of Mmax rows and n >= ACT_ROWS_WIDE_MIN_N -- the point measured at
+// batchSize 256 (Mmax 512), where two rounds cost more than the one workgroup's stream (profiles/act_rows_timing.json)
+constexpr long long ACT_ROWS_SMALL_NET = 192 * 1024;      // (HL_ACT_ROWS_SMALL_NET)
+constexpr int ACT_ROWS_WIDE_MIN_N = 1024;                 // (HL_ACT_ROWS_WIDE_MIN_N)
+struct ActRowsArgs {
+  const float* W; const float* stMean; const float* stScale;
+  const float* in; double* out; volatile unsigned* done; unsigned tag;      // pinned host memory (device-mapped); done: one word per row block
+  int n, dS, dIn, nL, nDense, nSig, nOut, ldWo; long long indWo, indBo, indBp;
+  int outFunc;
+  int ld, ldO, ng; size_t ldsBytes;       // act_rows_plan: row pitch of the activations / of the output values in LDS, column groups per wavefront, dynamic LDS
+  ActLayer L[HL_MAX_HIDDEN];
+};
+bool act_rows_plan(ActRowsArgs* a);       // the kernel serves this net (every width and the input row <= 2048): LDS layout filled in
+int act_rows_blocks(int n);               // row blocks (= stamps) of a launch over n rows
+hipError_t launch_act_rows(const ActRowsArgs& a, hipStream_t s);
 // rollout inference of recurrent nets for many agents (actseq.hip: act_seq_kernel): a workgroup stages the recurrent stack once and
 // walks its agents' windows; states, window offsets, outputs and per-agent stamps in pinned host memory
 constexpr int ACT_SEQ_CHUNK = 512;      // agents per launch (HL_ACT_SEQ_CHUNK of include/smarties_hip_act.h)

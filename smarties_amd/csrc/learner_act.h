@@ -2,6 +2,8 @@
 #pragma once
 #include "../../include/smarties_hip_act.h"
 static_assert(ACT_SEQ_CHUNK == HL_ACT_SEQ_CHUNK, "the chunk capacity the header states");
+static_assert(ACT_ROWS_CHUNK == HL_ACT_ROWS_CHUNK, "the chunk capacity the header states");
+static_assert(ACT_ROWS_SMALL_NET == HL_ACT_ROWS_SMALL_NET && ACT_ROWS_WIDE_MIN_N == HL_ACT_ROWS_WIDE_MIN_N, "the switch the header states");
 
 static size_t actPinFloats(const hl_learner* h) { return std::max((size_t)ACT_MAXROWS * h->dIn, (size_t)(std::max(h->recWin, 1) + h->nApp) * h->dS); }
 // the batched window kernel (actseq.hip) serves this net: one recurrent layer type, no convolutions in front, layers within its bounds
@@ -86,11 +88,56 @@ static int actWait(hl_learner* h, volatile unsigned* pDone, int n, unsigned tag)
   std::atomic_thread_fence(std::memory_order_acquire);
   return HL_OK;
 }
+// the row-block kernel (actrows.hip) serves this net: dense, no convolutions in front, input rows and layers within its bounds;
+// SMARTIES_HIP_GENERIC bit 2 keeps the route over the training buffers
+static bool act_rows_ok(hl_learner* h) {
+  if (h->actRowsState) return h->actRowsState > 0;
+  h->actRowsState = -1;
+  if (h->recurrent || h->nConv > 0 || h->dIn > ACT_ROWS_MAXW || (h->generic & 2)) return false;
+  ActRowsArgs& a = h->actRows; a = ActRowsArgs{};
+  a.dS = h->dS; a.dIn = h->dIn; a.nL = h->nHidden; a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo;
+  a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp; a.outFunc = h->cfg.nnOutputFunc;
+  for (int j = 0; j < h->nHidden; ++j) { const DevHidden& d = h->hid[j];
+    a.L[j] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
+  if (!act_rows_plan(&a)) return false;
+  long long nW = (long long)h->hid[h->nHidden - 1].size * h->ldWo;
+  for (int j = 0; j < h->nHidden; ++j) nW += (long long)h->hid[j].nIn * h->hid[j].ldW;
+  h->actRowsSmall = nW <= ACT_ROWS_SMALL_NET;
+  h->actRowsState = 1;
+  return true;
+}
+// n rows of a dense net in chunks of ACT_ROWS_CHUNK: per chunk one copy into pinned staging -- [outputs | raw rows | one stamp per row
+// block], allocated here at the first call --, one launch, a poll of the block stamps, one copy out.  Neither the minibatch buffers nor
+// a minibatch drawn ahead are touched, and the stream is not synchronised
+static int actRowsForward(hl_learner* h, int n, const float* states, double* outputs) {
+  const size_t outBytes = (size_t)ACT_ROWS_CHUNK * h->nOut * sizeof(double), inBytes = (size_t)ACT_ROWS_CHUNK * h->dIn * sizeof(float);
+  if (!h->actRowsPin) {
+    const size_t bytes = outBytes + inBytes + (size_t)act_rows_blocks(ACT_ROWS_CHUNK) * sizeof(unsigned);
+    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actRowsPin), bytes, hipHostMallocMapped));
+    std::memset(h->actRowsPin, 0, bytes);
+  }
+  double* pOut = reinterpret_cast<double*>(h->actRowsPin);
+  float* pIn = reinterpret_cast<float*>(h->actRowsPin + outBytes);
+  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(h->actRowsPin + outBytes + inBytes);
+  for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
+    const int m = std::min(ACT_ROWS_CHUNK, n - r0);
+    std::memcpy(pIn, states + (size_t)r0 * h->dIn, (size_t)m * h->dIn * sizeof(float));
+    ActRowsArgs a = h->actRows;
+    a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
+    a.in = pIn; a.out = pOut; a.done = pDone; a.n = m;
+    a.tag = ++h->actTag; if (a.tag == 0) a.tag = ++h->actTag;
+    HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+    { int rc = actWait(h, pDone, act_rows_blocks(m), a.tag); if (rc) return rc; }
+    std::memcpy(outputs + (size_t)r0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
+  }
+  return HL_OK;
+}
 int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   if (!h || n < 0 || (n > 0 && (!states || !outputs))) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   if (h->inStep) return fail(h, HL_ERR_STATE, "hl_forward between hl_step_begin and hl_step_end");
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, "forward of a recurrent net needs the agent's history");
+  if (n == 0) return HL_OK;
   // a few agents, dense network: one kernel, states and outputs through pinned host memory (misc.hip: act_forward_kernel)
   if (n > 0 && n <= ACT_MAXROWS && h->nConv == 0 && h->dIn <= ACT_MAXW && h->actFastOk) {
     { int rc = actPinEnsure(h); if (rc) return rc; }
@@ -109,6 +156,10 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
     std::memcpy(outputs, pOut, (size_t)n * h->nOut * sizeof(double));
     return HL_OK;
   }
+  // more rows than that, or a layer / an input row wider: the whole net per block of 16 rows on the MFMA (actrows.hip: act_rows_kernel)
+  // (a net beyond ACT_ROWS_SMALL_NET weights: only from ACT_ROWS_WIDE_MIN_N rows on and where the launches over the training buffers would
+  // need two rounds of Mmax rows or more -- below, one workgroup per 16 rows streaming all weights takes longer than they do)
+  if (act_rows_ok(h) && (h->actRowsSmall || (n >= ACT_ROWS_WIDE_MIN_N && n >= 2 * h->Mmax))) return actRowsForward(h, n, states, outputs);
   { int rc = dropPresample(h); if (rc) return rc; }      // the forward pass borrows minibatch buffer 0
   // (with appended observations a row holds the raw state of step t followed by those of t-1 .. t-nAppendedObs)
   if (!h->dActS) { HIPCK(devAlloc(&h->dActS, (size_t)h->Mmax * h->dIn)); HIPCK(devAlloc(&h->dActO, (size_t)h->Mmax * h->nOut)); }

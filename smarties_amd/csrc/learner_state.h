@@ -107,6 +107,7 @@ struct hl_learner {
   // 0 before the first step.  Computed on the device when needed (dStatsIns), at most once per step.
   double* dStatsIns = nullptr; bool statsFresh = false, anyStep = false;
   unsigned char* actPin = nullptr; unsigned actTag = 0; bool actFastOk = false;     // rollout inference of a few agents (hl_forward)
+  int actRowsState = 0; bool actRowsSmall = false; unsigned char* actRowsPin = nullptr; ActRowsArgs actRows{};      // many rows of a dense net (actrows.hip): 0 not looked at yet / 1 the row-block kernel serves the net / -1 not; the net is small enough for the route at any row count (ACT_ROWS_SMALL_NET); its pinned staging (allocated at the first call that takes the route); the launch arguments
   int actTmState = 0;      // ... of a net whose layers run time-step-major (rectm.hip): 0 not looked at yet / 1 its acting windows go through those launches, many agents as one chain / -1 not
   int actWinState = 0;     // ... of every other recurrent net (rec.hip's workgroup-per-sample kernels, agent b = workgroup b): 0 not looked at yet / 1 many agents as one chain / -1 not
   int actSeqState = 0, actSeqCus = 0; size_t actSeqPinOff = 0; ActSeqArgs actSeq{};      // many agents of a recurrent net (hl_forward_sequences): 0 not looked at yet / 1 the batched kernel serves the net / -1 not; compute units; its part of actPin; the launch arguments
