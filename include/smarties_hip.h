@@ -336,7 +336,9 @@ HL_API int hl_prepare_steps(hl_learner* h, int32_t n_steps);
  * HL_ACT_ROWS_SMALL_NET (192 K) weights that the one kernel does not serve -- a single row of a
  * 2 x 2048 net, 70 rows of a 3 x 1024 net -- runs the training forward launches on minibatch
  * buffer 0 (a minibatch drawn ahead is dropped and drawn again) until n reaches 1024 rows and
- * 4 x batchSize rows; so do nets with convolutions and input rows beyond 2048.  Which route
+ * 4 x batchSize rows; so do input rows beyond 2048 and nets with convolutions in front, except
+ * feed-forward ones with raw rows up to HL_ACT_CONV_MAX_ROW_BYTES (two launches per chunk, the
+ * minibatch buffers untouched).  Which route
  * when, the measurements behind the switch and how closely the routes agree:
  * include/smarties_hip_act.h.  n == 0: HL_OK, the device is not touched. */
 HL_API int hl_forward(hl_learner* h, int32_t n, const float* states /*[n][dimS]*/, double* outputs /*[n][nOut]*/);

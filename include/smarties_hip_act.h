@@ -16,7 +16,18 @@
  *                         chunk of HL_ACT_ROWS_CHUNK rows ONE launch in which a workgroup runs the whole net for a block of 16 rows on
  *                         the MFMA, rows and outputs through pinned host memory; the minibatch buffers are not touched and a minibatch
  *                         drawn ahead stays as it is.  Nets beyond HL_ACT_ROWS_SMALL_NET weights take it only from HL_ACT_ROWS_WIDE_MIN_N
- *                         rows and 4 x batchSize rows on (below).  Everything else (convolutions in front, input rows beyond 2048, SMARTIES_HIP_GENERIC bit 2): the
+ *                         rows and 4 x batchSize rows on (below).  Feed-forward nets with convolutional layers in front whose raw rows
+ *                         are at most HL_ACT_CONV_MAX_ROW_BYTES long, any n >= 1: per chunk (HL_ACT_CONV_STAGE_BYTES below) the raw rows
+ *                         go into pinned staging, then TWO launches -- the whole conv stack of a row per workgroup with every map in LDS,
+ *                         the rows read from the mapped staging, the filters from the parameter blob as the reference lays them out
+ *                         (right directly behind hl_set_params / hl_restart); the dense layers on the feature rows by the many-row
+ *                         kernel --, completion by that kernel's stamps.  It leaves alone the minibatch buffers, the training
+ *                         activations, the prepared filter copies, a minibatch drawn ahead and the stream (no synchronisation); the
+ *                         choice depends on the net only, so a row's result is the same bit for bit alone, among others and through
+ *                         hl_forward_sequence(s).  Conv nets that fall back: longer raw rows (RACER_atari.json's 110 KB among them: the
+ *                         figures below), image, maps and offset tables beyond the 160 KB of LDS of a workgroup, a feature row
+ *                         [extras | last map] or a dense layer wider than 2048, recurrent layers behind.  Everything
+ *                         else (those, input rows of dense nets beyond 2048, SMARTIES_HIP_GENERIC bit 2): the
  *                         training forward launches over minibatch buffer 0, a minibatch drawn ahead dropped and drawn again.  The two
  *                         dense routes form their sums in different orders: they agree to rounding (both within 1e-5 of the CPU
  *                         oracle), not bit for bit; a row's result on the many-row route depends neither on n nor on its place.
@@ -62,6 +73,28 @@ extern "C" {
  * dimS (1 + nAppendedObs) floats each) are staged in pinned host memory, and a chunk holds no more agents than fit this many
  * bytes (512 agents of an 84 x 84 x 4 image window would pin hundreds of megabytes), though never fewer than one */
 #define HL_ACT_WIN_STAGE_BYTES (32u << 20)
+/* hl_forward behind convolutions: the raw rows of a chunk (dimS (1 + nAppendedObs) floats each) are staged in pinned, device-mapped
+ * host memory, and a chunk holds no more rows than fit this many bytes -- HL_ACT_ROWS_CHUNK rows of an 84 x 84 x 4 image would pin
+ * 116 MB --: min(HL_ACT_ROWS_CHUNK, HL_ACT_CONV_STAGE_BYTES / row bytes) rows, rounded down to whole blocks of 16 and never below 16
+ * (288 rows of 84 x 84 x 4).  The kernel reads the rows from the mapped staging itself.  The alternative, one hipMemcpyAsync from the
+ * staging into a device buffer ahead of the launch, was tried during development and was slower by 11 - 24 us per call (one and 16 rows
+ * of 110 KB, 16 rows of 2.3 KB); that variant is not in the tree and its run is not in the profile, so these figures cannot be
+ * reproduced from the repository. */
+#define HL_ACT_CONV_STAGE_BYTES (32u << 20)
+/* which conv nets take the route: raw rows of at most this many bytes.  Measured on an MI355X at batchSize 128
+ * (profiles/act_conv_timing.json: this build with the switch held open, SMARTIES_HIP_GENERIC=4096, against the parent commit's
+ * training forward launches; us per iteration of hl_step(1) + hl_forward(n), in brackets the bare call):
+ *     rows of 2.3 KB  (12 x 12 x 4, two layers)            n = 1: 119 against 153 (44 / 50), n = 1024: 190 against 435 (167 / 333)  -- wins
+ *     rows of 12.5 KB (20 x 20 x 8, one layer)             n = 1: 175 against 135 (93 / 51), n = 1024: 669 against 605 (637 / 512)  -- loses
+ *     rows of 27.6 KB (42 x 42 x 4, two layers)            n = 1: 272 against 212 (145 / 62), n = 1024: 1764 against 1039            -- loses
+ *     rows of 110 KB  (RACER_atari.json, four layers)      n = 1: 304 against 220 (181 / 74), n = 1024: 7658 against 2628            -- loses
+ * One workgroup per row is latency-bound on its row (the load over the bus, then a chain of filter loads and MFMA blocks of ONE
+ * compute unit); at 1024 rows of 110 KB the call costs 7.4 us per row against 2.4 (which part of it -- the host copy into the staging,
+ * the reads over the bus, the kernel -- was not measured apart).  The crossing lies between 2.3 and 12.5 KB and was not located more
+ * finely: the constant sits between the two measured points, and every longer row keeps the training forward launches.  Row bytes
+ * stand in for the conv work per row as well, WITHOUT a measurement of that: a net with short rows and much conv work (4.1 KB rows
+ * through 32- and 64-channel layers, about ten times the MFMA steps of the measured 2.3 KB net) takes the route unmeasured. */
+#define HL_ACT_CONV_MAX_ROW_BYTES (6u << 10)
 
 /* n agents.  n_steps[i] = min(nnBPTTseq, t_i) + 1 (+ up to nAppendedObs states in front), as for hl_forward_sequence.
  * states: the windows back to back, oldest state first in each (sum of n_steps[i] rows of dimS raw floats).

@@ -6,6 +6,7 @@
 // act_forward_kernel (misc.hip) runs one row per workgroup with VALU dot products and serves up to 64 rows of nets up to 1024 wide.
 // Here a workgroup of 256 threads owns a block of 16 rows and runs the whole net for them on v_mfma_f32_16x16x4_f32:
 //   * the raw rows come straight from device-mapped pinned host memory and are standardised on load (rows beyond n: zeros, never read);
+//     behind convolutions the rows are act_conv_kernel's feature rows in device memory, standardised already (ActRowsArgs::stMean == nullptr);
 //   * the block's activations live in ONE LDS buffer [16][ld] from layer to layer (ld = 4 mod 32: the 64 lanes of an A-operand read
 //     -- row lane & 15, reduction index 4 s + (lane >> 4) -- fall on 64 different banks).  A layer's whole output is held in
 //     accumulators -- size / 16 tiles spread over the four wavefronts, NG groups of 64 columns each, NG = 1 / 2 / 4 / 8 picked on the
@@ -88,9 +89,10 @@ __global__ __launch_bounds__(256) void act_rows_kernel(ActRowsArgs a) {
   // loads from host memory in flight
   {
     const float* src = a.in + (size_t)row0 * a.dIn;
+    const bool raw = a.stMean != nullptr;      // (no statistics: rows standardised already -- act_conv_kernel's feature rows; (v - 0) 1 is v)
     for (int c = tid; c < a.dIn; c += 256) {
       const int k = c % a.dS;
-      const float mean = a.stMean[k], scale = a.stScale[k];
+      const float mean = raw ? a.stMean[k] : 0.f, scale = raw ? a.stScale[k] : 1.f;
       float v[AR_ROWS];
 #pragma unroll
       for (int r = 0; r < AR_ROWS; ++r) v[r] = r < rows ? src[(size_t)r * a.dIn + c] : 0.f;

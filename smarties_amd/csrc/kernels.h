@@ -369,7 +369,7 @@ constexpr int ACT_ROWS_CHUNK = 1024;      // rows per launch (HL_ACT_ROWS_CHUNK 
 constexpr long long ACT_ROWS_SMALL_NET = 192 * 1024;      // (HL_ACT_ROWS_SMALL_NET)
 constexpr int ACT_ROWS_WIDE_MIN_N = 1024;                 // (HL_ACT_ROWS_WIDE_MIN_N)
 struct ActRowsArgs {
-  const float* W; const float* stMean; const float* stScale;
+  const float* W; const float* stMean; const float* stScale;      // stMean == nullptr: the rows are standardised already (the feature rows of act_conv_kernel, device memory)
   const float* in; double* out; volatile unsigned* done; unsigned tag;      // pinned host memory (device-mapped); done: one word per row block
   int n, dS, dIn, nL, nDense, nSig, nOut, ldWo; long long indWo, indBo, indBp;
   int outFunc;
@@ -379,6 +379,22 @@ struct ActRowsArgs {
 bool act_rows_plan(ActRowsArgs* a);       // the kernel serves this net (every width and the input row <= 2048): LDS layout filled in
 int act_rows_blocks(int n);               // row blocks (= stamps) of a launch over n rows
 hipError_t launch_act_rows(const ActRowsArgs& a, hipStream_t s);
+// rollout inference of feed-forward nets behind convolutions (actconv.hip: act_conv_kernel): the conv stack of one raw row per workgroup
+// with every map in LDS, filters read from the blob in the reference layout; the row's features [extras | last map] go to a device
+// buffer that act_rows_kernel takes as its (standardised) input rows
+struct ActConvLayer { int InC, InY, InX, KnC, KnY, KnX, S, OpY, OpX, K, P; long long indW, indB;
+                      int tabOff, npg, vec; /* act_conv_plan: the layer's offset table in LDS, position tiles per unit of work, 16-byte filter loads */ };
+struct ActConvArgs {
+  const float* W; const float* stMean; const float* stScale;
+  const float* in;                 // [n][dIn] raw rows (device-mapped pinned host memory)
+  float* feat; int ldF;            // [n][ldF] feature rows
+  int n, dS, dIn, nL, recurrent;
+  int img, extras, nF, vec;        // act_conv_plan: floats of the image, state variables behind it, width of a feature row, 16-byte row loads
+  int imgOff, bufOff[2]; size_t ldsBytes;      // ... LDS offsets (floats) of the image and the two map buffers, dynamic LDS
+  ActConvLayer L[HL_MAX_CONV];
+};
+bool act_conv_plan(ActConvArgs* a);       // the kernel serves this net (feed-forward behind the stack, image + maps + offset tables within 160 KB of LDS, feature row <= ACT_ROWS_MAXW): layout filled in
+hipError_t launch_act_conv(const ActConvArgs& a, int nBlocks, hipStream_t s);
 // rollout inference of recurrent nets for many agents (actseq.hip: act_seq_kernel): a workgroup stages the recurrent stack once and
 // walks its agents' windows; states, window offsets, outputs and per-agent stamps in pinned host memory
 constexpr int ACT_SEQ_CHUNK = 512;      // agents per launch (HL_ACT_SEQ_CHUNK of include/smarties_hip_act.h)

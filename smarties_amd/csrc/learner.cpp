@@ -407,6 +407,8 @@ int hl_destroy(hl_learner* h) {
   if (h->comm) ncclCommDestroy(h->comm);
   if (h->actPin) hipHostFree(h->actPin);
   if (h->actRowsPin) hipHostFree(h->actRowsPin);
+  if (h->actConvPin) hipHostFree(h->actConvPin);
+  if (h->actConvFeat) hipFree(h->actConvFeat);
   if (h->notifyPin) hipHostFree(h->notifyPin);
   for (void* q : h->xchg.opened) hipIpcCloseMemHandle(q);
   if (h->xchg.win) { windowPoolPut(h->dev, h->xchg.winBytes, h->xchg.win); h->xchg.win = nullptr; }      // (never back to the allocator: windowPoolGet)

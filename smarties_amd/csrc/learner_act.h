@@ -132,6 +132,73 @@ static int actRowsForward(hl_learner* h, int n, const float* states, double* out
   }
   return HL_OK;
 }
+// the conv-stack kernel (actconv.hip) and the row-block kernel behind it serve this net: feed-forward, convolutions in front, image and maps
+// within a workgroup's LDS, feature rows and dense layers within the row-block kernel's bounds; SMARTIES_HIP_GENERIC bit 2 keeps the route
+// over the training buffers.  Depends on the net only, never on n: a row's result is the same alone, among others and through the
+// window calls
+static bool act_conv_ok(hl_learner* h) {
+  if (h->actConvState) return h->actConvState > 0;
+  h->actConvState = -1;
+  if (h->nConv < 1 || h->nHidden < 2 || (h->generic & 2)) return false;
+  // raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES: the copy into pinned staging costs more than the route saves (the header's figures);
+  // SMARTIES_HIP_GENERIC bit 4096 holds the switch open (tests, tools/act_conv_timing.py)
+  if ((size_t)h->dIn * sizeof(float) > (size_t)HL_ACT_CONV_MAX_ROW_BYTES && !(h->generic & 4096)) return false;
+  ActConvArgs& c = h->actConv; c = ActConvArgs{};
+  c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = h->recurrent ? 1 : 0;
+  for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
+    c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
+  if (!act_conv_plan(&c) || c.extras != h->extras || c.nF != h->hid[1].nIn) return false;
+  // the dense layers behind: hid[1 ..] on feature rows [extras | last map], standardised already
+  ActRowsArgs& a = h->actConvRows; a = ActRowsArgs{};
+  a.dS = c.nF; a.dIn = c.nF; a.nL = h->nHidden - 1; a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo;
+  a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp; a.outFunc = h->cfg.nnOutputFunc;
+  for (int j = 1; j < h->nHidden; ++j) { const DevHidden& d = h->hid[j];
+    a.L[j - 1] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
+  if (!act_rows_plan(&a)) return false;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return false;
+  h->actConvCus = cus;
+  // rows per chunk: no more than HL_ACT_CONV_STAGE_BYTES of staged raw rows, whole blocks of 16 rows, at least one
+  const size_t fit = (size_t)HL_ACT_CONV_STAGE_BYTES / ((size_t)h->dIn * sizeof(float));
+  h->actConvCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, fit) & ~(size_t)15));
+  h->actConvState = 1;
+  return true;
+}
+// n rows of such a net in chunks of actConvCap rows: per chunk one copy into pinned staging -- [outputs | raw rows | one stamp per block
+// of 16 rows], sized here at the first call together with the device buffer of a chunk's feature rows --, two launches in the learner's
+// stream (the conv stack, a workgroup per row up to the number of compute units, which reads the raw rows from the mapped staging itself
+// -- a device copy made by one hipMemcpyAsync ahead of the launch was slower in development, include/smarties_hip_act.h --; the dense layers on the feature rows), a poll of the second launch's block stamps, one copy out.  Neither
+// the minibatch buffers, the training activations, the prepared filter layouts nor a minibatch drawn ahead are touched, and the stream
+// is not synchronised
+static int actConvForward(hl_learner* h, int n, const float* states, double* outputs) {
+  const int cap = h->actConvCap, nF = h->actConv.nF;
+  const size_t outBytes = (size_t)cap * h->nOut * sizeof(double), inBytes = (size_t)cap * h->dIn * sizeof(float);
+  if (!h->actConvPin) {
+    const size_t bytes = outBytes + inBytes + (size_t)act_rows_blocks(cap) * sizeof(unsigned);
+    if (!h->actConvFeat) HIPCK(devAlloc(&h->actConvFeat, (size_t)cap * nF));      // (kept if the pinned block below fails: the next call tries that again)
+    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actConvPin), bytes, hipHostMallocMapped));
+    std::memset(h->actConvPin, 0, bytes);
+  }
+  double* pOut = reinterpret_cast<double*>(h->actConvPin);
+  float* pIn = reinterpret_cast<float*>(h->actConvPin + outBytes);
+  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(h->actConvPin + outBytes + inBytes);
+  for (int r0 = 0; r0 < n; r0 += cap) {
+    const int m = std::min(cap, n - r0);
+    std::memcpy(pIn, states + (size_t)r0 * h->dIn, (size_t)m * h->dIn * sizeof(float));
+    ActConvArgs c = h->actConv;
+    c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
+    c.in = pIn; c.feat = h->actConvFeat; c.ldF = nF; c.n = m;
+    ActRowsArgs a = h->actConvRows;
+    a.W = h->W; a.stMean = nullptr; a.stScale = nullptr;
+    a.in = h->actConvFeat; a.out = pOut; a.done = pDone; a.n = m;
+    a.tag = ++h->actTag; if (a.tag == 0) a.tag = ++h->actTag;
+    HIPCK(timed(h, "act_conv", h->stream, [&] { return launch_act_conv(c, h->actConvCus, h->stream); }));
+    HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+    { int rc = actWait(h, pDone, act_rows_blocks(m), a.tag); if (rc) return rc; }
+    std::memcpy(outputs + (size_t)r0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
+  }
+  return HL_OK;
+}
 int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   if (!h || n < 0 || (n > 0 && (!states || !outputs))) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
@@ -160,6 +227,8 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   // (a net beyond ACT_ROWS_SMALL_NET weights: only from ACT_ROWS_WIDE_MIN_N rows on and where the launches over the training buffers would
   // need two rounds of Mmax rows or more -- below, one workgroup per 16 rows streaming all weights takes longer than they do)
   if (act_rows_ok(h) && (h->actRowsSmall || (n >= ACT_ROWS_WIDE_MIN_N && n >= 2 * h->Mmax))) return actRowsForward(h, n, states, outputs);
+  // convolutions in front of a feed-forward net: the conv stack of a row per workgroup, then the row-block kernel on its features -- any n
+  if (act_conv_ok(h)) return actConvForward(h, n, states, outputs);
   { int rc = dropPresample(h); if (rc) return rc; }      // the forward pass borrows minibatch buffer 0
   // (with appended observations a row holds the raw state of step t followed by those of t-1 .. t-nAppendedObs)
   if (!h->dActS) { HIPCK(devAlloc(&h->dActS, (size_t)h->Mmax * h->dIn)); HIPCK(devAlloc(&h->dActO, (size_t)h->Mmax * h->nOut)); }

@@ -108,6 +108,11 @@ struct hl_learner {
   double* dStatsIns = nullptr; bool statsFresh = false, anyStep = false;
   unsigned char* actPin = nullptr; unsigned actTag = 0; bool actFastOk = false;     // rollout inference of a few agents (hl_forward)
   int actRowsState = 0; bool actRowsSmall = false; unsigned char* actRowsPin = nullptr; ActRowsArgs actRows{};      // many rows of a dense net (actrows.hip): 0 not looked at yet / 1 the row-block kernel serves the net / -1 not; the net is small enough for the route at any row count (ACT_ROWS_SMALL_NET); its pinned staging (allocated at the first call that takes the route); the launch arguments
+  // many rows of a feed-forward net behind convolutions (actconv.hip + actrows.hip): 0 not looked at yet / 1 the two kernels serve the net / -1 not;
+  // compute units; rows per chunk; pinned staging [outputs | raw rows | stamps] and the device buffer of a chunk's feature rows
+  // (all allocated at the first call that takes the route); the launch arguments of the two kernels
+  int actConvState = 0, actConvCus = 0, actConvCap = 0; unsigned char* actConvPin = nullptr; float* actConvFeat = nullptr;
+  ActConvArgs actConv{}; ActRowsArgs actConvRows{};
   int actTmState = 0;      // ... of a net whose layers run time-step-major (rectm.hip): 0 not looked at yet / 1 its acting windows go through those launches, many agents as one chain / -1 not
   int actWinState = 0;     // ... of every other recurrent net (rec.hip's workgroup-per-sample kernels, agent b = workgroup b): 0 not looked at yet / 1 many agents as one chain / -1 not
   int actSeqState = 0, actSeqCus = 0; size_t actSeqPinOff = 0; ActSeqArgs actSeq{};      // many agents of a recurrent net (hl_forward_sequences): 0 not looked at yet / 1 the batched kernel serves the net / -1 not; compute units; its part of actPin; the launch arguments
@@ -134,6 +139,7 @@ struct hl_learner {
   //   1 no two-kernel fused step            2 no forward chain / activation kernel / deferred beta      4 recurrent: unfused launches, chunked dW
   //   8 conv: per-layer launches behind the first layer       16 conv: any-geometry kernels       32 conv: gather-form filter gradients
   //  64 conv: stacked rows, no row-block kernels              128 large batches: the common tile launches      256 weight-gradient tiles in launches of their own
+  // 4096 acting behind convolutions: the route of actconv.hip also for raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES (tests, tools/act_conv_timing.py)
   int generic = 0;
   bool plainGraph = false;      // the replayed steps of this net are stepEager's launches as graph nodes (the next minibatch's sampler in front): nets none of the rider forms serves
   // graphs of exactly n steps (hl_prepare_steps, or a call size seen three times in a row): the whole call is one launch
