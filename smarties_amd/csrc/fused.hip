@@ -36,6 +36,17 @@ namespace hl {
 #ifndef FUSED_NT
 #define FUSED_NT 512        // threads per workgroup of the fused kernel
 #endif
+// chained h1 -> x2 (512 threads, H >= 64): how many wavefronts chain (4: waves 4-7, the others run the fp64 head terms beside them;
+// 8: all of them, H >= 128) and where those head terms sit (0: beside / behind the chain, 1: under the wait of the panel barrier).
+// The shipped values are the ones measured fastest (docs/EXPERIMENTS.md); the others build for comparison.  With 4 every weight keeps
+// the bits of the panel form; with 8 the K split is finer (redSum<8>).
+#ifndef FUSED_CHAINW
+#define FUSED_CHAINW 8
+#endif
+#ifndef FUSED_PRE_LATE
+#define FUSED_PRE_LATE 1
+#endif
+#define FTLD 17             // leading dimension of the own-tile scratch of the chained form (x1 at 0, h1 at 16 * FTLD + 16)
 
 // development time stamps of workgroup (panel 0, tile 1), 100 MHz clock: -DHL_FSTAMPS (its own flag: the tail stamps of
 // -DHL_TAIL_STAMPS use the same slots of DevScalars::dbgT)
@@ -44,8 +55,11 @@ namespace hl {
 #define HL_FSTAMP_PANEL 0      // (another panel: a workgroup in the crowd of a larger batch)
 #endif
 #define FSTAMP(i) do { if (threadIdx.x == 0 && panel == HL_FSTAMP_PANEL && n == 1) a.sc->dbgT[i] = wall_clock64(); } while (0)
+// the same for thread t: the first lane of the wavefront that chains this tile (slots 14 - 16 of the chained form)
+#define FSTAMPT(t, i) do { if (threadIdx.x == (t) && panel == HL_FSTAMP_PANEL && n == 1) a.sc->dbgT[i] = wall_clock64(); } while (0)
 #else
 #define FSTAMP(i) do { } while (0)
+#define FSTAMPT(t, i) do { } while (0)
 #endif
 
 // (-DHL_FSTAMPS) when does the LAST workgroup of each kind finish?  dbgT[20] ordinary panels, [21] panels with next-state rows (they
@@ -64,14 +78,14 @@ namespace hl {
 #define FVARIANT_STOP(n) do { } while (0)
 #endif
 
-// LDS carve-up (floats).  R1: h1 panel, later the W1 row tile of the dX contraction.  R2: W0
+// LDS carve-up (floats).  R1: h1 panel (chained form: unused until then), later the W1 row tile of the dX contraction.  R2: W0
 // (k-major, leading dimension H+16).  R3: W1 column tile, later f'(x2) -> delta_x2 panel.
 __host__ __device__ inline int fusedR2Floats(int dSp, int H) { return dSp * (H + 16); }
 __host__ __device__ inline int fusedR3Floats(int H) { const int a = H * 16, b = 16 * FLDR; return a > b ? a : b; }
 __host__ __device__ inline size_t fusedLdsBytes(int dS, int H) {
   const int dSp = (dS + 3) & ~3;
   const size_t fl = (size_t)16 * FLDR + fusedR2Floats(dSp, H) + fusedR3Floats(H) + (size_t)H * 8 /*Wout*/ + 16 * FLDS +
-                    2048 /*red*/ + 3 * (size_t)H /*b0, wres, bres*/ + 512 /*sO*/ + 128 /*sDo*/ + 256 /*own tile scratch*/ + 32 /*bo, bp*/ + 4 /*beta hand-off*/;
+                    2048 /*red*/ + 3 * (size_t)H /*b0, wres, bres*/ + 512 /*sO*/ + 128 /*sDo*/ + 2 * (16 * FTLD + 16) /*own tile scratch: x1, h1*/ + 32 /*bo, bp*/ + 4 /*beta hand-off*/;
   const size_t bytes = fl * 4;
   return bytes > TAIL_LDS_BYTES ? bytes : TAIL_LDS_BYTES;
 }
@@ -129,6 +143,14 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   constexpr int QO = (H * 2 + NT - 1) / NT;      // float4 per thread of Wout [H][8]
   constexpr int Q0 = (32 * H4 + NT - 1) / NT;    // float4 per thread of W0 (dS <= 32)
   constexpr int QS = 512 / NT;                   // state-tile elements per thread
+  // chained form: the wavefronts that contract x2 compute the h1 tiles of their own K range with swapped operands, so that the
+  // accumulators of the first product are the A operand of the second (no h1 panel in LDS, no barrier between the two)
+  constexpr bool CHAIN = (NW == 8 && H >= 64);
+  constexpr int CW = (FUSED_CHAINW == 8 && H >= 128) ? 8 : 4;      // chaining wavefronts
+  constexpr int CT = CHAIN ? H / (16 * CW) : 1;                    // h1 tiles per chaining wavefront
+  constexpr int CTID = CW == 8 ? 0 : 256;                          // (stamps) first lane of the wavefront that chains tile 1
+  constexpr int TLD = CHAIN ? FTLD : 16;                           // own-tile scratch: leading dimension, offset of the h1 tile
+  constexpr int TY1 = 16 * FTLD + 16;
 #if defined(HL_FSTAMPS)
   if (threadIdx.x == 0 && blockIdx.x == 8 + 8) a.sc->dbgT[31] = wall_clock64();   // (panel 0, tile 1): kernel entry
 #endif
@@ -166,8 +188,8 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   float* sBr = sWr + H;                                        // [H] residual b
   double* sO = reinterpret_cast<double*>(sBr + H);             // [16][16]  (offset is a multiple of 8 bytes)
   float* sDo = reinterpret_cast<float*>(sO + 256);             // [16][8]
-  float* sT = sDo + 128;                                       // [16][16] own-tile scratch (x1, later delta_y3)
-  float* sBo = sT + 256;                                       // [16] output bias, [16] ParamLayer bias
+  float* sT = sDo + 128;                                       // own-tile scratch: x1 [16][16]; chained form: x1 and h1, [16][FTLD] each
+  float* sBo = sT + 2 * (16 * FTLD + 16);                      // [16] output bias, [16] ParamLayer bias
   float* sBp = sBo + 16;
   double* sBeta = reinterpret_cast<double*>(sBp + 16);          // [0] beta of this step, [1] != 0: it has arrived (deferBeta)
 
@@ -262,7 +284,35 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
     if (arr) misc = arr[sl];
   }
 
+  float aggv = 0.f;
+  if constexpr (CHAIN) {      // (nothing between here and the x2 barrier for the element threads to wait behind)
+    asm volatile("" : "+v"(eidv));
+    if (aggOwner) aggv = en < AGG_USED ? a.rp.epAgg[(size_t)eidv * AGG_N + en] : (en == AGG_LEN ? (float)a.rp.epN[eidv] : 0.f);
+  }
 
+  // ---- head terms that do not depend on the network outputs of this step (the policy stdev comes
+  // from the ParamLayer bias alone).  With 8 waves the element threads (waves 0-3) compute them
+  // while waves 4-7 run the x2 contraction; with 4 waves they follow the exchange stores. ------------
+  const bool live = rowValid && !isNext;
+  const double MAXM = 8.31776613503286;
+  double stdev = 1, invStd = 1, dPos = 0, bInv = 1, invVarMu = 1, u2 = 0, lq = 0, CmuCpi = 1;
+  bool bnd = false;
+  auto headPrecompute = [&]() {
+    asm volatile("" : "+v"(act), "+v"(bMean), "+v"(bStd));   // keep the fp64 work (and its wait on the gathers) here
+    if (live && en < dA) {
+      bnd = ((a.boundedMask >> en) & 1ull) != 0;
+      const double pp = (double)sBp[en];
+      const double rt = sqrt(1 + pp * pp);
+      stdev = (pp + rt) / 2; invStd = 1 / stdev; dPos = (1 + pp / rt) / 2;
+      bInv = 1 / bStd; invVarMu = 1 / (bStd * bStd);
+      u2 = (act - bMean) * bInv;
+      const double qq = stdev * bInv;
+      lq = log(qq); CmuCpi = qq * qq;
+    }
+  };
+
+  float x1o = 0.f, y1o = 0.f;
+  if constexpr (!CHAIN) {
   // ---- h1 = f(S W0 + b0), whole panel: wave w computes column tiles w, w+4, ... --------------------
   if (wave < HT) {
     f32x4 acc[TPW];
@@ -307,40 +357,97 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   }
   FSTAMP(15);
   __syncthreads();
-  const float x1o = sT[em * 16 + en], y1o = sY1[em * FLDR + n0 + en];
+  x1o = sT[em * 16 + en]; y1o = sY1[em * FLDR + n0 + en];
   FSTAMP(2);
   FVARIANT_STOP(2);
   if (eth && row < B) a.Y1[(size_t)row * ldA0 + n0 + en] = y1o;     // A operand of the dW1 contraction
-  float aggv = 0.f;
   asm volatile("" : "+v"(eidv));      // keeps the index arithmetic (and the wait for the load) from being hoisted into the prologue
   if (aggOwner) aggv = en < AGG_USED ? a.rp.epAgg[(size_t)eidv * AGG_N + en] : (en == AGG_LEN ? (float)a.rp.epN[eidv] : 0.f);
-
-  // ---- head terms that do not depend on the network outputs of this step (the policy stdev comes
-  // from the ParamLayer bias alone).  With 8 waves the element threads (waves 0-3) compute them
-  // while waves 4-7 run the x2 contraction; with 4 waves they follow the exchange stores. ------------
-  const bool live = rowValid && !isNext;
-  const double MAXM = 8.31776613503286;
-  double stdev = 1, invStd = 1, dPos = 0, bInv = 1, invVarMu = 1, u2 = 0, lq = 0, CmuCpi = 1;
-  bool bnd = false;
-  auto headPrecompute = [&]() {
-    asm volatile("" : "+v"(act), "+v"(bMean), "+v"(bStd));   // keep the fp64 work (and its wait on the gathers) here
-    if (live && en < dA) {
-      bnd = ((a.boundedMask >> en) & 1ull) != 0;
-      const double pp = (double)sBp[en];
-      const double rt = sqrt(1 + pp * pp);
-      stdev = (pp + rt) / 2; invStd = 1 / stdev; dPos = (1 + pp / rt) / 2;
-      bInv = 1 / bStd; invVarMu = 1 / (bStd * bStd);
-      u2 = (act - bMean) * bInv;
-      const double qq = stdev * bInv;
-      lq = log(qq); CmuCpi = qq * qq;
-    }
-  };
+  }
   constexpr bool SPLITW = (NW == 8 && H >= 16);      // waves 4-7 contract, waves 0-3 do the fp64 terms
-  constexpr int XW = SPLITW ? 4 : KWAVES;            // waves sharing the x2 contraction
+  constexpr int XW = CHAIN ? CW : (SPLITW ? 4 : KWAVES);      // waves sharing the x2 contraction
   constexpr int XKW = H / XW, XNK = XKW / 4;
 
+  if constexpr (CHAIN) {
+    // ---- h1 tiles of this wave's K range, then straight on to its share of x2 = h1 W1 + b1.  The first product runs with the
+    // operands exchanged, x1^T = W0^T S^T: lane (li, lc) supplies W0[4s + lc][column of row li] as A and S[li][4s + lc] as B and
+    // gets acc[r] = x1[sample li][row 4 lc + r of the tile] back -- the sample it supplies as A of the second product.  Row i of
+    // the tile is column c0 + (i >> 2) + 4 (i & 3), so acc[r] is column c0 + 4 r + lc: step (tile, r) of the second product
+    // contracts k = c0 + 4 r + lc, lc = 0..3, against W1[k][n0 + li] -- the k grouping, the step order and the accumulator of
+    // every step are those of waveMma over the h1 panel, and so are the bits of x2 ----------------------------------------------
+    const int cw = CW == 8 ? wave : wave - 4;
+    if (cw >= 0) {
+      const int cb = cw * XKW;                         // first h1 column = first k of this wave
+      const int pc = (li >> 2) + 4 * (li & 3);
+      // B operands of the second product, requested before the first MFMA: R3 is staged
+      float w1b[CT][4];
+#pragma unroll
+      for (int t = 0; t < CT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w1b[t][r] = sR3[(cb + 16 * t + 4 * r + lc) * 16 + li];
+      }
+      f32x4 acc[CT];
+#pragma unroll
+      for (int t = 0; t < CT; ++t) acc[t] = z4;
+      const int nk4 = dSp >> 2;
+      // operands of step s+1 are read while the MFMAs of step s run
+      float bv = sS[li * FLDS + lc], av[CT];
+#pragma unroll
+      for (int t = 0; t < CT; ++t) av[t] = sR2[lc * LDW0 + cb + 16 * t + pc];
+      for (int s = 0; s < nk4; ++s) {
+        const int kn = s + 1 < nk4 ? 4 * (s + 1) + lc : lc;
+        const float bvn = sS[li * FLDS + kn];
+        float avn[CT];
+#pragma unroll
+        for (int t = 0; t < CT; ++t) avn[t] = sR2[kn * LDW0 + cb + 16 * t + pc];
+#pragma unroll
+        for (int t = 0; t < CT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bv, acc[t], 0, 0, 0);
+        bv = bvn;
+#pragma unroll
+        for (int t = 0; t < CT; ++t) av[t] = avn[t];
+      }
+      FSTAMPT(CTID, 14);
+      // bias and activation in place; the workgroup's own column tile also goes to LDS, x1 and h1, for the element threads
+      // (residual path, A operand of dW1, f'(x1))
+      float bb[CT][4];
+#pragma unroll
+      for (int t = 0; t < CT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bb[t][r] = sB0[cb + 16 * t + 4 * r + lc];
+      }
+      dispatchFunc<CF>(func, [&](auto F) {
+        constexpr int FN = decltype(F)::value;
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+          const bool own = cb + 16 * t == n0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x = acc[t][r] + bb[t][r], y = actEvalT<FN>(x);
+            acc[t][r] = y;
+            if (own) { sT[li * TLD + 4 * r + lc] = x; sT[TY1 + li * TLD + 4 * r + lc] = y; }
+          }
+        }
+      });
+      FSTAMPT(CTID, 15);
+      f32x4 xa0 = z4, xa1 = z4;
+#pragma unroll
+      for (int t = 0; t < CT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (r & 1) xa1 = __builtin_amdgcn_mfma_f32_16x16x4f32(acc[t][r], w1b[t][r], xa1, 0, 0, 0);
+          else xa0 = __builtin_amdgcn_mfma_f32_16x16x4f32(acc[t][r], w1b[t][r], xa0, 0, 0, 0);
+        }
+      }
+      const f32x4 xacc = xa0 + xa1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[cw * 256 + (lc * 4 + r) * 16 + li] = xacc[r];
+      FSTAMPT(CTID, 16);
+      if (CW == 8 && !FUSED_PRE_LATE) headPrecompute();
+    } else if (!FUSED_PRE_LATE) headPrecompute();
+    FSTAMP(2);
+    FVARIANT_STOP(2);
+  } else {
   // ---- own tile of x2 = h1 W1 + b1: K split over XW waves ------------------------------------------------
-  {
     const int xw = SPLITW ? wave - 4 : wave;
     if (xw >= 0 && xw < XW) {
       const int k0 = xw * XKW + lc;
@@ -351,6 +458,10 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   }
   __syncthreads();
   FSTAMP(3);
+  if constexpr (CHAIN) {
+    x1o = sT[em * TLD + en]; y1o = sT[TY1 + em * TLD + en];
+    if (eth && row < B) a.Y1[(size_t)row * ldA0 + n0 + en] = y1o;     // A operand of the dW1 contraction
+  }
   float y3 = 0.f;      // (padding rows: zero, they add nothing to the partial outputs)
   if (rowValid) {
     const float v = redSum<XW>(red, tid);
@@ -400,7 +511,7 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   // (one L2 round trip: the target comes from the early read `ctr0`, the arrival returns nothing, polling starts at once; the
   // counter wraps soundly: HT is a power of two and the comparison is a signed difference)
   if (HT > 1 && tid == 0) __hip_atomic_fetch_add(a.panelCtr + panel * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // h1 is dead (own tile kept in registers): R1 takes the W1 row tile of the dX contraction while the peers arrive
+  // h1 is dead (own tile kept in registers; chained form: it never was there): R1 takes the W1 row tile of the dX contraction while the peers arrive
   float* sF2 = sR3; float* sBx = sY1;
 #pragma unroll
   for (int q = 0; q < QP; ++q) {
@@ -411,6 +522,7 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
       d[0] = make_float2(w1r[q][0], w1r[q][1]); d[1] = make_float2(w1r[q][2], w1r[q][3]);
     }
   }
+  if (CHAIN && FUSED_PRE_LATE) { headPrecompute(); FSTAMP(17); }      // (the gathers are in: vmcnt(0) above)
   if (HT > 1 && tid == 0) {
     unsigned* ctr = a.panelCtr + panel * 32;
     const unsigned barTarget = (ctr0 / (unsigned)HT + 1u) * (unsigned)HT;
