@@ -186,7 +186,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     HIPCK(hipStreamCreateWithFlags(&h->sideStream, hipStreamNonBlocking));
     HIPCK(hipEventCreateWithFlags(&h->evMain, hipEventDisableTiming)); HIPCK(hipEventCreateWithFlags(&h->evSide, hipEventDisableTiming));
   }
-  // (+ PARAM_TAIL unused floats: scratch "bias" rows of weight-gradient problems that have no bias, step_exec.h)
+  // (+ PARAM_TAIL unused floats: scratch "bias" rows of weight-gradient problems that have no bias, step_exec.h; allocated ONCE: the acting predicates cache W, learner_act.h: actFillShared)
   HIPCK(devAlloc(&h->W, (size_t)h->nParams + PARAM_TAIL)); HIPCK(devAlloc(&h->M1, (size_t)h->nParams + PARAM_TAIL));
   HIPCK(devAlloc(&h->M2, (size_t)h->nParams + PARAM_TAIL)); HIPCK(devAlloc(&h->G, (size_t)h->nParams + PARAM_TAIL));
   HIPCK(devAlloc(&h->sc, 1));
@@ -231,8 +231,6 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     if (h->nConv > 1 && !(h->generic & 8)) conv_tail_plan(h->cg, h->nConv, &h->convTail);
     if (h->generic & 16) { h->convTail.atari = 0; h->convRowsAtari = false; }
   }
-  h->actFastOk = !h->recurrent && h->nConv == 0 && !(h->generic & 2);
-  for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_MAXW || h->hid[j].nIn > ACT_MAXW) h->actFastOk = false;
   if (h->recurrent && cfg->encoder_rnn && h->nEncLayers > 0 && h->nEncLayers < h->nHidden - (h->nConv > 0 ? 1 : 0)) {
     const int j0 = h->nConv > 0 ? 1 : 0; const DevHidden& top = h->hid[j0 + h->nEncLayers - 1]; const DevHidden& up = h->hid[j0 + h->nEncLayers];
     if ((up.lstm * up.size) % 4 != 0) return fail(h, HL_ERR_UNSUPPORTED, "MGU layer behind RNN encoder layers: an even number of cells is needed");
@@ -367,7 +365,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   }
   HIPCK(devAlloc(&h->dFlatGiven, B));
   HIPCK(devAlloc(&h->dMoments, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dMomentsPrev, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dStatsOut, 16)); HIPCK(devAlloc(&h->dStatsIns, 16));
-  HIPCK(devAlloc(&h->rp.stMean, h->dS)); HIPCK(devAlloc(&h->rp.stScale, h->dS)); HIPCK(devAlloc(&h->rp.stStd, h->dS));
+  HIPCK(devAlloc(&h->rp.stMean, h->dS)); HIPCK(devAlloc(&h->rp.stScale, h->dS)); HIPCK(devAlloc(&h->rp.stStd, h->dS));      // (ONCE: cached by the acting predicates, as W)
   HIPCK(devAlloc(&h->rp.farStart, 4 * 256));
   {   // ring slack: an eighth of the budget plus room for the episodes in flight (bounded in bytes for image-sized states)
     const long long slack = std::max<long long>(512, std::min<long long>(8192, (64ll << 20) / ((long long)h->dS * 4)));
@@ -405,10 +403,7 @@ int hl_destroy(hl_learner* h) {
   timerFlush(h);
   invalidateGraphs(h);
   if (h->comm) ncclCommDestroy(h->comm);
-  if (h->actPin) hipHostFree(h->actPin);
-  if (h->actRowsPin) hipHostFree(h->actRowsPin);
-  if (h->actConvPin) hipHostFree(h->actConvPin);
-  if (h->actConvFeat) hipFree(h->actConvFeat);
+  for (unsigned char* q : {h->act.pin, h->act.rowsPin, h->act.convPin}) if (q) hipHostFree(q);
   if (h->notifyPin) hipHostFree(h->notifyPin);
   for (void* q : h->xchg.opened) hipIpcCloseMemHandle(q);
   if (h->xchg.win) { windowPoolPut(h->dev, h->xchg.winBytes, h->xchg.win); h->xchg.win = nullptr; }      // (never back to the allocator: windowPoolGet)
@@ -417,7 +412,7 @@ int hl_destroy(hl_learner* h) {
     h->dRedMax, h->dRedErr, h->dMomPartial, h->dMoments, h->dMomentsPrev, h->dStatsOut, h->dStatsIns,
     h->rp.S, h->rp.A, h->rp.MU, h->rp.R, h->rp.V, h->rp.ADV, h->rp.RET, h->rp.DQ, h->rp.IMPW, h->rp.DKL,
     h->rp.epOff, h->rp.epN, h->rp.epTerm, h->rp.epAgg, h->rp.posEid, h->rp.posPrefix, h->rp.stMean, h->rp.stScale,
-    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->dActS, h->dActO};
+    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->act.dS, h->act.dO, h->act.convFeat};
   for (int pb = 0; pb < 2; ++pb) {
     DevBatch& bt = h->buf[pb].bt;
     void* bp[] = {h->buf[pb].X0, bt.sVals, bt.tag, bt.pEid, bt.pNextOf, bt.flat, bt.pos, bt.eid, bt.t, bt.slot, bt.nextOf, bt.nextSrc,

@@ -1,81 +1,18 @@
 // smarties_amd/csrc/learner_act.h -- part of learner.cpp's ONE translation unit (included there, like step_exec.h): rollout inference (Learner::select's network evaluation): hl_forward, hl_forward_sequence, hl_forward_sequences
 #pragma once
 #include "../../include/smarties_hip_act.h"
+#include "act_host.h"
 static_assert(ACT_SEQ_CHUNK == HL_ACT_SEQ_CHUNK, "the chunk capacity the header states");
 static_assert(ACT_ROWS_CHUNK == HL_ACT_ROWS_CHUNK, "the chunk capacity the header states");
 static_assert(ACT_ROWS_SMALL_NET == HL_ACT_ROWS_SMALL_NET && ACT_ROWS_WIDE_MIN_N == HL_ACT_ROWS_WIDE_MIN_N, "the switch the header states");
 
-static size_t actPinFloats(const hl_learner* h) { return std::max((size_t)ACT_MAXROWS * h->dIn, (size_t)(std::max(h->recWin, 1) + h->nApp) * h->dS); }
-// the batched window kernel (actseq.hip) serves this net: one recurrent layer type, no convolutions in front, layers within its bounds
-static bool actSeqOk(hl_learner* h) {
-  if (h->actSeqState) return h->actSeqState > 0;
-  h->actSeqState = -1;
-  if (!h->recurrent || h->nConv > 0 || h->recSplit) return false;
-  const RecArgs ra = recArgs(h, 0);
-  ActSeqArgs& a = h->actSeq; a = ActSeqArgs{};
-  a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
-  a.dS = h->dS; a.nApp = h->nApp; a.recWin = h->recWin; a.nL = ra.nL; a.gates = ra.gates; a.func = ra.func;
-  a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo; a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp;
-  a.outFunc = h->cfg.nnOutputFunc;
-  for (int j = 0; j < ra.nL; ++j) { const RecLayer& L = ra.L[j]; a.L[j] = ActSeqLayer{L.nIn, L.nC, L.hasRes, L.resW, L.indW, L.indB, L.indWr, L.indBr, 0, 0}; }
-  if (!act_seq_plan(&a)) return false;
+extern "C++" {      // (learner.cpp includes this file among its extern "C" entry points; the chunk drivers below are templates)
+static unsigned actNextTag(hl_learner* h) { if (++h->act.tag == 0) ++h->act.tag; return h->act.tag; }      // (0 is what a fresh stage holds)
+// compute units of the device (0: the runtime does not say)
+static int actCus(hl_learner* h) {
   int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return false;
-  h->actSeqCus = cus; h->actSeqState = 1;
-  return true;
-}
-// the time-step-major launches (rectm.hip) serve this net's acting window -- hl_forward_sequence's route where a layer is wider than 256
-// cells --: many agents' windows then run as the samples of one chain of those launches
-static bool actTmOk(hl_learner* h) {
-  if (h->actTmState) return h->actTmState > 0;
-  h->actTmState = -1;
-  if (!h->recurrent || h->nConv > 0 || h->recSplit) return false;
-  static const float one = 0.f;      // (the predicate asks for given states, it does not read them)
-  RecArgs ra = recArgs(h, 0); ra.B = 1; ra.actStates = &one; ra.actSteps = 1; ra.actCtx = 0;
-  if (!rec_tm_act_ok(ra)) return false;
-  h->actTmState = 1;
-  return true;
-}
-// the workgroup-per-sample window kernels (rec.hip) serve this net's acting window -- hl_forward_sequence's route for every net the two
-// predicates above leave: convolutions in front, RNN encoder layers under MGU layers, a window beyond the batched kernel's LDS --: many
-// agents' windows then run as the samples of hl_forward_sequence's own launches, workgroup b on agent b's window
-static bool actWinOk(hl_learner* h) {
-  if (h->actWinState) return h->actWinState > 0;
-  h->actWinState = -1;
-  if (!h->recurrent) return false;
-  static const float one = 0.f;      // (the predicate asks for given states, it does not read them)
-  for (int seg = h->recSplit ? 0 : -1; seg < (h->recSplit ? 2 : 0); ++seg) {
-    RecArgs ra = recArgs(h, 0, seg); ra.B = 1; ra.actStates = &one; ra.actSteps = 1; ra.actCtx = 0;
-    if (!rec_win_act_ok(ra)) return false;
-  }
-  h->actWinState = 1;
-  return true;
-}
-// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the chains of the other two routes borrow
-// the training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples -- and, behind
-// convolutions, no more than whose stacked window rows fit HL_ACT_WIN_STAGE_BYTES of pinned staging (never fewer than one)
-static int actWinCap(const hl_learner* h) {
-  size_t cap = (size_t)std::min(h->B, ACT_SEQ_CHUNK);
-  if (h->nConv > 0) cap = std::min(cap, (size_t)HL_ACT_WIN_STAGE_BYTES / ((size_t)h->recK * h->dIn * sizeof(float)));
-  return (int)std::max(cap, (size_t)1);
-}
-static int actChunkCap(hl_learner* h) { return actSeqOk(h) ? ACT_SEQ_CHUNK : (actTmOk(h) ? std::min(h->B, ACT_SEQ_CHUNK) : (actWinOk(h) ? actWinCap(h) : 0)); }
-// one pinned block: [outputs of ACT_MAXROWS rows | their states | their stamps] of hl_forward / hl_forward_sequence, then (recurrent nets)
-// [outputs | stamps | window offsets | state counts | states] of a chunk of actChunkCap agents; behind convolutions the states are the
-// agents' stacked window rows, recK rows of dIn floats each
-static size_t actSeqStateFloats(const hl_learner* h, int cap) {
-  return h->nConv > 0 ? (size_t)cap * h->recK * h->dIn : (size_t)cap * (h->recWin + h->nApp) * h->dS;
-}
-static int actPinEnsure(hl_learner* h) {
-  if (h->actPin) return HL_OK;
-  size_t bytes = (size_t)ACT_MAXROWS * (h->nOut * sizeof(double) + sizeof(unsigned)) + actPinFloats(h) * sizeof(float) + 256;
-  bytes = (bytes + 255) & ~(size_t)255;
-  h->actSeqPinOff = bytes;
-  const size_t cap = (size_t)actChunkCap(h);
-  if (cap) bytes += cap * (h->nOut * sizeof(double) + sizeof(unsigned)) + (2 * cap + 2) * sizeof(int) + actSeqStateFloats(h, (int)cap) * sizeof(float);
-  HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actPin), bytes, hipHostMallocMapped));
-  std::memset(h->actPin, 0, bytes);
-  return HL_OK;
+  if (!h->act.cus && hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->act.cus = cus;
+  return h->act.cus;
 }
 // the kernel stamps a row once its outputs are in host memory: poll the stamps (a stream synchronisation costs ~10 us more),
 // give up after 2 s and fall back to it
@@ -88,117 +25,230 @@ static int actWait(hl_learner* h, volatile unsigned* pDone, int n, unsigned tag)
   std::atomic_thread_fence(std::memory_order_acquire);
   return HL_OK;
 }
+// the output layer on the first `rows` rows of the last hidden layer's activations; done != nullptr: the rows' stamps
+static hipError_t actOutput(hl_learner* h, int rows, double* out, volatile unsigned* done, unsigned tag) {
+  const DevHidden& q = h->hid[h->nHidden - 1];
+  return launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, rows,
+                           out, h->stream, const_cast<unsigned*>(done), tag, h->cfg.nnOutputFunc);
+}
+// what ActArgs, ActRowsArgs and ActSeqArgs spell alike: the blob, the standardisation, the output layer (all fixed from hl_create on)
+template <typename A> static void actFillShared(const hl_learner* h, A& a) {
+  a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
+  a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo; a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp;
+  a.outFunc = h->cfg.nnOutputFunc;
+}
+static int actFillLayers(const hl_learner* h, int first, ActLayer* L) {      // hid[first ..]; returns their number
+  for (int j = first; j < h->nHidden; ++j) { const DevHidden& d = h->hid[j];
+    L[j - first] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
+  return h->nHidden - first;
+}
+// the window launches' arguments for acting (segment seg of a stack of two layer types, -1: the whole stack): B windows of raw states;
+// off / cnt: the per-agent tables of a chain (nullptr: one window of `steps` states behind `ctx` context states)
+static RecArgs actRecArgs(hl_learner* h, int seg, int B, const float* states, const int* off, const int* cnt, int steps, int ctx) {
+  RecArgs ra = recArgs(h, 0, seg); ra.B = B; ra.actStates = states; ra.actOff = off; ra.actCnt = cnt; ra.actSteps = steps; ra.actCtx = ctx;
+  return ra;
+}
+static const float actNoState = 0.f;      // (a predicate asks for given states, it does not read them)
+// a few rows of a dense net, one workgroup per row (misc.hip: act_forward_kernel): layers and input rows within its bounds;
+// SMARTIES_HIP_GENERIC bit 2 keeps the route over the training buffers
+static bool actFewOk(hl_learner* h) {
+  if (h->act.fewOk) return h->act.fewOk > 0;
+  bool ok = !h->recurrent && h->nConv == 0 && !(h->generic & 2) && h->dIn <= ACT_MAXW;
+  for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_MAXW || h->hid[j].nIn > ACT_MAXW) ok = false;
+  h->act.fewOk = ok ? 1 : -1;
+  return ok;
+}
+// the batched window kernel (actseq.hip) serves this net: one recurrent layer type, no convolutions in front, layers within its bounds
+static bool actSeqOk(hl_learner* h) {
+  if (h->act.seqOk) return h->act.seqOk > 0;
+  h->act.seqOk = -1;
+  if (!h->recurrent || h->nConv > 0 || h->recSplit) return false;
+  const RecArgs ra = recArgs(h, 0);
+  ActSeqArgs& a = h->act.seqArgs; a = ActSeqArgs{};
+  actFillShared(h, a);
+  a.dS = h->dS; a.nApp = h->nApp; a.recWin = h->recWin; a.nL = ra.nL; a.gates = ra.gates; a.func = ra.func;
+  for (int j = 0; j < ra.nL; ++j) { const RecLayer& L = ra.L[j]; a.L[j] = ActSeqLayer{L.nIn, L.nC, L.hasRes, L.resW, L.indW, L.indB, L.indWr, L.indBr, 0, 0}; }
+  if (!act_seq_plan(&a) || actCus(h) < 1) return false;
+  h->act.seqOk = 1;
+  return true;
+}
+// the time-step-major launches (rectm.hip) serve this net's acting window -- hl_forward_sequence's route where a layer is wider than 256
+// cells --: many agents' windows then run as the samples of one chain of those launches
+static bool actTmOk(hl_learner* h) {
+  if (h->act.tmOk) return h->act.tmOk > 0;
+  const bool ok = h->recurrent && h->nConv == 0 && !h->recSplit && rec_tm_act_ok(actRecArgs(h, -1, 1, &actNoState, nullptr, nullptr, 1, 0));
+  h->act.tmOk = ok ? 1 : -1;
+  return ok;
+}
+// the workgroup-per-sample window kernels (rec.hip) serve this net's acting window -- hl_forward_sequence's route for every net the two
+// predicates above leave: convolutions in front, RNN encoder layers under MGU layers, a window beyond the batched kernel's LDS --: many
+// agents' windows then run as the samples of hl_forward_sequence's own launches, workgroup b on agent b's window
+static bool actWinOk(hl_learner* h) {
+  if (h->act.winOk) return h->act.winOk > 0;
+  bool ok = h->recurrent;
+  for (int seg = h->recSplit ? 0 : -1; ok && seg < (h->recSplit ? 2 : 0); ++seg) ok = rec_win_act_ok(actRecArgs(h, seg, 1, &actNoState, nullptr, nullptr, 1, 0));
+  h->act.winOk = ok ? 1 : -1;
+  return ok;
+}
 // the row-block kernel (actrows.hip) serves this net: dense, no convolutions in front, input rows and layers within its bounds;
 // SMARTIES_HIP_GENERIC bit 2 keeps the route over the training buffers
 static bool act_rows_ok(hl_learner* h) {
-  if (h->actRowsState) return h->actRowsState > 0;
-  h->actRowsState = -1;
+  if (h->act.rowsOk) return h->act.rowsOk > 0;
+  h->act.rowsOk = -1;
   if (h->recurrent || h->nConv > 0 || h->dIn > ACT_ROWS_MAXW || (h->generic & 2)) return false;
-  ActRowsArgs& a = h->actRows; a = ActRowsArgs{};
-  a.dS = h->dS; a.dIn = h->dIn; a.nL = h->nHidden; a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo;
-  a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp; a.outFunc = h->cfg.nnOutputFunc;
-  for (int j = 0; j < h->nHidden; ++j) { const DevHidden& d = h->hid[j];
-    a.L[j] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
+  ActRowsArgs& a = h->act.rowsArgs; a = ActRowsArgs{};
+  actFillShared(h, a);
+  a.dS = h->dS; a.dIn = h->dIn; a.nL = actFillLayers(h, 0, a.L);
   if (!act_rows_plan(&a)) return false;
   long long nW = (long long)h->hid[h->nHidden - 1].size * h->ldWo;
   for (int j = 0; j < h->nHidden; ++j) nW += (long long)h->hid[j].nIn * h->hid[j].ldW;
-  h->actRowsSmall = nW <= ACT_ROWS_SMALL_NET;
-  h->actRowsState = 1;
+  h->act.rowsSmall = nW <= ACT_ROWS_SMALL_NET;
+  h->act.rowsOk = 1;
   return true;
-}
-// n rows of a dense net in chunks of ACT_ROWS_CHUNK: per chunk one copy into pinned staging -- [outputs | raw rows | one stamp per row
-// block], allocated here at the first call --, one launch, a poll of the block stamps, one copy out.  Neither the minibatch buffers nor
-// a minibatch drawn ahead are touched, and the stream is not synchronised
-static int actRowsForward(hl_learner* h, int n, const float* states, double* outputs) {
-  const size_t outBytes = (size_t)ACT_ROWS_CHUNK * h->nOut * sizeof(double), inBytes = (size_t)ACT_ROWS_CHUNK * h->dIn * sizeof(float);
-  if (!h->actRowsPin) {
-    const size_t bytes = outBytes + inBytes + (size_t)act_rows_blocks(ACT_ROWS_CHUNK) * sizeof(unsigned);
-    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actRowsPin), bytes, hipHostMallocMapped));
-    std::memset(h->actRowsPin, 0, bytes);
-  }
-  double* pOut = reinterpret_cast<double*>(h->actRowsPin);
-  float* pIn = reinterpret_cast<float*>(h->actRowsPin + outBytes);
-  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(h->actRowsPin + outBytes + inBytes);
-  for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
-    const int m = std::min(ACT_ROWS_CHUNK, n - r0);
-    std::memcpy(pIn, states + (size_t)r0 * h->dIn, (size_t)m * h->dIn * sizeof(float));
-    ActRowsArgs a = h->actRows;
-    a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
-    a.in = pIn; a.out = pOut; a.done = pDone; a.n = m;
-    a.tag = ++h->actTag; if (a.tag == 0) a.tag = ++h->actTag;
-    HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
-    { int rc = actWait(h, pDone, act_rows_blocks(m), a.tag); if (rc) return rc; }
-    std::memcpy(outputs + (size_t)r0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
-  }
-  return HL_OK;
 }
 // the conv-stack kernel (actconv.hip) and the row-block kernel behind it serve this net: feed-forward, convolutions in front, image and maps
 // within a workgroup's LDS, feature rows and dense layers within the row-block kernel's bounds; SMARTIES_HIP_GENERIC bit 2 keeps the route
 // over the training buffers.  Depends on the net only, never on n: a row's result is the same alone, among others and through the
 // window calls
 static bool act_conv_ok(hl_learner* h) {
-  if (h->actConvState) return h->actConvState > 0;
-  h->actConvState = -1;
+  if (h->act.convOk) return h->act.convOk > 0;
+  h->act.convOk = -1;
   if (h->nConv < 1 || h->nHidden < 2 || (h->generic & 2)) return false;
   // raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES: the copy into pinned staging costs more than the route saves (the header's figures);
   // SMARTIES_HIP_GENERIC bit 4096 holds the switch open (tests, tools/act_conv_timing.py)
   if ((size_t)h->dIn * sizeof(float) > (size_t)HL_ACT_CONV_MAX_ROW_BYTES && !(h->generic & 4096)) return false;
-  ActConvArgs& c = h->actConv; c = ActConvArgs{};
+  ActConvArgs& c = h->act.convArgs; c = ActConvArgs{};
+  c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
   c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = h->recurrent ? 1 : 0;
   for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
     c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
   if (!act_conv_plan(&c) || c.extras != h->extras || c.nF != h->hid[1].nIn) return false;
+  c.ldF = c.nF;
   // the dense layers behind: hid[1 ..] on feature rows [extras | last map], standardised already
-  ActRowsArgs& a = h->actConvRows; a = ActRowsArgs{};
-  a.dS = c.nF; a.dIn = c.nF; a.nL = h->nHidden - 1; a.nDense = h->nDense; a.nSig = h->nSig; a.nOut = h->nOut; a.ldWo = h->ldWo;
-  a.indWo = h->indWo; a.indBo = h->indBo; a.indBp = h->indBp; a.outFunc = h->cfg.nnOutputFunc;
-  for (int j = 1; j < h->nHidden; ++j) { const DevHidden& d = h->hid[j];
-    a.L[j - 1] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
-  if (!act_rows_plan(&a)) return false;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return false;
-  h->actConvCus = cus;
+  ActRowsArgs& a = h->act.convRowsArgs; a = ActRowsArgs{};
+  actFillShared(h, a); a.stMean = nullptr; a.stScale = nullptr;
+  a.dS = c.nF; a.dIn = c.nF; a.nL = actFillLayers(h, 1, a.L);
+  if (!act_rows_plan(&a) || actCus(h) < 1) return false;
   // rows per chunk: no more than HL_ACT_CONV_STAGE_BYTES of staged raw rows, whole blocks of 16 rows, at least one
   const size_t fit = (size_t)HL_ACT_CONV_STAGE_BYTES / ((size_t)h->dIn * sizeof(float));
-  h->actConvCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, fit) & ~(size_t)15));
-  h->actConvState = 1;
+  h->act.convCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, fit) & ~(size_t)15));
+  h->act.convOk = 1;
   return true;
 }
-// n rows of such a net in chunks of actConvCap rows: per chunk one copy into pinned staging -- [outputs | raw rows | one stamp per block
-// of 16 rows], sized here at the first call together with the device buffer of a chunk's feature rows --, two launches in the learner's
-// stream (the conv stack, a workgroup per row up to the number of compute units, which reads the raw rows from the mapped staging itself
-// -- a device copy made by one hipMemcpyAsync ahead of the launch was slower in development, include/smarties_hip_act.h --; the dense layers on the feature rows), a poll of the second launch's block stamps, one copy out.  Neither
-// the minibatch buffers, the training activations, the prepared filter layouts nor a minibatch drawn ahead are touched, and the stream
-// is not synchronised
-static int actConvForward(hl_learner* h, int n, const float* states, double* outputs) {
-  const int cap = h->actConvCap, nF = h->actConv.nF;
-  const size_t outBytes = (size_t)cap * h->nOut * sizeof(double), inBytes = (size_t)cap * h->dIn * sizeof(float);
-  if (!h->actConvPin) {
-    const size_t bytes = outBytes + inBytes + (size_t)act_rows_blocks(cap) * sizeof(unsigned);
-    if (!h->actConvFeat) HIPCK(devAlloc(&h->actConvFeat, (size_t)cap * nF));      // (kept if the pinned block below fails: the next call tries that again)
-    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->actConvPin), bytes, hipHostMallocMapped));
-    std::memset(h->actConvPin, 0, bytes);
-  }
-  double* pOut = reinterpret_cast<double*>(h->actConvPin);
-  float* pIn = reinterpret_cast<float*>(h->actConvPin + outBytes);
-  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(h->actConvPin + outBytes + inBytes);
+// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the chains of the other two routes borrow
+// the training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples -- and, behind
+// convolutions, no more than whose stacked window rows fit HL_ACT_WIN_STAGE_BYTES of pinned staging (never fewer than one)
+static int actChunkCap(hl_learner* h) {
+  if (actSeqOk(h)) return ACT_SEQ_CHUNK;
+  if (!actTmOk(h) && !actWinOk(h)) return 0;
+  size_t cap = (size_t)std::min(h->B, ACT_SEQ_CHUNK);
+  if (h->nConv > 0) cap = std::min(cap, (size_t)HL_ACT_WIN_STAGE_BYTES / ((size_t)h->recK * h->dIn * sizeof(float)));
+  return (int)std::max(cap, (size_t)1);
+}
+// a pinned, device-mapped block of zeros
+static hipError_t actPinAlloc(unsigned char** pin, size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped);
+  if (e == hipSuccess) *pin = static_cast<unsigned char*>(std::memset(p, 0, bytes));
+  return e;
+}
+// the first block: a stage of ACT_MAXROWS rows of hl_forward, or of one window of hl_forward_sequence, and (recurrent nets) from the next multiple of
+// 256 bytes on a stage of actChunkCap agents' windows with their tables; behind convolutions its inputs are the agents' stacked window rows [recK][dIn]
+static int actPinEnsure(hl_learner* h) {
+  if (h->act.pin) return HL_OK;
+  const size_t window = (size_t)(std::max(h->recWin, 1) + h->nApp) * h->dS, cap = (size_t)actChunkCap(h);
+  const ActCarve few = act_carve(ACT_MAXROWS, h->nOut, std::max((size_t)ACT_MAXROWS * h->dIn, window), ACT_MAXROWS, false);
+  const ActCarve chunk = act_carve(cap, h->nOut, h->nConv > 0 ? cap * h->recK * h->dIn : cap * (h->recWin + h->nApp) * h->dS, cap, true);
+  const size_t chunkAt = (few.bytes + 256 + 255) & ~(size_t)255;
+  HIPCK(actPinAlloc(&h->act.pin, chunkAt + (cap ? chunk.bytes : 0)));
+  h->act.few = act_stage(h->act.pin, few);
+  if (cap) h->act.chunk = act_stage(h->act.pin + chunkAt, chunk);
+  h->act.chunkCap = (int)cap;
+  return HL_OK;
+}
+// a block of `cap` raw rows, their outputs and one stamp per block of 16 rows (the many-row routes)
+static int actRowsPinEnsure(hl_learner* h, unsigned char** pin, ActStage* st, int cap) {
+  if (*pin) return HL_OK;
+  const ActCarve c = act_carve(cap, h->nOut, (size_t)cap * h->dIn, act_rows_blocks(cap), false);
+  HIPCK(actPinAlloc(pin, c.bytes));
+  *st = act_stage(*pin, c);
+  return HL_OK;
+}
+// n rows in chunks of `cap` through a row stage: per chunk one copy in, a tag, launch(m, tag) -- whose last launch writes stamps(m) stamps --,
+// a poll of those stamps, one copy out.  Neither the minibatch buffers nor a minibatch drawn ahead are touched, and the stream is not synchronised
+template <typename Launch> static int actRowChunks(hl_learner* h, const ActStage& s, int cap, int (*stamps)(int), int n, const float* states, double* outputs, Launch&& launch) {
   for (int r0 = 0; r0 < n; r0 += cap) {
     const int m = std::min(cap, n - r0);
-    std::memcpy(pIn, states + (size_t)r0 * h->dIn, (size_t)m * h->dIn * sizeof(float));
-    ActConvArgs c = h->actConv;
-    c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
-    c.in = pIn; c.feat = h->actConvFeat; c.ldF = nF; c.n = m;
-    ActRowsArgs a = h->actConvRows;
-    a.W = h->W; a.stMean = nullptr; a.stScale = nullptr;
-    a.in = h->actConvFeat; a.out = pOut; a.done = pDone; a.n = m;
-    a.tag = ++h->actTag; if (a.tag == 0) a.tag = ++h->actTag;
-    HIPCK(timed(h, "act_conv", h->stream, [&] { return launch_act_conv(c, h->actConvCus, h->stream); }));
-    HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
-    { int rc = actWait(h, pDone, act_rows_blocks(m), a.tag); if (rc) return rc; }
-    std::memcpy(outputs + (size_t)r0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
+    std::memcpy(s.in, states + (size_t)r0 * h->dIn, (size_t)m * h->dIn * sizeof(float));
+    const unsigned tag = actNextTag(h);
+    { int rc = launch(m, tag); if (rc) return rc; }
+    { int rc = actWait(h, s.done, stamps(m), tag); if (rc) return rc; }
+    std::memcpy(outputs + (size_t)r0 * h->nOut, s.out, (size_t)m * h->nOut * sizeof(double));
   }
   return HL_OK;
 }
+// n checked windows in chunks of the chunk stage's capacity: per chunk the tables and the states (`stacked`, behind convolutions: every agent's recK
+// stacked window rows instead, step k of agent i at row i recK + k; the window kernel reads its rows from Xin, the tables give it the window's length),
+// check(m, winMax) -- the route's launch arguments, which may refuse the chunk --, a tag, launch(m, tag, &rc) -- the route's launches, rc an error
+// of the training launches among them -- inside ONE timed bracket, a poll of the agents' stamps, one copy out
+template <typename Check, typename Launch>
+static int actWindowChunks(hl_learner* h, const char* label, bool stacked, int n, const int32_t* nSteps, const float* states, double* outputs, Check&& check, Launch&& launch) {
+  { int rc = actPinEnsure(h); if (rc) return rc; }
+  const ActStage& s = h->act.chunk;
+  const int cap = h->act.chunkCap, K = h->recK;
+  size_t first = 0;      // states in front of the chunk
+  for (int i0 = 0; i0 < n; i0 += cap) {
+    const int m = std::min(cap, n - i0);
+    int sum = 0, winMax = 0;
+    if (!stacked) {
+      act_chunk_tables(nSteps + i0, m, h->recWin, s.off, s.cnt, &sum, &winMax);
+      std::memcpy(s.in, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
+    } else for (int i = 0; i < m; ++i) {
+      const int steps = nSteps[i0 + i], win = std::min(steps, h->recWin);
+      act_stack_window(s.in + (size_t)i * K * h->dIn, states + (first + sum) * h->dS, steps, h->recWin, K, h->nApp, h->dS);
+      s.off[i] = i * K * (1 + h->nApp); s.cnt[i] = win; sum += steps; winMax = std::max(winMax, win);
+    }
+    int rc = check(m, winMax); if (rc) return rc;
+    const unsigned tag = actNextTag(h);
+    HIPCK(timed(h, label, h->stream, [&] { return launch(m, tag, &rc); }));
+    if (rc) return rc;      // (carried out of the bracket: the events of a timed chain are recorded whatever a training launch says)
+    rc = actWait(h, s.done, m, tag); if (rc) return rc;
+    std::memcpy(outputs + (size_t)i0 * h->nOut, s.out, (size_t)m * h->nOut * sizeof(double));
+    first += sum;
+  }
+  return HL_OK;
+}
+// the window kernels on B windows: one agent's last `win` states (`ctx` more in front of them for appended observations), or (off, cnt: the per-agent
+// tables) a chunk's, workgroup b on agent b's; a stack of two layer types as two launches (lo, up), the lower segment's rows being the upper one's input
+struct ActRecPair { RecArgs lo, up; bool split; };
+static void actRecPair(hl_learner* h, ActRecPair& p, int B, const float* states, const int* off, const int* cnt, int win, int ctx) {
+  p.split = h->recSplit;
+  p.lo = actRecArgs(h, p.split ? 0 : -1, B, states, off, cnt, win, ctx);
+  if (p.split) p.up = actRecArgs(h, 1, B, states, off, cnt, win, 0);
+}
+static hipError_t actRecLaunch(hl_learner* h, const ActRecPair& p) {
+  const hipError_t e = launch_rec_forward(p.lo, h->stream);
+  return e == hipSuccess && p.split ? launch_rec_forward(p.up, h->stream) : e;
+}
+// the routes that borrow minibatch buffer 0: the minibatch drawn ahead dropped; their device buffers -- raw rows in: convMmax rows for a recurrent
+// net behind convolutions (the stacked window rows of a chunk), Mmax otherwise; outputs out: Mmax rows --; the filter layouts
+static int actTrainEnsure(hl_learner* h) {
+  int rc = dropPresample(h); if (rc) return rc;
+  if (!h->act.dS) HIPCK(devAlloc(&h->act.dS, (size_t)(h->recurrent && h->nConv > 0 ? h->convMmax : h->Mmax) * h->dIn));
+  if (!h->act.dO) HIPCK(devAlloc(&h->act.dO, (size_t)h->Mmax * h->nOut));
+  return ensureConvPrep(h);
+}
+// ... and their launches: nRows raw rows to the device, standardised into X0, through the whole forward pass or (`rec`) the convolutional front
+// followed by the window launches; then the output layer on the first nOut rows.  *rc: what the training launches say
+static hipError_t actTrainTail(hl_learner* h, const float* rows, int nRows, const ActRecPair* rec, int nOut, double* out, volatile unsigned* done, unsigned tag, int* rc) {
+  hipError_t e = hipMemcpyAsync(h->act.dS, rows, (size_t)nRows * h->dIn * sizeof(float), hipMemcpyHostToDevice, h->stream); if (e != hipSuccess) return e;
+  e = launch_act_standardize(h->sc, h->rp, h->act.dS, nRows, h->dS, h->dIn, h->buf[0].X0, h->ldX0, h->stream); if (e != hipSuccess) return e;
+  *rc = rec ? launchFront(h, 0, h->stream, /*gather*/false) : launchForward(h, 0, h->stream, false, /*gather*/false); if (*rc) return hipSuccess;
+  if (rec) { e = actRecLaunch(h, *rec); if (e != hipSuccess) return e; }
+  return actOutput(h, nOut, out, done, tag);
+}
+}  // extern "C++"
+
 int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   if (!h || n < 0 || (n > 0 && (!states || !outputs))) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
@@ -206,204 +256,128 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, "forward of a recurrent net needs the agent's history");
   if (n == 0) return HL_OK;
   // a few agents, dense network: one kernel, states and outputs through pinned host memory (misc.hip: act_forward_kernel)
-  if (n > 0 && n <= ACT_MAXROWS && h->nConv == 0 && h->dIn <= ACT_MAXW && h->actFastOk) {
+  if (n <= ACT_MAXROWS && actFewOk(h)) {
     { int rc = actPinEnsure(h); if (rc) return rc; }
-    double* pOut = reinterpret_cast<double*>(h->actPin);
-    float* pIn = reinterpret_cast<float*>(pOut + (size_t)ACT_MAXROWS * h->nOut);
-    volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pIn + actPinFloats(h));
-    std::memcpy(pIn, states, (size_t)n * h->dIn * sizeof(float));
-    ActArgs aa{}; aa.W = h->W; aa.stMean = h->rp.stMean; aa.stScale = h->rp.stScale; aa.in = pIn; aa.out = pOut; aa.done = pDone;
-    aa.tag = ++h->actTag; if (aa.tag == 0) aa.tag = ++h->actTag;
-    aa.dS = h->dS; aa.dIn = h->dIn; aa.nL = h->nHidden; aa.nDense = h->nDense; aa.nSig = h->nSig; aa.nOut = h->nOut; aa.ldWo = h->ldWo;
-    aa.indWo = h->indWo; aa.indBo = h->indBo; aa.indBp = h->indBp; aa.outFunc = h->cfg.nnOutputFunc;
-    for (int j = 0; j < h->nHidden; ++j) { const DevHidden& d = h->hid[j];
-      aa.L[j] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
-    HIPCK(launch_act_forward(aa, n, h->stream));
-    { int rc = actWait(h, pDone, n, aa.tag); if (rc) return rc; }
-    std::memcpy(outputs, pOut, (size_t)n * h->nOut * sizeof(double));
-    return HL_OK;
+    const ActStage& s = h->act.few;
+    return actRowChunks(h, s, ACT_MAXROWS, [](int m) { return m; }, n, states, outputs, [&](int m, unsigned tag) -> int {
+      ActArgs aa{}; actFillShared(h, aa);
+      aa.in = s.in; aa.out = s.out; aa.done = s.done; aa.tag = tag;
+      aa.dS = h->dS; aa.dIn = h->dIn; aa.nL = actFillLayers(h, 0, aa.L);
+      HIPCK(launch_act_forward(aa, m, h->stream));
+      return HL_OK;
+    });
   }
-  // more rows than that, or a layer / an input row wider: the whole net per block of 16 rows on the MFMA (actrows.hip: act_rows_kernel)
+  // more rows than that, or a layer / an input row wider: the whole net per block of 16 rows on the MFMA (actrows.hip: act_rows_kernel),
+  // one launch per chunk of ACT_ROWS_CHUNK rows
   // (a net beyond ACT_ROWS_SMALL_NET weights: only from ACT_ROWS_WIDE_MIN_N rows on and where the launches over the training buffers would
   // need two rounds of Mmax rows or more -- below, one workgroup per 16 rows streaming all weights takes longer than they do)
-  if (act_rows_ok(h) && (h->actRowsSmall || (n >= ACT_ROWS_WIDE_MIN_N && n >= 2 * h->Mmax))) return actRowsForward(h, n, states, outputs);
-  // convolutions in front of a feed-forward net: the conv stack of a row per workgroup, then the row-block kernel on its features -- any n
-  if (act_conv_ok(h)) return actConvForward(h, n, states, outputs);
-  { int rc = dropPresample(h); if (rc) return rc; }      // the forward pass borrows minibatch buffer 0
+  if (act_rows_ok(h) && (h->act.rowsSmall || (n >= ACT_ROWS_WIDE_MIN_N && n >= 2 * h->Mmax))) {
+    { int rc = actRowsPinEnsure(h, &h->act.rowsPin, &h->act.rows, ACT_ROWS_CHUNK); if (rc) return rc; }
+    const ActStage& s = h->act.rows;
+    return actRowChunks(h, s, ACT_ROWS_CHUNK, act_rows_blocks, n, states, outputs, [&](int m, unsigned tag) -> int {
+      ActRowsArgs a = h->act.rowsArgs; a.in = s.in; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
+      HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+      return HL_OK;
+    });
+  }
+  // convolutions in front of a feed-forward net, any n: per chunk of convCap rows two launches in the learner's stream -- the conv stack, a
+  // workgroup per row up to the number of compute units, which reads the raw rows from the mapped staging itself (a device copy ahead of the
+  // launch was slower in development, include/smarties_hip_act.h) and writes the chunk's feature rows; the dense layers on those.  The
+  // training activations and the prepared filter layouts are not touched either
+  if (act_conv_ok(h)) {
+    const int cap = h->act.convCap;
+    if (!h->act.convFeat) HIPCK(devAlloc(&h->act.convFeat, (size_t)cap * h->act.convArgs.nF));      // (kept if the pinned block fails: the next call tries that again)
+    { int rc = actRowsPinEnsure(h, &h->act.convPin, &h->act.conv, cap); if (rc) return rc; }
+    const ActStage& s = h->act.conv;
+    return actRowChunks(h, s, cap, act_rows_blocks, n, states, outputs, [&](int m, unsigned tag) -> int {
+      ActConvArgs c = h->act.convArgs; c.in = s.in; c.feat = h->act.convFeat; c.n = m;
+      ActRowsArgs a = h->act.convRowsArgs; a.in = h->act.convFeat; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
+      HIPCK(timed(h, "act_conv", h->stream, [&] { return launch_act_conv(c, h->act.cus, h->stream); }));
+      HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+      return HL_OK;
+    });
+  }
+  { int rc = actTrainEnsure(h); if (rc) return rc; }      // the forward pass borrows minibatch buffer 0
   // (with appended observations a row holds the raw state of step t followed by those of t-1 .. t-nAppendedObs)
-  if (!h->dActS) { HIPCK(devAlloc(&h->dActS, (size_t)h->Mmax * h->dIn)); HIPCK(devAlloc(&h->dActO, (size_t)h->Mmax * h->nOut)); }
-  const DevHidden& q = h->hid[h->nHidden - 1];
   for (int r0 = 0; r0 < n; r0 += h->Mmax) {
     const int m = std::min(h->Mmax, n - r0);
-    HIPCK(hipMemcpyAsync(h->dActS, states + (size_t)r0 * h->dIn, (size_t)m * h->dIn * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCK(launch_act_standardize(h->sc, h->rp, h->dActS, m, h->dS, h->dIn, h->buf[0].X0, h->ldX0, h->stream));
-    int rc = ensureConvPrep(h); if (rc) return rc;
-    rc = launchForward(h, 0, h->stream, false, /*gather*/false); if (rc) return rc;
-    HIPCK(launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, m,
-                            h->dActO, h->stream, nullptr, 0, h->cfg.nnOutputFunc));
-    HIPCK(hipMemcpyAsync(outputs + (size_t)r0 * h->nOut, h->dActO, (size_t)m * h->nOut * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int rc = HL_OK;
+    HIPCK(actTrainTail(h, states + (size_t)r0 * h->dIn, m, nullptr, m, h->act.dO, nullptr, 0, &rc)); if (rc) return rc;
+    HIPCK(hipMemcpyAsync(outputs + (size_t)r0 * h->nOut, h->act.dO, (size_t)m * h->nOut * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
   }
   return HL_OK;
 }
 
-// the window kernels on the agent's last `win` states (`ctx` more in front of them for appended observations); a stack of two layer
-// types as two launches, the lower segment's rows being the upper one's input
-static int recActingForward(hl_learner* h, const float* dStates, int win, int ctx) {
-  if (h->recSplit) {
-    RecArgs lo = recArgs(h, 0, 0); lo.B = 1; lo.actStates = dStates; lo.actSteps = win; lo.actCtx = ctx;
-    HIPCK(launch_rec_forward(lo, h->stream));
-    RecArgs up = recArgs(h, 0, 1); up.B = 1; up.actStates = dStates; up.actSteps = win; up.actCtx = 0;
-    HIPCK(launch_rec_forward(up, h->stream));
-    return HL_OK;
-  }
-  RecArgs ra = recArgs(h, 0); ra.B = 1; ra.actStates = dStates; ra.actSteps = win; ra.actCtx = ctx;
-  HIPCK(launch_rec_forward(ra, h->stream));
-  return HL_OK;
-}
 int hl_forward_sequence(hl_learner* h, int32_t nSteps, const float* states, double* outputs) {
   if (!h || nSteps < 1 || !states || !outputs) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   if (!h->recurrent) {
     if (h->nApp == 0) return hl_forward(h, 1, states + (size_t)(nSteps - 1) * h->dS, outputs);
-    // appended observations: the row hl_forward reads is the state of the last step followed by those of the steps before it
-    // (Episode::standardizedState, Episode.h:172-183; steps before the first given one repeat it)
+    // appended observations: the row hl_forward reads is that of the last step
     std::vector<float> row((size_t)h->dIn);
-    for (int j = 0; j <= h->nApp; ++j) { const int tt = std::max(nSteps - 1 - j, 0); std::memcpy(row.data() + (size_t)j * h->dS, states + (size_t)tt * h->dS, (size_t)h->dS * sizeof(float)); }
+    act_stack_row(row.data(), states, nSteps - 1, h->nApp, h->dS);
     return hl_forward(h, 1, row.data(), outputs);
   }
   if (h->inStep) return fail(h, HL_ERR_STATE, "hl_forward_sequence between hl_step_begin and hl_step_end");
+  // (appended observations: up to nAppendedObs further states in front of the window, which only feed the window's first steps)
+  if (nSteps > h->recWin + h->nApp) return fail(h, HL_ERR_BAD_ARG, "more steps than nnBPTTseq + 1 (+ nAppendedObs)");
+  const int win = std::min(nSteps, h->recWin);
+  ActRecPair rec;
   if (h->nConv > 0) {      // the window's stacked rows through the conv stack (as hl_forward does), then the window kernel on its rows
-    if (nSteps > h->recWin + h->nApp) return fail(h, HL_ERR_BAD_ARG, "more steps than nnBPTTseq + 1 (+ nAppendedObs)");
-    { int rc = dropPresample(h); if (rc) return rc; }
-    const int win = std::min(nSteps, h->recWin), ctx = nSteps - win;
+    int rc = actTrainEnsure(h); if (rc) return rc;
     std::vector<float> rows((size_t)win * h->dIn);
-    for (int k = 0; k < win; ++k) for (int j = 0; j <= h->nApp; ++j) { const int g = std::max(ctx + k - j, 0);
-      std::memcpy(rows.data() + (size_t)k * h->dIn + (size_t)j * h->dS, states + (size_t)g * h->dS, (size_t)h->dS * sizeof(float)); }
-    if (!h->dActS) { HIPCK(devAlloc(&h->dActS, (size_t)h->convMmax * h->dIn)); HIPCK(devAlloc(&h->dActO, (size_t)h->Mmax * h->nOut)); }
-    HIPCK(hipMemcpyAsync(h->dActS, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCK(launch_act_standardize(h->sc, h->rp, h->dActS, win, h->dS, h->dIn, h->buf[0].X0, h->ldX0, h->stream));
-    int rc = ensureConvPrep(h); if (rc) return rc;
-    rc = launchFront(h, 0, h->stream, /*gather*/false); if (rc) return rc;
-    const DevHidden& q = h->hid[h->nHidden - 1];
-    { const int rc2 = recActingForward(h, h->dActS, win, 0); if (rc2) return rc2; }      // (the rows come from Xin; the states only mark the call as acting)
-    HIPCK(launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, 1,
-                            h->dActO, h->stream, nullptr, 0, h->cfg.nnOutputFunc));
-    HIPCK(hipMemcpyAsync(outputs, h->dActO, (size_t)h->nOut * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    act_stack_window(rows.data(), states, nSteps, h->recWin, win, h->nApp, h->dS);
+    actRecPair(h, rec, 1, h->act.dS, nullptr, nullptr, win, 0);      // (the rows come from Xin; the states only mark the call as acting)
+    HIPCK(actTrainTail(h, rows.data(), win, &rec, 1, h->act.dO, nullptr, 0, &rc)); if (rc) return rc;
+    HIPCK(hipMemcpyAsync(outputs, h->act.dO, (size_t)h->nOut * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
     return HL_OK;
   }
-  // (appended observations: up to nAppendedObs further states in front of the window, which only feed the window's first steps)
-  if (nSteps > h->recWin + h->nApp) return fail(h, HL_ERR_BAD_ARG, "more steps than nnBPTTseq + 1 (+ nAppendedObs)");
   // states and outputs through pinned host memory, completion by stamp (as hl_forward): two launches, no staged copies
   { int rc = actPinEnsure(h); if (rc) return rc; }
-  double* pOut = reinterpret_cast<double*>(h->actPin);
-  float* pIn = reinterpret_cast<float*>(pOut + (size_t)ACT_MAXROWS * h->nOut);
-  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pIn + actPinFloats(h));
-  std::memcpy(pIn, states, (size_t)nSteps * h->dS * sizeof(float));
-  unsigned tag = ++h->actTag; if (tag == 0) tag = ++h->actTag;
-  const DevHidden& q = h->hid[h->nHidden - 1];
-  { const int win = std::min(nSteps, h->recWin); const int rc2 = recActingForward(h, pIn, win, nSteps - win); if (rc2) return rc2; }
-  HIPCK(launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, 1,
-                          pOut, h->stream, const_cast<unsigned*>(pDone), tag, h->cfg.nnOutputFunc));
-  { int rc = actWait(h, pDone, 1, tag); if (rc) return rc; }
-  std::memcpy(outputs, pOut, (size_t)h->nOut * sizeof(double));
+  const ActStage& s = h->act.few;
+  std::memcpy(s.in, states, (size_t)nSteps * h->dS * sizeof(float));
+  const unsigned tag = actNextTag(h);
+  actRecPair(h, rec, 1, s.in, nullptr, nullptr, win, nSteps - win);
+  HIPCK(actRecLaunch(h, rec));
+  HIPCK(actOutput(h, 1, s.out, s.done, tag));
+  { int rc = actWait(h, s.done, 1, tag); if (rc) return rc; }
+  std::memcpy(outputs, s.out, (size_t)h->nOut * sizeof(double));
   return HL_OK;
 }
 
 // n checked windows of a net whose layers run time-step-major (actTmOk): agent i of a chunk is sample row i of ONE chain of launches --
 // prepare, the forward diagonals up to the chunk's longest window, the output layer on the chunk's rows of Yout.  The chain borrows rows
 // 0 .. m - 1 of the training buffers between steps, as hl_forward_sequence borrows row 0: every training step writes its rows anew
-static int actTmForward(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
-  { int rc = actPinEnsure(h); if (rc) return rc; }
-  const int cap = actChunkCap(h);
-  double* pOut = reinterpret_cast<double*>(h->actPin + h->actSeqPinOff);
-  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pOut + (size_t)cap * h->nOut);
-  int* pOff = reinterpret_cast<int*>(const_cast<unsigned*>(pDone) + cap);
-  int* pCnt = pOff + cap + 2;
-  float* pIn = reinterpret_cast<float*>(pCnt + cap);
-  const DevHidden& q = h->hid[h->nHidden - 1];
-  size_t first = 0;      // states in front of the chunk
-  for (int i0 = 0; i0 < n; i0 += cap) {
-    const int m = std::min(cap, n - i0);
-    int sum = 0, winMax = 0;
-    for (int i = 0; i < m; ++i) { pOff[i] = sum; pCnt[i] = nSteps[i0 + i]; sum += nSteps[i0 + i]; winMax = std::max(winMax, std::min((int)nSteps[i0 + i], h->recWin)); }
-    std::memcpy(pIn, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
-    RecArgs ra = recArgs(h, 0); ra.B = m; ra.actStates = pIn; ra.actOff = pOff; ra.actCnt = pCnt; ra.actSteps = winMax; ra.actCtx = 0;
-    if (!rec_tm_act_ok(ra)) return fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the time-step-major launches refuse the chunk");
-    unsigned tag = ++h->actTag; if (tag == 0) tag = ++h->actTag;
-    HIPCK(timed(h, "act_tm_chain", h->stream, [&] {
-      const hipError_t e = launch_rec_tm_forward(ra, h->stream); if (e != hipSuccess) return e;
-      return launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, m,
-                               pOut, h->stream, const_cast<unsigned*>(pDone), tag, h->cfg.nnOutputFunc);
-    }));
-    { int rc = actWait(h, pDone, m, tag); if (rc) return rc; }
-    std::memcpy(outputs + (size_t)i0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
-    first += sum;
-  }
-  return HL_OK;
+static int actTmChain(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
+  const ActStage& s = h->act.chunk;
+  RecArgs ra;
+  return actWindowChunks(h, "act_tm_chain", false, n, nSteps, states, outputs, [&](int m, int winMax) {
+    ra = actRecArgs(h, -1, m, s.in, s.off, s.cnt, winMax, 0);
+    return rec_tm_act_ok(ra) ? HL_OK : fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the time-step-major launches refuse the chunk");
+  }, [&](int m, unsigned tag, int*) {
+    const hipError_t e = launch_rec_tm_forward(ra, h->stream);
+    return e == hipSuccess ? actOutput(h, m, s.out, s.done, tag) : e;
+  });
 }
-
 // n checked windows of a net whose windows the workgroup-per-sample kernels run (actWinOk): agent i of a chunk is sample i of ONE chain of
 // hl_forward_sequence's own launches -- behind convolutions the chunk's stacked rows through the front; the window launch (two for a
 // stack of two layer types) with the per-agent tables, workgroup i walking agent i's window alone; the output layer on the chunk's rows
 // of Yout.  The chain borrows the training rows of the first m samples between steps, as hl_forward_sequence borrows those of the first
-static int actWinForward(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
-  { int rc = actPinEnsure(h); if (rc) return rc; }
-  const int cap = actChunkCap(h), K = h->recK;
-  double* pOut = reinterpret_cast<double*>(h->actPin + h->actSeqPinOff);
-  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pOut + (size_t)cap * h->nOut);
-  int* pOff = reinterpret_cast<int*>(const_cast<unsigned*>(pDone) + cap);
-  int* pCnt = pOff + cap + 2;
-  float* pIn = reinterpret_cast<float*>(pCnt + cap);
-  const DevHidden& q = h->hid[h->nHidden - 1];
+static int actWinChain(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
   const bool conv = h->nConv > 0;
-  if (conv) {      // (as hl_forward_sequence: the front borrows minibatch buffer 0)
-    int rc = dropPresample(h); if (rc) return rc;
-    if (!h->dActS) { HIPCK(devAlloc(&h->dActS, (size_t)h->convMmax * h->dIn)); HIPCK(devAlloc(&h->dActO, (size_t)h->Mmax * h->nOut)); }
-    rc = ensureConvPrep(h); if (rc) return rc;
-  }
-  size_t first = 0;      // states in front of the chunk
-  for (int i0 = 0; i0 < n; i0 += cap) {
-    const int m = std::min(cap, n - i0);
-    int sum = 0, winMax = 0;
-    for (int i = 0; i < m; ++i) {
-      const int steps = nSteps[i0 + i], win = std::min(steps, h->recWin), ctx = steps - win;
-      winMax = std::max(winMax, win);
-      if (!conv) { pOff[i] = sum; pCnt[i] = steps; sum += steps; continue; }
-      // the agent's stacked rows, window step k at row i K + k (the state of the step followed by the nApp before it); rows of steps its
-      // window lacks repeat its last one
-      const float* st = states + (first + sum) * h->dS;
-      float* rows = pIn + (size_t)i * K * h->dIn;
-      for (int k = 0; k < win; ++k) for (int j = 0; j <= h->nApp; ++j) { const int g = std::max(ctx + k - j, 0);
-        std::memcpy(rows + (size_t)k * h->dIn + (size_t)j * h->dS, st + (size_t)g * h->dS, (size_t)h->dS * sizeof(float)); }
-      for (int k = win; k < K; ++k) std::memcpy(rows + (size_t)k * h->dIn, rows + (size_t)(win - 1) * h->dIn, (size_t)h->dIn * sizeof(float));
-      pOff[i] = i * K * (1 + h->nApp); pCnt[i] = win; sum += steps;      // (the window kernel reads its rows from Xin; the tables give it the window's length)
-    }
-    if (!conv) std::memcpy(pIn, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
-    const float* actStates = conv ? h->dActS : pIn;
-    auto table = [&](RecArgs ra) { ra.B = m; ra.actStates = actStates; ra.actOff = pOff; ra.actCnt = pCnt; ra.actSteps = winMax; ra.actCtx = 0; return ra; };
-    const RecArgs lo = table(recArgs(h, 0, h->recSplit ? 0 : -1)), up = table(recArgs(h, 0, h->recSplit ? 1 : -1));
-    if (!rec_win_act_ok(lo) || !rec_win_act_ok(up)) return fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the window kernels refuse the chunk");
-    unsigned tag = ++h->actTag; if (tag == 0) tag = ++h->actTag;
-    int rcFront = HL_OK;
-    HIPCK(timed(h, "act_win_chain", h->stream, [&] {
-      if (conv) {
-        hipError_t e = hipMemcpyAsync(h->dActS, pIn, (size_t)m * K * h->dIn * sizeof(float), hipMemcpyHostToDevice, h->stream); if (e != hipSuccess) return e;
-        e = launch_act_standardize(h->sc, h->rp, h->dActS, m * K, h->dS, h->dIn, h->buf[0].X0, h->ldX0, h->stream); if (e != hipSuccess) return e;
-        rcFront = launchFront(h, 0, h->stream, /*gather*/false); if (rcFront) return hipSuccess;
-      }
-      hipError_t e = launch_rec_forward(lo, h->stream); if (e != hipSuccess) return e;
-      if (h->recSplit) { e = launch_rec_forward(up, h->stream); if (e != hipSuccess) return e; }
-      return launch_act_output(q.hasRes ? q.Rr : q.Y, q.ldA, q.size, h->W, h->indWo, h->indBo, h->indBp, h->ldWo, h->nDense, h->nSig, m,
-                               pOut, h->stream, const_cast<unsigned*>(pDone), tag, h->cfg.nnOutputFunc);
-    }));
-    if (rcFront) return rcFront;
-    { int rc = actWait(h, pDone, m, tag); if (rc) return rc; }
-    std::memcpy(outputs + (size_t)i0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
-    first += sum;
-  }
-  return HL_OK;
+  if (conv) { int rc = actTrainEnsure(h); if (rc) return rc; }      // (as hl_forward_sequence: the front borrows minibatch buffer 0)
+  const ActStage& s = h->act.chunk;
+  ActRecPair rec;
+  return actWindowChunks(h, "act_win_chain", conv, n, nSteps, states, outputs, [&](int m, int winMax) {
+    actRecPair(h, rec, m, conv ? h->act.dS : s.in, s.off, s.cnt, winMax, 0);
+    return rec_win_act_ok(rec.lo) && (!rec.split || rec_win_act_ok(rec.up)) ? HL_OK : fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the window kernels refuse the chunk");
+  }, [&](int m, unsigned tag, int* rc) {
+    if (conv) return actTrainTail(h, s.in, m * h->recK, &rec, m, s.out, s.done, tag, rc);
+    const hipError_t e = actRecLaunch(h, rec);
+    return e == hipSuccess ? actOutput(h, m, s.out, s.done, tag) : e;
+  });
 }
 
 // n agents' windows (include/smarties_hip_act.h)
@@ -418,50 +392,27 @@ int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const 
     if (h->recurrent && nSteps[i] > maxSteps) return fail(h, HL_ERR_BAD_ARG, "more steps than nnBPTTseq + 1 (+ nAppendedObs)");
   }
   if (!h->recurrent) {
-    // dense net: the rows hl_forward reads -- the state of the last step followed by those of the steps before it (Episode::standardizedState,
-    // Episode.h:172-183; steps before the first given one repeat it) -- then ONE call for all agents
+    // dense net: the rows hl_forward reads -- that of every agent's last step -- then ONE call for all agents
     std::vector<float> rows((size_t)n * h->dIn);
     size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-      for (int j = 0; j <= h->nApp; ++j) { const int tt = std::max(nSteps[i] - 1 - j, 0);
-        std::memcpy(rows.data() + (size_t)i * h->dIn + (size_t)j * h->dS, states + (off + tt) * h->dS, (size_t)h->dS * sizeof(float)); }
-      off += nSteps[i];
-    }
+    for (int i = 0; i < n; ++i) { act_stack_row(rows.data() + (size_t)i * h->dIn, states + off * h->dS, nSteps[i] - 1, h->nApp, h->dS); off += nSteps[i]; }
     return hl_forward(h, n, rows.data(), outputs);
   }
-  if (!actSeqOk(h)) {
-    if (actTmOk(h)) return actTmForward(h, n, nSteps, states, outputs);       // layers wider than 256 cells
-    if (actWinOk(h)) return actWinForward(h, n, nSteps, states, outputs);     // convolutions in front, two layer types, a window beyond the batched kernel's LDS
-    // a net all three predicates refuse -- layers or inputs beyond the bounds the window kernels state (256 cells, 1024 inputs) that the
-    // time-step-major launches do not take either --: hl_forward_sequence's own route, agent by agent, as before
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-      const int rc = hl_forward_sequence(h, nSteps[i], states + off * h->dS, outputs + (size_t)i * h->nOut); if (rc) return rc;
-      off += nSteps[i];
-    }
-    return HL_OK;
+  if (actSeqOk(h)) {      // one launch per chunk: a workgroup per agent up to the number of compute units
+    const ActStage& s = h->act.chunk;
+    return actWindowChunks(h, "act_seq", false, n, nSteps, states, outputs, [](int, int) { return HL_OK; }, [&](int m, unsigned tag, int*) {
+      ActSeqArgs a = h->act.seqArgs; a.states = s.in; a.offset = s.off; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
+      return launch_act_seq(a, std::min(m, h->act.cus), h->stream);
+    });
   }
-  { int rc = actPinEnsure(h); if (rc) return rc; }
-  double* pOut = reinterpret_cast<double*>(h->actPin + h->actSeqPinOff);
-  volatile unsigned* pDone = reinterpret_cast<volatile unsigned*>(pOut + (size_t)ACT_SEQ_CHUNK * h->nOut);
-  int* pOff = reinterpret_cast<int*>(const_cast<unsigned*>(pDone) + ACT_SEQ_CHUNK);
-  float* pIn = reinterpret_cast<float*>(pOff + ACT_SEQ_CHUNK + 2);
-  size_t first = 0;      // states in front of the chunk
-  for (int i0 = 0; i0 < n; i0 += ACT_SEQ_CHUNK) {
-    const int m = std::min(ACT_SEQ_CHUNK, n - i0);
-    int sum = 0;
-    for (int i = 0; i < m; ++i) { pOff[i] = sum; sum += nSteps[i0 + i]; }
-    pOff[m] = sum;
-    std::memcpy(pIn, states + first * h->dS, (size_t)sum * h->dS * sizeof(float));
-    ActSeqArgs a = h->actSeq;
-    a.W = h->W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
-    a.states = pIn; a.offset = pOff; a.out = pOut; a.done = pDone; a.n = m;
-    a.tag = ++h->actTag; if (a.tag == 0) a.tag = ++h->actTag;
-    const int blocks = std::min(m, h->actSeqCus);
-    HIPCK(timed(h, "act_seq", h->stream, [&] { return launch_act_seq(a, blocks, h->stream); }));
-    { int rc = actWait(h, pDone, m, a.tag); if (rc) return rc; }
-    std::memcpy(outputs + (size_t)i0 * h->nOut, pOut, (size_t)m * h->nOut * sizeof(double));
-    first += sum;
+  if (actTmOk(h)) return actTmChain(h, n, nSteps, states, outputs);       // layers wider than 256 cells
+  if (actWinOk(h)) return actWinChain(h, n, nSteps, states, outputs);     // convolutions in front, two layer types, a window beyond the batched kernel's LDS
+  // a net all three predicates refuse -- layers or inputs beyond the bounds the window kernels state (256 cells, 1024 inputs) that the
+  // time-step-major launches do not take either --: hl_forward_sequence's own route, agent by agent, as before
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    const int rc = hl_forward_sequence(h, nSteps[i], states + off * h->dS, outputs + (size_t)i * h->nOut); if (rc) return rc;
+    off += nSteps[i];
   }
   return HL_OK;
 }

@@ -1,5 +1,6 @@
 // smarties_amd/csrc/learner_state.h -- part of learner.cpp's ONE translation unit (included there, like step_exec.h): the learner's state (struct hl_learner), error / allocation / timing helpers, the network description built by hl_create
 #pragma once
+#include "act_host.h"
 
 namespace {
 
@@ -21,7 +22,20 @@ struct StepBuf {
   DwTable dwTable{}, dwTableAdam{};        // the dW problems by value (kernel-argument table of dw_table_kernel)
 };
 struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int steps = 0; };
-
+// rollout inference (learner_act.h).  Every route's predicate is looked at once: 0 not looked at yet / 1 the route serves the net / -1 not
+struct ActState {
+  unsigned tag = 0; int cus = 0;      // the last completion stamp handed out (actNextTag); compute units of the device, asked once (actCus)
+  int fewOk = 0;                      // a few rows of a dense net, a workgroup per row (misc.hip: act_forward_kernel)
+  int rowsOk = 0; bool rowsSmall = false; ActRowsArgs rowsArgs{};      // many rows of a dense net (actrows.hip); the net takes the route at any row count (ACT_ROWS_SMALL_NET)
+  int convOk = 0, convCap = 0; ActConvArgs convArgs{}; ActRowsArgs convRowsArgs{};      // rows of a feed-forward net behind convolutions (actconv.hip + actrows.hip); rows per chunk
+  int seqOk = 0; ActSeqArgs seqArgs{};      // many agents' windows: the batched window kernel (actseq.hip)
+  int tmOk = 0, winOk = 0;            // ... as one chain of the time-step-major launches (rectm.hip) / of the workgroup-per-sample window kernels (rec.hip)
+  // three pinned, device-mapped blocks, each allocated at the first call that takes a route through it, and their carves (act_host.h):
+  // [a few rows or one window | a chunk of chunkCap agents' windows], a chunk of many rows, a chunk of rows behind convolutions
+  unsigned char *pin = nullptr, *rowsPin = nullptr, *convPin = nullptr; ActStage few{}, chunk{}, rows{}, conv{}; int chunkCap = 0;
+  float* convFeat = nullptr;          // the feature rows of a chunk behind convolutions (device; allocated with convPin)
+  float* dS = nullptr; double* dO = nullptr;      // the routes over minibatch buffer 0: raw rows in, outputs out (actTrainEnsure)
+};
 }  // namespace
 
 struct hl_learner {
@@ -106,23 +120,13 @@ struct hl_learner {
   // MemoryBuffer.cpp:486-487): the value of the last gradient step's statistics pass, taken BEFORE that step's removals;
   // 0 before the first step.  Computed on the device when needed (dStatsIns), at most once per step.
   double* dStatsIns = nullptr; bool statsFresh = false, anyStep = false;
-  unsigned char* actPin = nullptr; unsigned actTag = 0; bool actFastOk = false;     // rollout inference of a few agents (hl_forward)
-  int actRowsState = 0; bool actRowsSmall = false; unsigned char* actRowsPin = nullptr; ActRowsArgs actRows{};      // many rows of a dense net (actrows.hip): 0 not looked at yet / 1 the row-block kernel serves the net / -1 not; the net is small enough for the route at any row count (ACT_ROWS_SMALL_NET); its pinned staging (allocated at the first call that takes the route); the launch arguments
-  // many rows of a feed-forward net behind convolutions (actconv.hip + actrows.hip): 0 not looked at yet / 1 the two kernels serve the net / -1 not;
-  // compute units; rows per chunk; pinned staging [outputs | raw rows | stamps] and the device buffer of a chunk's feature rows
-  // (all allocated at the first call that takes the route); the launch arguments of the two kernels
-  int actConvState = 0, actConvCus = 0, actConvCap = 0; unsigned char* actConvPin = nullptr; float* actConvFeat = nullptr;
-  ActConvArgs actConv{}; ActRowsArgs actConvRows{};
-  int actTmState = 0;      // ... of a net whose layers run time-step-major (rectm.hip): 0 not looked at yet / 1 its acting windows go through those launches, many agents as one chain / -1 not
-  int actWinState = 0;     // ... of every other recurrent net (rec.hip's workgroup-per-sample kernels, agent b = workgroup b): 0 not looked at yet / 1 many agents as one chain / -1 not
-  int actSeqState = 0, actSeqCus = 0; size_t actSeqPinOff = 0; ActSeqArgs actSeq{};      // many agents of a recurrent net (hl_forward_sequences): 0 not looked at yet / 1 the batched kernel serves the net / -1 not; compute units; its part of actPin; the launch arguments
+  ActState act;      // rollout inference (learner_act.h)
   // prioritised samplers (per.hip): probabilities / cumulative table of the stored transitions, rebuilt before every minibatch
   float *perProb = nullptr, *perKey = nullptr, *perKeyS = nullptr; double* perCp = nullptr; unsigned *perIdx = nullptr, *perIdxS = nullptr; void* perScan = nullptr; size_t perScanBytes = 0;
   void* perTemp = nullptr; size_t perTempBytes = 0; long long perCap = 0;
   // staging
   void* pinned = nullptr; size_t pinnedBytes = 0;
   long long* dFlatGiven = nullptr; int* dEidList = nullptr; int eidListCap = 0;
-  float* dActS = nullptr; double* dActO = nullptr;     // staging of hl_forward: raw states in, outputs out [Mmax rows]
   bool stepChainOk = false;               // ... and the head and the input-gradient products with them (gemm16.hip: step_chain_kernel): the two-launch step for those networks
   bool chainOk = false; int chainHT = 0;  // the dense forward layers of a network off the fused path go out as one launch (gemm16.hip: fwd_chain_kernel)
   bool noConvReplay = false;            // (SMARTIES_HIP_GENERIC & 64) stack the minibatch rows (stack_gather_kernel) also when the first layer could read the replay

@@ -1,7 +1,7 @@
 """hl_forward_sequences for the recurrent nets neither the batched window kernel nor the time-step-major chain serves
 (include/smarties_hip_act.h): recurrent layers behind convolutions, RNN encoder layers under MGU layers, nets of at most 256 cells whose
 window exceeds the batched kernel's 64 KB.  The agents of a chunk are the samples of ONE chain of hl_forward_sequence's own launches
-(smarties_amd/csrc/learner_act.h: actWinForward): workgroup b of the window kernels (smarties_amd/csrc/rec.hip) walks agent b's window,
+(smarties_amd/csrc/learner_act.h: actWinChain): workgroup b of the window kernels (smarties_amd/csrc/rec.hip) walks agent b's window,
 taken from a per-agent table; a chunk holds min(batchSize, ACT_SEQ_CHUNK) agents.
 
 GPU suite: every agent bit for bit against the library's own single-agent hl_forward_sequence and within TOL32 of the CPU oracle, in any

@@ -1,5 +1,5 @@
 """Wall-clock cost of acting with the recurrent nets whose many-agent call is a chain of hl_forward_sequence's own window launches
-(include/smarties_hip_act.h; smarties_amd/csrc/learner_act.h: actWinForward): hl_forward_sequence for one agent against
+(include/smarties_hip_act.h; smarties_amd/csrc/learner_act.h: actWinChain): hl_forward_sequence for one agent against
 hl_forward_sequences for n agents, on two shapes --
 
   pomdp      the partially observable cart-pole of apps/cart_pole_many: dimS 6, one bounded action, an RNN encoder layer of 128 cells
