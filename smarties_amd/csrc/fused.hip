@@ -46,6 +46,15 @@ namespace hl {
 #ifndef FUSED_PRE_LATE
 #define FUSED_PRE_LATE 1
 #endif
+// h1 product: 1 = straight-line code per k-step count with every operand read up front (h1Product), 0 = the loop that reads the
+// operands of step s + 1 under the MFMAs of step s (the compiler serialises it: one full LDS wait per step).  Same bits either way.
+#ifndef FUSED_H1_PRE
+#define FUSED_H1_PRE 1
+#endif
+// 1: what the first batch of loads needs is taken as ONE batch of scalar loads in front of everything else (see the kernel)
+#ifndef FUSED_ARGS_FIRST
+#define FUSED_ARGS_FIRST 1
+#endif
 #define FTLD 17             // leading dimension of the own-tile scratch of the chained form (x1 at 0, h1 at 16 * FTLD + 16)
 
 // development time stamps of workgroup (panel 0, tile 1), 100 MHz clock: -DHL_FSTAMPS (its own flag: the tail stamps of
@@ -106,6 +115,45 @@ __device__ __forceinline__ f32x4 waveMma(FA fa, FB fb) {
   return acc0 + acc1;
 }
 
+// The first layer's product S W0 over a run-time count of k-steps (dSp / 4 = 1..8) as straight-line code per count: every operand
+// of the product is requested before its first MFMA (one exposed LDS latency, like waveMma), where a loop over the count waits for
+// the LDS in every step.  One operand is shared by the NTL tiles of the wavefront (fs(s)), the other is the tile's own (ft(s, t));
+// TILE_A says which of the two is the A operand.  Step order and the accumulator of every step are those of the loop: for s, for t.
+// No padding to a fixed count: a step with zero operands could turn a -0 into +0.
+template <int NQ, int NTL, bool TILE_A, class FS, class FT>
+__device__ __forceinline__ void h1Steps(f32x4* acc, FS fs, FT ft) {
+  float sv[NQ], tv[NQ][NTL];
+#pragma unroll
+  for (int s = 0; s < NQ; ++s) {
+    sv[s] = fs(s);
+#pragma unroll
+    for (int t = 0; t < NTL; ++t) tv[s][t] = ft(s, t);
+  }
+  __builtin_amdgcn_sched_barrier(0);      // (the scheduler would otherwise sink half of the reads between the MFMAs to save registers)
+#pragma unroll
+  for (int s = 0; s < NQ; ++s) {
+#pragma unroll
+    for (int t = 0; t < NTL; ++t) {
+      if constexpr (TILE_A) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv[s][t], sv[s], acc[t], 0, 0, 0);
+      else acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(sv[s], tv[s][t], acc[t], 0, 0, 0);
+    }
+  }
+}
+template <int NTL, bool TILE_A, class FS, class FT>
+__device__ __forceinline__ void h1Product(int nk4, f32x4* acc, FS fs, FT ft) {      // nk4 is wave-uniform: a scalar branch
+  switch (nk4) {
+    case 1: h1Steps<1, NTL, TILE_A>(acc, fs, ft); break;
+    case 2: h1Steps<2, NTL, TILE_A>(acc, fs, ft); break;
+    case 3: h1Steps<3, NTL, TILE_A>(acc, fs, ft); break;
+    case 4: h1Steps<4, NTL, TILE_A>(acc, fs, ft); break;
+    case 5: h1Steps<5, NTL, TILE_A>(acc, fs, ft); break;
+    case 6: h1Steps<6, NTL, TILE_A>(acc, fs, ft); break;
+    case 7: h1Steps<7, NTL, TILE_A>(acc, fs, ft); break;
+    case 8: h1Steps<8, NTL, TILE_A>(acc, fs, ft); break;
+    default: break;
+  }
+}
+
 // NT threads per workgroup (256 or 512): threads 0..255 own one output element / one (sample, action
 // component) each; with 512 the panel-wide phases and the K-split contractions are spread over 8 waves
 // sum of the K-split partial tiles (fixed association: pairs, then pairs of pairs)
@@ -160,21 +208,35 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
 #ifdef HL_STEP_STAMPS
   if (threadIdx.x == 0 && blockIdx.x == 8 + 8) a.sc->dbgStep[a.sc->nGradSteps & 63] = wall_clock64();      // tools/step_stamps.py
 #endif
+  // what the first batch of loads needs (weights, states, vectors, the panel counter).  FUSED_ARGS_FIRST: held in scalar registers
+  // at this point, so that they come as ONE batch of scalar loads with one wait; otherwise the compiler fetches the arguments batch
+  // by batch in program order, each batch with a wait of its own, and this one comes last
   const DevScalars* sc = a.sc;
-  const int dS = a.dS, dSp = (dS + 3) & ~3, B = a.B, dA = a.dA, nDense = a.nDense;
+  const float* W = a.W; const float* X0 = a.X0; unsigned* panelCtr = a.panelCtr;
+  long long iW0 = a.indW0, iW1 = a.indW1, iWo = a.indWo, iB0 = a.indB0, iB1 = a.indB1, iWr = a.indWr, iBr = a.indBr, iBo = a.indBo, iBp = a.indBp;
+  int ldW0 = a.ldW0, ldW1 = a.ldW1, ldX0 = a.ldX0, dSa = a.dS, Ba = a.B, parity = a.parity;
+#if FUSED_ARGS_FIRST
+  // (inputs only: the compiler still knows where the values come from -- global pointers, kernel arguments)
+  asm volatile("" :: "s"(W), "s"(iW0), "s"(iW1), "s"(iWo), "s"(iB0), "s"(iB1), "s"(iWr), "s"(iBr), "s"(iBo), "s"(iBp),
+               "s"(X0), "s"(panelCtr), "s"(sc), "s"(ldW0), "s"(ldW1), "s"(ldX0), "s"(dSa), "s"(Ba), "s"(parity),
+               "s"(a.bt.nextSrc), "s"(a.bt.slot), "s"(a.bt.eid));
+#endif
+  const int dS = dSa, dSp = (dS + 3) & ~3, B = Ba, dA = a.dA, nDense = a.nDense;
   // arguments used inside the hot loops, pinned in VGPRs: under SGPR pressure the compiler would
   // otherwise re-load them from the kernarg segment at every use (~1 us per epilogue)
   const int func = __builtin_amdgcn_readfirstlane(a.func);
   int resN = a.resN, ldA0 = a.ldA0, ldA1 = a.ldA1;
-  asm volatile("" : "+v"(resN), "+v"(ldA0), "+v"(ldA1));
   float* gR2 = a.R2; float* gX2 = a.X2; float* gD2 = a.D2; float* gDres2 = a.Dres2;
-  asm volatile("" : "+v"(gR2), "+v"(gX2), "+v"(gD2), "+v"(gDres2));
+#define FUSED_PIN_ARGS() do { asm volatile("" : "+v"(resN), "+v"(ldA0), "+v"(ldA1)); asm volatile("" : "+v"(gR2), "+v"(gX2), "+v"(gD2), "+v"(gDres2)); } while (0)
+#if !FUSED_ARGS_FIRST
+  FUSED_PIN_ARGS();
+#endif
   const int bid = blockIdx.x - 8, xcd = bid & 7, gi = bid >> 3;
   const int panel = (gi / HT) * 8 + xcd, n = gi % HT;
   const int m0 = panel * 16, n0 = n * 16;
   // panels made of sampled rows only never wait for the row count of this minibatch
-  int nRows = a.B;
-  if (m0 + 16 > a.B) { nRows = sc->nRows[a.parity]; if (m0 >= nRows) return; }
+  int nRows = B;
+  if (m0 + 16 > B) { nRows = sc->nRows[parity]; if (m0 >= nRows) return; }
   FSTAMP(0);
 
   float* sY1 = reinterpret_cast<float*>(smem);                 // [16][FLDR]
@@ -199,8 +261,7 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
   const int li = lane & 15, lc = lane >> 4;
   const bool eth = tid < 256;                                  // element thread: owns output element / (sample, dim) (em, en)
   const int em = (tid >> 4) & 15, en = tid & 15;
-  const float* W = a.W;
-  const float* W0 = W + a.indW0; const float* W1 = W + a.indW1; const float* Wo = W + a.indWo;
+  const float* W0 = W + iW0; const float* W1 = W + iW1; const float* Wo = W + iWo;
 
   // ---- every load that does not depend on the exchange, issued up front --------------------------
   const int row = m0 + em;
@@ -213,7 +274,7 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
 #pragma unroll
   for (int q = 0; q < QS; ++q) {
     const int idx = tid + NT * q, r = idx >> 5, c = idx & 31;
-    sv[q] = (c < dS && m0 + r < nRows) ? a.X0[(size_t)(m0 + r) * a.ldX0 + c] : 0.f;
+    sv[q] = (c < dS && m0 + r < nRows) ? X0[(size_t)(m0 + r) * ldX0 + c] : 0.f;
   }
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 w0v[Q0], w1c[QC], w1r[QP], wov[QO];
@@ -223,25 +284,28 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
     // no guards: rows >= dS read row dS-1 again (finite weights) and meet state columns that are zero, so they add
     // exactly 0; a guarded load would make the compiler wait for it at the join, ahead of all the loads below
     const int f = tid + NT * q, k = f / H4, c4 = f % H4;
-    w0v[q] = *reinterpret_cast<const f32x4*>(W0 + (size_t)(k < dS ? k : dS - 1) * a.ldW0 + 4 * c4);
+    w0v[q] = *reinterpret_cast<const f32x4*>(W0 + (size_t)(k < dS ? k : dS - 1) * ldW0 + 4 * c4);
   }
 #pragma unroll
   for (int q = 0; q < QC; ++q) {
     const int f = tid + NT * q; w1c[q] = z4;
-    if (f < H * 4) { const int k = f >> 2, c = n0 + (f & 3) * 4; w1c[q] = *reinterpret_cast<const f32x4*>(W1 + (size_t)k * a.ldW1 + c); }
+    if (f < H * 4) { const int k = f >> 2, c = n0 + (f & 3) * 4; w1c[q] = *reinterpret_cast<const f32x4*>(W1 + (size_t)k * ldW1 + c); }
   }
 #pragma unroll
   for (int q = 0; q < QO; ++q) { const int f = tid + NT * q; wov[q] = f < H * 2 ? *reinterpret_cast<const f32x4*>(Wo + (size_t)f * 4) : z4; }
-  const float b0v = tid < H ? W[a.indB0 + tid] : 0.f;
-  const float wrv = tid < H ? W[a.indWr + tid] : 0.f, brv = tid < H ? W[a.indBr + tid] : 0.f;
-  const float b1e = eth ? W[a.indB1 + n0 + en] : 0.f;
-  const float bov = tid < nDense ? W[a.indBo + tid] : 0.f, bpv = tid < dA ? W[a.indBp + tid] : 0.f;
+  const float b0v = tid < H ? W[iB0 + tid] : 0.f;
+  const float wrv = tid < H ? W[iWr + tid] : 0.f, brv = tid < H ? W[iBr + tid] : 0.f;
+  const float b1e = eth ? W[iB1 + n0 + en] : 0.f;
+  const float bov = tid < nDense ? W[iBo + tid] : 0.f, bpv = tid < dA ? W[iBp + tid] : 0.f;
   double beta = sc->beta; const double Cmax = sc->Cmax, Cinv = sc->Cinv;
   const long long betaWant = sc->nGradSteps;      // (deferBeta: the rider in block 1 publishes beta under this number)
   // the panel's arrive counter as it stands before this workgroup's own arrival: it advances by HT per launch (the whole group of a
   // panel runs or leaves), so any such value lies in [base, base + HT - 1] and gives the barrier's target without a returning atomic
   unsigned ctr0 = 0;
-  if constexpr (HT > 1) ctr0 = __hip_atomic_load(a.panelCtr + panel * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (HT > 1) ctr0 = __hip_atomic_load(panelCtr + panel * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if FUSED_ARGS_FIRST
+  FUSED_PIN_ARGS();      // behind the first batch: the arguments of the later phases
+#endif
   // ---- stage: states, W0 (k-major), W1 column tile (k-major), Wout, vectors ------------------------
 #pragma unroll
   for (int q = 0; q < QS; ++q) { const int idx = tid + NT * q, r = idx >> 5, c = idx & 31; sS[r * FLDS + c] = sv[q]; }
@@ -319,6 +383,13 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
 #pragma unroll
     for (int t = 0; t < TPW; ++t) acc[t] = z4;
     const int nk4 = dSp >> 2;
+    float bb[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) bb[t] = sB0[(wave + NW * t) * 16 + li];      // (depends on nothing: requested with the operands)
+#if FUSED_H1_PRE
+    h1Product<TPW, false>(nk4, acc, [&](int s) { return sS[li * FLDS + 4 * s + lc]; },
+                          [&](int s, int t) { return sR2[(4 * s + lc) * LDW0 + (wave + NW * t) * 16 + li]; });
+#else
     // operands of step s+1 are read while the MFMAs of step s run
     float av = sS[li * FLDS + lc], bv[TPW];
 #pragma unroll
@@ -335,10 +406,8 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
 #pragma unroll
       for (int t = 0; t < TPW; ++t) bv[t] = bvn[t];
     }
+#endif
     FSTAMP(14);
-    float bb[TPW];
-#pragma unroll
-    for (int t = 0; t < TPW; ++t) bb[t] = sB0[(wave + NW * t) * 16 + li];
     dispatchFunc<CF>(func, [&](auto F) {
       constexpr int FN = decltype(F)::value;
 #pragma unroll
@@ -390,6 +459,17 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
 #pragma unroll
       for (int t = 0; t < CT; ++t) acc[t] = z4;
       const int nk4 = dSp >> 2;
+      // the bias of the h1 tiles depends on nothing: requested with the operands, consumed behind the product
+      float bb[CT][4];
+#pragma unroll
+      for (int t = 0; t < CT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bb[t][r] = sB0[cb + 16 * t + 4 * r + lc];
+      }
+#if FUSED_H1_PRE
+      h1Product<CT, true>(nk4, acc, [&](int s) { return sS[li * FLDS + 4 * s + lc]; },
+                          [&](int s, int t) { return sR2[(4 * s + lc) * LDW0 + cb + 16 * t + pc]; });
+#else
       // operands of step s+1 are read while the MFMAs of step s run
       float bv = sS[li * FLDS + lc], av[CT];
 #pragma unroll
@@ -406,15 +486,10 @@ __global__ __launch_bounds__(NT, NT / 128) void fused_fwd_head_dx_kernel(FusedAr
 #pragma unroll
         for (int t = 0; t < CT; ++t) av[t] = avn[t];
       }
+#endif
       FSTAMPT(CTID, 14);
       // bias and activation in place; the workgroup's own column tile also goes to LDS, x1 and h1, for the element threads
       // (residual path, A operand of dW1, f'(x1))
-      float bb[CT][4];
-#pragma unroll
-      for (int t = 0; t < CT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bb[t][r] = sB0[cb + 16 * t + 4 * r + lc];
-      }
       dispatchFunc<CF>(func, [&](auto F) {
         constexpr int FN = decltype(F)::value;
 #pragma unroll

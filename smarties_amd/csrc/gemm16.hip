@@ -225,6 +225,16 @@ __device__ __forceinline__ void dwDirectTile(const GemmProblem& P, int tile, uns
   }
 }
 
+// (-DHL_DWSTAMPS, tools/dwstamps.py) when does the LAST workgroup of each kind of dw_table_kernel finish?  dbgT[24] weight-gradient
+// tiles, [25] the bookkeeping rider, [26] the sampler rider, [27] the gather helpers -- maxima of a monotonic 100 MHz clock, taken in
+// the launches inside a call only (POST_DEFER: the last launch of a call carries a longer bookkeeping rider), so after a call they
+// belong to its last launch but one, like dbgT[28], the entry of the first tile workgroup.  Compiled out otherwise.
+#if defined(HL_DWSTAMPS)
+#define DWEND(i) do { __syncthreads(); if (threadIdx.x == 0 && postOn && (post.mode & POST_DEFER)) atomicMax(reinterpret_cast<unsigned long long*>(&const_cast<DevScalars*>(sc)->dbgT[i]), (unsigned long long)wall_clock64()); } while (0)
+#else
+#define DWEND(i) do { } while (0)
+#endif
+
 // the weight-gradient launch of the fused path: the problem table travels in the kernel arguments
 // (scalar loads from the kernarg segment instead of two dependent global round trips)
 // (the two riders' arguments travel unpacked: two whole ExtraArgs records would push the kernel-argument segment past 4 KB)
@@ -242,19 +252,22 @@ __global__ __launch_bounds__(256) void dw_table_kernel(DwTable tbl, const DevSca
   const int r1 = postOn ? 1 : 0, r2 = sampPhases ? 1 + helpers : 0, nRiders = r1 + r2;
   if ((int)blockIdx.x < nRiders) {
     const int b = blockIdx.x;
-    if (b < r1) postPhase(post, smem);
-    else if (b == r1) samplePhases(samp, sampPhases, smem);
-    else gatherHelper(samp, b - r1 - 1, helpers, smem);
+    if (b < r1) { postPhase(post, smem); DWEND(25); }
+    else if (b == r1) { samplePhases(samp, sampPhases, smem); DWEND(26); }
+    else { gatherHelper(samp, b - r1 - 1, helpers, smem); DWEND(27); }
     return;
   }
   const int bid = blockIdx.x - nRiders;
+#if defined(HL_DWSTAMPS)
+  if (threadIdx.x == 0 && bid == 0 && postOn && (post.mode & POST_DEFER)) const_cast<DevScalars*>(sc)->dbgT[28] = wall_clock64();
+#endif
   int p = 0;
 #pragma unroll
   for (int i = 1; i < DW_TABLE_MAX; ++i) if (i < tbl.n && bid >= tbl.p[i].tileStart) p = i;
   const GemmProblem P = tbl.p[p];      // by value: the whole record in one batch of scalar loads
   if (P.flavor == GEMM_W) {
 #ifndef HL_DW_TABLE_STAGED
-    if (!hyp.push.on && P.K <= 1024) { dwDirectTile(P, bid - P.tileStart, smem, sc, hyp); return; }      // (peer-window push: the staged form's epilogue)
+    if (!hyp.push.on && P.K <= 1024) { dwDirectTile(P, bid - P.tileStart, smem, sc, hyp); DWEND(24); return; }      // (peer-window push: the staged form's epilogue)
 #endif
     gemmTile<GEMM_ROLE_DW, GEMM_W>(P, bid - P.tileStart, smem, sc, hyp, 0);
   }
