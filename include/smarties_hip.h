@@ -84,6 +84,18 @@ enum { HL_NN_FFNN = 0, HL_NN_LSTM = 1, HL_NN_MGU = 2 /* Layer_GRU.h: what a part
                         (BaseLayer with bRecurrent, Layer_Base.h:64-113).  Up to 256 cells per layer: the per-sample kernels of rec.hip; up to
                         1024 where every layer is a multiple of 16 cells and no encoder layers or convolutions lie in front: nets with a
                         layer above 256 cells run time-step-major on the MFMA, as wide LSTM / MGU layers do (rectm.hip) */ };
+/* Input width of recurrent nets (HL_NN_LSTM, HL_NN_MGU, HL_NN_RNN) without convolutional layers.  Up to dimS = 256 with
+ * dimS (1 + nAppendedObs) <= 1024: every shape above, as before.  Beyond either, up to dimS (1 + nAppendedObs) = 8192: every layer a
+ * multiple of 16 cells up to 1024, no encoder layers and no encoder_rnn; such a net runs time-step-major whatever its cell count, the
+ * first layer's input product of all window rows as one launch of its own in front of the forward chain (rectm.hip:
+ * tm_win_product_kernel), in training, hl_forward_sequence and hl_forward_sequences alike.  hl_create returns HL_ERR_UNSUPPORTED for
+ * any other wide-input shape (checked before the device is opened, so without a handle to ask for a message), and with a message where
+ * batch x (nnBPTTseq + 2) window rows of input + cells + 1 floats reach 2^31 floats or the weight-gradient partials exceed 2^30 floats.
+ * Measured on an MI355X (tools/wide_in_timing.py -> profiles/wide_in_timing.json: V-RACER, LSTM 2 x 128 cells, batch 128, nnBPTTseq 16,
+ * nAppendedObs 3, replayed graphs of 20 steps, median of 240 steps): 1024 inputs, the route as before, 583 us per step; 1040 inputs, the
+ * product launch, 449 us (device time of the forward pass: 349 us against 11 + 53 + 149 for prepare, product and chain); 2048 inputs
+ * 548 us; 8192 inputs 1066 us.  Nothing else about the speed of these nets has been measured: other cell counts, batches and window
+ * lengths, and where the product launch would start to win below 1024 inputs, are open. */
 
 /* settings key returnsEstimator (Settings/HyperParameters.cpp:135; MemoryProcessing::createReturnEstimator,
  * ReplayMemory/MemoryProcessing.cpp:391-450): how the per-step return estimates are swept backwards over an episode */

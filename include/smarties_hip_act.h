@@ -124,6 +124,13 @@ extern "C" {
  * training rows of that many samples between steps (as hl_forward_sequence borrows those of one); the minibatch index
  * buffers and a minibatch drawn ahead stay as they are.  The kernels and their order of summation are those of the
  * single-agent call, an agent's row of a tile does not see the other rows: bit-identical to hl_forward_sequence.
+ * Batched, wide inputs (a state beyond 256 components or dimS (1 + nAppendedObs) beyond 1024, up to 8192, in front of LSTM, MGU
+ * or RNN layers of any multiple of 16 cells up to 1024; smarties_hip.h): the same chain with one launch more in front of the
+ * diagonals, the first layer's input product of the chunk's agents x steps rows.  hl_forward_sequence runs that chain on its one
+ * window.  A chunk holds min(local batch size, HL_ACT_SEQ_CHUNK) agents and no more than whose windows of
+ * nnBPTTseq + 1 + nAppendedObs states fit HL_ACT_WIN_STAGE_BYTES of pinned staging (60 agents of 17 states of 8192 floats),
+ * though never fewer than one.  An element of the product is one chain of MFMAs over its row's inputs whatever the row's
+ * place in the launch: bit-identical to hl_forward_sequence.
  * Dense nets: the [n][dimS (1 + nAppendedObs)] rows are built on the host and go through ONE hl_forward(n) call.
  * Batched, every other recurrent net -- recurrent layers behind convolutions, RNN encoder layers under MGU layers (encoder_rnn),
  * nets of at most 256 cells whose window exceeds the 64 KB above; every layer <= 256 cells with <= 1024 inputs --: agent i of a
@@ -137,7 +144,7 @@ extern "C" {
  * of summation: bit-identical to hl_forward_sequence.  Behind convolutions a minibatch drawn ahead is dropped and drawn again
  * with the same generator state, as by hl_forward_sequence.
  * Looped, agent by agent through hl_forward_sequence's own route: only a net beyond those bounds (more than 1024 inputs to the
- * first recurrent layer) which the time-step-major launches do not take either.
+ * first recurrent layer behind convolutions) which the time-step-major launches do not take either.
  *
  * For a single agent the call costs more than hl_forward_sequence (which runs the window with the weights in registers
  * where the shape allows): hl_forward_sequence stays the call for one agent. */

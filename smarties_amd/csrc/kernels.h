@@ -92,7 +92,15 @@ struct RecArgs {
   unsigned* tmCtr; int tmCtrN; int tmCtrOff[HL_MAX_HIDDEN];      // LSTM backward by diagonals: one arrival counter per (layer, 16-cell tile, 16-sample block), the layer's first one
   float* YoutRows; int ldYR;       // != nullptr: the last block's output of EVERY window step goes here (row b K + k, next rows behind B K): the upper segment's Xin
   const float* DresRows; int ldDR; // != nullptr: gradient w.r.t. those outputs per window row, from the upper segment (instead of Dres at the sampled step only)
+  // (last, so that every field above keeps its place in the kernels' argument block)
+  float* tmP;                      // != nullptr: wide inputs (rectm.hip: tm_win_product_kernel) -- [R][gates nC], the first layer's input product
+                                   // A[r][0 .. nIn) W_in of every window row from ONE launch in front of the forward chain; the first layer's
+                                   // forward launches then stage and reduce over the recurrent part of the row alone and add P[r] beside the bias
 };
+// wide inputs: the stacked input of the first recurrent layer beyond what a forward tile stages ([input | previous output] of 16 samples in LDS)
+constexpr int TM_WIN_MAX_IN = 8192;
+// the parts of the time-step-major forward pass (launch_rec_tm_forward; the product only where RecArgs::tmP is given)
+enum { TM_PART_PREPARE = 1, TM_PART_PRODUCT = 2, TM_PART_CHAIN = 4, TM_PART_ALL = 7 };
 struct WinRowsArgs { const DevScalars* sc; DevScalars* scW; const long long* slot; const int* t; const int* nextSrc; int B, K, nBPTT, parity;
                      long long* slotW; int* tW; int* nextSrcW; };
 hipError_t launch_window_rows(const WinRowsArgs& a, hipStream_t s);
@@ -101,7 +109,7 @@ hipError_t launch_rec_backward(const RecArgs& a, hipStream_t s);
 bool rec_tm_ok(const RecArgs& a);                                     // rectm.hip serves this net: a launch per (layer, window step) over the whole minibatch
 bool rec_tm_act_ok(const RecArgs& a);                                 // ... and this acting window, or these B agents' windows (layers beyond 256 cells)
 bool rec_win_act_ok(const RecArgs& a);                                // rec.hip's workgroup-per-sample kernels serve this acting window, or these B agents' windows (one workgroup each)
-hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s);
+hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s, int parts = TM_PART_ALL);
 hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s);
 // window forward + output layer + head + back-propagation through time of a sample as ONE launch (rec.hip: lstm32_step_wave_kernel)
 struct ExtraArgs;

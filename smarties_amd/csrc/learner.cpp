@@ -76,7 +76,15 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   if (cfg->nnOutputFunc < HL_FUNC_LINEAR || cfg->nnOutputFunc > HL_FUNC_EXP) return HL_ERR_UNSUPPORTED;
   if (cfg->n_encoder < 0 || cfg->n_encoder + cfg->n_hidden > HL_MAX_HIDDEN) return HL_ERR_BAD_ARG;
   if (cfg->nn_type != HL_NN_FFNN) {   // rec.hip: 256-thread workgroups looping over gates and cells (REC_GENC, REC_GENIN)
-    if (cfg->n_conv <= 0 && (cfg->dimS > 256 || (long long)cfg->dimS * (1 + std::max(cfg->nAppendedObs, 0)) > 1024)) return HL_ERR_UNSUPPORTED;
+    // wide inputs -- a state beyond the 256 components, or a stacked input beyond the 1024, that the per-sample kernels hold in LDS (REC_MAXIN /
+    // REC_GENIN; nothing else rests on them: recurrent nets read their inputs from the replay themselves, the sampler gathers nothing for them) --:
+    // the time-step-major launches with the first layer's input product as one launch of its own (rectm.hip: tm_win_product_kernel), whatever the
+    // cell count: no encoder layers, every layer a multiple of 16 cells up to 1024, a stacked input of up to TM_WIN_MAX_IN
+    const long long stacked = (long long)cfg->dimS * (1 + std::max(cfg->nAppendedObs, 0));
+    if (cfg->n_conv <= 0 && (cfg->dimS > 256 || stacked > 1024)) {
+      if (stacked > TM_WIN_MAX_IN || cfg->n_encoder > 0 || cfg->encoder_rnn) return HL_ERR_UNSUPPORTED;
+      for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] < 16 || cfg->hidden[j] % 16 != 0 || cfg->hidden[j] > 1024) return HL_ERR_UNSUPPORTED;
+    }
     // (encoder layers are hidden layers of the same network, Learner_approximator.cpp:149-166: the same limits hold for them)
     // (LSTM / MGU / RNN layers of up to 1024 cells, all multiples of 16, without encoder layers or convolutions in front: the time-step-major
     //  launches -- rectm.hip -- serve their training windows and their acting windows; checked again where recTm is decided)
@@ -162,12 +170,22 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     h->tmMinCells = cfg->nn_type == HL_NN_LSTM ? 48 : (cfg->nn_type == HL_NN_MGU ? 64 : 256);      // (RNN: 256 = REC_GENC, the per-sample kernels' limit, not a crossover)
     for (int j = 0; j < h->cfg.n_hidden; ++j) { wide = wide || h->cfg.hidden[j] > h->tmMinCells; ok = ok && h->cfg.hidden[j] % 16 == 0; }
     // (the crossover, measured at batch 128 and 17 steps: 2 x 64 cells 325 us with the per-sample kernels against 452 time-step-major, 2 x 96: 631 against 499)
-    h->recTm = wide && ok;
+    // wide inputs (checked at the top): these launches are their only route, tmMinCells does not apply
+    h->wideIn = cfg->dimS > 256 || h->dIn > 1024;
+    h->recTm = (wide || h->wideIn) && ok;
     if (h->recTm) h->recK += 1;
     // their weight gradients (2304 rows x 513 x 1024 per layer at 2 x 256 cells): the large-batch launch's 64 x 64 tiles over row chunks
     // (bigmm.hip: big_dw_kernel + the split-row join: 74 + 14 us against 197 of dw_wide_kernel's 16 x 16 tiles, which read their operands
     // 4 x as often)
     if (h->recTm && !(h->generic & 128)) h->bigMm |= 2;
+  }
+  if (h->recurrent && h->nConv == 0 && (cfg->dimS > 256 || h->dIn > 1024) && !(h->recTm && h->wideIn))
+    return fail(h, HL_ERR_UNSUPPORTED, "recurrent net on a state beyond 256 components or a stacked input beyond 1024: served by the time-step-major launches only (SMARTIES_HIP_GENERIC bit 4 switches them off)");
+  if (h->recurrent && h->wideIn) {
+    // what the launches index with 32-bit row offsets and what the partial buffers hold: the operand rows [B recK][input + cells + 1] of
+    // the first layer below 2^31 floats (its weight-gradient partials are bounded where they are sized: buildProblems)
+    const long long rows = (long long)B * h->recK, pitch = roundUp((long long)h->dIn + h->cfg.hidden[0] + 1, 16);
+    if (rows * pitch >= (1ll << 31)) return fail(h, HL_ERR_UNSUPPORTED, "wide recurrent input: batch x (nnBPTTseq + 2) window rows of input + cells + 1 floats reach 2^31 floats");
   }
   if (h->recurrent && !h->recTm)
     for (int j = 0; j < h->cfg.n_hidden; ++j) if (h->cfg.hidden[j] > 256) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer wider than 256 cells: every LSTM / MGU / RNN layer must be a multiple of 16 cells, without encoder layers or convolutions in front (time-step-major launches)");
@@ -260,6 +278,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       int nCtr = 0;
       for (int j = 0; j < h->nHidden; ++j) { h->tmCtrOff[j] = nCtr; nCtr += (h->hid[j].size / 16) * ((B + 15) / 16); }      // (recTm: no convolutions in front)
       HIPCK(devAlloc(&h->tmCtr, (size_t)nCtr)); h->tmCtrN = nCtr;
+      if (h->wideIn) HIPCK(devAlloc(&h->tmP, R * (size_t)h->hid[0].lstm * h->hid[0].size));      // (a row per window row, as the layer's X)
     }
   }
   {   // fused forward + head + dX kernel: two equal hidden blocks of width H <= 256, small state / action spaces
@@ -390,6 +409,8 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   HIPCK(hipMemcpy(h->rp.stScale, ones.data(), h->dS * sizeof(float), hipMemcpyHostToDevice));
   HIPCK(hipMemcpy(h->rp.stStd, ones.data(), h->dS * sizeof(float), hipMemcpyHostToDevice));
   rc = buildProblems(h); if (rc) return rc;
+  // (wide inputs have no other route: the per-sample kernels stage an input row of at most 1024 floats)
+  if (h->wideIn && !rec_tm_ok(recArgs(h, 0))) return fail(h, HL_ERR_UNSUPPORTED, "wide recurrent input: the time-step-major launches refuse this net");
   if (const char* e = getenv("SMARTIES_HIP_NO_GRAPH")) { if (e[0] == '1') h->useGraph = false; }
   if (const char* e = getenv("SMARTIES_HIP_XCHG_TIMEOUT_MS")) h->xchgTimeoutTicks = std::max(1LL, atoll(e)) * 100000LL;
   return HL_OK;
@@ -424,7 +445,7 @@ int hl_destroy(hl_learner* h) {
   for (void* q : {(void*)h->winSlot, (void*)h->winT, (void*)h->winNextSrc, (void*)h->scW}) if (q) hipFree(q);
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* q : {h->rec[j].A, h->rec[j].X, h->rec[j].Y, h->rec[j].D, h->rec[j].Rd, h->rec[j].A2}) if (q) hipFree(q);
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* q : {h->tmER[j], h->tmSD[j], h->tmFP[j], h->tmET[j]}) if (q) hipFree(q);
-  for (void* q : {(void*)h->tmT, (void*)h->tmSteps, (void*)h->tmNext, (void*)h->tmCtr}) if (q) hipFree(q);
+  for (void* q : {(void*)h->tmT, (void*)h->tmSteps, (void*)h->tmNext, (void*)h->tmCtr, (void*)h->tmP}) if (q) hipFree(q);
   for (void* p : ptrs) if (p) hipFree(p);
   for (int l = 0; l < h->nConv; ++l) { ConvGeo& g = h->cg[l];
     if (l != h->nConv - 1) for (float* p : {g.X, g.Y, g.D}) if (p) hipFree(p);

@@ -62,7 +62,7 @@ static bool actFewOk(hl_learner* h) {
 static bool actSeqOk(hl_learner* h) {
   if (h->act.seqOk) return h->act.seqOk > 0;
   h->act.seqOk = -1;
-  if (!h->recurrent || h->nConv > 0 || h->recSplit) return false;
+  if (!h->recurrent || h->nConv > 0 || h->recSplit || h->wideIn) return false;      // (wide inputs: the time-step-major chain, as hl_forward_sequence)
   const RecArgs ra = recArgs(h, 0);
   ActSeqArgs& a = h->act.seqArgs; a = ActSeqArgs{};
   actFillShared(h, a);
@@ -143,6 +143,8 @@ static int actChunkCap(hl_learner* h) {
   if (!actTmOk(h) && !actWinOk(h)) return 0;
   size_t cap = (size_t)std::min(h->B, ACT_SEQ_CHUNK);
   if (h->nConv > 0) cap = std::min(cap, (size_t)HL_ACT_WIN_STAGE_BYTES / ((size_t)h->recK * h->dIn * sizeof(float)));
+  // (wide inputs: a window of nnBPTTseq + 1 + nAppendedObs states of up to 8192 floats -- the same bound on the staged states)
+  if (h->wideIn) cap = std::min(cap, (size_t)HL_ACT_WIN_STAGE_BYTES / ((size_t)(h->recWin + h->nApp) * h->dS * sizeof(float)));
   return (int)std::max(cap, (size_t)1);
 }
 // a pinned, device-mapped block of zeros

@@ -68,6 +68,9 @@ struct hl_learner {
   float* tmER[HL_MAX_HIDDEN] = {}; float* tmSD[HL_MAX_HIDDEN] = {}; float* tmFP[HL_MAX_HIDDEN] = {};
   unsigned* tmCtr = nullptr; int tmCtrN = 0; int tmCtrOff[HL_MAX_HIDDEN] = {}; float* tmET[HL_MAX_HIDDEN] = {};
   int tmMinCells = 64;      // layers wider than this: time-step-major
+  // wide inputs (dimS > 256 or a stacked input beyond 1024, no convolutions in front): time-step-major whatever the cell count, the first
+  // layer's input product of all window rows from one launch into tmP [B recK][gates x cells] (rectm.hip: tm_win_product_kernel)
+  bool wideIn = false; float* tmP = nullptr;
   bool recurrent = false; int recK = 0;    // LSTM hidden layers: rows per sample of the per-step buffers (nnBPTTseq + 1; one more for the time-step-major launches)
   int recWin = 0;                          // ... steps of a window: nnBPTTseq + 1
   // hl_config::encoder_rnn: the first recSplit recurrent layers are plain recurrent ("RNN") ones under MGU layers.  The window kernels

@@ -127,7 +127,9 @@ __device__ __forceinline__ bool tmAnyActive(const int* sAct) {
 //   REC_ELSEWHERE = false   the row is [input | previous output] of L.A (its pitch is a multiple of 16 floats): 16-byte loads
 //   REC_ELSEWHERE = true    the recurrent part comes from rec[r ldRec + .] (MGU phase 1: A2; no alignment of its pitch is asked
 //                           for by tmLayersOk): element by element
-template <bool REC_ELSEWHERE>
+//   REC_ONLY (wide inputs)  the tile is the recurrent part alone, Kt = nC floats of rec[r ldRec + .]: the first layer's input product
+//                           comes from tm_win_product_kernel (nIn need not be a multiple of 4: element by element as well)
+template <bool REC_ELSEWHERE, bool REC_ONLY = false>
 __device__ __forceinline__ void tmStageA(float* sA, int lds, const RecArgs& a, const RecLayer& L, const float* rec, int ldRec, int Kt, int Kt4, int b0, int k, int tid) {
   const int q4 = Kt4 >> 2;
   for (int i = tid; i < 16 * q4; i += TM_FNT) {
@@ -138,7 +140,8 @@ __device__ __forceinline__ void tmStageA(float* sA, int lds, const RecArgs& a, c
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int x = 4 * q + e;
-        v[e] = x < L.nIn ? L.A[r * L.ldA + x] : (x < Kt ? rec[r * ldRec + (x - L.nIn)] : 0.f);
+        if constexpr (REC_ONLY) v[e] = x < Kt ? rec[r * ldRec + x] : 0.f;
+        else v[e] = x < L.nIn ? L.A[r * L.ldA + x] : (x < Kt ? rec[r * ldRec + (x - L.nIn)] : 0.f);
       }
     } else {
       v = *reinterpret_cast<const f32x4*>(L.A + ((size_t)b * a.K + k) * L.ldA + 4 * q);
@@ -294,7 +297,11 @@ __device__ __forceinline__ void tmFinishTile(const RecArgs& a, int j, int k, int
 // One launch = one DIAGONAL of the (layer, step) grid: blockIdx.z picks (j0 + z, k0 - z) -- layer j at step k needs layer j - 1 at step k
 // and its own step k - 1, both on the diagonal in front, so a window of K steps through nL layers is K + nL - 1 launches instead of K nL
 // (what they write into a shared row -- the block output of the layer below, the recurrent input of the step before -- are different columns)
-__global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, int k0) {
+// WIN (wide inputs, tm_win_lstm_fwd_kernel): the FIRST layer's tile is the recurrent part of the row alone -- its wavefronts reduce over W_rec,
+// and the cell adds the row of the input product P (tm_win_product_kernel) beside the bias; the layers above are the code below as it stands.
+// A flag of the kernel, as RecActWin<MANY> and tmStageA<REC_ELSEWHERE>: without it nothing of this is compiled
+template <bool WIN>
+__device__ __forceinline__ void tmLstmForward(const RecArgs& a, int j0, int k0) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;
   const RecLayer& L = a.L[j];
@@ -306,17 +313,20 @@ __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, 
 #define TMSTMP(i) do { } while (0)
 #endif
   TMSTMP(0);
-  const int nIn = L.nIn, nC = L.nC, NO = 4 * nC, Kt = nIn + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
+  const int nIn = L.nIn, nC = L.nC, NO = 4 * nC;
+  bool win = false;                      // this member of the diagonal takes its input product from P
+  if constexpr (WIN) win = j == 0;
+  const int Kt = win ? nC : nIn + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
   float* sA = sm;                        // [16][lds]
   float* sG = sA + 16 * lds;             // [8][16][17]
   __shared__ int sAct[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int b0 = blockIdx.y * 16, c0 = blockIdx.x * 16;
   tmActiveMask(sAct, a, b0, k, tid);
-  // this wavefront's W column (gate, cell li) over its half of the rows [W_in; W_rec]: the first batch is requested in front of the A tile
+  // this wavefront's W column (gate, cell li) over its half of the rows [W_in; W_rec] (WIN, first layer: of W_rec): the first batch is requested in front of the A tile
   const int gate = wave & 3, half = wave >> 2;
   const int nS = Kt4 >> 2, nSh = (nS + 1) >> 1, sBeg = half * nSh, sEnd = min(nS, sBeg + nSh);
-  const float* Wg = a.W + L.indW + (size_t)gate * nC + c0 + li;
+  const float* Wg = a.W + L.indW + (win ? (size_t)nIn * NO : (size_t)0) + (size_t)gate * nC + c0 + li;
   float bv[TM_UN];
   tmLoadW(bv, Wg, NO, sBeg, lc, Kt);
   // what the cell's epilogue reads from memory -- the four biases, the state of the step before, the window's length: requested here, used
@@ -329,6 +339,14 @@ __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, 
   const int stepsE = a.tmSteps[eB], TE = a.tmT[eB];
   float wrE = 0.f, brE = 0.f;
   if (L.hasRes && eC < L.resW) { wrE = a.W[L.indWr + eC]; brE = a.W[L.indBr + eC]; }
+  // (P rows of steps a sample does not have hold whatever the product made of stale inputs: read for the samples that have the step only)
+  float pE0 = 0.f, pE1 = 0.f, pE2 = 0.f, pE3 = 0.f;
+  if constexpr (WIN) if (win && b0 + eRow < a.B && stepsE > k) {
+    const float* Pr = a.tmP + eR * NO + eC;
+    pE0 = Pr[0]; pE1 = Pr[nC]; pE2 = Pr[2 * nC]; pE3 = Pr[3 * nC];
+  }
+  if (win) tmStageA<true, true>(sA, lds, a, L, L.A + nIn, L.ldA, Kt, Kt4, b0, k, tid);
+  else
   tmStageA<false>(sA, lds, a, L, nullptr, 0, Kt, Kt4, b0, k, tid);
   TMSTMP(1);
   __syncthreads();
@@ -344,18 +362,21 @@ __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, 
   if (!sAct[row]) return;
   const long long r = (long long)b * a.K + k;
   auto gsum = [&](int g) { return sG[(g * 16 + row) * 17 + cc] + sG[((4 + g) * 16 + row) * 17 + cc]; };
-  const float ci = gsum(0) + bi0;
-  const float ig = recSigm(gsum(1) + bi1);
-  const float fg = recSigm(gsum(2) + bi2);
-  const float og = recSigm(gsum(3) + bi3);
+  auto pre = [&](int g, float bi, float p) { if constexpr (WIN) return (gsum(g) + p) + bi; else return gsum(g) + bi; };      // (WIN, layers above the first: p = 0)
+  const float ci = pre(0, bi0, pE0);
+  const float ig = recSigm(pre(1, bi1, pE1));
+  const float fg = recSigm(pre(2, bi2, pE2));
+  const float og = recSigm(pre(3, bi3, pE3));
   const float st = ci * ig + prevStE * fg;
   const float co = actEval(HL_FUNC_TANH, st);
   const float out = og * co;
   L.X[r * NO + c] = ci; L.X[r * NO + nC + c] = ig; L.X[r * NO + 2 * nC + c] = fg; L.X[r * NO + 3 * nC + c] = og;
   L.Y[r * NO + c] = out; L.Y[r * NO + nC + c] = st; L.Y[r * NO + 2 * nC + c] = co;
-  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wrE, brE, stepsE, TE);
+  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wrE, brE, stepsE, TE);      // (the first layer has no residual: its staged row is read above it only)
   TMSTMP(5);
 }
+__global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, int k0) { tmLstmForward<false>(a, j0, k0); }
+__global__ __launch_bounds__(TM_FNT) void tm_win_lstm_fwd_kernel(RecArgs a, int j0, int k0) { tmLstmForward<true>(a, j0, k0); }
 // the cell's deltas of (layer j, step k, sample b, cell c), Layer_LSTM.h:127-165: eTop = error from the block above (same step), eRec = error
 // handed back by step k + 1 (zero at the sample's last step)
 __device__ __forceinline__ void tmDelta(const RecArgs& a, int j, int k, int b, int c, int T, float eTop, float eRec) {
@@ -406,24 +427,31 @@ __global__ __launch_bounds__(256) void lstm_tm_bwd_kernel(RecArgs a, int j0, int
 //                      (1 - f) dLdO + f fp + g.  Its epilogue forms dLdO and dS of the cell whose inputs it completes (as the LSTM
 //                      kernel does): the block below at this step, the last layer at the previous step
 // W is [nIn + nC][2 nC] (forget columns first); rows kept per (sample, step): X = [f | s], Y = output, D = [dF | dS].
-__global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, int k0, int phase) {
+template <bool WIN>      // (wide inputs: tmLstmForward; both phases have an input term)
+__device__ __forceinline__ void tmMguForward(const RecArgs& a, int j0, int k0, int phase) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;      // (a diagonal per launch: lstm_tm_fwd_kernel)
   const RecLayer& L = a.L[j];
   if ((int)blockIdx.x * 16 >= L.nC) return;
-  const int nIn = L.nIn, nC = L.nC, NO = 2 * nC, Kt = nIn + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
+  const int nIn = L.nIn, nC = L.nC, NO = 2 * nC;
+  bool win = false;
+  if constexpr (WIN) win = j == 0;
+  const int nInS = win ? 0 : nIn;        // input columns in front of the recurrent part of the staged row
+  const int Kt = nInS + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
   float* sA = sm;                        // [16][lds]
   float* sG = sA + 16 * lds;             // [8][16][17]
   __shared__ int sAct[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
   const int b0 = blockIdx.y * 16, c0 = blockIdx.x * 16;
   tmActiveMask(sAct, a, b0, k, tid);
-  // wavefront w: an eighth of the rows [W_in; W_rec] of column (phase, cell li)
+  // wavefront w: an eighth of the rows [W_in; W_rec] (WIN, first layer: of W_rec) of column (phase, cell li)
   const int nS = Kt4 >> 2, nSe = (nS + 7) >> 3, sBeg = wave * nSe, sEnd = min(nS, sBeg + nSe);
-  const float* Wg = a.W + L.indW + (size_t)phase * nC + c0 + li;
+  const float* Wg = a.W + L.indW + (win ? (size_t)nIn * NO : (size_t)0) + (size_t)phase * nC + c0 + li;
   float bv[TM_UN];
   tmLoadW(bv, Wg, NO, sBeg, lc, Kt);
   // A tile: [in | prevOut] (phase 0) or [in | f * prevOut] (phase 1)
+  if (win) tmStageA<true, true>(sA, lds, a, L, phase ? L.A2 : L.A + nIn, phase ? L.ldA2 : L.ldA, Kt, Kt4, b0, k, tid);
+  else
   tmStageA<true>(sA, lds, a, L, phase ? L.A2 : L.A + nIn, phase ? L.ldA2 : L.ldA, Kt, Kt4, b0, k, tid);
   __syncthreads();
   if (!tmAnyActive(sAct)) return;
@@ -433,10 +461,11 @@ __global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, i
   const int row = tid >> 4, cc = tid & 15, b = b0 + row, c = c0 + cc;
   if (!sAct[row]) return;
   float sum = a.W[L.indB + phase * nC + c];
+  if constexpr (WIN) if (win) sum += a.tmP[((long long)b * a.K + k) * NO + phase * nC + c];      // (behind sAct: a row of a step this sample has)
 #pragma unroll
   for (int w = 0; w < 8; ++w) sum += sG[(w * 16 + row) * 17 + cc];
   const long long r = (long long)b * a.K + k;
-  const float po = sA[row * lds + nIn + c];      // phase 0: prevOut; phase 1: f * prevOut
+  const float po = sA[row * lds + nInS + c];     // phase 0: prevOut; phase 1: f * prevOut
   if (phase == 0) {
     const float f = recSigm(sum);
     L.X[r * NO + c] = f;
@@ -452,6 +481,8 @@ __global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, i
   if (L.hasRes && c < L.resW) { wr = a.W[L.indWr + c]; br = a.W[L.indBr + c]; }
   tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wr, br, a.tmSteps[b], a.tmT[b]);
 }
+__global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, int k0, int phase) { tmMguForward<false>(a, j0, k0, phase); }
+__global__ __launch_bounds__(TM_FNT) void tm_win_mgu_fwd_kernel(RecArgs a, int j0, int k0, int phase) { tmMguForward<true>(a, j0, k0, phase); }
 // dLdO and the state delta of (layer j, step k, sample b, cell c): eTop = error from the block above, eRec = error handed back by step k + 1
 __device__ __forceinline__ void tmMguOpen(const RecArgs& a, int j, int k, int b, int c, int T, float eTop, float eRec) {
   const RecLayer& L = a.L[j];
@@ -527,12 +558,16 @@ __global__ __launch_bounds__(256) void mgu_tm_bwd_kernel(RecArgs a, int j0, int 
 // of 2 x 512 cells 239 us -- 3.5 x the operations for 28 % more time, so at these sizes the dependent launches set the time and not the
 // product.  The other two shapes were not built: the choice between them rests on the arithmetic above.
 constexpr int RNN_TM_TILES = 2;
-__global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, int k0) {
+template <bool WIN>      // (wide inputs: tmLstmForward)
+__device__ __forceinline__ void tmRnnForward(const RecArgs& a, int j0, int k0) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int j = j0 + (int)blockIdx.z, k = k0 - (int)blockIdx.z;      // (a diagonal per launch: lstm_tm_fwd_kernel)
   const RecLayer& L = a.L[j];
   if ((int)blockIdx.x * 16 * RNN_TM_TILES >= L.nC) return;           // (the grid is as wide as the diagonal's widest layer)
-  const int nIn = L.nIn, nC = L.nC, Kt = nIn + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
+  const int nIn = L.nIn, nC = L.nC;
+  bool win = false;
+  if constexpr (WIN) win = j == 0;
+  const int Kt = win ? nC : nIn + nC, Kt4 = (Kt + 3) & ~3, lds = Kt4 + TM_LDA;
   float* sA = sm;                        // [16][lds]
   float* sG = sA + 16 * lds;             // [8][16][17]
   __shared__ int sAct[16];
@@ -542,7 +577,7 @@ __global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, i
   // this wavefront's W column (tile, cell li) over its quarter of the rows [W_in; W_rec]: the first batch is requested in front of the A tile
   const int tile = wave & 1, quarter = wave >> 1;
   const int nS = Kt4 >> 2, nSq = (nS + 3) >> 2, sBeg = quarter * nSq, sEnd = min(nS, sBeg + nSq);
-  const float* Wg = a.W + L.indW + min(cBase + 16 * tile, nC - 16) + li;      // (W's row pitch is nC: a multiple of 16)
+  const float* Wg = a.W + L.indW + (win ? (size_t)nIn * nC : (size_t)0) + min(cBase + 16 * tile, nC - 16) + li;      // (W's row pitch is nC: a multiple of 16)
   float bv[TM_UN];
   tmLoadW(bv, Wg, nC, sBeg, lc, Kt);
   // what the epilogue reads from memory: requested here, used behind the products (lstm_tm_fwd_kernel)
@@ -552,6 +587,10 @@ __global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, i
   const int stepsE = a.tmSteps[eB], TE = a.tmT[eB];
   float wrE = 0.f, brE = 0.f;
   if (L.hasRes && eC < L.resW) { wrE = a.W[L.indWr + eC]; brE = a.W[L.indBr + eC]; }
+  float pE = 0.f;      // (read for the samples that have the step only: tmLstmForward)
+  if constexpr (WIN) if (win && eOk && b0 + eRow < a.B && stepsE > k) pE = a.tmP[((long long)eB * a.K + k) * nC + eC];
+  if (win) tmStageA<true, true>(sA, lds, a, L, L.A + nIn, L.ldA, Kt, Kt4, b0, k, tid);
+  else
   tmStageA<false>(sA, lds, a, L, nullptr, 0, Kt, Kt4, b0, k, tid);
   __syncthreads();
   if (!tmAnyActive(sAct)) return;
@@ -562,11 +601,14 @@ __global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, i
   if (!eOk || !sAct[row]) return;
   const long long r = (long long)b * a.K + k;
   auto part = [&](int q) { return sG[((RNN_TM_TILES * q + eTile) * 16 + row) * 17 + cc]; };
-  const float x = biE + ((part(0) + part(1)) + (part(2) + part(3)));
+  float x;
+  if constexpr (WIN) x = biE + (((part(0) + part(1)) + (part(2) + part(3))) + pE); else x = biE + ((part(0) + part(1)) + (part(2) + part(3)));
   const float out = actEval(a.func, x);
   L.X[r * nC + c] = x; L.Y[r * nC + c] = out;
   tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wrE, brE, stepsE, TE);
 }
+__global__ __launch_bounds__(TM_FNT) void rnn_tm_fwd_kernel(RecArgs a, int j0, int k0) { tmRnnForward<false>(a, j0, k0); }
+__global__ __launch_bounds__(TM_FNT) void tm_win_rnn_fwd_kernel(RecArgs a, int j0, int k0) { tmRnnForward<true>(a, j0, k0); }
 // the delta of (layer j, step k, sample b, cell c), BaseLayer::backward (Layer_Base.h:97-113): eTop = error from the block above (same step),
 // eRec = error handed back by step k + 1 (zero at the sample's last step) -- as rnn_backward_kernel forms it
 __device__ __forceinline__ void tmRnnDelta(const RecArgs& a, int j, int k, int b, int c, int T, float eTop, float eRec) {
@@ -599,25 +641,104 @@ __global__ __launch_bounds__(256) void rnn_tm_bwd_kernel(RecArgs a, int j0, int 
   tmFinishTile<tmRnnDelta>(a, j, k, i0, b0 + (tid >> 4), i0 + (tid & 15), sT[tid >> 4], e, e, sArr);
 }
 
+// ---- wide inputs: the first layer's input product of a whole forward pass as ONE launch -------------------------------------------------
+//   P[r][o] = sum_{i < nIn} A0[r][i] W_in[i][o],   o < gates nC,   r = b K + k for b < nB, k < nK
+// (training: every row of the windows; acting: the given steps of one window or of a chunk's agents).  The forward tiles stage the whole
+// operand row of 16 samples in LDS, which bounds nIn + nC; here the rows the prepare launch left in HBM are read in slices of 32
+// columns instead: a workgroup = 64 rows x 64 columns, wavefront w its rows 16 w .. 16 w + 15 over the four column tiles
+// (v_mfma_f32_16x16x4_f32, gemm_tile.h's operand conventions: A element = (row li, k = 4 s + lc), B element = (k = 4 s + lc, column li),
+// result element q = (row 4 lc + q, column li)), the next slice in registers while this one's products run.  An element of P is one chain
+// of MFMAs over i = 0 .. nIn - 1 whatever its row's place in the launch: a window's rows come out the same alone and among others.
+// Nothing behind nIn is read in a row of A (the recurrent part belongs to the chain), nothing behind row nIn of W (W_rec), and rows past
+// nB nK are clamped on the way in and masked on the way out.  Rows of steps a sample does not have are computed from whatever their
+// inputs hold and never read (the forward kernels' epilogues).
+constexpr int WP_T = 64, WP_KC = 32, WP_PA = WP_KC + 4, WP_PB = 80;
+__global__ __launch_bounds__(256) void tm_win_product_kernel(RecArgs a, int nB, int nK) {
+  __shared__ __attribute__((aligned(16))) float sA[WP_T * WP_PA], sB[WP_KC * WP_PB];
+  const RecLayer& L = a.L[0];
+  const int nIn = L.nIn, NO = a.gates * L.nC, nRows = nB * nK;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
+  const int n0 = blockIdx.x * WP_T, m0 = blockIdx.y * WP_T;
+  const float* Wb = a.W + L.indW;
+  // a slice = 64 rows x 32 columns of A (thread: rows tid / 8 and + 32, four columns from 4 (tid % 8)) and 32 rows x 64 columns of W_in
+  // (rows tid / 16 and + 16, four columns from 4 (tid % 16))
+  const int ar0 = tid >> 3, ac = (tid & 7) * 4, wr0 = tid >> 4, wc = (tid & 15) * 4;
+  const float* aRow[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int ri = min(m0 + ar0 + 32 * q, nRows - 1), b = ri / nK, k = ri - b * nK;
+    aRow[q] = L.A + ((size_t)b * a.K + k) * L.ldA;
+  }
+  const bool wIn = n0 + wc < NO;      // (NO is a multiple of 16: a 16-byte piece is inside the row or behind it)
+  f32x4 va[2], vw[2];
+  auto loadSlice = [&](int i0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int x = i0 + ac, i = i0 + wr0 + 16 * q;
+      va[q] = f32x4{0.f, 0.f, 0.f, 0.f}; vw[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (x + 3 < nIn) va[q] = *reinterpret_cast<const f32x4*>(aRow[q] + x);      // (the rows' pitch is a multiple of 16 floats)
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (x + e < nIn) va[q][e] = aRow[q][x + e];
+      }
+      if (wIn && i < nIn) vw[q] = *reinterpret_cast<const f32x4*>(Wb + (size_t)i * NO + n0 + wc);
+    }
+  };
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[4] = {z4, z4, z4, z4};
+  const float* ar = sA + (16 * wave + li) * WP_PA + lc;
+  const float* br = sB + lc * WP_PB + li;
+  loadSlice(0);
+  for (int i0 = 0; i0 < nIn; i0 += WP_KC) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      *reinterpret_cast<f32x4*>(sA + (ar0 + 32 * q) * WP_PA + ac) = va[q];
+      *reinterpret_cast<f32x4*>(sB + (wr0 + 16 * q) * WP_PB + wc) = vw[q];
+    }
+    __syncthreads();
+    if (i0 + WP_KC < nIn) loadSlice(i0 + WP_KC);
+#pragma unroll
+    for (int s = 0; s < WP_KC / 4; ++s) {
+      const float av = ar[4 * s];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, br[4 * s * WP_PB + 16 * t], acc[t], 0, 0, 0);
+    }
+    __syncthreads();      // (the slice's readers are through before the next one is stored)
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int ri = m0 + 16 * wave + 4 * lc + q;
+    if (ri >= nRows) continue;
+    const int b = ri / nK, k = ri - b * nK;
+    float* Pr = a.tmP + ((size_t)b * a.K + k) * NO;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { const int o = n0 + 16 * t + li; if (o < NO) Pr[o] = acc[t][q]; }
+  }
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 static bool tmGatesOk(const RecArgs& a) { return a.gates == 4 || a.gates == 2 || a.gates == 1; }
-static size_t tmFwdLds(const RecLayer& L) { return (size_t)(16 * (((L.nIn + L.nC + 3) & ~3) + TM_LDA) + 8 * 16 * 17) * 4; }
+// (wide inputs -- RecArgs::tmP --: the first layer's tile is the recurrent part of the row alone)
+static size_t tmFwdLds(const RecArgs& a, int j) { const RecLayer& L = a.L[j]; return (size_t)(16 * ((((a.tmP && j == 0 ? 0 : L.nIn) + L.nC + 3) & ~3) + TM_LDA) + 8 * 16 * 17) * 4; }
 static bool tmLayersOk(const RecArgs& a) {
   for (int j = 0; j < a.nL; ++j) {
     const RecLayer& L = a.L[j];
     if (L.nC % 16 || L.indW % 4 || (L.ldA & 3) || (j > 0 && L.nIn != a.L[j - 1].nC)) return false;
     if (a.gates == 2 && a.tmFP[j] == nullptr) return false;
-    if (tmFwdLds(L) > 150 * 1024) return false;
+    if (tmFwdLds(a, j) > 150 * 1024) return false;
   }
+  // the input product: raw states as the first layer's input (no rows from launches in front), no residual on it (its epilogue would read
+  // the input part of a staged row), 16-byte pieces of the operand rows, nothing wider than the bound hl_create states
+  if (a.tmP && (a.Xin != nullptr || a.L[0].hasRes || (a.L[0].ldA & 15) || a.L[0].nIn > TM_WIN_MAX_IN || a.L[0].nC > 1024)) return false;
   return true;
 }
 // acting (one window of a.actSteps given states, or with the per-agent tables a.B windows of up to a.actSteps) through the same launches:
-// used where a layer is wider than the per-sample kernels hold
+// used where a layer is wider than the per-sample kernels hold, or the input wider than they stage (tmP)
 bool rec_tm_act_ok(const RecArgs& a) {
   const bool many = a.actOff != nullptr && a.actCnt != nullptr;
   if ((a.actOff != nullptr) != (a.actCnt != nullptr) || (many ? a.B < 1 || a.actSteps > a.nBPTT + 1 : a.B != 1)) return false;
   if (!tmGatesOk(a) || a.actStates == nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
-  bool wide = false;
+  bool wide = a.tmP != nullptr;
   for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > 256;
   return wide && tmLayersOk(a);
 }
@@ -630,22 +751,41 @@ bool rec_tm_ok(const RecArgs& a) {
 template <class Launch>
 static hipError_t tmForwardDiagonals(const RecArgs& a, int kLast, const void* kernel, int tiles, Launch launch) {
   size_t ldsMax = 0;
-  for (int j = 0; j < a.nL; ++j) ldsMax = std::max(ldsMax, tmFwdLds(a.L[j]));
+  for (int j = 0; j < a.nL; ++j) ldsMax = std::max(ldsMax, tmFwdLds(a, j));
   hipError_t e = ensureDynLds(kernel, ldsMax); if (e != hipSuccess) return e;
   for (int d = 0; d <= kLast + a.nL - 1; ++d) {
     const int jLo = std::max(0, d - kLast), jHi = std::min(a.nL - 1, d);
     int gx = 0; size_t lds = 0;
-    for (int j = jLo; j <= jHi; ++j) { gx = std::max(gx, a.L[j].nC / 16); lds = std::max(lds, tmFwdLds(a.L[j])); }
+    for (int j = jLo; j <= jHi; ++j) { gx = std::max(gx, a.L[j].nC / 16); lds = std::max(lds, tmFwdLds(a, j)); }
     launch(dim3((gx + tiles - 1) / tiles, (a.B + 15) / 16, jHi - jLo + 1), lds, jLo, d - jLo);
   }
   return hipGetLastError();
 }
-hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s) {
+// parts: TM_PART_*, for a caller that times them apart; one call with all of them is the pass
+hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s, int parts) {
   const bool acting = a.actStates != nullptr;
   const int kLast = acting ? a.actSteps - 1 : a.nBPTT + 1;
-  if (acting && a.actOff) hipLaunchKernelGGL(lstm_tm_prepare_acts_kernel, dim3(a.B, a.actSteps), dim3(256), 0, s, a);
-  else if (acting) hipLaunchKernelGGL(lstm_tm_prepare_act_kernel, dim3(1), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(lstm_tm_prepare_kernel, dim3(a.B, a.K), dim3(256), 0, s, a);
+  if (parts & TM_PART_PREPARE) {
+    if (acting && a.actOff) hipLaunchKernelGGL(lstm_tm_prepare_acts_kernel, dim3(a.B, a.actSteps), dim3(256), 0, s, a);
+    else if (acting) hipLaunchKernelGGL(lstm_tm_prepare_act_kernel, dim3(1), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(lstm_tm_prepare_kernel, dim3(a.B, a.K), dim3(256), 0, s, a);
+  }
+  if (a.tmP && (parts & TM_PART_PRODUCT)) {      // wide inputs: W_in's part of every row's gate sums, in front of the chain
+    const int nB = acting && !a.actOff ? 1 : a.B, nK = acting ? a.actSteps : a.K;
+    hipLaunchKernelGGL(tm_win_product_kernel, dim3((a.gates * a.L[0].nC + WP_T - 1) / WP_T, (nB * nK + WP_T - 1) / WP_T), dim3(256), 0, s, a, nB, nK);
+  }
+  if (!(parts & TM_PART_CHAIN)) return hipGetLastError();
+  if (a.tmP) {      // ... and the kernels whose first layer takes it from there
+    if (a.gates == 2) return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(tm_win_mgu_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
+      for (int ph = 0; ph < 2; ++ph) hipLaunchKernelGGL(tm_win_mgu_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0, ph);
+    });
+    if (a.gates == 1) return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(tm_win_rnn_fwd_kernel), RNN_TM_TILES, [&](dim3 g, size_t lds, int jLo, int k0) {
+      hipLaunchKernelGGL(tm_win_rnn_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0);
+    });
+    return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(tm_win_lstm_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
+      hipLaunchKernelGGL(tm_win_lstm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0);
+    });
+  }
   if (a.gates == 2) return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(mgu_tm_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
     for (int ph = 0; ph < 2; ++ph) hipLaunchKernelGGL(mgu_tm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0, ph);
   });

@@ -188,6 +188,8 @@ int buildProblems(hl_learner* h) {
     {   // scratch of the split problems (shared by both minibatch buffers: steps are sequential)
       size_t need = 0; sb.splitMaxMN = 0;
       for (int i = 0; i < sb.dwCount; ++i) { const GemmProblem& q = P[sb.dwIdx + i]; if (q.nSplit > 1) { const int mn = q.flavor == RED_COL ? q.N : q.M * q.N; need += (size_t)q.nSplit * mn; sb.splitMaxMN = std::max(sb.splitMaxMN, mn); } }
+      // (wide inputs: the first layer's gradient is up to 8192 + 1024 + 1 rows of up to 4096 columns per chunk of window rows; 4 GB of partials at most)
+      if (h->wideIn && need > ((size_t)1 << 30)) return fail(h, HL_ERR_UNSUPPORTED, "wide recurrent input: the weight-gradient partials (row chunks x (input + cells + 1) x gates x cells) exceed 2^30 floats");
       if (need > h->splitPartFloats) { if (h->splitPart) hipFree(h->splitPart); h->splitPart = nullptr; HIPCK(devAlloc(&h->splitPart, need)); h->splitPartFloats = need; }
       size_t off = 0;
       for (int i = 0; i < sb.dwCount; ++i) { GemmProblem& q = P[sb.dwIdx + i]; if (q.nSplit > 1) { q.part = h->splitPart + off; off += (size_t)q.nSplit * (q.flavor == RED_COL ? q.N : q.M * q.N); } }
@@ -835,6 +837,7 @@ RecArgs recArgs(hl_learner* h, int parity, int seg = -1) {
   ra.K = h->recK; ra.nBPTT = h->recWin - 1; ra.W = h->W; ra.gates = h->hid[jBeg].lstm; ra.func = h->cfg.nnFunc; ra.nApp = (j0 || seg == 1) ? 0 : h->nApp;
   for (int j = jBeg; j < jEnd; ++j) ra.L[j - jBeg] = h->rec[j];
   if (h->recTm && seg < 0) { ra.tmT = h->tmT; ra.tmSteps = h->tmSteps; ra.tmNext = h->tmNext; for (int j = jBeg; j < jEnd; ++j) { ra.tmER[j - jBeg] = h->tmER[j]; ra.tmSD[j - jBeg] = h->tmSD[j]; ra.tmFP[j - jBeg] = h->tmFP[j]; ra.tmCtrOff[j - jBeg] = h->tmCtrOff[j]; ra.tmET[j - jBeg] = h->tmET[j]; } ra.tmCtr = h->tmCtr; ra.tmCtrN = h->tmCtrN; }
+  if (h->recTm && h->wideIn && seg < 0) ra.tmP = h->tmP;      // wide inputs: the first layer's input product has a launch of its own
   if (seg == 1) { ra.Xin = h->segY; ra.ldXin = h->ldSeg; }
   else if (j0) { ra.Xin = h->hid[0].Y; ra.ldXin = h->hid[0].ldA; }
   if (seg == 0) { ra.YoutRows = h->segY; ra.ldYR = h->ldSeg; ra.DresRows = h->segDres; ra.ldDR = h->ldSeg; }
@@ -869,6 +872,11 @@ int launchMlp(hl_learner* h, int parity, bool fuseAdam, hipStream_t s) {
         return launchBackward(h, parity, fuseAdam, s);
       }
     }
+    if (ra.tmP && rec_tm_ok(ra)) {      // wide inputs: the same launches in the same order, the product timed apart from the chain (tools/wide_in_timing.py)
+      HIPCK(timed(h, "rec_prepare", s, [&] { return launch_rec_tm_forward(ra, s, TM_PART_PREPARE); }));
+      HIPCK(timed(h, "rec_in_product", s, [&] { return launch_rec_tm_forward(ra, s, TM_PART_PRODUCT); }));
+      HIPCK(timed(h, "rec_forward", s, [&] { return launch_rec_tm_forward(ra, s, TM_PART_CHAIN); }));
+    } else
     HIPCK(timed(h, "rec_forward", s, [&] { return launch_rec_forward(ra, s); }));
     int rc = launchHead(h, parity, s); if (rc) return rc;
     HIPCK(timed(h, "rec_backward", s, [&] { return launch_rec_backward(ra, s); }));
@@ -1120,7 +1128,8 @@ bool graphUsable(const hl_learner* h, int U, int p0) {
   if (U == 999 && p0 != 0) return false;
   // time-step-major recurrent layers: 2 (LSTM) or 4 (MGU) launches per layer and window step.  The runtime instantiated 83 k nodes in a
   // chain (999 steps of 2 LSTM layers, 18 window steps) and died on 156 k (the same with MGU layers): 64 k nodes at most
-  if (h->recTm && (long long)U * (h->recK * h->cfg.n_hidden * (h->cfg.nn_type == HL_NN_MGU ? 4 : 2) + 12) > 65536) return false;
+  // (wide inputs: one launch more per step, the first layer's input product)
+  if (h->recTm && (long long)U * (h->recK * h->cfg.n_hidden * (h->cfg.nn_type == HL_NN_MGU ? 4 : 2) + 12 + (h->wideIn ? 1 : 0)) > 65536) return false;
   return true;
 }
 
