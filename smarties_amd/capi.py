@@ -549,6 +549,14 @@ class Learner:
         self._ck(self.api.fn("timing_get")(self.h, kernel.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def debug_rec_route(self, backward=False):
+        """The kernel the recurrent layers' training launches take, template arguments included (development entry hl_debug_rec_route)."""
+        f = self.api.lib.hl_debug_rec_route
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32]
+        buf = C.create_string_buffer(256)
+        self._ck(f(self.h, int(backward), buf, 256))
+        return buf.value.decode()
+
     def kernel_profile(self, which, reps=200):
         """Average microseconds per launch of one kernel of the step (see hl_kernel_profile)."""
         us = C.c_double()

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
+#include <string>
 #include <utility>
 #include "hl_types.h"
 
@@ -109,6 +110,7 @@ hipError_t launch_rec_backward(const RecArgs& a, hipStream_t s);
 bool rec_tm_ok(const RecArgs& a);                                     // rectm.hip serves this net: a launch per (layer, window step) over the whole minibatch
 bool rec_tm_act_ok(const RecArgs& a);                                 // ... and this acting window, or these B agents' windows (layers beyond 256 cells)
 bool rec_win_act_ok(const RecArgs& a);                                // rec.hip's workgroup-per-sample kernels serve this acting window, or these B agents' windows (one workgroup each)
+std::string rec_route_name(const RecArgs& a, bool backward);          // the kernel launch_rec_forward / launch_rec_backward take for this net, template arguments included
 hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s, int parts = TM_PART_ALL);
 hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s);
 // window forward + output layer + head + back-propagation through time of a sample as ONE launch (rec.hip: lstm32_step_wave_kernel)

@@ -127,6 +127,18 @@ extern "C" HL_API int64_t hl_debug_graph_kernels(hl_learner* h, int32_t steps) {
   }
   return -1;
 }
+// which kernel the recurrent layers' window forward / back-propagation through time take for this learner's training launches, as text
+// (rec.hip: rec_route_name, e.g. "lstm_forward_lds_kernel<3, 0>"; a stack of two layer types: "lower + upper"); tests pin the shapes
+// that reach each instantiation
+extern "C" HL_API int hl_debug_rec_route(hl_learner* h, int32_t backward, char* buf, int32_t n) {
+  if (!h || !buf || n < 1) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  if (!h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, "no recurrent layers");
+  const std::string name = h->recSplit ? rec_route_name(recArgs(h, 0, 0), backward != 0) + " + " + rec_route_name(recArgs(h, 0, 1), backward != 0)
+                                       : rec_route_name(recArgs(h, 0), backward != 0);
+  std::snprintf(buf, (size_t)n, "%s", name.c_str());
+  return HL_OK;
+}
 // sets every arrive counter of the in-kernel panel barriers to `value` (tests: the counters are monotonic and wrap; the barrier's
 // target arithmetic must survive that).  A barrier's group adds HT per launch to its counter, so only multiples of HT are states
 // the kernels can meet: anything else is refused.

@@ -10,7 +10,18 @@
 // (sample, step) row, the operands of the weight-gradient contractions -- inputs [in | previous output] and the four
 // gate deltas -- so that all weight gradients (and Adam) are formed by the same dW kernel as for dense layers, as
 // X^T delta over the rows; rows of unused steps carry zero deltas.
-#include "head_rows.h"      // (tail_dev.h; the head of the one-launch step: lstm32_step_wave_kernel)
+//
+// Three families of kernels, each folded onto __device__ __forceinline__ pieces that stand once:
+//   workgroup per sample   rec_*, lstm_*_lds, mgu_*, rnn_* (below): every net the other two do not take.  Pieces: stage8, recCols /
+//                          recLdsFloats / recStageWeights / RecWeights (one layout of [W_in; W_rec]), recCopyLayers, RecWin, recLoadParams,
+//                          recPreloadStates / recStateOf / recFirstInput, recStoreOperandRow, recBlockOutput, recStoreYout, recZeroRows,
+//                          recTopError, recResidualBack, recErrorRows, lstmCellDeltas
+//   wavefront per (sample, layer)   two layers of 32 cells (wave32*, lstm32*, mgu32*), alone or as the one-launch step
+//   time-step-major        rectm.hip
+// Which kernel a net gets is decided in ONE place, recRoute() near the end of this file; rec_route_name() prints it.
+#include <cstdio>
+#include <string>
+#include "head_rows.h"     // (tail_dev.h; the head of the one-launch step: lstm32_step_wave_kernel)
 #include "rec_dev.h"
 
 namespace hl {
@@ -32,31 +43,217 @@ __device__ __forceinline__ void ldsBarrier() { asm volatile("s_waitcnt lgkmcnt(0
 __device__ __forceinline__ void vmDrain() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // vmcnt(0), expcnt / lgkmcnt untouched
 
 
-// weights of all LSTM layers staged in LDS with a padded row stride (4 nC + 1: the forward pass reads columns, the backward
-// pass rows, both conflict-free); nets that do not fit read them through the L2 (ldsW = 0)
-__device__ __forceinline__ void recStageWeights(const RecArgs& a, float* sW, int tid) {
+// ---- pieces of the workgroup-per-sample kernels (rec_*, lstm_*_lds, mgu_*, rnn_*: every net the specialised kernels further down do
+// not take).  Each stands once.  A kernel keeps what is its own: its LDS arrays, its split of the gates over threads, its gate sums and
+// cell, and its barriers -- no piece holds an ldsBarrier() or the vmDrain() of the prologue. ----
+// copy loop with eight loads in flight per thread, then eight stores (a rolled loop pays one L2 / HBM round trip per element: 50 in a
+// row at 32 cells); load(e) / store(e, value) of elements e < total
+template <class T, class Load, class Store>
+__device__ __forceinline__ void stage8(int total, Load load, Store store) {
+  for (int e0 = threadIdx.x; e0 < total; e0 += 256 * 8) {
+    T v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; v[u] = T{}; if (e < total) v[u] = load(e); }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; if (e < total) store(e, v[u]); }
+  }
+}
+// Layout of [W_in; W_rec] (rec_*, mgu_*, rnn_*), stated once for the staging loop, the kernels' accessor and the launcher's byte count:
+// rows of recCols() floats in global memory (the gate columns; "RNN" layers: the dense layers' pitch roundUp(cells, 8)); the LDS copy
+// of all layers pads every row by one float (the forward pass reads columns, the backward pass rows, both conflict-free), layer behind
+// layer.  Nets whose copy does not fit read the weights through the L2 (LDSW = 0).
+__host__ __device__ __forceinline__ int recCols(int gates, int nC) { return gates == 1 ? (nC + 7) & ~7 : gates * nC; }
+// ... floats of a layer in the LDS copy; first float of layer j (j = nL: the size of the copy)
+__host__ __device__ __forceinline__ int recLayerFloats(int gates, const RecLayer& L) { return (L.nIn + L.nC) * (recCols(gates, L.nC) + 1); }
+__host__ __device__ __forceinline__ int recLdsFloats(const RecArgs& a, int gates, int j) {
+  int off = 0;
+  for (int q = 0; q < j; ++q) off += recLayerFloats(gates, a.L[q]);
+  return off;
+}
+__device__ __forceinline__ void recStageWeights(const RecArgs& a, int gates, float* sW) {
   int off = 0;
   for (int j = 0; j < a.nL; ++j) {
     const RecLayer& L = a.L[j];
-    const int NO = a.gates * L.nC, rows = L.nIn + L.nC;
+    const int cols = recCols(gates, L.nC);
     const float* src = a.W + L.indW;
-    // eight loads in flight per thread (a rolled loop pays one L2 / HBM round trip per element: 50 in a row at 32 cells)
-    const int total = rows * NO;
-    for (int e0 = tid; e0 < total; e0 += 256 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; v[u] = e < total ? src[e] : 0.f; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; if (e < total) { const int i = e / NO, o = e - i * NO; sW[off + i * (NO + 1) + o] = v[u]; } }
-    }
-    off += rows * (NO + 1);
+    stage8<float>((L.nIn + L.nC) * cols, [&](int e) { return src[e]; },
+                  [&](int e, float v) { const int i = e / cols, o = e - i * cols; sW[off + i * (cols + 1) + o] = v; });
+    off += recLayerFloats(gates, L);
   }
 }
-// offset of layer j's weights inside the LDS copy
-__device__ __forceinline__ int recLdsOffset(const RecArgs& a, int j) {
-  int off = 0;
-  for (int q = 0; q < j; ++q) off += (a.L[q].nIn + a.L[q].nC) * (a.gates * a.L[q].nC + 1);
-  return off;
+// element (i, o) of layer j's [W_in; W_rec]: the LDS copy or global memory, decided at compile time
+template <bool LDSW>
+struct RecWeights {
+  const float* base; int ld;
+  __device__ __forceinline__ RecWeights(const RecArgs& a, const float* sW, int gates, int j, const RecLayer& L)
+    : base(LDSW ? sW + recLdsFloats(a, gates, j) : a.W + L.indW), ld(recCols(gates, L.nC) + (LDSW ? 1 : 0)) {}
+  __device__ __forceinline__ float operator()(int i, int o) const { if constexpr (LDSW) return base[i * ld + o]; else return base[(size_t)i * ld + o]; }
+};
+// layer descriptors copied out of the kernel-argument segment once (inside the step loops every field access was a scalar load of its
+// own).  LL is indexed inside unrolled loops only: a run-time index puts the whole array on the stack (976 bytes of scratch per lane in
+// lstm_backward_lds_kernel<0> until round 5) -- the pieces below take the one layer, or the arrays by reference.
+template <int MAXL>
+__device__ __forceinline__ void recCopyLayers(const RecArgs& a, RecLayer (&LL)[MAXL]) {
+#pragma unroll
+  for (int j = 0; j < MAXL; ++j) LL[j] = a.L[j];
+}
+// Sample b's window: steps t - T .. t and, behind a truncated episode end, step t + 1 (output row nextRow).  Acting (MemoryBuffer::
+// agentToMinibatch, MemoryBuffer.cpp:440-467): the agent's last `actWin` steps, from a zero recurrent state.
+struct RecWinGeo { int t, T, nextRow, nSteps; long long slot; };
+__device__ __forceinline__ RecWinGeo recWindowGeo(const RecArgs& a, int b, bool acting, int actWin) {
+  RecWinGeo g;
+  g.t = acting ? 0 : a.bt.t[b]; g.slot = acting ? 0 : a.bt.slot[b];
+  g.T = acting ? actWin - 1 : min(a.nBPTT, g.t);
+  g.nextRow = acting ? -1 : a.bt.nextOf[b];
+  g.nSteps = g.T + 1 + (g.nextRow >= 0 ? 1 : 0);
+  return g;
+}
+// ... of workgroup b of the forward kernels (acting: the one agent's window or, MANY, agent b's of the per-agent tables)
+template <bool MANY>
+struct RecWin : RecWinGeo {
+  RecActWin<MANY> aw; bool acting;
+  __device__ __forceinline__ RecWin(const RecArgs& a, int b) : aw(a, b), acting(a.actStates != nullptr) { static_cast<RecWinGeo&>(*this) = recWindowGeo(a, b, acting, aw.win(a)); }
+};
+// this thread's parameters per layer, requested in the prologue (they must land ahead of vmDrain()): the bias of gate column `tid`
+// (GATES columns per cell) and the residual weight and bias of cell `tid`; backward: the residual weight alone
+template <int GATES, int MAXL>
+__device__ __forceinline__ void recLoadParams(const RecArgs& a, int nL, float (&bias)[MAXL], float (&wr)[MAXL], float (&br)[MAXL]) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < MAXL; ++j) {
+    bias[j] = 0.f; wr[j] = 0.f; br[j] = 0.f;
+    if (j < nL) {
+      const RecLayer& L = a.L[j];
+      if (tid < GATES * L.nC) bias[j] = a.W[L.indB + tid];
+      if (L.hasRes && tid < L.resW) { wr[j] = a.W[L.indWr + tid]; br[j] = a.W[L.indBr + tid]; }
+    }
+  }
+}
+template <int MAXL>
+__device__ __forceinline__ void recLoadResWeights(const RecLayer* L, const float* W, int nL, float (&wr)[MAXL]) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < MAXL; ++j) { wr[j] = 0.f; if (j < nL && L[j].hasRes && tid < L[j].resW) wr[j] = W[L[j].indWr + tid]; }
+}
+// The first layer's input.  plain: a step's input is that step's observed state (no rows of a convolutional stack, no appended
+// observations; GENERAL = 0: the kernel is launched for nothing else); preload: the standardised states of the whole window
+// (Episode::standardizedState, Episode.h:172-183) sit in sStates, fetched in one round -- where they fit REC_STATES (PRELOAD = 0: the
+// kernel has no sStates); otherwise component `tid` of each step is fetched when its step comes, with this thread's mean and scale.
+struct RecIn { bool plain, preload; int dIn; float sMean, sScale; };
+template <bool GENERAL, bool PRELOAD, bool MANY>
+__device__ __forceinline__ RecIn recPreloadStates(const RecArgs& a, const RecWin<MANY>& win, float* sStates) {
+  const int tid = threadIdx.x;
+  RecIn in; in.dIn = a.L[0].nIn;
+  in.plain = !GENERAL || (a.Xin == nullptr && a.nApp == 0);
+  in.preload = PRELOAD && in.plain && win.nSteps * a.dS <= REC_STATES;
+  if constexpr (PRELOAD) if (in.preload) for (int e = tid; e < win.nSteps * a.dS; e += 256) {
+    const int kk = e / a.dS, i = e - kk * a.dS;
+    const float raw = win.acting ? win.aw.states(a)[e] : a.rp.S[(size_t)(win.slot - win.T + kk) * a.dS + i];
+    sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
+  }
+  in.sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f; in.sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
+  return in;
+}
+// standardised state component `tid` of step k (threads tid < dS)
+template <bool MANY>
+__device__ __forceinline__ float recStateOf(const RecArgs& a, const RecWin<MANY>& win, const RecIn& in, const float* sStates, int k) {
+  const int tid = threadIdx.x;
+  if (in.preload) return sStates[k * a.dS + tid];
+  const float raw = win.acting ? win.aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(win.slot - win.T + k) * a.dS + tid];
+  return (raw - in.sMean) * in.sScale;
+}
+// step k's input of the first layer into dst
+template <bool MANY>
+__device__ __forceinline__ void recFirstInput(const RecArgs& a, const RecWin<MANY>& win, const RecIn& in, const float* sStates, int b, int k, float* dst) {
+  const int tid = threadIdx.x;
+  if (!in.plain) { for (int e = tid; e < in.dIn; e += 256) dst[e] = recInputAtWin<MANY>(a, win.acting, win.aw, b, win.slot, win.t, win.T, win.nextRow, k, e); }
+  else if (tid < a.dS) dst[tid] = recStateOf(a, win, in, sStates, k);
+}
+// row r of the dW operand [input | previous output] (zero at the window's first step)
+__device__ __forceinline__ void recStoreOperandRow(const RecLayer& L, long long r, const float* in, const float* prevOut, int k) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < L.nIn; i += 256) L.A[r * L.ldA + i] = in[i];
+  if (tid < L.nC) L.A[r * L.ldA + L.nIn + tid] = k > 0 ? prevOut[tid] : 0.f;
+}
+// ParametricResidualLayer::forward (Layers.h:347-361): the block's output for cell c, whose layer output is `out` and whose block input in[c]
+__device__ __forceinline__ float recBlockOutput(const RecLayer& L, float out, const float* in, float wr, float br, int c) {
+  float blk = out;
+  if (L.hasRes && c < L.resW) blk += in[c] * wr + br;
+  return blk;
+}
+// component c of the last block's output at step k (*v, read where it is stored): the head's input row at the sampled step (k = T) and at the next state (k = T + 1)
+// or -- ROWS: the lower segment of a two-type stack -- every step's, as an input row of the segment above
+template <bool ROWS, bool MANY>
+__device__ __forceinline__ void recStoreYout(const RecArgs& a, const RecWin<MANY>& win, int b, int k, int c, const float* v) {
+  if (ROWS && a.YoutRows) {
+    const long long ro = k <= win.T ? (long long)b * a.K + k : (long long)a.B * a.K + (win.nextRow - a.B);
+    a.YoutRows[ro * a.ldYR + c] = *v;
+  } else {
+    if (k == win.T) a.Yout[(size_t)b * a.ldY + c] = *v;
+    if (k == win.T + 1) a.Yout[(size_t)win.nextRow * a.ldY + c] = *v;
+  }
+}
+// backward: rows of the steps this sample does not have get zero deltas (their stale inputs then add nothing to the gradients)
+__device__ __forceinline__ void recZeroRows(const RecArgs& a, int nL, int gates, int b, int T) {
+  const int tid = threadIdx.x;
+  for (int k = T + 1; k < a.K; ++k) {
+    const long long r = (long long)b * a.K + k;
+    for (int j = 0; j < nL; ++j) {
+      const RecLayer& L = a.L[j];
+      for (int o = tid; o < gates * L.nC; o += 256) L.D[r * gates * L.nC + o] = 0.f;
+      if (L.hasRes && tid < L.nC) L.Rd[r * L.ldR + tid] = 0.f;
+    }
+  }
+}
+// error w.r.t. component c of the last block's output at step k (row r): the head's at the sampled step or -- ROWS -- the upper segment's of every step
+template <bool ROWS>
+__device__ __forceinline__ float recTopError(const RecArgs& a, int b, long long r, int k, int T, int c) {
+  if (ROWS && a.DresRows) return a.DresRows[r * a.ldDR + c];
+  return k == T ? a.Dres[(size_t)b * a.ldD + c] : 0.f;
+}
+// ParametricResidualLayer::backward (Layers.h:363-393): the delta passes to the layer's output, and through w to the block input (threads tid < nC)
+__device__ __forceinline__ void recResidualBack(const RecLayer& L, long long r, float eTop, float wr, float* sRes) {
+  const int tid = threadIdx.x;
+  if (L.hasRes) { L.Rd[r * L.ldR + tid] = eTop; sRes[tid] = tid < L.resW ? eTop * wr : 0.f; }
+}
+// Layer::backward (Layers.h:123-188): one row of [W_in; W_rec] (nCols delta columns) per group of four lanes, each lane its columns in
+// ascending order, quarter sums joined by two shuffles.  Rows 0..nIn-1 give the error of the block below (skipped under the first
+// layer), rows nIn.. the error handed to step k - 1.  QUADS: nCols is a multiple of 4 (the four gates of LSTM cells), so all lanes walk
+// the same number of columns -- a loop on a scalar counter, unrolled by 8; otherwise a lane's own count, left to the compiler (measured
+// on the 24-cell encoder of pomdp_rnn24_mgu2x16_b128_bptt5: unrolled by 8 its six terms per lane all run in the remainder loop, 14.1 -> 14.6 us).
+template <bool QUADS, class Weights>
+__device__ __forceinline__ void recErrorRows(const RecLayer& L, const Weights& w, int j, int k, int nCols, const float* sD, const float* sRes, float* topBelow, float* recNew) {
+  const int tid = threadIdx.x, part = tid & 3, nIn = L.nIn, row0 = j > 0 ? 0 : nIn, nRow = nIn + (k > 0 ? L.nC : 0);
+  for (int i0 = row0; i0 < nRow; i0 += 64) {
+    const int i = i0 + (tid >> 2);
+    float e = 0.f;
+    if (i < nRow) {
+      if constexpr (QUADS) {
+#pragma unroll 8
+        for (int u = 0; u < nCols / 4; ++u) { const int o = 4 * u + part; e += w(i, o) * sD[o]; }
+      } else for (int o = part; o < nCols; o += 4) e += w(i, o) * sD[o];
+    }
+    e += __shfl_xor(e, 1, 64); e += __shfl_xor(e, 2, 64);
+    if (part == 0 && i < nRow) {
+      if (i < nIn) topBelow[i] = (L.hasRes && i < L.resW ? sRes[i] : 0.f) + e;
+      else recNew[i - nIn] = e;
+    }
+  }
+}
+// LSTMLayer::backward (Layer_LSTM.h:127-165) of cell `tid` at step k (row r): D the error w.r.t. its output, the step's stored
+// activations, prevSt the state of step k - 1; deltas into sD and the row of L.D, the state delta and forget gate kept for step k - 1
+__device__ __forceinline__ void lstmCellDeltas(const RecLayer& L, long long r, int k, int T, float D, float cellInpt, float IG, float FG, float OG, float co,
+                                               float prevSt, float* sD, float* nxtSt, float* nxtF) {
+  const int tid = threadIdx.x, nC = L.nC, NO = 4 * nC;
+  const float diff = (1.f - co * co) * D;
+  const float sd = diff * OG + (k < T ? nxtSt[tid] * nxtF[tid] : 0.f);
+  const float d0 = IG * sd;
+  const float d1 = IG * (1.f - IG) * cellInpt * sd;
+  const float d2 = k > 0 ? FG * (1.f - FG) * prevSt * sd : 0.f;
+  const float d3 = OG * (1.f - OG) * D * co;
+  sD[tid] = d0; sD[nC + tid] = d1; sD[2 * nC + tid] = d2; sD[3 * nC + tid] = d3;
+  L.D[r * NO + tid] = d0; L.D[r * NO + nC + tid] = d1; L.D[r * NO + 2 * nC + tid] = d2; L.D[r * NO + 3 * nC + tid] = d3;
+  nxtSt[tid] = sd; nxtF[tid] = FG;
 }
 
 #ifdef REC_STAMPS
@@ -67,6 +264,10 @@ __device__ unsigned long long recStamps[256];
 #else
 #define REC_STAMP(sample, thread, i) do {} while (0)
 #endif
+// rec_forward_kernel keeps the body it had before the pieces above were cut out of the other seven kernels: written with them it computes the
+// same bits, but its <false, false> form (weights through the L2: an LSTM layer behind convolutions, conv2_lstm32_b64_bptt4 of bench.py) came
+// out 2 us per launch slower (97.3 -> 99.3 us; 1362 -> 1473 reloads of spilled scalars in its unrolled eight-layer body), beyond the
+// parent's own spread.  It shares the layout (recStageWeights, recLdsFloats) and nothing else.
 template <bool LDSW, bool MANY>
 __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sW[];
@@ -89,7 +290,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
 #pragma unroll
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) LL[j] = a.L[j];
   REC_STAMP(blockIdx.x, 0, 1);
-  if constexpr (LDSW) recStageWeights(a, sW, tid);
+  if constexpr (LDSW) recStageWeights(a, 4, sW);
   REC_STAMP(blockIdx.x, 0, 2);
   float bias[HL_MAX_HIDDEN], wr[HL_MAX_HIDDEN], br[HL_MAX_HIDDEN];      // this thread's gate bias / residual parameters per layer
 #pragma unroll
@@ -132,7 +333,7 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
       const int nIn = L.nIn, nC = L.nC, NO = 4 * nC;
       const float* in = sBuf[cur];
       // element (i, o) of [W_in; W_rec] of this layer: LDS copy (padded rows) or global memory, decided at compile time
-      const int ldw = LDSW ? NO + 1 : NO, wOff = LDSW ? recLdsOffset(a, j) : 0;
+      const int ldw = LDSW ? NO + 1 : NO, wOff = LDSW ? recLdsFloats(a, 4, j) : 0;
       const float* gWj = W + L.indW;
       auto wAt = [&](int i, int o) -> float { if constexpr (LDSW) return sW[wOff + i * ldw + o]; else return gWj[(size_t)i * ldw + o]; };
       if (store) {
@@ -190,10 +391,11 @@ __global__ __launch_bounds__(256) void rec_forward_kernel(RecArgs a) {
 //   * the four gates of a cell sit in neighbouring lanes, so the cell update gathers them by shuffles instead of LDS + barrier:
 //     ONE barrier per layer-step, none per step (the next step's state is written into the idle copy during the step).
 // Sums are formed in a different order than in the oracle (four partial sums per lane, bias last): 1e-7-level differences.
-struct LstmGeo { int inPad, recPad, nT, ld; };
+// layout of a layer's transposed copy: padded input / recurrent parts, floats per gate row, row pitch, floats of the layer
+struct LstmGeo { int inPad, recPad, nT, ld, floats; };
 __host__ __device__ __forceinline__ LstmGeo lstmGeo(int nIn, int nC) {
   LstmGeo g; g.inPad = (nIn + 3) & ~3; g.recPad = (nC + 3) & ~3; g.nT = g.inPad + g.recPad + 4;
-  g.ld = ((g.nT >> 2) & 1) ? g.nT : g.nT + 4;
+  g.ld = ((g.nT >> 2) & 1) ? g.nT : g.nT + 4; g.floats = 4 * nC * g.ld;
   return g;
 }
 #define LSTM_VEC (REC_MAXIN + REC_MAXC + 8)
@@ -208,40 +410,24 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
   __shared__ float sStates[REC_STATES];
   const int b = blockIdx.x, tid = threadIdx.x;
   REC_STAMP(blockIdx.x, 0, 0);
-  const bool acting = a.actStates != nullptr;
-  const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
-  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
-  const int nextRow = acting ? -1 : a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
+  const RecWin<MANY> win(a, b);
   const float* W = a.W;
   RecLayer LL[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) LL[j] = a.L[j];
+  recCopyLayers(a, LL);
   REC_STAMP(blockIdx.x, 0, 1);
   // weights, transposed (coalesced 16-byte global reads along the gates of one input row, scattered LDS writes)
   {
     int off = 0;
     for (int j = 0; j < nL; ++j) {
       const RecLayer& L = a.L[j];
-      const int nIn = L.nIn, nC = NC ? NC : L.nC, NO = 4 * nC, rows = nIn + nC, q4 = nC;          // q4: float4 per row (NO / 4)
+      const int nIn = L.nIn, nC = NC ? NC : L.nC, NO = 4 * nC, q4 = nC;          // q4: float4 per row (NO / 4)
       const LstmGeo g = lstmGeo(nIn, nC);
       const float4* src = reinterpret_cast<const float4*>(W + L.indW);                  // (indW is a multiple of 4: checked by the launcher)
-      const int total = rows * q4;
-      for (int e0 = tid; e0 < total; e0 += 256 * 8) {
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; v[u] = src[e < total ? e : 0]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int e = e0 + 256 * u;
-          if (e < total) {
-            const int i = e / q4, o = 4 * (e - i * q4), ti = i < nIn ? i : g.inPad + (i - nIn);
-            float* d = sW + off + o * g.ld + ti;
-            d[0] = v[u].x; d[g.ld] = v[u].y; d[2 * g.ld] = v[u].z; d[3 * g.ld] = v[u].w;
-          }
-        }
-      }
+      stage8<float4>((nIn + nC) * q4, [&](int e) { return src[e]; }, [&](int e, const float4& v) {
+        const int i = e / q4, o = 4 * (e - i * q4), ti = i < nIn ? i : g.inPad + (i - nIn);
+        float* d = sW + off + o * g.ld + ti;
+        d[0] = v.x; d[g.ld] = v.y; d[2 * g.ld] = v.z; d[3 * g.ld] = v.w;
+      });
       for (int o = tid; o < NO; o += 256) {
         float* d = sW + off + o * g.ld;
         for (int i = nIn; i < g.inPad; ++i) d[i] = 0.f;
@@ -252,7 +438,7 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
         const int c = i / LSTM_VEC, e = i - c * LSTM_VEC;
         sA[j][c][e] = e == g.nT - 4 ? 1.f : 0.f;
       }
-      off += NO * g.ld;
+      off += g.floats;
     }
   }
   REC_STAMP(blockIdx.x, 0, 2);
@@ -268,27 +454,16 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
       if (L.hasRes && c < L.resW && c < nCj) { wr[j] = W[L.indWr + c]; br[j] = W[L.indBr + c]; }
     }
   }
-  const bool preload = nSteps * a.dS <= REC_STATES;
-  if (preload) for (int e = tid; e < nSteps * a.dS; e += 256) {
-    const int kk = e / a.dS, i = e - kk * a.dS;
-    const float raw = acting ? aw.states(a)[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
-    sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
-  }
-  const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
-  auto stateOf = [&](int k) -> float {     // standardised state component `tid` of step k (Episode::standardizedState, Episode.h:172-183)
-    if (preload) return sStates[k * a.dS + tid];
-    const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(slot - T + k) * a.dS + tid];
-    return (raw - sMean) * sScale;
-  };
+  const RecIn in0 = recPreloadStates<false, true>(a, win, sStates);
   vmDrain(); ldsBarrier();
-  if (tid < a.dS) sA[0][0][tid] = stateOf(0);
+  if (tid < a.dS) sA[0][0][tid] = recStateOf(a, win, in0, sStates, 0);
   ldsBarrier();
   REC_STAMP(blockIdx.x, 0, 3);
-  for (int k = 0; k < nSteps; ++k) {
-    const bool store = !acting && k <= T;
+  for (int k = 0; k < win.nSteps; ++k) {
+    const bool store = !win.acting && k <= win.T;
     const long long r = (long long)b * a.K + k;
     const int cb = k & 1;
-    if (k + 1 < nSteps && tid < a.dS) sA[0][cb ^ 1][tid] = stateOf(k + 1);             // (that copy was last read a step ago)
+    if (k + 1 < win.nSteps && tid < a.dS) sA[0][cb ^ 1][tid] = recStateOf(a, win, in0, sStates, k + 1);   // (that copy was last read a step ago)
     REC_STAMP(blockIdx.x, 0, 4 + k * 5);
     int off = 0;
 #pragma unroll
@@ -337,18 +512,14 @@ __global__ __launch_bounds__(256) void lstm_forward_lds_kernel(RecArgs a) {
         const float out = x3 * co;
         prevSt[j] = st;
         if (store) { L.Y[r * NO + c] = out; L.Y[r * NO + nC + c] = st; L.Y[r * NO + 2 * nC + c] = co; }
-        float blk = out;                                   // ParametricResidualLayer::forward (Layers.h:347-361)
-        if (L.hasRes && c < L.resW) blk += vec[c] * wr[j] + br[j];
+        const float blk = recBlockOutput(L, out, vec, wr[j], br[j], c);
         sA[j][cb ^ 1][g.inPad + c] = out;                  // recurrent input of the next step
         if (j + 1 < nL) sA[j + 1][cb][c] = blk;
-        else {
-          if (k == T) a.Yout[(size_t)b * a.ldY + c] = blk;
-          if (k == T + 1) a.Yout[(size_t)nextRow * a.ldY + c] = blk;
-        }
+        else recStoreYout<false>(a, win, b, k, c, &blk);
       }
       ldsBarrier();
       if (j < 2) REC_STAMP(blockIdx.x, 0, 4 + k * 5 + 2 + 2 * j);
-      off += NO * g.ld;
+      off += g.floats;
     }
   }
   REC_STAMP(blockIdx.x, 0, 250);
@@ -362,33 +533,18 @@ __global__ __launch_bounds__(256) void rec_backward_kernel(RecArgs a) {
   __shared__ float sNxtSt[HL_MAX_HIDDEN][REC_GENC], sNxtF[HL_MAX_HIDDEN][REC_GENC];
   __shared__ float sD[4 * REC_GENC], sRes[REC_GENC], sRecNew[REC_GENC];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int t = a.bt.t[b];
-  const int T = min(a.nBPTT, t);
-  const float* W = a.W;
-  // layer descriptors copied out of the kernel-argument segment once (inside the step loops every field access was a scalar
-  // load of its own)
+  const int T = min(a.nBPTT, a.bt.t[b]);
   RecLayer LL[HL_MAX_HIDDEN];
-#pragma unroll
-  for (int j = 0; j < HL_MAX_HIDDEN; ++j) LL[j] = a.L[j];
-  if constexpr (LDSW) recStageWeights(a, sW, tid);
+  recCopyLayers(a, LL);
+  if constexpr (LDSW) recStageWeights(a, 4, sW);
   float wr[HL_MAX_HIDDEN];
-#pragma unroll
-  for (int j = 0; j < HL_MAX_HIDDEN; ++j) { wr[j] = 0.f; if (j < a.nL && a.L[j].hasRes && tid < a.L[j].resW) wr[j] = W[a.L[j].indWr + tid]; }
+  recLoadResWeights(a.L, a.W, a.nL, wr);
   vmDrain(); ldsBarrier();
-  // rows of the steps this sample does not have: zero deltas (their stale inputs then add nothing to the gradients)
-  for (int k = T + 1; k < a.K; ++k) {
-    const long long r = (long long)b * a.K + k;
-    for (int j = 0; j < a.nL; ++j) {
-      const RecLayer& L = a.L[j];
-      for (int o = tid; o < 4 * L.nC; o += 256) L.D[r * 4 * L.nC + o] = 0.f;
-      if (L.hasRes && tid < L.nC) L.Rd[r * L.ldR + tid] = 0.f;
-    }
-  }
+  recZeroRows(a, a.nL, 4, b, T);
   for (int k = T; k >= 0; --k) {
     const long long r = (long long)b * a.K + k;
     int cur = 0;
-    const int nCl = a.L[a.nL - 1].nC;
-    if (tid < nCl) sTop[0][tid] = k == T ? a.Dres[(size_t)b * a.ldD + tid] : 0.f;
+    if (tid < a.L[a.nL - 1].nC) sTop[0][tid] = recTopError<false>(a, b, r, k, T, tid);
     // this step's stored activations of every layer, fetched in one round
     float vCo[HL_MAX_HIDDEN], vCi[HL_MAX_HIDDEN], vIG[HL_MAX_HIDDEN], vFG[HL_MAX_HIDDEN], vOG[HL_MAX_HIDDEN], vPs[HL_MAX_HIDDEN];
 #pragma unroll
@@ -405,64 +561,32 @@ __global__ __launch_bounds__(256) void rec_backward_kernel(RecArgs a) {
 #pragma unroll
     for (int j = HL_MAX_HIDDEN - 1; j >= 0; --j) if (j < a.nL) {
       const RecLayer& L = LL[j];
-      const int nIn = L.nIn, nC = L.nC, NO = 4 * nC;
-      const int ldw = LDSW ? NO + 1 : NO, wOff = LDSW ? recLdsOffset(a, j) : 0;
-      const float* gWj = W + L.indW;
-      auto wAt = [&](int i, int o) -> float { if constexpr (LDSW) return sW[wOff + i * ldw + o]; else return gWj[(size_t)i * ldw + o]; };
-      if (tid < nC) {
+      const RecWeights<LDSW> w(a, sW, 4, j, L);
+      if (tid < L.nC) {
         const float eTop = sTop[cur][tid];
-        // ParametricResidualLayer::backward (Layers.h:363-393): the delta passes to the LSTM output, and through w to the block input
-        if (L.hasRes) { L.Rd[r * L.ldR + tid] = eTop; sRes[tid] = tid < L.resW ? eTop * wr[j] : 0.f; }
+        recResidualBack(L, r, eTop, wr[j], sRes);
         const float D = eTop + (k < T ? sRec[j][tid] : 0.f);
-        // LSTMLayer::backward (Layer_LSTM.h:127-165)
-        const float co = vCo[j];
-        const float cellInpt = vCi[j], IG = vIG[j], FG = vFG[j], OG = vOG[j];
-        const float diff = (1.f - co * co) * D;
-        const float sd = diff * OG + (k < T ? sNxtSt[j][tid] * sNxtF[j][tid] : 0.f);
-        const float d0 = IG * sd;
-        const float d1 = IG * (1.f - IG) * cellInpt * sd;
-        const float d2 = k > 0 ? FG * (1.f - FG) * vPs[j] * sd : 0.f;
-        const float d3 = OG * (1.f - OG) * D * co;
-        sD[tid] = d0; sD[nC + tid] = d1; sD[2 * nC + tid] = d2; sD[3 * nC + tid] = d3;
-        L.D[r * NO + tid] = d0; L.D[r * NO + nC + tid] = d1; L.D[r * NO + 2 * nC + tid] = d2; L.D[r * NO + 3 * nC + tid] = d3;
-        sNxtSt[j][tid] = sd; sNxtF[j][tid] = FG;
+        lstmCellDeltas(L, r, k, T, D, vCi[j], vIG[j], vFG[j], vOG[j], vCo[j], vPs[j], sD, sNxtSt[j], sNxtF[j]);
       }
       ldsBarrier();
-      // Layer::backward (Layers.h:123-188): errors to the block below (not below the first layer) and to the previous step
-      // one row of [W_in; W_rec] per group of four lanes (quarter sums joined by two shuffles): rows 0..nIn-1 give the error
-      // of the block below (skipped under the first layer), rows nIn.. the error handed to the previous step
-      {
-        const int part = tid & 3, row0 = j > 0 ? 0 : nIn, nRow = nIn + (k > 0 ? nC : 0);
-        for (int i0 = row0; i0 < nRow; i0 += 64) {
-          const int i = i0 + (tid >> 2);
-          float e = 0.f;
-          if (i < nRow) {
-#pragma unroll 8
-            for (int u = 0; u < NO / 4; ++u) { const int o = 4 * u + part; e += wAt(i, o) * sD[o]; }
-          }
-          e += __shfl_xor(e, 1, 64); e += __shfl_xor(e, 2, 64);
-          if (part == 0 && i < nRow) {
-            if (i < nIn) sTop[cur ^ 1][i] = (L.hasRes && i < L.resW ? sRes[i] : 0.f) + e;
-            else sRecNew[i - nIn] = e;
-          }
-        }
-      }
+      recErrorRows<true>(L, w, j, k, 4 * L.nC, sD, sRes, sTop[cur ^ 1], sRecNew);
       ldsBarrier();
-      if (tid < nC) sRec[j][tid] = k > 0 ? sRecNew[tid] : 0.f;
+      if (tid < L.nC) sRec[j][tid] = k > 0 ? sRecNew[tid] : 0.f;
       cur ^= 1;
     }
     ldsBarrier();
   }
 }
 
-// ---- MGU layers (Network/Layers/Layer_GRU.h): forget = sigm(Wff in + Wfr prevOut + bf), state = tanh(Wsf in + Wsr (forget * prevOut)
-// + bs), output = forget * state + (1 - forget) * prevOut.  Same structure as the LSTM kernels: one workgroup per sample. ----
 // ---- LSTM back-propagation through the window, weights AND the window's stored activations resident in LDS ----------------
 // Same findings as for the forward kernel; in addition the per-step reads of the stored gates sat behind the acknowledgement
 // of the previous step's delta stores (one in-order memory counter).  Here the gates and states of the whole window are
 // fetched once into LDS, so the step loop only stores; [W_in; W_rec] rows have a pitch of 16 (mod 64) floats so that the
 // 16-byte reads of four rows x four lanes touch every bank once; two barriers per layer-step instead of three.
+// layout: per layer its rows at lstmBwdPitch(), layer behind layer; behind them, per step, 6 floats per cell of every layer
 __host__ __device__ __forceinline__ int lstmBwdPitch(int NO) { return NO + ((16 - NO % 64) + 64) % 64; }
+__host__ __device__ __forceinline__ int lstmBwdFloats(int nIn, int nC) { return (nIn + nC) * lstmBwdPitch(4 * nC); }
+__host__ __device__ __forceinline__ int lstmBwdActFloats(int nC) { return 6 * nC; }
 template <int NL>
 __global__ __launch_bounds__(256) void lstm_backward_lds_kernel(RecArgs a) {
   constexpr int MAXL = NL ? NL : HL_MAX_HIDDEN;
@@ -474,12 +598,9 @@ __global__ __launch_bounds__(256) void lstm_backward_lds_kernel(RecArgs a) {
   __shared__ __attribute__((aligned(16))) float sD[4 * REC_MAXC];
   __shared__ float sRes[REC_MAXC];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int t = a.bt.t[b];
-  const int T = min(a.nBPTT, t);
-  const float* W = a.W;
+  const int T = min(a.nBPTT, a.bt.t[b]);
   RecLayer LL[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) LL[j] = a.L[j];
+  recCopyLayers(a, LL);
   // weights: rows of [W_in; W_rec] as in global memory, padded pitch
   int wOffs[MAXL], aOffs[MAXL];
   int off = 0, actPitch = 0;
@@ -488,58 +609,32 @@ __global__ __launch_bounds__(256) void lstm_backward_lds_kernel(RecArgs a) {
     wOffs[j] = off; aOffs[j] = actPitch;
     if (j < nL) {
       const RecLayer& L = LL[j];
-      const int nC = L.nC, NO = 4 * nC, rows = L.nIn + nC, ldb = lstmBwdPitch(NO), total = rows * nC;
-      const float4* src = reinterpret_cast<const float4*>(W + L.indW);
-      for (int e0 = tid; e0 < total; e0 += 256 * 8) {
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; v[u] = src[e < total ? e : 0]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int e = e0 + 256 * u;
-          if (e < total) { const int i = e / nC, q = e - i * nC; *reinterpret_cast<float4*>(sW + off + i * ldb + 4 * q) = v[u]; }
-        }
-      }
-      off += rows * ldb; actPitch += 6 * nC;
+      const int nC = L.nC, ldb = lstmBwdPitch(4 * nC);
+      const float4* src = reinterpret_cast<const float4*>(a.W + L.indW);
+      stage8<float4>((L.nIn + nC) * nC, [&](int e) { return src[e]; },
+                     [&](int e, const float4& v) { const int i = e / nC, q = e - i * nC; *reinterpret_cast<float4*>(sW + off + i * ldb + 4 * q) = v; });
+      off += lstmBwdFloats(L.nIn, nC); actPitch += lstmBwdActFloats(nC);
     }
   }
   // stored activations of the window, per (step, layer): [cell input | input, forget, output gate | state | tanh(state)]
   float* sAct = sW + off;
-  {
-    const int total = (T + 1) * actPitch;
-    for (int e0 = tid; e0 < total; e0 += 256 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + 256 * u, ee = e < total ? e : 0, k = ee / actPitch, q = ee - k * actPitch;
-        const long long r = (long long)b * a.K + k;
-        const float* p = nullptr;
-#pragma unroll
-        for (int j = 0; j < MAXL; ++j) if (j < nL && q >= aOffs[j] && q < aOffs[j] + 6 * LL[j].nC) {
-          const int x = q - aOffs[j], nC = LL[j].nC;
-          p = x < 4 * nC ? LL[j].X + r * 4 * nC + x : LL[j].Y + r * 4 * nC + nC + (x - 4 * nC);
-        }
-        v[u] = *p;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; if (e < total) sAct[e] = v[u]; }
-    }
-  }
-  float wr[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) { wr[j] = 0.f; if (j < nL && LL[j].hasRes && tid < LL[j].resW) wr[j] = W[LL[j].indWr + tid]; }
-  const int nCl = a.L[nL - 1].nC;      // (from the arguments: a run-time index into LL would put the whole array on the stack -- 976 bytes of scratch per lane in the any-depth variant until round 5)
-  const float dres = tid < nCl ? a.Dres[(size_t)b * a.ldD + tid] : 0.f;
-  vmDrain(); ldsBarrier();
-  // rows of the steps this sample does not have: zero deltas (their stale inputs then add nothing to the gradients)
-  for (int k = T + 1; k < a.K; ++k) {
+  stage8<float>((T + 1) * actPitch, [&](int e) {
+    const int k = e / actPitch, q = e - k * actPitch;
     const long long r = (long long)b * a.K + k;
-    for (int j = 0; j < nL; ++j) {
-      const RecLayer& L = a.L[j];
-      if (tid < 4 * L.nC) L.D[r * 4 * L.nC + tid] = 0.f;
-      if (L.hasRes && tid < L.nC) L.Rd[r * L.ldR + tid] = 0.f;
+    const float* p = nullptr;
+#pragma unroll
+    for (int j = 0; j < MAXL; ++j) if (j < nL && q >= aOffs[j] && q < aOffs[j] + 6 * LL[j].nC) {
+      const int x = q - aOffs[j], nC = LL[j].nC;
+      p = x < 4 * nC ? LL[j].X + r * 4 * nC + x : LL[j].Y + r * 4 * nC + nC + (x - 4 * nC);
     }
-  }
+    return *p;
+  }, [&](int e, float v) { sAct[e] = v; });
+  float wr[MAXL];
+  recLoadResWeights(LL, a.W, nL, wr);
+  const int nCl = a.L[nL - 1].nC;      // (from the arguments: a run-time index into LL would put the whole array on the stack)
+  const float dres = tid < nCl ? recTopError<false>(a, b, 0, T, T, tid) : 0.f;
+  vmDrain(); ldsBarrier();
+  recZeroRows(a, nL, 4, b, T);
   for (int k = T; k >= 0; --k) {
     const long long r = (long long)b * a.K + k;
     int cur = 0;
@@ -548,25 +643,14 @@ __global__ __launch_bounds__(256) void lstm_backward_lds_kernel(RecArgs a) {
 #pragma unroll
     for (int j = MAXL - 1; j >= 0; --j) if (j < nL) {
       const RecLayer& L = LL[j];
-      const int nIn = L.nIn, nC = L.nC, NO = 4 * nC, ldb = lstmBwdPitch(NO);
+      const int nIn = L.nIn, nC = L.nC, ldb = lstmBwdPitch(4 * nC);
       if (tid < nC) {
         const float* act = sAct + k * actPitch + aOffs[j];
         const float eTop = sTop[cur][tid];
-        // ParametricResidualLayer::backward (Layers.h:363-393): the delta passes to the LSTM output, and through w to the block input
-        if (L.hasRes) { L.Rd[r * L.ldR + tid] = eTop; sRes[tid] = tid < L.resW ? eTop * wr[j] : 0.f; }
+        recResidualBack(L, r, eTop, wr[j], sRes);
         const float D = eTop + (k < T ? sRec[j][tid] : 0.f);
-        // LSTMLayer::backward (Layer_LSTM.h:127-165)
-        const float cellInpt = act[tid], IG = act[nC + tid], FG = act[2 * nC + tid], OG = act[3 * nC + tid], co = act[5 * nC + tid];
-        const float prevSt = k > 0 ? (act - actPitch)[4 * nC + tid] : 0.f;
-        const float diff = (1.f - co * co) * D;
-        const float sd = diff * OG + (k < T ? sNxtSt[j][tid] * sNxtF[j][tid] : 0.f);
-        const float d0 = IG * sd;
-        const float d1 = IG * (1.f - IG) * cellInpt * sd;
-        const float d2 = k > 0 ? FG * (1.f - FG) * prevSt * sd : 0.f;
-        const float d3 = OG * (1.f - OG) * D * co;
-        sD[tid] = d0; sD[nC + tid] = d1; sD[2 * nC + tid] = d2; sD[3 * nC + tid] = d3;
-        L.D[r * NO + tid] = d0; L.D[r * NO + nC + tid] = d1; L.D[r * NO + 2 * nC + tid] = d2; L.D[r * NO + 3 * nC + tid] = d3;
-        sNxtSt[j][tid] = sd; sNxtF[j][tid] = FG;
+        lstmCellDeltas(L, r, k, T, D, act[tid], act[nC + tid], act[2 * nC + tid], act[3 * nC + tid], act[5 * nC + tid],
+                       k > 0 ? (act - actPitch)[4 * nC + tid] : 0.f, sD, sNxtSt[j], sNxtF[j]);
       }
       ldsBarrier();
       // Layer::backward (Layers.h:123-188): one row of [W_in; W_rec] per group of four lanes, 16-byte chunks of the row and of
@@ -606,6 +690,8 @@ __global__ __launch_bounds__(256) void lstm_backward_lds_kernel(RecArgs a) {
   }
 }
 
+// ---- MGU layers (Network/Layers/Layer_GRU.h): forget = sigm(Wff in + Wfr prevOut + bf), state = tanh(Wsf in + Wsr (forget * prevOut)
+// + bs), output = forget * state + (1 - forget) * prevOut.  Same structure as the LSTM kernels: one workgroup per sample. ----
 template <bool LDSW, int NL, bool MANY>
 __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
   constexpr int MAXL = NL ? NL : HL_MAX_HIDDEN;
@@ -616,47 +702,19 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
   __shared__ float sF[REC_GENC], sS[REC_GENC];
   __shared__ float sStates[REC_STATES];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const bool acting = a.actStates != nullptr;
-  const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
-  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
-  const int nextRow = acting ? -1 : a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
+  const RecWin<MANY> win(a, b);
   const float* W = a.W;
-  // layer descriptors copied out of the kernel-argument segment once (inside the step loops every field access was a scalar
-  // load of its own)
   RecLayer LL[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) LL[j] = a.L[j];
-  if constexpr (LDSW) recStageWeights(a, sW, tid);
+  recCopyLayers(a, LL);
+  if constexpr (LDSW) recStageWeights(a, 2, sW);
   float bias[MAXL], wr[MAXL], br[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) {
-    bias[j] = 0.f; wr[j] = 0.f; br[j] = 0.f;
-    if (j < nL) {
-      const RecLayer& L = a.L[j];
-      if (tid < 2 * L.nC) bias[j] = W[L.indB + tid];
-      if (L.hasRes && tid < L.resW) { wr[j] = W[L.indWr + tid]; br[j] = W[L.indBr + tid]; }
-    }
-  }
-  const int dIn = a.L[0].nIn;
-  const bool plain = a.Xin == nullptr && a.nApp == 0;      // the input of a step is that step's observed state
-  const bool preload = plain && nSteps * a.dS <= REC_STATES;
-  if (preload) for (int e = tid; e < nSteps * a.dS; e += 256) {
-    const int kk = e / a.dS, i = e - kk * a.dS;
-    const float raw = acting ? aw.states(a)[e] : a.rp.S[(size_t)(slot - T + kk) * a.dS + i];
-    sStates[e] = (raw - a.rp.stMean[i]) * a.rp.stScale[i];
-  }
-  const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
+  recLoadParams<2>(a, nL, bias, wr, br);
+  const RecIn in0 = recPreloadStates<true, true>(a, win, sStates);
   vmDrain(); ldsBarrier();
-  for (int k = 0; k < nSteps; ++k) {
-    const bool store = !acting && k <= T;
+  for (int k = 0; k < win.nSteps; ++k) {
+    const bool store = !win.acting && k <= win.T;
     const long long r = (long long)b * a.K + k;
-    if (!plain) { for (int e = tid; e < dIn; e += 256) sBuf[0][e] = recInputAtWin<MANY>(a, acting, aw, b, slot, t, T, nextRow, k, e); }
-    else if (tid < a.dS) {
-      if (preload) sBuf[0][tid] = sStates[k * a.dS + tid];
-      else { const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)(slot - T + k) * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
-    }
+    recFirstInput(a, win, in0, sStates, b, k, sBuf[0]);
     ldsBarrier();
     int cur = 0;
 #pragma unroll
@@ -664,22 +722,17 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
       const RecLayer& L = LL[j];
       const int nIn = L.nIn, nC = L.nC, NO = 2 * nC;
       const float* in = sBuf[cur];
-      const int ldw = LDSW ? NO + 1 : NO, wOff = LDSW ? recLdsOffset(a, j) : 0;
-      const float* gWj = W + L.indW;
-      auto wAt = [&](int i, int o) -> float { if constexpr (LDSW) return sW[wOff + i * ldw + o]; else return gWj[(size_t)i * ldw + o]; };
-      if (store) {
-        for (int i = tid; i < nIn; i += 256) L.A[r * L.ldA + i] = in[i];
-        if (tid < nC) L.A[r * L.ldA + nIn + tid] = k > 0 ? sPrevOut[j][tid] : 0.f;
-      }
+      const RecWeights<LDSW> w(a, sW, 2, j, L);
+      if (store) recStoreOperandRow(L, r, in, sPrevOut[j], k);
       // (one gate per thread up to 128 cells, two at 256; the state gates' input sums wait in sS for the forget gates)
       for (int o = tid; o < NO; o += 256) {
         float acc = o == tid ? bias[j] : W[L.indB + o];
 #pragma unroll 8
-        for (int i = 0; i < nIn; ++i) acc += in[i] * wAt(i, o);
+        for (int i = 0; i < nIn; ++i) acc += in[i] * w(i, o);
         if (o < nC) {          // forget gate
           if (k > 0) {
 #pragma unroll 8
-            for (int i = 0; i < nC; ++i) acc += wAt(nIn + i, o) * sPrevOut[j][i];
+            for (int i = 0; i < nC; ++i) acc += w(nIn + i, o) * sPrevOut[j][i];
           }
           acc = recSigm(acc);
           sF[o] = acc;
@@ -691,7 +744,7 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
         float acc = sS[o - nC];
         if (k > 0) {
 #pragma unroll 8
-          for (int i = 0; i < nC; ++i) acc += wAt(nIn + i, o) * sPrevOut[j][i] * sF[i];
+          for (int i = 0; i < nC; ++i) acc += w(nIn + i, o) * sPrevOut[j][i] * sF[i];
         }
         acc = actEval(HL_FUNC_TANH, acc);
         sS[o - nC] = acc;
@@ -703,17 +756,13 @@ __global__ __launch_bounds__(256) void mgu_forward_kernel(RecArgs a) {
         const float f = sF[tid], st = sS[tid], po = k > 0 ? sPrevOut[j][tid] : 0.f;
         out = k > 0 ? f * st + (1.f - f) * po : f * st;
         if (store) { L.Y[r * NO + tid] = out; L.A2[r * L.ldA2 + tid] = po * f; }
-        float blk = out;
-        if (L.hasRes && tid < L.resW) blk += in[tid] * wr[j] + br[j];
-        sBuf[cur ^ 1][tid] = blk;
+        sBuf[cur ^ 1][tid] = recBlockOutput(L, out, in, wr[j], br[j], tid);
       }
       ldsBarrier();
       if (tid < nC) sPrevOut[j][tid] = out;
       cur ^= 1;
     }
-    const int nCl = a.L[nL - 1].nC;
-    if (k == T && tid < nCl) a.Yout[(size_t)b * a.ldY + tid] = sBuf[cur][tid];
-    if (k == T + 1 && tid < nCl) a.Yout[(size_t)nextRow * a.ldY + tid] = sBuf[cur][tid];
+    if (tid < a.L[nL - 1].nC) recStoreYout<false>(a, win, b, k, tid, &sBuf[cur][tid]);
     ldsBarrier();
   }
 }
@@ -727,32 +776,18 @@ __global__ __launch_bounds__(256) void mgu_backward_kernel(RecArgs a) {
   __shared__ float sRec[MAXL][REC_GENC];          // dLdprevOut handed from step k+1 to step k
   __shared__ float sDF[REC_GENC], sDS[REC_GENC], sFP[REC_GENC], sRes[REC_GENC];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int t = a.bt.t[b];
-  const int T = min(a.nBPTT, t);
-  const float* W = a.W;
-  // layer descriptors copied out of the kernel-argument segment once (inside the step loops every field access was a scalar
-  // load of its own)
+  const int T = min(a.nBPTT, a.bt.t[b]);
   RecLayer LL[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) LL[j] = a.L[j];
-  if constexpr (LDSW) recStageWeights(a, sW, tid);
+  recCopyLayers(a, LL);
+  if constexpr (LDSW) recStageWeights(a, 2, sW);
   float wr[MAXL];
-#pragma unroll
-  for (int j = 0; j < MAXL; ++j) { wr[j] = 0.f; if (j < nL && a.L[j].hasRes && tid < a.L[j].resW) wr[j] = W[a.L[j].indWr + tid]; }
+  recLoadResWeights(a.L, a.W, nL, wr);
   vmDrain(); ldsBarrier();
-  for (int k = T + 1; k < a.K; ++k) {
-    const long long r = (long long)b * a.K + k;
-    for (int j = 0; j < nL; ++j) {
-      const RecLayer& L = a.L[j];
-      for (int o = tid; o < 2 * L.nC; o += 256) L.D[r * 2 * L.nC + o] = 0.f;
-      if (L.hasRes && tid < L.nC) L.Rd[r * L.ldR + tid] = 0.f;
-    }
-  }
+  recZeroRows(a, nL, 2, b, T);
   for (int k = T; k >= 0; --k) {
     const long long r = (long long)b * a.K + k;
     int cur = 0;
-    const int nCl = a.L[nL - 1].nC;
-    if (tid < nCl) sTop[0][tid] = k == T ? a.Dres[(size_t)b * a.ldD + tid] : 0.f;
+    if (tid < a.L[nL - 1].nC) sTop[0][tid] = recTopError<false>(a, b, r, k, T, tid);
     float vF[MAXL], vS[MAXL], vP[MAXL];
 #pragma unroll
     for (int j = 0; j < MAXL; ++j) {
@@ -768,13 +803,11 @@ __global__ __launch_bounds__(256) void mgu_backward_kernel(RecArgs a) {
     for (int j = MAXL - 1; j >= 0; --j) if (j < nL) {
       const RecLayer& L = LL[j];
       const int nIn = L.nIn, nC = L.nC, NO = 2 * nC;
-      const int ldw = LDSW ? NO + 1 : NO, wOff = LDSW ? recLdsOffset(a, j) : 0;
-      const float* gWj = W + L.indW;
-      auto wAt = [&](int i, int o) -> float { if constexpr (LDSW) return sW[wOff + i * ldw + o]; else return gWj[(size_t)i * ldw + o]; };
+      const RecWeights<LDSW> w(a, sW, 2, j, L);
       float dLdO = 0.f;
       if (tid < nC) {
         const float eTop = sTop[cur][tid];
-        if (L.hasRes) { L.Rd[r * L.ldR + tid] = eTop; sRes[tid] = tid < L.resW ? eTop * wr[j] : 0.f; }
+        recResidualBack(L, r, eTop, wr[j], sRes);
         dLdO = eTop + (k < T ? sRec[j][tid] : 0.f);
         sDS[tid] = dLdO * vF[j] * (1.f - vS[j] * vS[j]);                         // 1) dLdS
       }
@@ -782,7 +815,7 @@ __global__ __launch_bounds__(256) void mgu_backward_kernel(RecArgs a) {
       float fp = 0.f;
       if (tid < nC && k > 0) {                                                   // 2) dLdFprevOut = Wsr dLdS
 #pragma unroll 8
-        for (int o = 0; o < nC; ++o) fp += wAt(nIn + tid, nC + o) * sDS[o];
+        for (int o = 0; o < nC; ++o) fp += w(nIn + tid, nC + o) * sDS[o];
       }
       if (tid < nC) {
         sFP[tid] = fp;
@@ -794,7 +827,7 @@ __global__ __launch_bounds__(256) void mgu_backward_kernel(RecArgs a) {
       if (j > 0) for (int i = tid; i < nIn; i += 256) {
         float e1 = 0.f, e2 = 0.f;
 #pragma unroll 8
-        for (int o = 0; o < nC; ++o) { e1 += wAt(i, o) * sDF[o]; e2 += wAt(i, nC + o) * sDS[o]; }
+        for (int o = 0; o < nC; ++o) { e1 += w(i, o) * sDF[o]; e2 += w(i, nC + o) * sDS[o]; }
         sTop[cur ^ 1][i] = ((L.hasRes && i < L.resW ? sRes[i] : 0.f) + e1) + e2;
       }
       float rec = 0.f;
@@ -802,7 +835,7 @@ __global__ __launch_bounds__(256) void mgu_backward_kernel(RecArgs a) {
         rec = (1.f - vF[j]) * dLdO + vF[j] * sFP[tid];
         float g = 0.f;
 #pragma unroll 8
-        for (int o = 0; o < nC; ++o) g += wAt(nIn + tid, o) * sDF[o];
+        for (int o = 0; o < nC; ++o) g += w(nIn + tid, o) * sDF[o];
         rec += g;
       }
       ldsBarrier();
@@ -812,6 +845,7 @@ __global__ __launch_bounds__(256) void mgu_backward_kernel(RecArgs a) {
     ldsBarrier();
   }
 }
+
 
 // ---- LSTM, two layers of 32 cells (settings/RACER_RNN.json): ONE WAVEFRONT PER (SAMPLE, LAYER), weights in registers ----------
 // The kernels above spend a layer-step (128 gates x 64 terms = 8 k multiply-adds) mostly on LDS round trips for weights and
@@ -893,12 +927,8 @@ __device__ __forceinline__ void lstm32LayerStep(const RecLayer& L, const f32x2 (
 // sample b's window: steps t - T .. t and, behind a truncated episode end, step t + 1 (output row nextRow); `acting`: the agent's last states
 struct WaveWin { int b, T, nextRow, nSteps; long long slot; };
 __device__ __forceinline__ WaveWin wave32Window(const RecArgs& a, int b, bool acting) {
-  WaveWin win; win.b = b;
-  const int t = acting ? 0 : a.bt.t[b]; win.slot = acting ? 0 : a.bt.slot[b];
-  win.T = acting ? a.actSteps - 1 : min(a.nBPTT, t);
-  win.nextRow = acting ? -1 : a.bt.nextOf[b];
-  win.nSteps = win.T + 1 + (win.nextRow >= 0 ? 1 : 0);
-  return win;
+  const RecWinGeo g = recWindowGeo(a, b, acting, a.actSteps);
+  return WaveWin{b, g.T, g.nextRow, g.nSteps, g.slot};
 }
 // residual scalars of this lane's cell (forward)
 __device__ __forceinline__ void wave32ResScalars(const RecLayer& L, const float* W, int lane, float& wr, float& br) {
@@ -1517,32 +1547,9 @@ __global__ __launch_bounds__(256) void mgu32_step_wave_kernel(RecArgs a, HeadArg
 // ---- nnType "RNN": dense layers with a recurrent term (BaseLayer with bRecurrent; Network/Builder.cpp:76-81,
 // Network/Layers/Layer_Base.h:64-113): x_t = W_in^T in_t + W_rec^T y_{t-1} + b, y_t = f(x_t); weights [W_in; W_rec] row-major with the
 // dense layers' pitch roundUp(cells, 8); backward Layer::backward with NR = cells (Layers.h:123-188).  One workgroup per sample
-// walks the window; the weights of all layers sit in LDS (pitch + 1: the forward pass reads columns, the backward pass rows);
-// a cell's sum is split over the four wavefronts (rows i = wave, wave + 4, ...) and joined in wave order.  Rows kept per
-// (sample, step): [input | previous output] (A operand of the weight gradients), x, y, and the deltas after f'. ----
-__device__ __forceinline__ int rnnPitch(int nC) { return ((nC + 7) & ~7) + 1; }
-__device__ __forceinline__ void rnnStageWeights(const RecArgs& a, float* sW, int tid) {
-  int off = 0;
-  for (int j = 0; j < a.nL; ++j) {
-    const RecLayer& L = a.L[j];
-    const int ld = (L.nC + 7) & ~7, rows = L.nIn + L.nC, pitch = ld + 1;
-    const float* src = a.W + L.indW;
-    const int total = rows * ld;
-    for (int e0 = tid; e0 < total; e0 += 256 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; v[u] = e < total ? src[e] : 0.f; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int e = e0 + 256 * u; if (e < total) { const int i = e / ld, o = e - i * ld; sW[off + i * pitch + o] = v[u]; } }
-    }
-    off += rows * pitch;
-  }
-}
-__device__ __forceinline__ int rnnLdsOffset(const RecArgs& a, int j) {
-  int off = 0;
-  for (int q = 0; q < j; ++q) off += (a.L[q].nIn + a.L[q].nC) * rnnPitch(a.L[q].nC);
-  return off;
-}
+// walks the window; the weights of all layers sit in LDS (recCols(1, cells) + 1 floats per row); a cell's sum is split over the four
+// wavefronts (rows i = wave, wave + 4, ...) and joined in wave order.  Rows kept per (sample, step): [input | previous output] (A
+// operand of the weight gradients), x, y, and the deltas after f'.  The window's states are fetched step by step (no sStates). ----
 template <bool LDSW, bool MANY>
 __global__ __launch_bounds__(256) void rnn_forward_kernel(RecArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sW[];
@@ -1550,52 +1557,31 @@ __global__ __launch_bounds__(256) void rnn_forward_kernel(RecArgs a) {
   __shared__ float sPrevOut[HL_MAX_HIDDEN][REC_GENC];
   __shared__ float sPart[4][REC_GENC];
   const int b = blockIdx.x, tid = threadIdx.x, c0 = tid & 63, part = tid >> 6;
-  const bool acting = a.actStates != nullptr;
-  const int t = acting ? 0 : a.bt.t[b]; const long long slot = acting ? 0 : a.bt.slot[b];
-  const RecActWin<MANY> aw(a, b);      // (acting: the one agent's window or, with the per-agent tables, agent b's)
-  const int T = acting ? aw.win(a) - 1 : min(a.nBPTT, t);
-  const int nextRow = acting ? -1 : a.bt.nextOf[b];
-  const int nSteps = T + 1 + (nextRow >= 0 ? 1 : 0);
-  const float* W = a.W;
-  if constexpr (LDSW) rnnStageWeights(a, sW, tid);
+  const RecWin<MANY> win(a, b);
+  if constexpr (LDSW) recStageWeights(a, 1, sW);
   float bias[HL_MAX_HIDDEN], wr[HL_MAX_HIDDEN], br[HL_MAX_HIDDEN];
-#pragma unroll
-  for (int j = 0; j < HL_MAX_HIDDEN; ++j) {
-    bias[j] = 0.f; wr[j] = 0.f; br[j] = 0.f;
-    if (j < a.nL) {
-      const RecLayer& L = a.L[j];
-      if (tid < L.nC) bias[j] = W[L.indB + tid];
-      if (L.hasRes && tid < L.resW) { wr[j] = W[L.indWr + tid]; br[j] = W[L.indBr + tid]; }
-    }
-  }
-  const float sMean = tid < a.dS ? a.rp.stMean[tid] : 0.f, sScale = tid < a.dS ? a.rp.stScale[tid] : 1.f;
+  recLoadParams<1>(a, a.nL, bias, wr, br);
+  const RecIn in0 = recPreloadStates<true, false>(a, win, nullptr);
   vmDrain(); ldsBarrier();
-  for (int k = 0; k < nSteps; ++k) {
-    const bool store = !acting && k <= T;
+  for (int k = 0; k < win.nSteps; ++k) {
+    const bool store = !win.acting && k <= win.T;
     const long long r = (long long)b * a.K + k;
-    const long long sl = slot - T + k;
-    if (a.Xin != nullptr || a.nApp > 0) { for (int e = tid; e < a.L[0].nIn; e += 256) sBuf[0][e] = recInputAtWin<MANY>(a, acting, aw, b, slot, t, T, nextRow, k, e); }
-    else if (tid < a.dS) { const float raw = acting ? aw.states(a)[(size_t)k * a.dS + tid] : a.rp.S[(size_t)sl * a.dS + tid]; sBuf[0][tid] = (raw - sMean) * sScale; }
+    recFirstInput(a, win, in0, nullptr, b, k, sBuf[0]);
     ldsBarrier();
     int cur = 0;
     for (int j = 0; j < a.nL; ++j) {
       const RecLayer& L = a.L[j];
-      const int nIn = L.nIn, nC = L.nC, ld = (nC + 7) & ~7;
+      const int nIn = L.nIn, nC = L.nC;
       const float* in = sBuf[cur];
-      const int pitch = LDSW ? ld + 1 : ld, wOff = LDSW ? rnnLdsOffset(a, j) : 0;
-      const float* gWj = W + L.indW;
-      auto wAt = [&](int i, int o) -> float { if constexpr (LDSW) return sW[wOff + i * pitch + o]; else return gWj[(size_t)i * pitch + o]; };
-      if (store) {
-        for (int i = tid; i < nIn; i += 256) L.A[r * L.ldA + i] = in[i];
-        if (tid < nC) L.A[r * L.ldA + nIn + tid] = k > 0 ? sPrevOut[j][tid] : 0.f;
-      }
+      const RecWeights<LDSW> w(a, sW, 1, j, L);
+      if (store) recStoreOperandRow(L, r, in, sPrevOut[j], k);
       for (int c = c0; c < nC; c += 64) {       // quarter sums over the rows i = part, part + 4, ...: first the inputs, then the previous outputs
         float acc = 0.f;
 #pragma unroll 4
-        for (int i = part; i < nIn; i += 4) acc += in[i] * wAt(i, c);
+        for (int i = part; i < nIn; i += 4) acc += in[i] * w(i, c);
         if (k > 0) {
 #pragma unroll 4
-          for (int i = part; i < nC; i += 4) acc += sPrevOut[j][i] * wAt(nIn + i, c);
+          for (int i = part; i < nC; i += 4) acc += sPrevOut[j][i] * w(nIn + i, c);
         }
         sPart[part][c] = acc;
       }
@@ -1605,22 +1591,13 @@ __global__ __launch_bounds__(256) void rnn_forward_kernel(RecArgs a) {
         const float x = bias[j] + ((sPart[0][tid] + sPart[1][tid]) + (sPart[2][tid] + sPart[3][tid]));
         out = actEval(a.func, x);
         if (store) { L.X[r * nC + tid] = x; L.Y[r * nC + tid] = out; }
-        float blk = out;                                   // ParametricResidualLayer::forward (Layers.h:347-361)
-        if (L.hasRes && tid < L.resW) blk += in[tid] * wr[j] + br[j];
-        sBuf[cur ^ 1][tid] = blk;
+        sBuf[cur ^ 1][tid] = recBlockOutput(L, out, in, wr[j], br[j], tid);
       }
       ldsBarrier();
       if (tid < nC) sPrevOut[j][tid] = out;
       cur ^= 1;
     }
-    const int nCl = a.L[a.nL - 1].nC;
-    if (a.YoutRows) {      // lower segment of a two-type stack: every step's output is an input row of the segment above
-      const long long ro = k <= T ? (long long)b * a.K + k : (long long)a.B * a.K + (nextRow - a.B);
-      if (tid < nCl) a.YoutRows[ro * a.ldYR + tid] = sBuf[cur][tid];
-    } else {
-    if (k == T && tid < nCl) a.Yout[(size_t)b * a.ldY + tid] = sBuf[cur][tid];
-    if (k == T + 1 && tid < nCl) a.Yout[(size_t)nextRow * a.ldY + tid] = sBuf[cur][tid];
-    }
+    if (tid < a.L[a.nL - 1].nC) recStoreYout<true>(a, win, b, k, tid, &sBuf[cur][tid]);
     ldsBarrier();
   }
 }
@@ -1631,56 +1608,30 @@ __global__ __launch_bounds__(256) void rnn_backward_kernel(RecArgs a) {
   __shared__ float sRec[HL_MAX_HIDDEN][REC_GENC];          // error w.r.t. this step's output coming from step k+1
   __shared__ float sD[REC_GENC], sRes[REC_GENC], sRecNew[REC_GENC];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int t = a.bt.t[b];
-  const int T = min(a.nBPTT, t);
-  const float* W = a.W;
-  if constexpr (LDSW) rnnStageWeights(a, sW, tid);
+  const int T = min(a.nBPTT, a.bt.t[b]);
+  if constexpr (LDSW) recStageWeights(a, 1, sW);
   float wr[HL_MAX_HIDDEN];
-#pragma unroll
-  for (int j = 0; j < HL_MAX_HIDDEN; ++j) { wr[j] = 0.f; if (j < a.nL && a.L[j].hasRes && tid < a.L[j].resW) wr[j] = W[a.L[j].indWr + tid]; }
+  recLoadResWeights(a.L, a.W, a.nL, wr);
   vmDrain(); ldsBarrier();
-  for (int k = T + 1; k < a.K; ++k) {      // rows of the steps this sample does not have: zero deltas
-    const long long r = (long long)b * a.K + k;
-    for (int j = 0; j < a.nL; ++j) {
-      const RecLayer& L = a.L[j];
-      if (tid < L.nC) { L.D[r * L.nC + tid] = 0.f; if (L.hasRes) L.Rd[r * L.ldR + tid] = 0.f; }
-    }
-  }
+  recZeroRows(a, a.nL, 1, b, T);
   for (int k = T; k >= 0; --k) {
     const long long r = (long long)b * a.K + k;
     int cur = 0;
-    const int nCl = a.L[a.nL - 1].nC;
-    if (tid < nCl) sTop[0][tid] = a.DresRows ? a.DresRows[r * a.ldDR + tid] : (k == T ? a.Dres[(size_t)b * a.ldD + tid] : 0.f);
+    if (tid < a.L[a.nL - 1].nC) sTop[0][tid] = recTopError<true>(a, b, r, k, T, tid);
     ldsBarrier();
     for (int j = a.nL - 1; j >= 0; --j) {
       const RecLayer& L = a.L[j];
-      const int nIn = L.nIn, nC = L.nC, ld = (nC + 7) & ~7;
-      const int pitch = LDSW ? ld + 1 : ld, wOff = LDSW ? rnnLdsOffset(a, j) : 0;
-      const float* gWj = W + L.indW;
-      auto wAt = [&](int i, int o) -> float { if constexpr (LDSW) return sW[wOff + i * pitch + o]; else return gWj[(size_t)i * pitch + o]; };
+      const int nC = L.nC;
+      const RecWeights<LDSW> w(a, sW, 1, j, L);
       if (tid < nC) {
         const float eTop = sTop[cur][tid];
-        if (L.hasRes) { L.Rd[r * L.ldR + tid] = eTop; sRes[tid] = tid < L.resW ? eTop * wr[j] : 0.f; }
+        recResidualBack(L, r, eTop, wr[j], sRes);
         const float D = eTop + (k < T ? sRec[j][tid] : 0.f);
         const float d = D * actDiff(a.func, L.X[r * nC + tid], L.Y[r * nC + tid]);     // BaseLayer::backward (Layer_Base.h:97-113)
         sD[tid] = d; L.D[r * nC + tid] = d;
       }
       ldsBarrier();
-      // Layer::backward (Layers.h:123-188): rows 0..nIn-1 of [W_in; W_rec] give the error of the block below (not below the first
-      // layer), rows nIn.. the error handed to the previous step; one row per group of four lanes, quarter sums joined by shuffles
-      {
-        const int part = tid & 3, row0 = j > 0 ? 0 : nIn, nRow = nIn + (k > 0 ? nC : 0);
-        for (int i0 = row0; i0 < nRow; i0 += 64) {
-          const int i = i0 + (tid >> 2);
-          float e = 0.f;
-          if (i < nRow) for (int o = part; o < nC; o += 4) e += wAt(i, o) * sD[o];
-          e += __shfl_xor(e, 1, 64); e += __shfl_xor(e, 2, 64);
-          if (part == 0 && i < nRow) {
-            if (i < nIn) sTop[cur ^ 1][i] = (L.hasRes && i < L.resW ? sRes[i] : 0.f) + e;
-            else sRecNew[i - nIn] = e;
-          }
-        }
-      }
+      recErrorRows<false>(L, w, j, k, nC, sD, sRes, sTop[cur ^ 1], sRecNew);
       ldsBarrier();
       if (tid < nC) sRec[j][tid] = k > 0 ? sRecNew[tid] : 0.f;
       cur ^= 1;
@@ -1688,6 +1639,7 @@ __global__ __launch_bounds__(256) void rnn_backward_kernel(RecArgs a) {
     ldsBarrier();
   }
 }
+
 // Convolutional layers in front of recurrent ones: every step of a sample's window passes through the conv stack, so the conv
 // launches run over B K window rows (+ the truncated next states behind them) instead of B sampled rows.  This kernel writes the
 // row -> (replay slot, step) map in the form stack_gather_kernel / the conv kernels already read: rows r = b K + k < B K hold step
@@ -1710,11 +1662,6 @@ hipError_t launch_window_rows(const WinRowsArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-static size_t rnnLdsBytes(const RecArgs& a) {
-  size_t fl = 0;
-  for (int j = 0; j < a.nL; ++j) fl += (size_t)(a.L[j].nIn + a.L[j].nC) * (((a.L[j].nC + 7) & ~7) + 1);
-  return fl * sizeof(float);
-}
 
 // the wave-per-(sample, layer) kernels serve two LSTM (gates = 4) or MGU (2) layers of 32 cells each over up to 32 inputs and 17 steps
 static bool wave32(const RecArgs& a, int gates) {      // (forward: training windows and rollout inference; backward: training only)
@@ -1737,23 +1684,90 @@ static bool recGeneral(const RecArgs& a) {
   for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > REC_MAXC || a.L[j].nIn > REC_MAXIN;
   return wide || a.Xin != nullptr || a.nApp > 0;
 }
-static size_t recLdsBytes(const RecArgs& a) {
-  size_t fl = 0;
-  for (int j = 0; j < a.nL; ++j) fl += (size_t)(a.L[j].nIn + a.L[j].nC) * (a.gates * a.L[j].nC + 1);
-  return fl * sizeof(float);
+// ---- which kernel a net gets, stated ONCE: the launchers, rec_win_act_ok and rec_route_name read this.  The choice follows from the
+// layers, the input form and K alone -- the two time-step-major predicates are the only rules that read B or the per-agent tables. ----
+enum RecKind { REC_TM, REC_WAVE32, REC_RNN, REC_MGU, REC_LSTM, REC_LSTM_LDS };      // rectm.hip | *32_*_wave_kernel | rnn_* | mgu_* | rec_* | lstm_*_lds
+struct RecRoute { RecKind kind; bool ldsw; int NL, NC; size_t lds; };               // ... its LDSW, NL, NC template arguments; dynamic LDS in bytes
+static RecRoute recRoute(const RecArgs& a, bool backward) {
+  // wide layers: time-step-major on the MFMA; forward also the acting window of nets wider than the kernels here hold
+  if (rec_tm_ok(a) || (!backward && rec_tm_act_ok(a))) return {REC_TM, false, 0, 0, 0};
+  const bool general = recGeneral(a);
+  // two layers of 32 cells: one wavefront per (sample, layer), weights in registers
+  if (a.gates != 1 && !general && (wave32(a, 2) || wave32(a, 4))) return {REC_WAVE32, false, 0, 0, 0};
+  // the one-gate-per-thread kernels, weights in LDS where they fit (their static LDS, up to 46 KB, comes on top; 160 KB per workgroup)
+  const size_t lds = (size_t)recLdsFloats(a, a.gates, a.nL) * sizeof(float); const bool fit = lds <= 100 * 1024;
+  RecRoute r = {a.gates == 1 ? REC_RNN : (a.gates == 2 ? REC_MGU : REC_LSTM), fit, 0, 0, fit ? lds : 0};
+  if (a.gates == 1 || general) return r;
+  if (a.gates == 2) { if (fit && a.nL <= 2) r.NL = a.nL; return r; }
+  // LSTM over the step's own state, up to 64 cells: the kernels with their own LDS layouts, each direction where ITS copy fits
+  size_t fl = 0; bool al = true, same = true;
+  for (int j = 0; j < a.nL; ++j) {
+    const RecLayer& L = a.L[j];
+    fl += backward ? (size_t)lstmBwdFloats(L.nIn, L.nC) + (size_t)a.K * lstmBwdActFloats(L.nC) : (size_t)lstmGeo(L.nIn, L.nC).floats;
+    al = al && L.indW % 4 == 0 && L.nIn <= REC_MAXIN;
+    // (hidden layers above the first take the block below as input; the specialised forward body relies on nIn == cells there)
+    same = same && L.nC == a.L[0].nC && (j == 0 || L.nIn == a.L[0].nC);
+  }
+  if (al && fl * sizeof(float) <= 120 * 1024) {
+    if (!backward && same && a.nL == 2 && a.L[0].nC == 32) return {REC_LSTM_LDS, true, 2, 32, fl * sizeof(float)};      // RACER_RNN.json behind other inputs
+    return {REC_LSTM_LDS, true, a.nL <= 3 ? a.nL : 0, 0, fl * sizeof(float)};
+  }
+  if (!backward) { r.ldsw = false; r.lds = 0; }      // (the forward kernel then reads its weights through the L2; the backward one stages them where they fit)
+  return r;
 }
-template <class K> static hipError_t recLaunch(K kernel, const RecArgs& a, size_t lds, size_t*, hipStream_t s) {
+typedef void (*RecKernel)(RecArgs);
+template <bool MANY> static RecKernel recForwardKernel(const RecRoute& r) {
+  if (r.kind == REC_RNN) { if (r.ldsw) return rnn_forward_kernel<true, MANY>; return rnn_forward_kernel<false, MANY>; }
+  if (r.kind == REC_LSTM) { if (r.ldsw) return rec_forward_kernel<true, MANY>; return rec_forward_kernel<false, MANY>; }
+  if (r.kind == REC_MGU) {
+    if (!r.ldsw) return mgu_forward_kernel<false, 0, MANY>;
+    if (r.NL == 1) return mgu_forward_kernel<true, 1, MANY>;
+    if (r.NL == 2) return mgu_forward_kernel<true, 2, MANY>;
+    return mgu_forward_kernel<true, 0, MANY>;
+  }
+  if (r.NC == 32) return lstm_forward_lds_kernel<2, 32, MANY>;
+  if (r.NL == 1) return lstm_forward_lds_kernel<1, 0, MANY>;
+  if (r.NL == 2) return lstm_forward_lds_kernel<2, 0, MANY>;
+  if (r.NL == 3) return lstm_forward_lds_kernel<3, 0, MANY>;
+  return lstm_forward_lds_kernel<0, 0, MANY>;
+}
+static RecKernel recBackwardKernel(const RecRoute& r) {
+  if (r.kind == REC_RNN) { if (r.ldsw) return rnn_backward_kernel<true>; return rnn_backward_kernel<false>; }
+  if (r.kind == REC_LSTM) { if (r.ldsw) return rec_backward_kernel<true>; return rec_backward_kernel<false>; }
+  if (r.kind == REC_MGU) {
+    if (!r.ldsw) return mgu_backward_kernel<false, 0>;
+    if (r.NL == 1) return mgu_backward_kernel<true, 1>;
+    if (r.NL == 2) return mgu_backward_kernel<true, 2>;
+    return mgu_backward_kernel<true, 0>;
+  }
+  if (r.NL == 1) return lstm_backward_lds_kernel<1>;
+  if (r.NL == 2) return lstm_backward_lds_kernel<2>;
+  if (r.NL == 3) return lstm_backward_lds_kernel<3>;
+  return lstm_backward_lds_kernel<0>;
+}
+// the kernel of this net with its template arguments as text (the forward kernels' last one, the form for the per-agent tables, left out)
+std::string rec_route_name(const RecArgs& a, bool backward) {
+  const RecRoute r = recRoute(a, backward);
+  const char* dir = backward ? "backward" : "forward"; const char* ldsw = r.ldsw ? "true" : "false";
+  char t[96];
+  switch (r.kind) {
+    case REC_TM: snprintf(t, sizeof(t), "launch_rec_tm_%s", dir); break;
+    case REC_WAVE32: snprintf(t, sizeof(t), "%s32_%s_wave_kernel", a.gates == 2 ? "mgu" : "lstm", dir); break;
+    case REC_RNN: snprintf(t, sizeof(t), "rnn_%s_kernel<%s>", dir, ldsw); break;
+    case REC_MGU: snprintf(t, sizeof(t), "mgu_%s_kernel<%s, %d>", dir, ldsw, r.NL); break;
+    case REC_LSTM: snprintf(t, sizeof(t), "rec_%s_kernel<%s>", dir, ldsw); break;
+    case REC_LSTM_LDS: if (backward) snprintf(t, sizeof(t), "lstm_backward_lds_kernel<%d>", r.NL); else snprintf(t, sizeof(t), "lstm_forward_lds_kernel<%d, %d>", r.NL, r.NC); break;
+  }
+  return t;
+}
+static hipError_t recLaunch(RecKernel kernel, const RecArgs& a, size_t lds, hipStream_t s) {
   if (lds > 0) { hipError_t e = ensureDynLds(reinterpret_cast<const void*>(kernel), lds); if (e != hipSuccess) return e; }
   hipLaunchKernelGGL(kernel, dim3(a.B), dim3(256), lds, s, a);
   return hipGetLastError();
 }
-// launch_rec_forward takes one of the wave-per-(sample, layer) kernels for this net
-static bool recWaveForward(const RecArgs& a) { return a.gates != 1 && !recGeneral(a) && (wave32(a, 2) || wave32(a, 4)); }
-// Acting through the workgroup-per-sample kernels whose acting form knows the per-agent tables (rnn_forward_kernel, mgu_forward_kernel,
-// rec_forward_kernel, lstm_forward_lds_kernel): one window of a.actSteps given states (B = 1) or, with actOff / actCnt, the windows of a.B
-// agents, workgroup b walking agent b's.  True exactly where launch_rec_forward picks one of the four: its choice follows from the layers,
-// the input form and K alone -- the two time-step-major predicates are asked for the single-agent call, the only rule among them that
-// reads B or the tables.
+// Acting through the workgroup-per-sample kernels, whose acting form knows the per-agent tables: one window of a.actSteps given states
+// (B = 1) or, with actOff / actCnt, the windows of a.B agents, workgroup b walking agent b's.  True exactly where launch_rec_forward
+// takes one of them; the route is asked for the single-agent call.
 bool rec_win_act_ok(const RecArgs& a) {
   const bool many = a.actOff != nullptr && a.actCnt != nullptr;
   if (a.actStates == nullptr || (a.actOff != nullptr) != (a.actCnt != nullptr) || (many ? a.B < 1 : a.B != 1)) return false;
@@ -1761,46 +1775,20 @@ bool rec_win_act_ok(const RecArgs& a) {
   if (a.gates != 1 && a.YoutRows != nullptr) return false;      // (every step's output as a row: the plain recurrent kernel alone)
   for (int j = 0; j < a.nL; ++j) if (a.L[j].nC > REC_GENC || a.L[j].nIn > REC_GENIN) return false;
   RecArgs one = a; one.B = 1; one.actOff = nullptr; one.actCnt = nullptr;
-  return !rec_tm_ok(one) && !rec_tm_act_ok(one) && !recWaveForward(one);
+  const RecKind kind = recRoute(one, false).kind;
+  return kind != REC_TM && kind != REC_WAVE32;
 }
-// (static LDS of the kernels comes on top of the weights; 160 KB per workgroup)
-// one of the four workgroup-per-sample forward kernels: its form for the per-agent tables where they are given, else the form it had
-#define REC_FWD(lds, kernel, ...) (many ? recLaunch(kernel<__VA_ARGS__, true>, a, lds, nullptr, s) : recLaunch(kernel<__VA_ARGS__, false>, a, lds, nullptr, s))
 hipError_t launch_rec_forward(const RecArgs& a, hipStream_t s) {
-  if (rec_tm_ok(a)) return launch_rec_tm_forward(a, s);      // wide LSTM layers, training windows: time-step-major on the MFMA (rectm.hip)
-  if (rec_tm_act_ok(a)) return launch_rec_tm_forward(a, s);  // ... and the acting window of nets wider than the kernels below hold
-  // (static LDS of the general kernels: up to 46 KB)
-  const bool many = a.actStates != nullptr && a.actCnt != nullptr;
-  const size_t lds = recLdsBytes(a); const bool fit = lds <= 100 * 1024; const bool general = recGeneral(a);
-  if (a.gates == 1) { const size_t l1 = rnnLdsBytes(a); return l1 <= 100 * 1024 ? REC_FWD(l1, rnn_forward_kernel, true) : REC_FWD(0, rnn_forward_kernel, false); }
-  if (general) {
-    if (a.gates == 2) return fit ? REC_FWD(lds, mgu_forward_kernel, true, 0) : REC_FWD(0, mgu_forward_kernel, false, 0);
-    return fit ? REC_FWD(lds, rec_forward_kernel, true) : REC_FWD(0, rec_forward_kernel, false);
-  }
-  if (wave32(a, 2))          // two layers of 32 cells, training pass: one wavefront per (sample, layer), weights in registers
-    return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(mgu32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
-  if (a.gates == 2) {
-    if (fit && a.nL == 1) return REC_FWD(lds, mgu_forward_kernel, true, 1);
-    if (fit && a.nL == 2) return REC_FWD(lds, mgu_forward_kernel, true, 2);
-    return fit ? REC_FWD(lds, mgu_forward_kernel, true, 0) : REC_FWD(0, mgu_forward_kernel, false, 0);
-  }
-  if (wave32(a, 4))          // the same arrangement for LSTM layers
+  const RecRoute r = recRoute(a, false);
+  if (r.kind == REC_TM) return launch_rec_tm_forward(a, s);
+  if (r.kind == REC_WAVE32) {
+    if (a.gates == 2) return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(mgu32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
     return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(lstm32_forward_wave_kernel<decltype(in0)::value>, dim3(a.B), dim3(128), 0, s, a); });
-  size_t fl = 0; bool al = true;
-  for (int j = 0; j < a.nL; ++j) { fl += (size_t)4 * a.L[j].nC * lstmGeo(a.L[j].nIn, a.L[j].nC).ld; al = al && a.L[j].indW % 4 == 0 && a.L[j].nIn <= REC_MAXIN; }
-  if (al && fl * sizeof(float) <= 120 * 1024) {
-    // (hidden layers above the first take the block below as input; the specialised bodies rely on nIn == cells there)
-    bool same = true;
-    for (int j = 0; j < a.nL; ++j) same = same && a.L[j].nC == a.L[0].nC && (j == 0 || a.L[j].nIn == a.L[0].nC);
-    if (same && a.nL == 2 && a.L[0].nC == 32) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 2, 32);   // RACER_RNN.json
-    if (a.nL == 1) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 1, 0);
-    if (a.nL == 2) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 2, 0);
-    if (a.nL == 3) return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 3, 0);
-    return REC_FWD(fl * sizeof(float), lstm_forward_lds_kernel, 0, 0);
   }
-  return REC_FWD(0, rec_forward_kernel, false);
+  // its form for the per-agent tables where they are given, else the form it had
+  const bool many = a.actStates != nullptr && a.actCnt != nullptr;
+  return recLaunch(many ? recForwardKernel<true>(r) : recForwardKernel<false>(r), a, r.lds, s);
 }
-#undef REC_FWD
 // the one-launch step (lstm32_step_wave_kernel): the shapes of the wave-per-(sample, layer) LSTM kernels with a head of up to 32
 // dense outputs and 16 action components / options
 bool rec_step_fused_ok(const RecArgs& a, const HeadArgs& ha) {
@@ -1817,34 +1805,14 @@ hipError_t launch_rec_step_fused(const RecArgs& a, const HeadArgs& ha, const Ext
   return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(lstm32_step_wave_kernel<decltype(in0)::value>, grid, block, 0, s, a, ha, mask, ex); });
 }
 hipError_t launch_rec_backward(const RecArgs& a, hipStream_t s) {
-  if (rec_tm_ok(a)) return launch_rec_tm_backward(a, s);
-  static size_t attr[4] = {0, 0, 0, 0}; const size_t lds = recLdsBytes(a); const bool fit = lds <= 100 * 1024; const bool general = recGeneral(a);
-  if (a.gates == 1) { const size_t l1 = rnnLdsBytes(a); return l1 <= 100 * 1024 ? recLaunch(rnn_backward_kernel<true>, a, l1, &attr[0], s) : recLaunch(rnn_backward_kernel<false>, a, 0, &attr[1], s); }
-  if (general) {
-    if (a.gates == 2) return fit ? recLaunch(mgu_backward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_backward_kernel<false, 0>, a, 0, &attr[1], s);
-    return fit ? recLaunch(rec_backward_kernel<true>, a, lds, &attr[2], s) : recLaunch(rec_backward_kernel<false>, a, 0, &attr[3], s);
+  const RecRoute r = recRoute(a, true);
+  if (r.kind == REC_TM) return launch_rec_tm_backward(a, s);
+  if (r.kind == REC_WAVE32) {
+    if (a.gates == 2) hipLaunchKernelGGL(mgu32_backward_wave_kernel, dim3(a.B), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL(lstm32_backward_wave_kernel, dim3(a.B), dim3(128), 0, s, a);
+    return hipGetLastError();
   }
-  if (a.gates == 2) {
-    static size_t attrM[4] = {0, 0, 0, 0};
-    if (wave32(a, 2)) { hipLaunchKernelGGL(mgu32_backward_wave_kernel, dim3(a.B), dim3(128), 0, s, a); return hipGetLastError(); }
-    if (fit && a.nL == 1) return recLaunch(mgu_backward_kernel<true, 1>, a, lds, &attrM[1], s);
-    if (fit && a.nL == 2) return recLaunch(mgu_backward_kernel<true, 2>, a, lds, &attrM[2], s);
-    return fit ? recLaunch(mgu_backward_kernel<true, 0>, a, lds, &attr[0], s) : recLaunch(mgu_backward_kernel<false, 0>, a, 0, &attr[1], s);
-  }
-  if (wave32(a, 4)) { hipLaunchKernelGGL(lstm32_backward_wave_kernel, dim3(a.B), dim3(128), 0, s, a); return hipGetLastError(); }
-  size_t fl = 0; bool al = true;
-  for (int j = 0; j < a.nL; ++j) {
-    fl += (size_t)(a.L[j].nIn + a.L[j].nC) * lstmBwdPitch(4 * a.L[j].nC) + (size_t)a.K * 6 * a.L[j].nC;
-    al = al && a.L[j].indW % 4 == 0 && a.L[j].nIn <= REC_MAXIN;
-  }
-  if (al && fl * sizeof(float) <= 120 * 1024) {
-    static size_t attrS[4] = {0, 0, 0, 0};
-    if (a.nL == 1) return recLaunch(lstm_backward_lds_kernel<1>, a, fl * sizeof(float), &attrS[1], s);
-    if (a.nL == 2) return recLaunch(lstm_backward_lds_kernel<2>, a, fl * sizeof(float), &attrS[2], s);
-    if (a.nL == 3) return recLaunch(lstm_backward_lds_kernel<3>, a, fl * sizeof(float), &attrS[3], s);
-    return recLaunch(lstm_backward_lds_kernel<0>, a, fl * sizeof(float), &attrS[0], s);
-  }
-  return fit ? recLaunch(rec_backward_kernel<true>, a, lds, &attr[2], s) : recLaunch(rec_backward_kernel<false>, a, 0, &attr[3], s);
+  return recLaunch(recBackwardKernel(r), a, r.lds, s);
 }
 
 }  // namespace hl
