@@ -35,6 +35,9 @@
  *   hl_forward_sequences  n agents' windows, any net.  Per chunk of agents one launch, or -- layers wider than 256 cells, recurrent
  *                         layers behind convolutions, RNN encoder layers under MGU layers, nets of at most 256 cells whose window
  *                         is beyond the one launch's 64 KB -- one chain of hl_forward_sequence's own launches (listed below).
+ *   hl_forward_dev,       dense nets, rows, actions and finished episodes that live in DEVICE memory (a simulator on the learner's GPU):
+ *   hl_select_actions_dev, include/smarties_hip_dev.h.  The two acting kernels of hl_forward on the caller's arrays, ordered against the caller's
+ *   hl_append_episodes_dev stream, without staging and without a host wait.
  */
 #ifndef SMARTIES_HIP_ACT_H
 #define SMARTIES_HIP_ACT_H

@@ -1,0 +1,83 @@
+/*
+ * include/smarties_hip_dev.h -- acting and episode ingestion for simulators that keep their rollouts in DEVICE memory.
+ *
+ * An addition to the C-ABI of include/smarties_hip.h (same library, same conventions: plain C, an int status per call).  It lives in
+ * a header of its own, as include/smarties_hip_act.h does, because the CPU oracle (oracle/port) mirrors smarties_hip.h declaration
+ * by declaration and needs no twin of these calls: hl_forward, hl_append_episode and the host code of
+ * smarties_amd/host/vracer_hip.h define their results.
+ *
+ * hl_forward takes its rows from a host pointer (pinned staging, a poll of the kernel's stamps, a copy out), hl_append_episode copies
+ * an episode into a pinned buffer the ingest kernel reads over the bus, and the action head of RACER::selectAction runs per agent in
+ * host fp64.  A simulator on the learner's GPU holds states, actions and rewards as device arrays already: the three calls below take
+ * DEVICE pointers (a torch tensor's data_ptr(): the library shares the process's HIP runtime) and never touch host copies of the data.
+ *
+ * Streams.  `stream` is the caller's hipStream_t passed as void*; NULL is the null stream.  Every call takes the learner's lock,
+ * refuses between hl_step_begin and hl_step_end (HL_ERR_STATE, as hl_forward), records an event on `stream` that the learner's stream
+ * waits for, enqueues its work on the learner's stream, makes `stream` wait for the learner's completion event, and returns WITHOUT
+ * waiting on the host: the inputs may be written by work queued on `stream` before the call, the outputs are valid for work queued
+ * on `stream` after it, and gradient steps queued by an earlier hl_step are ahead of the call as they are ahead of hl_forward.
+ * The arrays must stay allocated until that work has run.
+ */
+#ifndef SMARTIES_HIP_DEV_H
+#define SMARTIES_HIP_DEV_H
+
+#include "smarties_hip_act.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* hl_forward for rows in device memory.  dStates: [n][dimS (1 + nAppendedObs)] floats (appended observations stacked in the row by
+ * the caller, as for hl_forward), dOutputs: [n][nOutputs] doubles, both device memory.
+ *
+ * Served: dense nets without convolutions whose input row and layers are at most 2048 wide (the nets hl_forward's many-row route
+ * takes).  The kernels are hl_forward's own, run straight on the caller's arrays -- no staging copy, no host poll, their completion
+ * stamps go to a scratch block: up to 64 rows of a net at most 1024 wide the one-kernel route (a workgroup per row), everything else
+ * the row-block kernel in chunks of HL_ACT_ROWS_CHUNK rows.  Where hl_forward picks the same kernel the result is the same bit for bit;
+ * that is every call except a net beyond HL_ACT_ROWS_SMALL_NET weights below HL_ACT_ROWS_WIDE_MIN_N or 4 x batchSize rows, which
+ * hl_forward sends over the training buffers and this call does not (the two agree to rounding there).
+ * The minibatch buffers and a minibatch drawn ahead are not touched.
+ *
+ * Status: HL_ERR_UNSUPPORTED (with a message) for every other net -- recurrent layers, convolutions in front, wider rows or layers,
+ * SMARTIES_HIP_GENERIC bit 2.  HL_ERR_STATE between hl_step_begin and hl_step_end.  n == 0: HL_OK, nothing is enqueued. */
+HL_API int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream);
+
+/* RACER::selectAction (Learners/RACER.cpp:30-47) for n agents without leaving the device: the forward pass of hl_forward_dev into a
+ * buffer of the library, then ONE launch of the fp64 head kernel (smarties_amd/csrc/actdev.hip: act_head_kernel), which restates
+ * smarties_amd/host/vracer_hip.h:209-258 for HL_ADV_ZERO, HL_ADV_GAUSSIAN and HL_ADV_DISCRETE:
+ *   continuous  stdev = SoftPlus of the ParamLayer value; a = mean + stdev * noise (Continuous_policy.h:192-194), clipped to
+ *               +-8.31776613503286 on bounded components; V = scaleNet2V(output 0); the Gaussian advantage with the clipped mean.
+ *   discrete    SoftPlus-normalised probabilities; the label by inverse CDF -- the first option whose running sum in option order
+ *               exceeds u --; the action stored as label + 0.1; the advantage A[label] - sum p A.
+ * dNoise: [n][dimA] doubles already clipped to +-NORMDIST_MAX (Agent::sampleActionNoise); discrete head: [n] uniforms in [0, 1).
+ * dNoise == NULL: the evaluation action (the mean; the arg-max option, Continuous_policy.h:779).
+ * Outputs, device memory, in exactly the types hl_append_episode takes so that a simulator writes them straight into its rollout
+ * buffers: dActions f64 [n][dimA], dMu f64 [n][polDim] (mean | stdev, or the probabilities), dValues f32 [n],
+ * dAdvantages f32 [n] = (Fval)((Fval)(V + A) - (Fval)V).
+ * The env-facing scaling of actions (tanh, bounds) is the caller's, as it is for the host code.
+ * Status: as hl_forward_dev. */
+HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const double* dNoise, double* dActions, double* dMu,
+                                 float* dValues, float* dAdvantages, void* stream);
+
+/* hl_append_episode for a batch of finished episodes held in device memory.  nsteps, terminated, tags, first_row: HOST arrays of nEp
+ * entries (free after return).  Step t of episode e is row first_row[e] + t * row_stride of each device array: dStates f32
+ * [rows][dimS], dActions f64 [rows][dimA], dMu f64 [rows][polDim], dRewards f64 [rows], dValues f32 [rows], dAdvantages f32 [rows] or
+ * NULL.  A [T][nEnv] rollout buffer is ingested with row_stride = nEnv and first_row = t0 * nEnv + env, a packed one with
+ * row_stride = 1.  Every row first_row[e] + t * row_stride, t < nsteps[e], must lie inside the arrays: the library cannot check that.
+ *
+ * The host bookkeeping is hl_append_episode's, episode by episode in the order given (slots, episode ids, counters, order, pending
+ * Retrace; eviction follows with the next step).  The data moves with ingest_dev_kernel (smarties_amd/csrc/actdev.hip): a strided
+ * gather into the replay's arrays with the insertion values of the derived fields, the episode's reward sum formed in step order in
+ * fp64 -- the host route's value bit for bit.  Episodes staged by earlier hl_append_episode calls are handed to the device first.
+ * With hl_set_episode_log on, the call reads the sums back (one device wait) and writes hl_append_episode's log lines; otherwise it
+ * waits for nothing.
+ * Status: HL_ERR_BAD_ARG for nEp < 0, a null table or array, row_stride < 1, an episode of fewer than 2 steps or a negative first
+ * row -- checked before anything is stored.  HL_ERR_STATE between hl_step_begin and hl_step_end.  nEp == 0: HL_OK. */
+HL_API int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, const int32_t* terminated, const int64_t* tags,
+                                  const int64_t* first_row, int64_t row_stride, const float* dStates, const double* dActions,
+                                  const double* dMu, const double* dRewards, const float* dValues, const float* dAdvantages, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -215,6 +215,10 @@ class CApi:
             "forward": (C.c_int, [P, I32, pf, pd]),
             "forward_sequence": (C.c_int, [P, I32, pf, pd]),
             "forward_sequences": (C.c_int, [P, I32, pi32, pf, pd]),      # include/smarties_hip_act.h (product library only)
+            # include/smarties_hip_dev.h (product library only): device pointers and the caller's stream as void*
+            "forward_dev": (C.c_int, [P, I32, P, P, P]),
+            "select_actions_dev": (C.c_int, [P, I32, P, P, P, P, P, P, P]),
+            "append_episodes_dev": (C.c_int, [P, I32, pi32, pi32, pi64, pi64, I64, P, P, P, P, P, P, P]),
             "save": (C.c_int, [P, C.c_char_p]),
             "metrics": (C.c_int, [P, C.c_char_p, I32, C.c_char_p, I32]),
             "grad_stats": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -475,6 +479,90 @@ class Learner:
         out = np.zeros((st.shape[0], self.nOut), np.float64)
         self._ck(self.api.fn("forward")(self.h, st.shape[0], _ptr(st, C.c_float), _ptr(out, C.c_double)))
         return out
+
+    # -- device memory (include/smarties_hip_dev.h) --------------------------------------
+    @staticmethod
+    def _dev(a, dtype, numel, what, optional=False):
+        """device pointer of `a`: a contiguous torch tensor on the GPU of the given dtype with at least `numel` elements (checked), or a
+        raw integer pointer (taken as it is)"""
+        if a is None:
+            if optional:
+                return None
+            raise ValueError("%s: a device array is required" % what)
+        if isinstance(a, int):
+            return C.c_void_p(a)
+        import torch
+        want = {"f32": torch.float32, "f64": torch.float64}[dtype]
+        if not isinstance(a, torch.Tensor):
+            raise TypeError("%s: a torch tensor or an integer device pointer, not %s" % (what, type(a).__name__))
+        if not a.is_cuda:
+            raise ValueError("%s: the tensor lives on %s, not on the GPU" % (what, a.device))
+        if a.dtype != want:
+            raise TypeError("%s: dtype %s, expected %s" % (what, a.dtype, want))
+        if not a.is_contiguous():
+            raise ValueError("%s: the tensor is not contiguous" % what)
+        if a.numel() < numel:
+            raise ValueError("%s: %d elements, the call reads or writes %d" % (what, a.numel(), numel))
+        return C.c_void_p(a.data_ptr())
+
+    @staticmethod
+    def _stream(stream):
+        """the caller's hipStream_t: a torch stream, a raw handle, or (None) torch's current stream"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream()
+        return C.c_void_p(stream if isinstance(stream, int) else stream.cuda_stream)
+
+    def forward_dev(self, states, out=None, n=None, stream=None):
+        """hl_forward for rows in device memory: `states` [n][dIn] float32 on the GPU; returns (or fills `out` with) the network
+        outputs [n][nOut] float64 on the GPU, valid in `stream`'s order (default: torch's current stream).  No host wait.
+        Raw integer pointers need `n` and `out`."""
+        if n is None:
+            n = states.numel() // self.dIn
+        if out is None:
+            import torch
+            out = torch.empty((n, self.nOut), dtype=torch.float64, device=states.device)
+        self._ck(self.api.fn("forward_dev")(self.h, n, self._dev(states, "f32", n * self.dIn, "states"),
+                                            self._dev(out, "f64", n * self.nOut, "out"), self._stream(stream)))
+        return out
+
+    def select_actions_dev(self, states, noise=None, out=None, n=None, stream=None):
+        """RACER::selectAction for n agents on the GPU (hl_select_actions_dev).  `noise`: [n][dA] float64 clipped normal deviates
+        ([n] uniforms for the discrete head), None: the evaluation action.  Returns (actions f64 [n][dA], mu f64 [n][polDim],
+        values f32 [n], advantages f32 [n]) -- or fills the four arrays of `out` -- valid in `stream`'s order."""
+        if n is None:
+            n = states.numel() // self.dIn
+        if out is None:
+            import torch
+            dev = states.device
+            out = (torch.empty((n, self.dA), dtype=torch.float64, device=dev), torch.empty((n, self.polDim), dtype=torch.float64, device=dev),
+                   torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+        act, mu, val, adv = out
+        n_noise = n if self.nOptions else n * self.dA
+        self._ck(self.api.fn("select_actions_dev")(
+            self.h, n, self._dev(states, "f32", n * self.dIn, "states"), self._dev(noise, "f64", n_noise, "noise", optional=True),
+            self._dev(act, "f64", n * self.dA, "actions"), self._dev(mu, "f64", n * self.polDim, "mu"),
+            self._dev(val, "f32", n, "values"), self._dev(adv, "f32", n, "advantages"), self._stream(stream)))
+        return out
+
+    def append_episodes_dev(self, nsteps, terminated, tags, first_row, row_stride, states, actions, mu, rewards, values,
+                            advantages=None, stream=None):
+        """hl_append_episode for a batch of finished episodes in device memory: step t of episode e is row
+        first_row[e] + t * row_stride of every array (states f32 [rows][dS], actions f64 [rows][dA], mu f64 [rows][polDim],
+        rewards f64, values f32, advantages f32 or None).  Tensors are checked to hold the last row any episode reads."""
+        nsteps = np.ascontiguousarray(nsteps, dtype=np.int32)
+        terminated = np.ascontiguousarray(terminated, dtype=np.int32)
+        tags = np.ascontiguousarray(tags, dtype=np.int64)
+        first_row = np.ascontiguousarray(first_row, dtype=np.int64)
+        n_ep = nsteps.size
+        assert terminated.size == n_ep and tags.size == n_ep and first_row.size == n_ep
+        rows = int((first_row + (nsteps.astype(np.int64) - 1) * int(row_stride)).max()) + 1 if n_ep and row_stride >= 1 else 0
+        self._ck(self.api.fn("append_episodes_dev")(
+            self.h, n_ep, _ptr(nsteps, C.c_int32), _ptr(terminated, C.c_int32), _ptr(tags, C.c_int64), _ptr(first_row, C.c_int64),
+            int(row_stride), self._dev(states, "f32", rows * self.dS, "states"), self._dev(actions, "f64", rows * self.dA, "actions"),
+            self._dev(mu, "f64", rows * self.polDim, "mu"), self._dev(rewards, "f64", rows, "rewards"),
+            self._dev(values, "f32", rows, "values"), self._dev(advantages, "f32", rows, "advantages", optional=True),
+            self._stream(stream)))
 
     def set_episode_log(self, path):
         self._ck(self.api.fn("set_episode_log")(self.h, str(path).encode() if path else None))

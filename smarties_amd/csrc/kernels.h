@@ -334,6 +334,28 @@ struct IngestArgs {
 };
 constexpr int INGEST_MAX_EP = 1024;
 hipError_t launch_ingest(const IngestArgs& a, hipStream_t s);
+// episode ingestion from device memory (actdev.hip: ingest_dev_kernel): step t of episode e is row first + t * rowStride of the caller's
+// device arrays (states f32 [rows][dS], actions f64 [rows][dA], behaviour policies f64 [rows][polDim], rewards f64, values f32,
+// advantages f32 or nullptr); the descriptors travel in the kernel arguments, so nothing of a call outlives its launch on the host
+struct IngestDevDesc { long long off, tag, first; int N, eid, term, pad; };
+constexpr int INGEST_DEV_MAX_EP = 64;      // episodes per launch (40 bytes of kernel arguments each)
+struct IngestDevArgs {
+  DevReplay rp; const float* S; const double* A; const double* MU; const double* R; const float* V; const float* ADV;
+  long long rowStride; int nEp, dS, dA, polDim;
+  const double* stats; int nEpTable;      // as IngestArgs
+  double* sums;                           // nullptr, or [nEp][2]: the episode's reward sum in fp64 and as the episode log forms it (Fval += Real)
+  IngestDevDesc d[INGEST_DEV_MAX_EP];
+};
+hipError_t launch_ingest_dev(const IngestDevArgs& a, hipStream_t s);
+// RACER::selectAction's action head for n agents in fp64 (actdev.hip: act_head_kernel): network outputs [n][nOut] f64 in; actions
+// [n][dA] f64, behaviour policies [n][polDim] f64, state values and advantages f32 out
+struct ActHeadArgs {
+  const double* O; const double* noise;      // noise: [n][dA] clipped normal deviates (discrete head: [n] uniforms); nullptr: the evaluation action
+  double* act; double* mu; float* V; float* ADV;
+  int n, dA, nOut, nDense, nAdv, nOpt;       // nAdv: 1 + 2 dA under the Gaussian advantage, else 0; nOpt > 0: the discrete head
+  unsigned long long bounded;                // bit i: action component i is bounded (dA <= HL_MAX_DIMA = 64)
+};
+hipError_t launch_act_head(const ActHeadArgs& a, hipStream_t s);
 // forward / dX tile with the whole reduction in flight at once (gemm16.hip: gemm_os_kernel), 256 < K <= 640
 bool gemm_oneshot_ok(int flavor, int K);
 // all dense forward layers in one launch (gemm16.hip: fwd_chain_kernel)

@@ -4,10 +4,10 @@
 // There is no CPU compute path in this library: every entry point that needs the GPU fails
 // with HL_ERR_NO_DEVICE / HL_ERR_HIP if HIP is not usable.
 //
-// ONE translation unit in seven files (round 6; the launch lists were step_exec.h already): learner_state.h (struct hl_learner, helpers,
+// ONE translation unit in eight files (round 6; the launch lists were step_exec.h already): learner_state.h (struct hl_learner, helpers,
 // network description), step_exec.h (launch lists, graphs, exchanges), this file (create / destroy, parameters, ingestion, initialisation,
 // the stepping entry points, read-backs), learner_io.h (wire format, metrics, checkpoints), learner_act.h (rollout inference),
-// learner_xchg.h (communicator and exchange windows), learner_debug.h (timing and development entry points).
+// learner_dev.h (acting and ingestion from device memory), learner_xchg.h (communicator and exchange windows), learner_debug.h (timing and development entry points).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -433,7 +433,8 @@ int hl_destroy(hl_learner* h) {
     h->dRedMax, h->dRedErr, h->dMomPartial, h->dMoments, h->dMomentsPrev, h->dStatsOut, h->dStatsIns,
     h->rp.S, h->rp.A, h->rp.MU, h->rp.R, h->rp.V, h->rp.ADV, h->rp.RET, h->rp.DQ, h->rp.IMPW, h->rp.DKL,
     h->rp.epOff, h->rp.epN, h->rp.epTerm, h->rp.epAgg, h->rp.posEid, h->rp.posPrefix, h->rp.stMean, h->rp.stScale,
-    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->act.dS, h->act.dO, h->act.convFeat};
+    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->act.dS, h->act.dO, h->act.convFeat, h->act.devStamps, h->act.devOut, h->act.devSums};
+  for (hipEvent_t ev : {h->act.devIn, h->act.devDone}) if (ev) hipEventDestroy(ev);
   for (int pb = 0; pb < 2; ++pb) {
     DevBatch& bt = h->buf[pb].bt;
     void* bp[] = {h->buf[pb].X0, bt.sVals, bt.tag, bt.pEid, bt.pNextOf, bt.flat, bt.pos, bt.eid, bt.t, bt.slot, bt.nextOf, bt.nextSrc,
@@ -590,6 +591,35 @@ int hl_get_rng_state(hl_learner* h, uint32_t st[625]) {
   return HL_OK;
 }
 
+// the host bookkeeping of a finished episode, shared by hl_append_episode and hl_append_episodes_dev (learner_dev.h)
+extern "C++" {
+// its slot range and its storage id
+static int appendAlloc(hl_learner* h, int N, long long* off, int* eid) {
+  int rc = allocSlots(h, N, off); if (rc) return rc;
+  if (!h->freeEids.empty()) { *eid = h->freeEids.back(); h->freeEids.pop_back(); }
+  else { *eid = h->nextEid++; rc = growEpisodes(h, *eid + 1); if (rc) return rc; }
+  return HL_OK;
+}
+// counters, order, pending Retrace; returns the episode's ID (the time stamp of the episode log)
+static long long appendBook(hl_learner* h, int eid, long long off, int N, bool term, long long tag) {
+  // counters: storeAction increments for t = 1..N-2, ID taken before the final increment (:110,:167,:484)
+  h->nSeenSteps += N - 2;
+  const long long locTrain = h->nGatheredB4Startup == INT64_MAX ? -1 : h->nSeenSteps - h->nGatheredB4Startup;
+  EpMeta e{eid, off, N, term, tag, std::max(locTrain, (long long)0)};
+  h->nSeenSteps += 1; h->nSeenEps += 1;
+  h->order.push_front(e); h->minLenAtN = -1;
+  h->nTransitions += N - 1;
+  h->pendingRetrace.push_back(eid);
+  h->tableDirty = true; h->countsDirty = true;
+  return e.ID;
+}
+// MemoryBuffer.cpp:492-503: "%ld %ld %d %u %f" = nGradSteps, time stamp, agent, steps, total reward (Fval)
+static void appendLogLine(hl_learner* h, long long ID, int N, float totRf) {
+  if (FILE* f = std::fopen(h->episodeLog.c_str(), "a")) { std::fprintf(f, "%ld %ld %d %u %f\n", (long)h->nGradSteps, (long)ID, 0, (unsigned)N, totRf); std::fclose(f); }
+  else { h->err = "unable to open " + h->episodeLog + " (episode log switched off)"; h->episodeLog.clear(); }   // the episode is stored: it enters the training set regardless
+}
+}  // extern "C++"
+
 // MemoryBuffer::addEpisodeToTrainingSet + Episode::finalize + pushBackEpisode
 // (MemoryBuffer.cpp:131-170,479-520; Episode.cpp:244-274).  The host bookkeeping (slot range, episode id, counters, order)
 // is immediate; the data is copied into the pinned staging buffer -- the caller's arrays are free after return -- and
@@ -601,10 +631,7 @@ int hl_append_episode(hl_learner* h, int32_t N, const float* states, const doubl
   HL_LOCK(h);
   if (N < 2) return fail(h, HL_ERR_BAD_ARG, "Episode must at least have s0 and sT");
   const int dS = h->dS, dA = h->dA, pD = h->polDim;
-  long long off = 0; int rc = allocSlots(h, N, &off); if (rc) return rc;
-  int eid;
-  if (!h->freeEids.empty()) { eid = h->freeEids.back(); h->freeEids.pop_back(); }
-  else { eid = h->nextEid++; rc = growEpisodes(h, eid + 1); if (rc) return rc; }
+  long long off = 0; int eid = 0; int rc = appendAlloc(h, N, &off, &eid); if (rc) return rc;
   const size_t nf = (size_t)N;
   auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t bS = al16(nf * dS * 4), bA = nf * dA * 8, bMU = nf * pD * 8, bR = nf * 8, bV = nf * 4, bADV = nf * 4;
@@ -632,20 +659,11 @@ int hl_append_episode(hl_learner* h, int32_t N, const float* states, const doubl
   IngestDesc& d = reinterpret_cast<IngestDesc*>(st->host)[st->nEp];
   d.off = off; d.tag = tag; d.data = st->used; d.N = N; d.eid = eid; d.term = terminated ? 1 : 0; d.totR = (float)totR;
   st->used += need; st->nEp += 1;
-  // counters: storeAction increments for t = 1..N-2, ID taken before the final increment (:110,:167,:484)
-  h->nSeenSteps += N - 2;
-  const long long locTrain = h->nGatheredB4Startup == INT64_MAX ? -1 : h->nSeenSteps - h->nGatheredB4Startup;
-  EpMeta e{eid, off, N, terminated != 0, tag, std::max(locTrain, (long long)0)};
-  if (!h->episodeLog.empty()) {      // MemoryBuffer.cpp:492-503: "%ld %ld %d %u %f" = nGradSteps, time stamp, agent, steps, total reward (Fval)
+  const long long ID = appendBook(h, eid, off, N, terminated != 0, tag);
+  if (!h->episodeLog.empty()) {
     float totRf = 0; for (int t = 1; t < N; ++t) totRf = (float)((double)totRf + rewards[t]);      // Fval totR += Real reward (:95-96)
-    if (FILE* f = std::fopen(h->episodeLog.c_str(), "a")) { std::fprintf(f, "%ld %ld %d %u %f\n", (long)h->nGradSteps, (long)e.ID, 0, (unsigned)N, totRf); std::fclose(f); }
-    else { h->err = "unable to open " + h->episodeLog + " (episode log switched off)"; h->episodeLog.clear(); }   // the episode is staged: it enters the training set regardless
+    appendLogLine(h, ID, N, totRf);
   }
-  h->nSeenSteps += 1; h->nSeenEps += 1;
-  h->order.push_front(e); h->minLenAtN = -1;
-  h->nTransitions += N - 1;
-  h->pendingRetrace.push_back(eid);
-  h->tableDirty = true; h->countsDirty = true;
   return HL_OK;
 }
 
@@ -913,6 +931,7 @@ int hl_step_end(hl_learner* h) {
 }
 #include "learner_io.h"
 #include "learner_act.h"
+#include "learner_dev.h"
 
 int hl_sync(hl_learner* h) {
   if (!h) return HL_ERR_BAD_ARG;

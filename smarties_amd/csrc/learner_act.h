@@ -48,6 +48,13 @@ static RecArgs actRecArgs(hl_learner* h, int seg, int B, const float* states, co
   RecArgs ra = recArgs(h, 0, seg); ra.B = B; ra.actStates = states; ra.actOff = off; ra.actCnt = cnt; ra.actSteps = steps; ra.actCtx = ctx;
   return ra;
 }
+// the one-kernel route's arguments (misc.hip: act_forward_kernel) on the given rows, outputs and stamps
+static ActArgs actFewArgs(const hl_learner* h, const float* in, double* out, volatile unsigned* done, unsigned tag) {
+  ActArgs aa{}; actFillShared(h, aa);
+  aa.in = in; aa.out = out; aa.done = done; aa.tag = tag;
+  aa.dS = h->dS; aa.dIn = h->dIn; aa.nL = actFillLayers(h, 0, aa.L);
+  return aa;
+}
 static const float actNoState = 0.f;      // (a predicate asks for given states, it does not read them)
 // a few rows of a dense net, one workgroup per row (misc.hip: act_forward_kernel): layers and input rows within its bounds;
 // SMARTIES_HIP_GENERIC bit 2 keeps the route over the training buffers
@@ -262,10 +269,7 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
     { int rc = actPinEnsure(h); if (rc) return rc; }
     const ActStage& s = h->act.few;
     return actRowChunks(h, s, ACT_MAXROWS, [](int m) { return m; }, n, states, outputs, [&](int m, unsigned tag) -> int {
-      ActArgs aa{}; actFillShared(h, aa);
-      aa.in = s.in; aa.out = s.out; aa.done = s.done; aa.tag = tag;
-      aa.dS = h->dS; aa.dIn = h->dIn; aa.nL = actFillLayers(h, 0, aa.L);
-      HIPCK(launch_act_forward(aa, m, h->stream));
+      HIPCK(launch_act_forward(actFewArgs(h, s.in, s.out, s.done, tag), m, h->stream));
       return HL_OK;
     });
   }

@@ -1,0 +1,128 @@
+// smarties_amd/csrc/learner_dev.h -- part of learner.cpp's ONE translation unit (included there, behind learner_act.h): acting and episode ingestion from device memory: hl_forward_dev, hl_select_actions_dev, hl_append_episodes_dev
+#pragma once
+#include "../../include/smarties_hip_dev.h"
+static_assert(HL_MAX_DIMA <= 64, "ActHeadArgs::bounded holds one bit per action component");
+
+extern "C++" {
+// the handshake with the caller's stream: the learner's stream waits for what the caller queued so far ...
+static int devEnter(hl_learner* h, void* stream) {
+  if (!h->act.devIn) HIPCK(hipEventCreateWithFlags(&h->act.devIn, hipEventDisableTiming));
+  if (!h->act.devDone) HIPCK(hipEventCreateWithFlags(&h->act.devDone, hipEventDisableTiming));
+  HIPCK(hipEventRecord(h->act.devIn, static_cast<hipStream_t>(stream)));
+  HIPCK(hipStreamWaitEvent(h->stream, h->act.devIn, 0));
+  return HL_OK;
+}
+// ... and what the caller queues from here on waits for the learner's work; the host waits for neither
+static int devLeave(hl_learner* h, void* stream) {
+  HIPCK(hipEventRecord(h->act.devDone, h->stream));
+  HIPCK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->act.devDone, 0));
+  return HL_OK;
+}
+// a device buffer of at least `need` elements (a larger one replaces it once the stream is done with the old one)
+template <typename T> static int devEnsure(hl_learner* h, T** p, size_t* cap, size_t need) {
+  if (need <= *cap) return HL_OK;
+  if (*p) { HIPCK(hipStreamSynchronize(h->stream)); hipFree(*p); *p = nullptr; *cap = 0; }
+  HIPCK(devAlloc(p, need)); *cap = need;
+  return HL_OK;
+}
+// which nets the device calls serve, and what they allocate once: the scratch block the acting kernels stamp
+static int devActEnsure(hl_learner* h, const char* who) {
+  if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
+  if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets act on windows in host memory (hl_forward_sequences)");
+  if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act through hl_forward");
+  if (!act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2");
+  if (!h->act.devStamps) HIPCK(devAlloc(&h->act.devStamps, (size_t)std::max(ACT_MAXROWS, act_rows_blocks(ACT_ROWS_CHUNK))));
+  return HL_OK;
+}
+// hl_forward's kernels on device rows, enqueued on the learner's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
+// bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows
+static int devForward(hl_learner* h, int n, const float* in, double* out) {
+  if (n <= ACT_MAXROWS && actFewOk(h)) {
+    const ActArgs aa = actFewArgs(h, in, out, h->act.devStamps, actNextTag(h));
+    HIPCK(timed(h, "act_forward_dev", h->stream, [&] { return launch_act_forward(aa, n, h->stream); }));
+    return HL_OK;
+  }
+  for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
+    ActRowsArgs a = h->act.rowsArgs;
+    a.in = in + (size_t)r0 * h->dIn; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
+    HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+  }
+  return HL_OK;
+}
+}  // extern "C++"
+
+int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream) {
+  if (!h || n < 0 || (n > 0 && (!dStates || !dOutputs))) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  { int rc = devActEnsure(h, "hl_forward_dev"); if (rc) return rc; }
+  if (n == 0) return HL_OK;
+  { int rc = devEnter(h, stream); if (rc) return rc; }
+  { int rc = devForward(h, n, dStates, dOutputs); if (rc) return rc; }
+  return devLeave(h, stream);
+}
+
+int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const double* dNoise, double* dActions, double* dMu,
+                          float* dValues, float* dAdvantages, void* stream) {
+  if (!h || n < 0 || (n > 0 && (!dStates || !dActions || !dMu || !dValues || !dAdvantages))) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  { int rc = devActEnsure(h, "hl_select_actions_dev"); if (rc) return rc; }
+  if (n == 0) return HL_OK;
+  { int rc = devEnsure(h, &h->act.devOut, &h->act.devOutCap, (size_t)n * h->nOut); if (rc) return rc; }
+  { int rc = devEnter(h, stream); if (rc) return rc; }
+  { int rc = devForward(h, n, dStates, h->act.devOut); if (rc) return rc; }
+  ActHeadArgs a{};
+  a.O = h->act.devOut; a.noise = dNoise; a.act = dActions; a.mu = dMu; a.V = dValues; a.ADV = dAdvantages;
+  a.n = n; a.dA = h->dA; a.nOut = h->nOut; a.nDense = h->nDense; a.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; a.nOpt = h->nOpt;
+  for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) a.bounded |= 1ull << i;
+  HIPCK(timed(h, "act_head_kernel", h->stream, [&] { return launch_act_head(a, h->stream); }));
+  return devLeave(h, stream);
+}
+
+int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, const int32_t* terminated, const int64_t* tags,
+                           const int64_t* first_row, int64_t row_stride, const float* dStates, const double* dActions,
+                           const double* dMu, const double* dRewards, const float* dValues, const float* dAdvantages, void* stream) {
+  if (!h || nEp < 0) return HL_ERR_BAD_ARG;
+  if (nEp > 0 && (!nsteps || !terminated || !tags || !first_row || !dStates || !dActions || !dMu || !dRewards || !dValues)) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  if (h->inStep) return fail(h, HL_ERR_STATE, "hl_append_episodes_dev between hl_step_begin and hl_step_end");
+  if (nEp > 0 && row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_append_episodes_dev: row_stride below 1");
+  for (int e = 0; e < nEp; ++e) {
+    if (nsteps[e] < 2) return fail(h, HL_ERR_BAD_ARG, "Episode must at least have s0 and sT");
+    if (first_row[e] < 0) return fail(h, HL_ERR_BAD_ARG, "hl_append_episodes_dev: a negative first row");
+  }
+  if (nEp == 0) return HL_OK;
+  { int rc = flushStaging(h); if (rc) return rc; }      // episodes staged by hl_append_episode go first
+  const bool log = !h->episodeLog.empty();
+  if (log) { int rc = devEnsure(h, &h->act.devSums, &h->act.devSumsCap, (size_t)2 * nEp); if (rc) return rc; }
+  { int rc = devEnter(h, stream); if (rc) return rc; }
+  // the bookkeeping of hl_append_episode, episode by episode; an episode that finds no room ends the batch, the ones before it are stored
+  std::vector<long long> ids((size_t)nEp);
+  int booked = 0, rcBook = HL_OK;
+  for (; booked < nEp; ++booked) {
+    long long off = 0; int eid = 0;
+    rcBook = appendAlloc(h, nsteps[booked], &off, &eid); if (rcBook) break;
+    ids[(size_t)booked] = appendBook(h, eid, off, nsteps[booked], terminated[booked] != 0, tags[booked]);
+  }
+  // (a later episode's allocation may have re-packed the replay: the slot offsets are read from the order now; episode e sits at position booked - 1 - e)
+  { int rc = refreshInsertionStats(h); if (rc) return rc; }
+  for (int e0 = 0; e0 < booked; e0 += INGEST_DEV_MAX_EP) {
+    IngestDevArgs ia{};
+    ia.rp = h->rp; ia.S = dStates; ia.A = dActions; ia.MU = dMu; ia.R = dRewards; ia.V = dValues; ia.ADV = dAdvantages;
+    ia.rowStride = row_stride; ia.nEp = std::min(INGEST_DEV_MAX_EP, booked - e0); ia.dS = h->dS; ia.dA = h->dA; ia.polDim = h->polDim;
+    ia.stats = h->dStatsIns; ia.nEpTable = h->anyStep ? h->tableCount : 0;
+    ia.sums = log ? h->act.devSums + (size_t)2 * e0 : nullptr;
+    for (int k = 0; k < ia.nEp; ++k) {
+      const EpMeta& m = h->order[(size_t)(booked - 1 - (e0 + k))];
+      ia.d[k] = IngestDevDesc{m.off, m.tag, first_row[e0 + k], m.N, m.eid, m.term ? 1 : 0, 0};
+    }
+    HIPCK(timed(h, "ingest_dev_kernel", h->stream, [&] { return launch_ingest_dev(ia, h->stream); }));
+  }
+  { int rc = devLeave(h, stream); if (rc) return rc; }
+  if (log && booked > 0) {
+    std::vector<double> sums((size_t)2 * booked);
+    HIPCK(hipMemcpyAsync(sums.data(), h->act.devSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    for (int e = 0; e < booked && !h->episodeLog.empty(); ++e) appendLogLine(h, ids[(size_t)e], nsteps[e], (float)sums[(size_t)2 * e + 1]);
+  }
+  return rcBook;
+}

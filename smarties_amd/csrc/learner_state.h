@@ -35,6 +35,10 @@ struct ActState {
   unsigned char *pin = nullptr, *rowsPin = nullptr, *convPin = nullptr; ActStage few{}, chunk{}, rows{}, conv{}; int chunkCap = 0;
   float* convFeat = nullptr;          // the feature rows of a chunk behind convolutions (device; allocated with convPin)
   float* dS = nullptr; double* dO = nullptr;      // the routes over minibatch buffer 0: raw rows in, outputs out (actTrainEnsure)
+  // acting and ingestion from device memory (learner_dev.h): the events of the handshake with the caller's stream, a scratch block for the
+  // acting kernels' stamps, the network outputs between the forward pass and the head kernel, the episode sums read back for the episode log
+  hipEvent_t devIn = nullptr, devDone = nullptr; unsigned* devStamps = nullptr;
+  double* devOut = nullptr; size_t devOutCap = 0; double* devSums = nullptr; size_t devSumsCap = 0;
 };
 }  // namespace
 
