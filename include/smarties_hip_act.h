@@ -38,6 +38,11 @@
  *   hl_forward_dev,       dense nets, rows, actions and finished episodes that live in DEVICE memory (a simulator on the learner's GPU):
  *   hl_select_actions_dev, include/smarties_hip_dev.h.  The two acting kernels of hl_forward on the caller's arrays, ordered against the caller's
  *   hl_append_episodes_dev stream, without staging and without a host wait.
+ *   hl_forward_sequences_dev,        n agents' windows that live in DEVICE memory as rows of a strided rollout buffer: recurrent nets of
+ *   hl_select_actions_sequences_dev  hl_forward_sequences' one-launch route (one layer type, no convolutions, no encoder_rnn, layers up to
+ *                         256 cells and 1024 inputs) -- that kernel with the windows gathered and truncated in the kernel, ONE launch
+ *                         for any n, no chunks --, and the dense nets hl_forward_dev serves (appended observations stacked on the
+ *                         device).  Every other recurrent net acts through hl_forward_sequences.
  */
 #ifndef SMARTIES_HIP_ACT_H
 #define SMARTIES_HIP_ACT_H

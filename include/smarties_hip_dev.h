@@ -8,8 +8,11 @@
  *
  * hl_forward takes its rows from a host pointer (pinned staging, a poll of the kernel's stamps, a copy out), hl_append_episode copies
  * an episode into a pinned buffer the ingest kernel reads over the bus, and the action head of RACER::selectAction runs per agent in
- * host fp64.  A simulator on the learner's GPU holds states, actions and rewards as device arrays already: the three calls below take
+ * host fp64.  A simulator on the learner's GPU holds states, actions and rewards as device arrays already: the calls below take
  * DEVICE pointers (a torch tensor's data_ptr(): the library shares the process's HIP runtime) and never touch host copies of the data.
+ * hl_forward_dev and hl_select_actions_dev act on rows (dense nets), hl_forward_sequences_dev and hl_select_actions_sequences_dev on
+ * windows of a strided rollout buffer (recurrent nets, and dense nets whose appended observations they stack), hl_append_episodes_dev
+ * stores the finished episodes of any net.
  *
  * Streams.  `stream` is the caller's hipStream_t passed as void*; NULL is the null stream.  Every call takes the learner's lock,
  * refuses between hl_step_begin and hl_step_end (HL_ERR_STATE, as hl_forward), records an event on `stream` that the learner's stream
@@ -38,7 +41,7 @@ extern "C" {
  * hl_forward sends over the training buffers and this call does not (the two agree to rounding there).
  * The minibatch buffers and a minibatch drawn ahead are not touched.
  *
- * Status: HL_ERR_UNSUPPORTED (with a message) for every other net -- recurrent layers, convolutions in front, wider rows or layers,
+ * Status: HL_ERR_UNSUPPORTED (with a message) for every other net -- recurrent layers (hl_forward_sequences_dev below), convolutions in front, wider rows or layers,
  * SMARTIES_HIP_GENERIC bit 2.  HL_ERR_STATE between hl_step_begin and hl_step_end.  n == 0: HL_OK, nothing is enqueued. */
 HL_API int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream);
 
@@ -58,6 +61,46 @@ HL_API int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double
  * Status: as hl_forward_dev. */
 HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const double* dNoise, double* dActions, double* dMu,
                                  float* dValues, float* dAdvantages, void* stream);
+
+/* hl_forward_sequences for windows in device memory: what a partially observable simulator on the learner's GPU calls to act.
+ * dFirstRow [n] int64 and dNSteps [n] int32 are DEVICE arrays (the simulator knows its episode starts on the device; the host never
+ * reads them), dStates is a [rows][dimS] float array in device memory, dOutputs [n][nOutputs] doubles in device memory.  The addressing is
+ * hl_append_episodes_dev's: a [T][nEnv] buffer gives row_stride = nEnv and first_row = t0 * nEnv + env, a packed one row_stride = 1.
+ *
+ * The window of agent i, with len = dNSteps[i]:
+ *     ns   = max(1, min(len, nnBPTTseq + 1 + nAppendedObs))        states read
+ *     skip = max(len, 1) - ns                                      older states left out
+ *     state g of the window (0 = oldest) is row dFirstRow[i] + (skip + g) * row_stride
+ * A longer window is truncated to its newest nnBPTTseq + 1 + nAppendedObs states -- the window MemoryBuffer::agentToMinibatch forms
+ * (MemoryBuffer.cpp:440-467) --, so a simulator passes the episode's start row and t + 1 and never computes the truncation itself
+ * (hl_forward_sequences refuses such a window instead).  dNSteps[i] < 1 reads one row, dFirstRow[i].  Every row read must lie inside
+ * dStates: the library cannot check that.  Row arithmetic is done in 64 bits.
+ *
+ * Served, recurrent nets: those of hl_forward_sequences' one-launch batched kernel (smarties_amd/csrc/actseq.hip) -- LSTM / MGU / RNN
+ * layers of one type, no convolutions in front, no encoder_rnn layers, every layer at most 256 cells and 1024 inputs, the window within
+ * 64 KB.  The kernel is that call's own with the windows gathered, truncated and standardised in the kernel from the caller's array:
+ * ONE launch for any n (there is no staging, so HL_ACT_SEQ_CHUNK does not apply), min(n, compute units) workgroups walking the agents,
+ * outputs written to dOutputs, no stamps and no system-scope fence -- completion is stream order.  From the standardised window on the
+ * arithmetic and its order are the host route's: an agent's outputs equal hl_forward_sequences' on the same window bit for bit.
+ * Served, dense nets: those hl_forward_dev serves.  One small launch (smarties_amd/csrc/actdev.hip: act_stack_dev_kernel) builds the
+ * agents' rows [n][dimS (1 + nAppendedObs)] -- the last state, then the ones before it, steps before the first given state repeating
+ * it -- into a buffer of the library, then hl_forward_dev's kernels run on those rows (no truncation: a dense net reads
+ * 1 + nAppendedObs states whatever the window's length).
+ *
+ * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other net -- layers beyond 256 cells (the
+ * time-step-major nets), inputs beyond 1024, convolutions in front, encoder_rnn layers: they act on windows in host memory.
+ * HL_ERR_BAD_ARG for a null handle or array, n < 0 or row_stride < 1.  HL_ERR_STATE between hl_step_begin and hl_step_end.
+ * n == 0: HL_OK, nothing is enqueued.  The minibatch buffers and a minibatch drawn ahead are not touched. */
+HL_API int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride,
+                                    const float* dStates, double* dOutputs, void* stream);
+
+/* hl_select_actions_dev on windows: the forward pass of hl_forward_sequences_dev into a buffer of the library, then the same ONE launch
+ * of act_head_kernel.  dNoise and the four outputs as for hl_select_actions_dev; the windows, nets and status as for
+ * hl_forward_sequences_dev.  With hl_append_episodes_dev the loop act -> simulate -> append -> step of a recurrent net never leaves
+ * the device. */
+HL_API int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride,
+                                           const float* dStates, const double* dNoise, double* dActions, double* dMu, float* dValues,
+                                           float* dAdvantages, void* stream);
 
 /* hl_append_episode for a batch of finished episodes held in device memory.  nsteps, terminated, tags, first_row: HOST arrays of nEp
  * entries (free after return).  Step t of episode e is row first_row[e] + t * row_stride of each device array: dStates f32

@@ -219,6 +219,8 @@ class CApi:
             "forward_dev": (C.c_int, [P, I32, P, P, P]),
             "select_actions_dev": (C.c_int, [P, I32, P, P, P, P, P, P, P]),
             "append_episodes_dev": (C.c_int, [P, I32, pi32, pi32, pi64, pi64, I64, P, P, P, P, P, P, P]),
+            "forward_sequences_dev": (C.c_int, [P, I32, P, P, I64, P, P, P]),
+            "select_actions_sequences_dev": (C.c_int, [P, I32, P, P, I64, P, P, P, P, P, P, P]),
             "save": (C.c_int, [P, C.c_char_p]),
             "metrics": (C.c_int, [P, C.c_char_p, I32, C.c_char_p, I32]),
             "grad_stats": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -492,7 +494,7 @@ class Learner:
         if isinstance(a, int):
             return C.c_void_p(a)
         import torch
-        want = {"f32": torch.float32, "f64": torch.float64}[dtype]
+        want = {"f32": torch.float32, "f64": torch.float64, "i32": torch.int32, "i64": torch.int64}[dtype]
         if not isinstance(a, torch.Tensor):
             raise TypeError("%s: a torch tensor or an integer device pointer, not %s" % (what, type(a).__name__))
         if not a.is_cuda:
@@ -541,6 +543,41 @@ class Learner:
         n_noise = n if self.nOptions else n * self.dA
         self._ck(self.api.fn("select_actions_dev")(
             self.h, n, self._dev(states, "f32", n * self.dIn, "states"), self._dev(noise, "f64", n_noise, "noise", optional=True),
+            self._dev(act, "f64", n * self.dA, "actions"), self._dev(mu, "f64", n * self.polDim, "mu"),
+            self._dev(val, "f32", n, "values"), self._dev(adv, "f32", n, "advantages"), self._stream(stream)))
+        return out
+
+    def forward_sequences_dev(self, states, first_row, n_steps, row_stride, out=None, n=None, stream=None):
+        """hl_forward_sequences for windows in device memory (hl_forward_sequences_dev): `states` [rows][dimS] float32, `first_row` [n]
+        int64 and `n_steps` [n] int32 on the GPU; state t of agent i is row first_row[i] + t * row_stride, and the newest
+        nnBPTTseq + 1 + nAppendedObs of its n_steps[i] states are read.  Returns (or fills `out` with) the network outputs [n][nOut]
+        float64 on the GPU, valid in `stream`'s order.  No host wait; the rows are not checked against `states`' size (the tables
+        stay on the device).  Raw integer pointers need `n` and `out`."""
+        if n is None:
+            n = n_steps.numel()
+        if out is None:
+            import torch
+            out = torch.empty((n, self.nOut), dtype=torch.float64, device=states.device)
+        self._ck(self.api.fn("forward_sequences_dev")(
+            self.h, n, self._dev(first_row, "i64", n, "first_row"), self._dev(n_steps, "i32", n, "n_steps"), int(row_stride),
+            self._dev(states, "f32", self.dS if n else 0, "states"), self._dev(out, "f64", n * self.nOut, "out"), self._stream(stream)))
+        return out
+
+    def select_actions_sequences_dev(self, states, first_row, n_steps, row_stride, noise=None, out=None, n=None, stream=None):
+        """RACER::selectAction for n agents' windows in device memory (hl_select_actions_sequences_dev): the windows as for
+        forward_sequences_dev, `noise` and the returned (actions, mu, values, advantages) as for select_actions_dev."""
+        if n is None:
+            n = n_steps.numel()
+        if out is None:
+            import torch
+            dev = states.device
+            out = (torch.empty((n, self.dA), dtype=torch.float64, device=dev), torch.empty((n, self.polDim), dtype=torch.float64, device=dev),
+                   torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+        act, mu, val, adv = out
+        n_noise = n if self.nOptions else n * self.dA
+        self._ck(self.api.fn("select_actions_sequences_dev")(
+            self.h, n, self._dev(first_row, "i64", n, "first_row"), self._dev(n_steps, "i32", n, "n_steps"), int(row_stride),
+            self._dev(states, "f32", self.dS if n else 0, "states"), self._dev(noise, "f64", n_noise, "noise", optional=True),
             self._dev(act, "f64", n * self.dA, "actions"), self._dev(mu, "f64", n * self.polDim, "mu"),
             self._dev(val, "f32", n, "values"), self._dev(adv, "f32", n, "advantages"), self._stream(stream)))
         return out

@@ -88,6 +88,25 @@ hipError_t launch_act_head(const ActHeadArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// A thread per float of the stacked rows, workgroups striding over them: block j of agent i's row is the state max(last - j, 0) of its
+// window, last = max(nSteps[i], 1) - 1 (act_stack_row of act_host.h on a strided window).  Raw values: the acting kernels standardise
+__global__ __launch_bounds__(256) void act_stack_dev_kernel(ActStackDevArgs a) {
+  const int dS = a.dS, dIn = dS * (1 + a.nApp);
+  const long long total = (long long)a.n * dIn;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const int ag = (int)(e / dIn), c = (int)(e - (long long)ag * dIn), j = c / dS, i = c - j * dS;
+    const long long g = max(max(a.nSteps[ag], 1) - 1 - j, 0);
+    a.rows[e] = a.states[(a.firstRow[ag] + g * a.rowStride) * dS + i];
+  }
+}
+hipError_t launch_act_stack_dev(const ActStackDevArgs& a, hipStream_t s) {
+  if (a.n < 1) return hipSuccess;
+  if (!a.states || !a.firstRow || !a.nSteps || !a.rows || a.rowStride < 1 || a.dS < 1 || a.nApp < 0) return hipErrorInvalidValue;
+  const long long blocks = ((long long)a.n * a.dS * (1 + a.nApp) + 255) / 256;
+  hipLaunchKernelGGL(act_stack_dev_kernel, dim3((unsigned)std::min(blocks, 4096ll)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 // blockIdx.y = episode of the launch, blockIdx.x strides over its elements (as ingest_kernel).  Workgroup x = 0 of an episode also forms
 // its reward sum: the rewards pass through LDS 256 at a time and ONE thread adds them in step order, so the sum is the host route's
 // `for (t = 1; t < N; ++t) totR += rewards[t]` bit for bit (and, where the episode log wants it, the log's Fval += Real beside it).

@@ -13,6 +13,9 @@
 //     memory (prefix sums of the window lengths stand beside them), are standardised into LDS in one round, the window runs with
 //     the recurrent state in LDS and nothing stored per step, the output layer follows in the same kernel (the arithmetic of
 //     act_forward_kernel's tail, misc.hip), the outputs go to pinned host memory as doubles and the agent's stamp is released.
+// hl_forward_sequences_dev (include/smarties_hip_dev.h) runs the same kernel on windows that lie in DEVICE memory (template parameter DEV):
+// agent i's states are rows firstRow[i] + t rowStride of the caller's array, the tables are device arrays too, the newest
+// nnBPTTseq + 1 + nAppendedObs rows are gathered into LDS, the outputs go to device memory and nothing is stamped -- ONE launch for any n.
 // Gate sums: the G = gates x cells columns of a layer are spread over the 256 threads with P = 4 / 2 / 1 neighbouring lanes per
 // column (G <= 64 / 128 / more), lane p summing the 16-byte chunks p, p + P, ... of the column; the shares are joined by shuffles, the
 // first lane adds the bias and applies the gate's function, the cell's thread finishes the step behind ONE barrier (MGU: three).
@@ -64,7 +67,9 @@ __device__ __forceinline__ float asqJoin(float acc, int P) {
 
 // GATES: 4 LSTM, 2 MGU, 1 plain recurrent layers -- at compile time: with the layer type read from the arguments the walk of a window was
 // mostly scalar branches (measured: 2.2 us per layer-step at 32 cells)
-template <bool LDSW, int GATES>
+// DEV: the windows lie in the caller's device memory (hl_forward_sequences_dev) -- strided rows gathered here, the newest recWin + nApp
+// states of each; outputs to device memory, completion is stream order.  From sStates on both variants run the same code
+template <bool LDSW, int GATES, bool DEV>
 __global__ __launch_bounds__(256) void act_seq_kernel(ActSeqArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sDyn[];      // [weights (LDSW)] [bias | residual w | residual b per layer] [window states]
   __shared__ __attribute__((aligned(16))) float sBuf[2][ASQ_MAXIN];      // input of the current layer / output of the current block
@@ -114,11 +119,24 @@ __global__ __launch_bounds__(256) void act_seq_kernel(ActSeqArgs a) {
   __syncthreads();
   // ---- the workgroup's agents ----
   for (int ag = blockIdx.x; ag < a.n; ag += gridDim.x) {
-    const int off = a.offset[ag];
-    const int ns = max(1, min(a.offset[ag + 1] - off, maxSteps));      // (the host refuses longer windows; the LDS copy holds maxSteps states)
+    int off = 0, len = 0;
+    if constexpr (DEV) len = a.nSteps[ag]; else { off = a.offset[ag]; len = a.offset[ag + 1] - off; }
+    const int ns = max(1, min(len, maxSteps));      // (the host refuses longer windows; the LDS copy holds maxSteps states)
     const int win = min(ns, a.recWin), ctx = ns - win;
-    // the whole window in one round from pinned host memory, standardised (Episode::standardizedState, Episode.h:172-183)
-    {
+    if constexpr (DEV) {
+      // the window's newest ns rows of the caller's array (MemoryBuffer::agentToMinibatch's truncation), gathered and standardised in one
+      // round; row arithmetic in 64 bits
+      const long long stride = a.rowStride, row0 = a.firstRow[ag] + (long long)(max(len, 1) - ns) * stride;
+      const int total = ns * dS;
+      for (int e0 = tid; e0 < total; e0 += 256 * 4) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const int e = e0 + 256 * u, g = e / dS, i = e - g * dS; v[u] = e < total ? a.states[(row0 + g * stride) * dS + i] : 0.f; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const int e = e0 + 256 * u; if (e < total) { const int i = e % dS; sStates[e] = (v[u] - a.stMean[i]) * a.stScale[i]; } }
+      }
+    } else {
+      // the whole window in one round from pinned host memory, standardised (Episode::standardizedState, Episode.h:172-183)
       const float* src = a.states + (size_t)off * dS;
       const int total = ns * dS;
       for (int e0 = tid; e0 < total; e0 += 256 * 4) {
@@ -204,9 +222,11 @@ __global__ __launch_bounds__(256) void act_seq_kernel(ActSeqArgs a) {
       if (lane == 0) out[o] = (double)actEval(a.outFunc, s + W[a.indBo + o]);
     }
     if (tid < a.nSig) out[a.nDense + tid] = (double)W[a.indBp + tid];
-    __threadfence_system();
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(const_cast<unsigned*>(a.done) + ag, a.tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if constexpr (!DEV) {
+      __threadfence_system();
+      __syncthreads();
+      if (tid == 0) __hip_atomic_store(const_cast<unsigned*>(a.done) + ag, a.tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }      // (DEV: the next agent's first barrier stands behind these reads of sBuf)
   }
 }
 
@@ -233,15 +253,21 @@ bool act_seq_plan(ActSeqArgs* a) {
   a->parOff = (int)w; a->stOff = (int)(w + par); a->ldsBytes = (w + par + st) * sizeof(float);
   return true;
 }
-template <bool LDSW, int GATES> static hipError_t actSeqLaunch(const ActSeqArgs& a, int nBlocks, hipStream_t s) {
-  hipError_t e = ensureDynLds(reinterpret_cast<const void*>(act_seq_kernel<LDSW, GATES>), a.ldsBytes); if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((act_seq_kernel<LDSW, GATES>), dim3(nBlocks), dim3(256), a.ldsBytes, s, a);
+template <bool LDSW, int GATES, bool DEV> static hipError_t actSeqLaunch(const ActSeqArgs& a, int nBlocks, hipStream_t s) {
+  hipError_t e = ensureDynLds(reinterpret_cast<const void*>(act_seq_kernel<LDSW, GATES, DEV>), a.ldsBytes); if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((act_seq_kernel<LDSW, GATES, DEV>), dim3(nBlocks), dim3(256), a.ldsBytes, s, a);
   return hipGetLastError();
 }
-hipError_t launch_act_seq(const ActSeqArgs& a, int nBlocks, hipStream_t s) {
-  if (a.gates == 4) return a.ldsW ? actSeqLaunch<true, 4>(a, nBlocks, s) : actSeqLaunch<false, 4>(a, nBlocks, s);
-  if (a.gates == 2) return a.ldsW ? actSeqLaunch<true, 2>(a, nBlocks, s) : actSeqLaunch<false, 2>(a, nBlocks, s);
-  return a.ldsW ? actSeqLaunch<true, 1>(a, nBlocks, s) : actSeqLaunch<false, 1>(a, nBlocks, s);
+template <bool DEV> static hipError_t actSeqPick(const ActSeqArgs& a, int nBlocks, hipStream_t s) {
+  if (a.gates == 4) return a.ldsW ? actSeqLaunch<true, 4, DEV>(a, nBlocks, s) : actSeqLaunch<false, 4, DEV>(a, nBlocks, s);
+  if (a.gates == 2) return a.ldsW ? actSeqLaunch<true, 2, DEV>(a, nBlocks, s) : actSeqLaunch<false, 2, DEV>(a, nBlocks, s);
+  return a.ldsW ? actSeqLaunch<true, 1, DEV>(a, nBlocks, s) : actSeqLaunch<false, 1, DEV>(a, nBlocks, s);
+}
+hipError_t launch_act_seq(const ActSeqArgs& a, int nBlocks, hipStream_t s) { return actSeqPick<false>(a, nBlocks, s); }
+hipError_t launch_act_seq_dev(const ActSeqArgs& a, int nBlocks, hipStream_t s) {
+  if (a.n < 1 || nBlocks < 1) return hipSuccess;
+  if (!a.firstRow || !a.nSteps || !a.states || !a.out || a.rowStride < 1) return hipErrorInvalidValue;
+  return actSeqPick<true>(a, nBlocks, s);
 }
 
 }  // namespace hl

@@ -439,9 +439,21 @@ struct ActSeqArgs {
   int nDense, nSig, nOut, ldWo; long long indWo, indBo, indBp; int outFunc;
   int ldsW, parOff, stOff; size_t ldsBytes;     // act_seq_plan: weights in LDS, offsets (floats) of the parameters / the window, dynamic LDS
   ActSeqLayer L[HL_MAX_HIDDEN];
+  // windows in the caller's device memory (launch_act_seq_dev; behind everything the host launch reads, whose offsets stay): agent i's
+  // states are rows firstRow[i] + t * rowStride, t < nSteps[i], of `states` [rows][dS]; the kernel takes the newest recWin + nApp of them.
+  // `out` is device memory then, `offset`, `done` and `tag` are not read
+  const long long* firstRow; const int* nSteps; long long rowStride;
 };
 bool act_seq_plan(ActSeqArgs* a);             // the kernel serves this net (<= 256 cells and <= 1024 inputs per layer, window within the LDS): LDS layout filled in
 hipError_t launch_act_seq(const ActSeqArgs& a, int nBlocks, hipStream_t s);
+hipError_t launch_act_seq_dev(const ActSeqArgs& a, int nBlocks, hipStream_t s);      // completion is stream order: no stamps, no system-scope fence
+// the stacked input rows of a dense net with appended observations from strided windows in device memory (actdev.hip: act_stack_dev_kernel):
+// rows[i] = the last state of agent i's window, then the ones before it, steps before the first given state repeating it (act_stack_row)
+struct ActStackDevArgs {
+  const float* states; const long long* firstRow; const int* nSteps; long long rowStride;
+  float* rows; int n, dS, nApp;
+};
+hipError_t launch_act_stack_dev(const ActStackDevArgs& a, hipStream_t s);
 hipError_t launch_episode_sweep(const EpisodeSweepArgs& a, int nBlocks, hipStream_t s);
 hipError_t launch_far_build(DevReplay rp, int nEpisodes, hipStream_t s);    // after the table or all fractions changed
 hipError_t launch_sweep_finish(DevScalars* sc, DevReplay rp, const float* redMaxAbs, const double* redErr, int countRet, int nBlocks, hipStream_t s);

@@ -1,4 +1,4 @@
-// smarties_amd/csrc/learner_dev.h -- part of learner.cpp's ONE translation unit (included there, behind learner_act.h): acting and episode ingestion from device memory: hl_forward_dev, hl_select_actions_dev, hl_append_episodes_dev
+// smarties_amd/csrc/learner_dev.h -- part of learner.cpp's ONE translation unit (included there, behind learner_act.h): acting and episode ingestion from device memory: hl_forward_dev, hl_select_actions_dev, hl_forward_sequences_dev, hl_select_actions_sequences_dev, hl_append_episodes_dev
 #pragma once
 #include "../../include/smarties_hip_dev.h"
 static_assert(HL_MAX_DIMA <= 64, "ActHeadArgs::bounded holds one bit per action component");
@@ -25,14 +25,29 @@ template <typename T> static int devEnsure(hl_learner* h, T** p, size_t* cap, si
   HIPCK(devAlloc(p, need)); *cap = need;
   return HL_OK;
 }
-// which nets the device calls serve, and what they allocate once: the scratch block the acting kernels stamp
+// the scratch block the dense acting kernels stamp, allocated once
+static int devStampsEnsure(hl_learner* h) {
+  if (!h->act.devStamps) HIPCK(devAlloc(&h->act.devStamps, (size_t)std::max(ACT_MAXROWS, act_rows_blocks(ACT_ROWS_CHUNK))));
+  return HL_OK;
+}
+// which nets the row calls serve
 static int devActEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets act on windows in host memory (hl_forward_sequences)");
   if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act through hl_forward");
   if (!act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2");
-  if (!h->act.devStamps) HIPCK(devAlloc(&h->act.devStamps, (size_t)std::max(ACT_MAXROWS, act_rows_blocks(ACT_ROWS_CHUNK))));
-  return HL_OK;
+  return devStampsEnsure(h);
+}
+// ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk), the dense nets above
+static int devSeqEnsure(hl_learner* h, const char* who) {
+  if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
+  const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
+  if (h->recurrent) {
+    if (!actSeqOk(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs");
+    return HL_OK;
+  }
+  if (h->nConv > 0 || !act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets without convolutions, input row and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear");
+  return devStampsEnsure(h);
 }
 // hl_forward's kernels on device rows, enqueued on the learner's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
 // bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows
@@ -47,6 +62,30 @@ static int devForward(hl_learner* h, int n, const float* in, double* out) {
     a.in = in + (size_t)r0 * h->dIn; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
     HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
   }
+  return HL_OK;
+}
+// n windows of the caller's device arrays, enqueued on the learner's stream.  Recurrent nets: ONE launch of the batched window kernel, which
+// gathers and truncates the windows itself (no staging, so no chunks).  Dense nets: the agents' stacked rows built by one small launch,
+// then devForward on them
+static_assert(sizeof(long long) == sizeof(int64_t), "the row tables are passed on as they come");
+static int devSeqForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
+  if (h->recurrent) {
+    ActSeqArgs a = h->act.seqArgs;
+    a.states = states; a.firstRow = reinterpret_cast<const long long*>(firstRow); a.nSteps = nSteps; a.rowStride = rowStride; a.out = out; a.n = n;
+    HIPCK(timed(h, "act_seq_dev", h->stream, [&] { return launch_act_seq_dev(a, std::min(n, h->act.cus), h->stream); }));
+    return HL_OK;
+  }
+  ActStackDevArgs sa{states, reinterpret_cast<const long long*>(firstRow), nSteps, rowStride, h->act.devRows, n, h->dS, h->nApp};
+  HIPCK(timed(h, "act_stack_dev", h->stream, [&] { return launch_act_stack_dev(sa, h->stream); }));
+  return devForward(h, n, h->act.devRows, out);
+}
+// RACER::selectAction's head on n rows of network outputs (actdev.hip: act_head_kernel)
+static int devHead(hl_learner* h, int n, const double* O, const double* dNoise, double* dActions, double* dMu, float* dValues, float* dAdvantages) {
+  ActHeadArgs a{};
+  a.O = O; a.noise = dNoise; a.act = dActions; a.mu = dMu; a.V = dValues; a.ADV = dAdvantages;
+  a.n = n; a.dA = h->dA; a.nOut = h->nOut; a.nDense = h->nDense; a.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; a.nOpt = h->nOpt;
+  for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) a.bounded |= 1ull << i;
+  HIPCK(timed(h, "act_head_kernel", h->stream, [&] { return launch_act_head(a, h->stream); }));
   return HL_OK;
 }
 }  // extern "C++"
@@ -70,11 +109,35 @@ int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const 
   { int rc = devEnsure(h, &h->act.devOut, &h->act.devOutCap, (size_t)n * h->nOut); if (rc) return rc; }
   { int rc = devEnter(h, stream); if (rc) return rc; }
   { int rc = devForward(h, n, dStates, h->act.devOut); if (rc) return rc; }
-  ActHeadArgs a{};
-  a.O = h->act.devOut; a.noise = dNoise; a.act = dActions; a.mu = dMu; a.V = dValues; a.ADV = dAdvantages;
-  a.n = n; a.dA = h->dA; a.nOut = h->nOut; a.nDense = h->nDense; a.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; a.nOpt = h->nOpt;
-  for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) a.bounded |= 1ull << i;
-  HIPCK(timed(h, "act_head_kernel", h->stream, [&] { return launch_act_head(a, h->stream); }));
+  { int rc = devHead(h, n, h->act.devOut, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
+  return devLeave(h, stream);
+}
+
+int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride, const float* dStates,
+                             double* dOutputs, void* stream) {
+  if (!h || n < 0 || (n > 0 && (!dFirstRow || !dNSteps || !dStates || !dOutputs))) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  { int rc = devSeqEnsure(h, "hl_forward_sequences_dev"); if (rc) return rc; }
+  if (n == 0) return HL_OK;
+  if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_forward_sequences_dev: row_stride below 1");
+  if (!h->recurrent) { int rc = devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn); if (rc) return rc; }
+  { int rc = devEnter(h, stream); if (rc) return rc; }
+  { int rc = devSeqForward(h, n, dFirstRow, dNSteps, row_stride, dStates, dOutputs); if (rc) return rc; }
+  return devLeave(h, stream);
+}
+
+int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride, const float* dStates,
+                                    const double* dNoise, double* dActions, double* dMu, float* dValues, float* dAdvantages, void* stream) {
+  if (!h || n < 0 || (n > 0 && (!dFirstRow || !dNSteps || !dStates || !dActions || !dMu || !dValues || !dAdvantages))) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  { int rc = devSeqEnsure(h, "hl_select_actions_sequences_dev"); if (rc) return rc; }
+  if (n == 0) return HL_OK;
+  if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_select_actions_sequences_dev: row_stride below 1");
+  if (!h->recurrent) { int rc = devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn); if (rc) return rc; }
+  { int rc = devEnsure(h, &h->act.devOut, &h->act.devOutCap, (size_t)n * h->nOut); if (rc) return rc; }
+  { int rc = devEnter(h, stream); if (rc) return rc; }
+  { int rc = devSeqForward(h, n, dFirstRow, dNSteps, row_stride, dStates, h->act.devOut); if (rc) return rc; }
+  { int rc = devHead(h, n, h->act.devOut, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
   return devLeave(h, stream);
 }
 

@@ -39,6 +39,7 @@ struct ActState {
   // acting kernels' stamps, the network outputs between the forward pass and the head kernel, the episode sums read back for the episode log
   hipEvent_t devIn = nullptr, devDone = nullptr; unsigned* devStamps = nullptr;
   double* devOut = nullptr; size_t devOutCap = 0; double* devSums = nullptr; size_t devSumsCap = 0;
+  float* devRows = nullptr; size_t devRowsCap = 0;      // hl_forward_sequences_dev, dense nets with appended observations: the stacked rows
 };
 }  // namespace
 
