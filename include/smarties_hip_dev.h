@@ -11,8 +11,9 @@
  * host fp64.  A simulator on the learner's GPU holds states, actions and rewards as device arrays already: the calls below take
  * DEVICE pointers (a torch tensor's data_ptr(): the library shares the process's HIP runtime) and never touch host copies of the data.
  * hl_forward_dev and hl_select_actions_dev act on rows (dense nets), hl_forward_sequences_dev and hl_select_actions_sequences_dev on
- * windows of a strided rollout buffer (recurrent nets, and dense nets whose appended observations they stack), hl_append_episodes_dev
- * stores the finished episodes of any net.
+ * windows of a strided rollout buffer (recurrent nets, dense nets whose appended observations they stack, and feed-forward nets behind
+ * convolutions, whose stacked frames they read from a one-frame-per-step buffer), hl_append_episodes_dev stores the finished episodes
+ * of any net.
  *
  * Streams.  `stream` is the caller's hipStream_t passed as void*; NULL is the null stream.  Every call takes the learner's lock,
  * refuses between hl_step_begin and hl_step_end (HL_ERR_STATE, as hl_forward), records an event on `stream` that the learner's stream
@@ -41,7 +42,9 @@ extern "C" {
  * hl_forward sends over the training buffers and this call does not (the two agree to rounding there).
  * The minibatch buffers and a minibatch drawn ahead are not touched.
  *
- * Status: HL_ERR_UNSUPPORTED (with a message) for every other net -- recurrent layers (hl_forward_sequences_dev below), convolutions in front, wider rows or layers,
+ * Status: HL_ERR_UNSUPPORTED (with a message) for every other net -- recurrent layers (hl_forward_sequences_dev below),
+ * convolutions in front (hl_forward_sequences_dev below as well, the message names it: the conv-stack kernel reads an agent's row from
+ * the states of its window; a net without appended observations passes windows of one state), wider rows or layers,
  * SMARTIES_HIP_GENERIC bit 2.  HL_ERR_STATE between hl_step_begin and hl_step_end.  n == 0: HL_OK, nothing is enqueued. */
 HL_API int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream);
 
@@ -86,9 +89,27 @@ HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates,
  * agents' rows [n][dimS (1 + nAppendedObs)] -- the last state, then the ones before it, steps before the first given state repeating
  * it -- into a buffer of the library, then hl_forward_dev's kernels run on those rows (no truncation: a dense net reads
  * 1 + nAppendedObs states whatever the window's length).
+ * Served, feed-forward nets behind convolutions: those of hl_forward's conv-stack route (smarties_amd/csrc/actconv.hip) -- image, maps
+ * and offset tables within 160 KB of a workgroup's LDS, feature rows and the dense layers behind at most 2048 wide, SMARTIES_HIP_GENERIC
+ * bit 2 clear -- WHATEVER the row size: HL_ACT_CONV_MAX_ROW_BYTES is a switch of the host route's copy into pinned staging and does not
+ * apply to rows that lie in device memory (the stack of settings/RACER_atari.json, rows of 110 KB, is served without any environment
+ * switch).  With frame stacking (nAppendedObs = k: the image's channels are the last k + 1 frames) the simulator stores ONE frame per
+ * step in a [T][nEnv][dimS] buffer and passes the episode's start row and t + 1.  Element c of agent i's stacked row
+ * [dimS (1 + nAppendedObs)] is component c % dimS of the state j = c / dimS steps before the newest, read from row
+ *     dFirstRow[i] + max(max(dNSteps[i], 1) - 1 - j, 0) * row_stride
+ * -- steps before the first given state repeat it, a longer window is read from its newest 1 + nAppendedObs states only.  Two launches
+ * in the learner's stream: act_conv_dev_kernel, ONE launch for any n of min(n, compute units) workgroups walking the agents, each
+ * loading its agent's row straight from those states (no [n][row] intermediate; 16-byte loads where dimS, the row and the image are
+ * multiples of 4 floats and dStates is 16-byte aligned, scalar loads of the same values otherwise), standardising it on load and running
+ * the whole conv stack out of LDS; then the row-block kernel on the feature rows per HL_ACT_ROWS_CHUNK agents, outputs to dOutputs.
+ * From the standardised row on the arithmetic and its order are act_conv_kernel's: an agent's outputs equal hl_forward's on the same
+ * stacked row bit for bit wherever hl_forward takes the conv-stack route (rows up to HL_ACT_CONV_MAX_ROW_BYTES; beyond them hl_forward
+ * runs the training launches, which agree to rounding).
  *
- * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other net -- layers beyond 256 cells (the
- * time-step-major nets), inputs beyond 1024, convolutions in front, encoder_rnn layers: they act on windows in host memory.
+ * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other recurrent net -- layers beyond 256 cells (the
+ * time-step-major nets), inputs beyond 1024, convolutions in front, encoder_rnn layers: they act on windows in host memory -- and, with
+ * a message naming hl_forward, for feed-forward nets behind convolutions beyond the conv-stack kernel's plan (image plus maps beyond
+ * 160 KB of LDS; feature rows beyond 2048, the Nature-DQN stack among them; SMARTIES_HIP_GENERIC bit 2).
  * HL_ERR_BAD_ARG for a null handle or array, n < 0 or row_stride < 1.  HL_ERR_STATE between hl_step_begin and hl_step_end.
  * n == 0: HL_OK, nothing is enqueued.  The minibatch buffers and a minibatch drawn ahead are not touched. */
 HL_API int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride,
@@ -96,8 +117,8 @@ HL_API int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFi
 
 /* hl_select_actions_dev on windows: the forward pass of hl_forward_sequences_dev into a buffer of the library, then the same ONE launch
  * of act_head_kernel.  dNoise and the four outputs as for hl_select_actions_dev; the windows, nets and status as for
- * hl_forward_sequences_dev.  With hl_append_episodes_dev the loop act -> simulate -> append -> step of a recurrent net never leaves
- * the device. */
+ * hl_forward_sequences_dev.  With hl_append_episodes_dev the loop act -> simulate -> append -> step of a recurrent net, or of a net
+ * behind convolutions, never leaves the device. */
 HL_API int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride,
                                            const float* dStates, const double* dNoise, double* dActions, double* dMu, float* dValues,
                                            float* dAdvantages, void* stream);

@@ -42,9 +42,18 @@ __device__ __forceinline__ f32x4 acFilter(const float* __restrict__ wr, int k0, 
   return v;
 }
 
+// The kernels read their one argument through the kernel-argument segment (scalar loads of constant memory) and take the pointer as new
+// at every row and every layer: a field is then loaded where it is used, not kept in a scalar register from the kernel's start on.
+// (Read as a by-value parameter the fields of all layers and of both load paths stay live together: act_conv_kernel parked 13 scalar
+// registers in vector lanes that way, the window kernel 19; now neither parks any.)
+typedef const __attribute__((address_space(4))) ActConvArgs* AcArgs;
+typedef const __attribute__((address_space(4))) ActConvLayer& AcLayerRef;
+__device__ __forceinline__ AcArgs acArgs() { return (AcArgs)__builtin_amdgcn_kernarg_segment_ptr(); }
+__device__ __forceinline__ AcArgs acFresh(AcArgs a) { asm volatile("" : "+s"(a)); return a; }
+
 // one layer of one row: sIn -> out (LDS or the row's feature vector), [c][oy][ox]
 template <bool VEC>
-__device__ __forceinline__ void acLayer(const ActConvLayer& L, const float* __restrict__ W, const int* sTab, const float* sIn, float* out,
+__device__ __forceinline__ void acLayer(AcLayerRef L, const float* __restrict__ W, const int* sTab, const float* sIn, float* out,
                                         int wave, int li, int lc) {
   const int K = L.K, P = L.P, KnC = L.KnC;
   const int nPT = (P + 15) >> 4, npg = L.npg, nPG = (nPT + npg - 1) / npg, nU = ((KnC + 15) >> 4) * nPG, nB = (K + 15) >> 4;
@@ -99,14 +108,10 @@ __device__ __forceinline__ void acLayer(const ActConvLayer& L, const float* __re
   }
 }
 
-__global__ __launch_bounds__(256) void act_conv_kernel(ActConvArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sDyn[];      // offset tables | image | map buffer 0 | map buffer 1
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
-  int* sTab = reinterpret_cast<int*>(sDyn);
-  float* sImg = sDyn + a.imgOff;
-  const float* __restrict__ W = a.W;
-  for (int l = 0; l < a.nL; ++l) {
-    const ActConvLayer& L = a.L[l];
+// the layers' offset tables k -> ic InY InX + fy InX + fx, once per workgroup
+__device__ __forceinline__ void acTables(AcArgs a, int* sTab, int tid) {
+  for (int l = 0; l < a->nL; ++l) {
+    AcLayerRef L = a->L[l];
     const int fsz = L.KnY * L.KnX, Kp = (L.K + 15) & ~15;
     for (int k = tid; k < Kp; k += 256) {
       int off = 0;
@@ -114,58 +119,109 @@ __global__ __launch_bounds__(256) void act_conv_kernel(ActConvArgs a) {
       sTab[L.tabOff + k] = off;
     }
   }
-  const int img = a.img, dIn = a.dIn, dS = a.dS;
-  for (int row = blockIdx.x; row < a.n; row += gridDim.x) {
-    const float* src = a.in + (size_t)row * dIn;
-    float* fr = a.feat + (size_t)row * a.ldF;
-    // the raw row, standardised (Episode::standardizedState, Episode.h:172-183): image -> LDS, extras -> the feature vector's front
-    if (a.vec) {      // dIn, dS and the image are multiples of 4: 16-byte loads, four in flight per thread
-      const f32x4* src4 = reinterpret_cast<const f32x4*>(src);
-      const int n4 = dIn >> 2;
-      for (int i0 = 0; i0 < n4; i0 += 1024) {
-        f32x4 v[4];
+}
+
+// where element c of a row's raw values lies (vec: c is a multiple of 4 and four elements are contiguous and 16-byte aligned there)
+struct AcRowSrc {      // a row of [n][dIn] (act_conv_kernel)
+  const float* p;
+  __device__ __forceinline__ const float* at(int c, int) const { return p + c; }
+};
+struct AcWindowSrc {   // the newest 1 + nAppendedObs states of a strided window (act_conv_dev_kernel): block j of the row is the state max(last - j, 0)
+  const float* states; long long first, stride; int last;
+  __device__ __forceinline__ const float* at(int c, int dS) const {
+    const int j = c / dS, k = c - j * dS;
+    return states + (first + (long long)max(last - j, 0) * stride) * dS + k;
+  }
+};
+
+// the raw row, standardised (Episode::standardizedState, Episode.h:172-183): image -> LDS, extras -> the feature vector's front
+template <typename Src>
+__device__ __forceinline__ void acLoadRow(AcArgs a, const Src& src, float* sImg, float* fr, int tid) {
+  const int img = a->img, dIn = a->dIn, dS = a->dS;
+  if (a->vec) {      // dIn, dS and the image are multiples of 4: 16-byte loads, four in flight per thread
+    const int n4 = dIn >> 2;
+    for (int i0 = 0; i0 < n4; i0 += 1024) {
+      f32x4 v[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { const int i = i0 + tid + 256 * q; v[q] = i < n4 ? src4[i] : f32x4{0.f, 0.f, 0.f, 0.f}; }
+      for (int q = 0; q < 4; ++q) { const int i = i0 + tid + 256 * q; v[q] = i < n4 ? *reinterpret_cast<const f32x4*>(src.at(4 * i, dS)) : f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int i = i0 + tid + 256 * q;
-          if (i < n4) {
-            const int c = 4 * i, k = c % dS;
-            const f32x4 mean = *reinterpret_cast<const f32x4*>(a.stMean + k), scale = *reinterpret_cast<const f32x4*>(a.stScale + k);
-            const f32x4 y = (v[q] - mean) * scale;
-            if (c < img) *reinterpret_cast<f32x4*>(sImg + c) = y;
-            else {
+      for (int q = 0; q < 4; ++q) {
+        const int i = i0 + tid + 256 * q;
+        if (i < n4) {
+          const int c = 4 * i, k = c % dS;
+          const f32x4 mean = *reinterpret_cast<const f32x4*>(a->stMean + k), scale = *reinterpret_cast<const f32x4*>(a->stScale + k);
+          const f32x4 y = (v[q] - mean) * scale;
+          if (c < img) *reinterpret_cast<f32x4*>(sImg + c) = y;
+          else {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) fr[c - img + e] = y[e];
-            }
-          }
-        }
-      }
-    } else {
-      for (int c0 = 0; c0 < dIn; c0 += 1024) {
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int c = c0 + tid + 256 * q; v[q] = c < dIn ? src[c] : 0.f; }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int c = c0 + tid + 256 * q;
-          if (c < dIn) {
-            const int k = c % dS;
-            const float y = (v[q] - a.stMean[k]) * a.stScale[k];
-            if (c < img) sImg[c] = y; else fr[c - img] = y;
+            for (int e = 0; e < 4; ++e) fr[c - img + e] = y[e];
           }
         }
       }
     }
-    __syncthreads();
-    for (int l = 0; l < a.nL; ++l) {
-      const ActConvLayer& L = a.L[l];
-      const float* sIn = l == 0 ? sImg : sDyn + a.bufOff[(l - 1) & 1];
-      float* out = l == a.nL - 1 ? fr + a.extras : sDyn + a.bufOff[l & 1];
-      if (L.vec) acLayer<true>(L, W, sTab, sIn, out, wave, li, lc);
-      else acLayer<false>(L, W, sTab, sIn, out, wave, li, lc);
-      __syncthreads();      // the map is complete; every wavefront has read its input (the next row's image may take its place)
+  } else {
+    for (int c0 = 0; c0 < dIn; c0 += 1024) {
+      float v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { const int c = c0 + tid + 256 * q; v[q] = c < dIn ? *src.at(c, dS) : 0.f; }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = c0 + tid + 256 * q;
+        if (c < dIn) {
+          const int k = c % dS;
+          const float y = (v[q] - a->stMean[k]) * a->stScale[k];
+          if (c < img) sImg[c] = y; else fr[c - img] = y;
+        }
+      }
     }
+  }
+}
+
+// the conv stack on the row in LDS: the maps alternate between the two buffers, the last one goes behind the extras of the feature vector
+__device__ __forceinline__ void acRowLayers(AcArgs a, const int* sTab, float* sDyn, const float* sImg, float* fr, int wave, int li, int lc) {
+  const float* __restrict__ W = a->W;
+  __syncthreads();
+  for (int l = 0; l < a->nL; ++l) {
+    a = acFresh(a);
+    AcLayerRef L = a->L[l];
+    const float* sIn = l == 0 ? sImg : sDyn + a->bufOff[(l - 1) & 1];
+    float* out = l == a->nL - 1 ? fr + a->extras : sDyn + a->bufOff[l & 1];
+    if (L.vec) acLayer<true>(L, W, sTab, sIn, out, wave, li, lc);
+    else acLayer<false>(L, W, sTab, sIn, out, wave, li, lc);
+    __syncthreads();      // the map is complete; every wavefront has read its input (the next row's image may take its place)
+  }
+}
+
+__global__ __launch_bounds__(256) void act_conv_kernel(ActConvArgs) {
+  extern __shared__ __attribute__((aligned(16))) float sDyn[];      // offset tables | image | map buffer 0 | map buffer 1
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
+  AcArgs a = acArgs();
+  int* sTab = reinterpret_cast<int*>(sDyn);
+  float* sImg = sDyn + a->imgOff;
+  acTables(a, sTab, tid);
+  for (int row = blockIdx.x; row < a->n; row += gridDim.x) {
+    a = acFresh(a);
+    float* fr = a->feat + (size_t)row * a->ldF;
+    acLoadRow(a, AcRowSrc{a->in + (size_t)row * a->dIn}, sImg, fr, tid);
+    acRowLayers(a, sTab, sDyn, sImg, fr, wave, li, lc);
+  }
+}
+
+// the same on windows of the caller's device array (hl_forward_sequences_dev): agent `row` reads its stacked row straight from the states of
+// its window -- the mapping of act_stack_dev_kernel (actdev.hip) and act_stack_row (act_host.h), row arithmetic in 64 bits --, no
+// [n][dIn] intermediate.  Only the loads differ: from the standardised row on the arithmetic and its order are act_conv_kernel's
+__global__ __launch_bounds__(256) void act_conv_dev_kernel(ActConvArgs) {
+  extern __shared__ __attribute__((aligned(16))) float sDyn[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
+  AcArgs a = acArgs();
+  int* sTab = reinterpret_cast<int*>(sDyn);
+  float* sImg = sDyn + a->imgOff;
+  acTables(a, sTab, tid);
+  for (int row = blockIdx.x; row < a->n; row += gridDim.x) {
+    a = acFresh(a);
+    float* fr = a->feat + (size_t)row * a->ldF;
+    acLoadRow(a, AcWindowSrc{a->in, a->firstRow[row], a->rowStride, max(a->nSteps[row], 1) - 1}, sImg, fr, tid);
+    acRowLayers(a, sTab, sDyn, sImg, fr, wave, li, lc);
   }
 }
 
@@ -205,6 +261,14 @@ hipError_t launch_act_conv(const ActConvArgs& a, int nBlocks, hipStream_t s) {
   if (a.n < 1 || nBlocks < 1 || a.ldsBytes == 0 || a.ldF < a.nF) return hipErrorInvalidValue;
   hipError_t e = ensureDynLds(reinterpret_cast<const void*>(act_conv_kernel), a.ldsBytes); if (e != hipSuccess) return e;
   hipLaunchKernelGGL(act_conv_kernel, dim3(std::min(nBlocks, a.n)), dim3(256), a.ldsBytes, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_act_conv_dev(const ActConvArgs& a, int nBlocks, hipStream_t s) {
+  if (a.n < 1 || nBlocks < 1 || a.ldsBytes == 0 || a.ldF < a.nF || !a.in || !a.feat || !a.firstRow || !a.nSteps || a.rowStride < 1) return hipErrorInvalidValue;
+  hipError_t e = ensureDynLds(reinterpret_cast<const void*>(act_conv_dev_kernel), a.ldsBytes); if (e != hipSuccess) return e;
+  ActConvArgs d = a;
+  if (reinterpret_cast<uintptr_t>(a.in) & 15) d.vec = 0;      // (a state then starts at no 16-byte boundary: the scalar loads, the same values)
+  hipLaunchKernelGGL(act_conv_dev_kernel, dim3(std::min(nBlocks, a.n)), dim3(256), a.ldsBytes, s, d);
   return hipGetLastError();
 }
 

@@ -424,9 +424,13 @@ struct ActConvArgs {
   int img, extras, nF, vec;        // act_conv_plan: floats of the image, state variables behind it, width of a feature row, 16-byte row loads
   int imgOff, bufOff[2]; size_t ldsBytes;      // ... LDS offsets (floats) of the image and the two map buffers, dynamic LDS
   ActConvLayer L[HL_MAX_CONV];
+  // windows in the caller's device memory (launch_act_conv_dev; behind everything the host launch reads, whose offsets stay): `in` is the
+  // [rows][dS] array of states then, agent i's row [dIn] the states firstRow[i] + max(max(nSteps[i], 1) - 1 - j, 0) * rowStride, j = 0 .. nAppendedObs
+  const long long* firstRow; const int* nSteps; long long rowStride;
 };
 bool act_conv_plan(ActConvArgs* a);       // the kernel serves this net (feed-forward behind the stack, image + maps + offset tables within 160 KB of LDS, feature row <= ACT_ROWS_MAXW): layout filled in
 hipError_t launch_act_conv(const ActConvArgs& a, int nBlocks, hipStream_t s);
+hipError_t launch_act_conv_dev(const ActConvArgs& a, int nBlocks, hipStream_t s);      // 16-byte row loads only where a.vec and `in` is 16-byte aligned
 // rollout inference of recurrent nets for many agents (actseq.hip: act_seq_kernel): a workgroup stages the recurrent stack once and
 // walks its agents' windows; states, window offsets, outputs and per-agent stamps in pinned host memory
 constexpr int ACT_SEQ_CHUNK = 512;      // agents per launch (HL_ACT_SEQ_CHUNK of include/smarties_hip_act.h)

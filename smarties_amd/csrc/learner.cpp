@@ -433,7 +433,7 @@ int hl_destroy(hl_learner* h) {
     h->dRedMax, h->dRedErr, h->dMomPartial, h->dMoments, h->dMomentsPrev, h->dStatsOut, h->dStatsIns,
     h->rp.S, h->rp.A, h->rp.MU, h->rp.R, h->rp.V, h->rp.ADV, h->rp.RET, h->rp.DQ, h->rp.IMPW, h->rp.DKL,
     h->rp.epOff, h->rp.epN, h->rp.epTerm, h->rp.epAgg, h->rp.posEid, h->rp.posPrefix, h->rp.stMean, h->rp.stScale,
-    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->act.dS, h->act.dO, h->act.convFeat, h->act.devStamps, h->act.devOut, h->act.devSums, h->act.devRows};
+    h->rp.stStd, h->rp.epTag, h->rp.posRec, h->rp.farP, h->rp.farN, h->rp.farStart, h->panelCtr, h->panelOpart, h->act.dS, h->act.dO, h->act.convFeat, h->act.devStamps, h->act.devOut, h->act.devSums, h->act.devRows, h->act.devFeat};
   for (hipEvent_t ev : {h->act.devIn, h->act.devDone}) if (ev) hipEventDestroy(ev);
   for (int pb = 0; pb < 2; ++pb) {
     DevBatch& bt = h->buf[pb].bt;

@@ -113,17 +113,14 @@ static bool act_rows_ok(hl_learner* h) {
   h->act.rowsOk = 1;
   return true;
 }
-// the conv-stack kernel (actconv.hip) and the row-block kernel behind it serve this net: feed-forward, convolutions in front, image and maps
+// the conv-stack kernels (actconv.hip) and the row-block kernel behind them serve this net: feed-forward, convolutions in front, image and maps
 // within a workgroup's LDS, feature rows and dense layers within the row-block kernel's bounds; SMARTIES_HIP_GENERIC bit 2 keeps the route
-// over the training buffers.  Depends on the net only, never on n: a row's result is the same alone, among others and through the
-// window calls
-static bool act_conv_ok(hl_learner* h) {
-  if (h->act.convOk) return h->act.convOk > 0;
-  h->act.convOk = -1;
+// over the training buffers.  Depends on the net only, never on n or on where the rows lie: hl_forward's route (act_conv_ok) and the
+// window calls on device memory (learner_dev.h: devSeqEnsure) both ask it
+static bool act_conv_plan_ok(hl_learner* h) {
+  if (h->act.convPlanOk) return h->act.convPlanOk > 0;
+  h->act.convPlanOk = -1;
   if (h->nConv < 1 || h->nHidden < 2 || (h->generic & 2)) return false;
-  // raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES: the copy into pinned staging costs more than the route saves (the header's figures);
-  // SMARTIES_HIP_GENERIC bit 4096 holds the switch open (tests, tools/act_conv_timing.py)
-  if ((size_t)h->dIn * sizeof(float) > (size_t)HL_ACT_CONV_MAX_ROW_BYTES && !(h->generic & 4096)) return false;
   ActConvArgs& c = h->act.convArgs; c = ActConvArgs{};
   c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
   c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = h->recurrent ? 1 : 0;
@@ -136,6 +133,18 @@ static bool act_conv_ok(hl_learner* h) {
   actFillShared(h, a); a.stMean = nullptr; a.stScale = nullptr;
   a.dS = c.nF; a.dIn = c.nF; a.nL = actFillLayers(h, 1, a.L);
   if (!act_rows_plan(&a) || actCus(h) < 1) return false;
+  h->act.convPlanOk = 1;
+  return true;
+}
+// ... and hl_forward takes that route: rows in HOST memory go through pinned staging, so on top of the plan the row-size switch.
+// A row's result is the same alone, among others and through the window calls
+static bool act_conv_ok(hl_learner* h) {
+  if (h->act.convOk) return h->act.convOk > 0;
+  h->act.convOk = -1;
+  // raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES: the copy into pinned staging costs more than the route saves (the header's figures);
+  // SMARTIES_HIP_GENERIC bit 4096 holds the switch open (tests, tools/act_conv_timing.py)
+  if ((size_t)h->dIn * sizeof(float) > (size_t)HL_ACT_CONV_MAX_ROW_BYTES && !(h->generic & 4096)) return false;
+  if (!act_conv_plan_ok(h)) return false;
   // rows per chunk: no more than HL_ACT_CONV_STAGE_BYTES of staged raw rows, whole blocks of 16 rows, at least one
   const size_t fit = (size_t)HL_ACT_CONV_STAGE_BYTES / ((size_t)h->dIn * sizeof(float));
   h->act.convCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, fit) & ~(size_t)15));

@@ -34,11 +34,12 @@ static int devStampsEnsure(hl_learner* h) {
 static int devActEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets act on windows in host memory (hl_forward_sequences)");
-  if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act through hl_forward");
+  if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act on windows in device memory (hl_forward_sequences_dev; without appended observations: windows of one state)");
   if (!act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2");
   return devStampsEnsure(h);
 }
-// ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk), the dense nets above
+// ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk), the dense nets above, the feed-forward nets behind
+// convolutions of the conv-stack kernel's plan (act_conv_plan_ok: whatever the row size -- the rows lie in device memory)
 static int devSeqEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
@@ -46,8 +47,18 @@ static int devSeqEnsure(hl_learner* h, const char* who) {
     if (!actSeqOk(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs");
     return HL_OK;
   }
-  if (h->nConv > 0 || !act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets without convolutions, input row and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear");
+  if (h->nConv > 0) {
+    if (!act_conv_plan_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": this net acts on rows in host memory (hl_forward); served here behind convolutions: image and maps within 160 KB of LDS, feature rows and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear");
+    return devStampsEnsure(h);
+  }
+  if (!act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets with input row and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear");
   return devStampsEnsure(h);
+}
+// the library's buffer between the window calls' two launches: the stacked rows of a dense net, the feature rows of a net behind convolutions
+static int devSeqRowsEnsure(hl_learner* h, int n) {
+  if (h->recurrent) return HL_OK;
+  if (h->nConv > 0) return devEnsure(h, &h->act.devFeat, &h->act.devFeatCap, (size_t)n * h->act.convArgs.nF);
+  return devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn);
 }
 // hl_forward's kernels on device rows, enqueued on the learner's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
 // bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows
@@ -65,14 +76,26 @@ static int devForward(hl_learner* h, int n, const float* in, double* out) {
   return HL_OK;
 }
 // n windows of the caller's device arrays, enqueued on the learner's stream.  Recurrent nets: ONE launch of the batched window kernel, which
-// gathers and truncates the windows itself (no staging, so no chunks).  Dense nets: the agents' stacked rows built by one small launch,
-// then devForward on them
+// gathers and truncates the windows itself (no staging, so no chunks).  Behind convolutions: ONE launch of the conv-stack kernel, which reads
+// every agent's stacked row from its window's states, then the row-block kernel on the feature rows per chunk of ACT_ROWS_CHUNK (hl_forward's
+// two launches without the staging).  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
 static_assert(sizeof(long long) == sizeof(int64_t), "the row tables are passed on as they come");
 static int devSeqForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
   if (h->recurrent) {
     ActSeqArgs a = h->act.seqArgs;
     a.states = states; a.firstRow = reinterpret_cast<const long long*>(firstRow); a.nSteps = nSteps; a.rowStride = rowStride; a.out = out; a.n = n;
     HIPCK(timed(h, "act_seq_dev", h->stream, [&] { return launch_act_seq_dev(a, std::min(n, h->act.cus), h->stream); }));
+    return HL_OK;
+  }
+  if (h->nConv > 0) {
+    ActConvArgs c = h->act.convArgs;
+    c.in = states; c.firstRow = reinterpret_cast<const long long*>(firstRow); c.nSteps = nSteps; c.rowStride = rowStride; c.feat = h->act.devFeat; c.n = n;
+    HIPCK(timed(h, "act_conv_dev", h->stream, [&] { return launch_act_conv_dev(c, h->act.cus, h->stream); }));
+    for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
+      ActRowsArgs a = h->act.convRowsArgs;
+      a.in = h->act.devFeat + (size_t)r0 * c.nF; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
+      HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+    }
     return HL_OK;
   }
   ActStackDevArgs sa{states, reinterpret_cast<const long long*>(firstRow), nSteps, rowStride, h->act.devRows, n, h->dS, h->nApp};
@@ -120,7 +143,7 @@ int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow,
   { int rc = devSeqEnsure(h, "hl_forward_sequences_dev"); if (rc) return rc; }
   if (n == 0) return HL_OK;
   if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_forward_sequences_dev: row_stride below 1");
-  if (!h->recurrent) { int rc = devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn); if (rc) return rc; }
+  { int rc = devSeqRowsEnsure(h, n); if (rc) return rc; }
   { int rc = devEnter(h, stream); if (rc) return rc; }
   { int rc = devSeqForward(h, n, dFirstRow, dNSteps, row_stride, dStates, dOutputs); if (rc) return rc; }
   return devLeave(h, stream);
@@ -133,7 +156,7 @@ int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFi
   { int rc = devSeqEnsure(h, "hl_select_actions_sequences_dev"); if (rc) return rc; }
   if (n == 0) return HL_OK;
   if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_select_actions_sequences_dev: row_stride below 1");
-  if (!h->recurrent) { int rc = devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn); if (rc) return rc; }
+  { int rc = devSeqRowsEnsure(h, n); if (rc) return rc; }
   { int rc = devEnsure(h, &h->act.devOut, &h->act.devOutCap, (size_t)n * h->nOut); if (rc) return rc; }
   { int rc = devEnter(h, stream); if (rc) return rc; }
   { int rc = devSeqForward(h, n, dFirstRow, dNSteps, row_stride, dStates, h->act.devOut); if (rc) return rc; }

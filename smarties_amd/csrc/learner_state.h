@@ -27,7 +27,8 @@ struct ActState {
   unsigned tag = 0; int cus = 0;      // the last completion stamp handed out (actNextTag); compute units of the device, asked once (actCus)
   int fewOk = 0;                      // a few rows of a dense net, a workgroup per row (misc.hip: act_forward_kernel)
   int rowsOk = 0; bool rowsSmall = false; ActRowsArgs rowsArgs{};      // many rows of a dense net (actrows.hip); the net takes the route at any row count (ACT_ROWS_SMALL_NET)
-  int convOk = 0, convCap = 0; ActConvArgs convArgs{}; ActRowsArgs convRowsArgs{};      // rows of a feed-forward net behind convolutions (actconv.hip + actrows.hip); rows per chunk
+  int convPlanOk = 0; ActConvArgs convArgs{}; ActRowsArgs convRowsArgs{};      // a feed-forward net behind convolutions (actconv.hip + actrows.hip): the plan serves it
+  int convOk = 0, convCap = 0;        // ... and hl_forward takes that route for rows in host memory (the row-size switch); rows per chunk
   int seqOk = 0; ActSeqArgs seqArgs{};      // many agents' windows: the batched window kernel (actseq.hip)
   int tmOk = 0, winOk = 0;            // ... as one chain of the time-step-major launches (rectm.hip) / of the workgroup-per-sample window kernels (rec.hip)
   // three pinned, device-mapped blocks, each allocated at the first call that takes a route through it, and their carves (act_host.h):
@@ -40,6 +41,7 @@ struct ActState {
   hipEvent_t devIn = nullptr, devDone = nullptr; unsigned* devStamps = nullptr;
   double* devOut = nullptr; size_t devOutCap = 0; double* devSums = nullptr; size_t devSumsCap = 0;
   float* devRows = nullptr; size_t devRowsCap = 0;      // hl_forward_sequences_dev, dense nets with appended observations: the stacked rows
+  float* devFeat = nullptr; size_t devFeatCap = 0;      // ... nets behind convolutions: the agents' feature rows [n][nF] between the two launches
 };
 }  // namespace
 
