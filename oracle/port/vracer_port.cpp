@@ -33,10 +33,21 @@
 namespace {
 
 using Real = double;   // Settings/Definitions.h:27
+// -DOL_WIDE (liboracle_port64.so, `make port64`): the same restatement with the network's ARRAYS -- weights, moments,
+// gradients, activations, errors -- and the arithmetic on their elements in double.  It is the higher-precision yardstick
+// the fp32 restatement and the HIP kernels are both measured against.  Everything the reference computes as a float
+// SCALAR (nnScalar: Adam's step sizes and decay factors, the initialisation factors, the state / reward scaling, the
+// activation functions' constants) stays float in both builds, and so do the replay memory (Fval) and the samplers: the
+// two builds then take the same discrete decisions and differ only by the rounding of array elements.
+#ifdef OL_WIDE
+using nnReal = double;
+#else
 using nnReal = float;  // Settings/Definitions.h:46 (-DSINGLE_PREC)
+#endif
+using nnScalar = float;  // what Definitions.h:46 makes of a scalar nnReal, in either build
 using Fval = float;    // Settings/Definitions.h:50
 
-constexpr nnReal nnEPS = FLT_EPSILON;  // Settings/Bund.h:113
+constexpr nnScalar nnEPS = FLT_EPSILON;  // Settings/Bund.h:113
 
 inline int64_t roundUp8(int64_t n) { return (n + 7) / 8 * 8; }  // Utils/FunctionUtilities.h:74-83
 
@@ -116,7 +127,7 @@ inline nnReal fEval(int f, nnReal in) {
       else        { const nnReal e = std::exp( 2 * in); return (e - 1) / (1 + e); }
     case HL_FUNC_SOFTSIGN: return in / (1 + std::fabs(in));           // :328-331
     case HL_FUNC_RELU: return in > 0 ? in : 0;                        // :415-418
-    case HL_FUNC_LRELU: return in > 0 ? in : (nnReal)0.1 * in;         // :461-464 (PRELU_FAC = 0.1, :16-18)
+    case HL_FUNC_LRELU: return in > 0 ? in : (nnScalar)0.1 * in;         // :461-464 (PRELU_FAC = 0.1, :16-18)
     case HL_FUNC_SIGM:                                                // :158-165
       if (in > 0) return 1 / (1 + nnSafeExp(-in));
       else { const nnReal ex = nnSafeExp(in); return ex / (1 + ex); }
@@ -133,7 +144,7 @@ inline nnReal fDiff(int f, nnReal in, nnReal out) {
     case HL_FUNC_TANH: return 1 - out * out;                          // :119-122
     case HL_FUNC_SOFTSIGN: { const nnReal d = 1 + std::fabs(in); return 1 / (d * d); }  // :333-337
     case HL_FUNC_RELU: return in > 0 ? 1 : 0;
-    case HL_FUNC_LRELU: return in > 0 ? 1 : (nnReal)0.1;                 // :465-468
+    case HL_FUNC_LRELU: return in > 0 ? 1 : (nnScalar)0.1;                 // :465-468
     case HL_FUNC_SIGM: return out * (1 - out);                          // :179-182
     case HL_FUNC_HARDSIGN: { const nnReal d = std::sqrt(1 + in * in); return 1 / (d * d * d); }   // :225-229
     case HL_FUNC_SOFTPLUS: return (1 + in / std::sqrt(1 + in * in)) / 2;  // :560-563
@@ -165,7 +176,7 @@ inline nnReal fInverse(int f, nnReal in) {
     case HL_FUNC_HARDSIGN: return in / std::sqrt(1 - in * in);
     case HL_FUNC_SOFTSIGN: return in / (1 - std::fabs(in));
     case HL_FUNC_RELU: return in;
-    case HL_FUNC_LRELU: return in >= 0 ? in : in / (nnReal)0.1;
+    case HL_FUNC_LRELU: return in >= 0 ? in : in / (nnScalar)0.1;
     case HL_FUNC_EXPPLUS: return std::log(nnSafeExp(in) - 1);
     case HL_FUNC_SOFTPLUS: return (in * in - (nnReal)0.25) / in;
     case HL_FUNC_EXP: return std::log(in);
@@ -214,7 +225,7 @@ inline int actSize(const Layer& l) { return l.type == L_LSTM ? 4 * l.size : (l.t
 struct Episode {  // ReplayMemory/Episode.h:40-108
   int64_t tag = -1, ID = -1, seq = 0; int N = 0; bool term = false;
   std::vector<float> S; std::vector<double> A, MU, R;
-  std::vector<nnReal> V, ADV, RET;         // stateValue, actionAdvantage, returnEstimator
+  std::vector<Fval> V, ADV, RET;           // stateValue, actionAdvantage, returnEstimator
   std::vector<Fval> DQ, IMPW, DKL;         // deltaValue, offPolicImpW, KullbLeibDiv
   Fval totR = 0, avgKL = 0, fracFar = 0, avgSqErr = 0, maxAbsErr = 0;
   Fval sumQ2 = 0, sumQ = 0, maxQ = -1e9, minQ = 1e9;
@@ -237,7 +248,7 @@ struct ol_learner {
   MT19937 gen;
   // replay
   std::vector<std::unique_ptr<Episode>> episodes;
-  std::vector<nnReal> stMean, stStd, stScale; nnReal rewMean = 0, rewStd = 1, rewScale = 1;
+  std::vector<nnScalar> stMean, stStd, stScale; nnScalar rewMean = 0, rewStd = 1, rewScale = 1;
   Real beta = 1e-4, alpha = 0.5, CmaxRet = 5, CinvRet = 0.25;
   int64_t nGradSteps = 0, nTransitions = 0, nSeenSteps = 0, nSeenEps = 0;
   // ReplayCounters::nSeenEpisodes / nSeenTransitions: the (summed) counters as of the last updateCounters (MemoryProcessing.cpp:60-61)
@@ -368,27 +379,27 @@ void initWeights(ol_learner* h) {
     nnReal* W = h->W.data() + l.indW; nnReal* Bv = h->W.data() + l.indB;
     if (l.type == L_DENSE) {
       const Real initializationFac = l.bOutput ? c.outWeightsPrefac : 1;
-      const nnReal fac = (initializationFac > 0) ? initializationFac : 1;
-      const nnReal init = fac * fInitFactor(l.func, l.nIn, l.size);
-      for (int o = 0; o < l.size; ++o) Bv[o] = l.biasInit.size() == (size_t)l.size ? fInverse(l.func, (nnReal)l.biasInit[o]) : 0;  // pre-image of the init values (Layer_Base.h:122-125)
+      const nnScalar fac = (initializationFac > 0) ? initializationFac : 1;
+      const nnScalar init = fac * fInitFactor(l.func, l.nIn, l.size);
+      for (int o = 0; o < l.size; ++o) Bv[o] = l.biasInit.size() == (size_t)l.size ? (nnScalar)fInverse(l.func, (nnScalar)l.biasInit[o]) : 0;  // pre-image of the init values (Layer_Base.h:122-125)
       for (int i = 0; i < l.nIn + (l.rec ? l.size : 0); ++i)      // input weights, then the recurrent ones (:127-140)
         for (int o = 0; o < l.size; ++o) W[o + (int64_t)l.nOutSimd * i] = uniformFloat(h->gen, -init, init);
     } else if (l.type == L_LSTM) {   // Layer_LSTM.h:167-185: forget gate starts open, input / output gates closed (LSTM_PRIME_FAC = 1)
-      const nnReal init = fInitFactor(l.func, l.nIn, l.size);
+      const nnScalar init = fInitFactor(l.func, l.nIn, l.size);
       const int nC = l.size;
       for (int o = 0; o < nC; ++o) { Bv[o] = 0; Bv[nC + o] = -1; Bv[2 * nC + o] = 1; Bv[3 * nC + o] = -1; }
       for (int64_t w = 0; w < (int64_t)4 * nC * (l.nIn + nC); ++w) W[w] = uniformFloat(h->gen, -init, init);
     } else if (l.type == L_MGU) {    // Layer_GRU.h:232-246: forget gate starts open
-      const nnReal init = fInitFactor(l.func, l.nIn, l.size);
+      const nnScalar init = fInitFactor(l.func, l.nIn, l.size);
       const int nC = l.size;
       for (int o = 0; o < nC; ++o) { Bv[o] = 1; Bv[nC + o] = 0; }
       for (int64_t w = 0; w < (int64_t)2 * nC * (l.nIn + nC); ++w) W[w] = uniformFloat(h->gen, -init, init);
     } else if (l.type == L_PARAMRES) {
       for (int o = 0; o < l.size; ++o) { Bv[o] = 0; W[o] = 1; }
     } else if (l.type == L_PARAM) {
-      for (int o = 0; o < l.size; ++o) Bv[o] = (nnReal)l.biasInit[o];
+      for (int o = 0; o < l.size; ++o) Bv[o] = (nnScalar)l.biasInit[o];
     } else if (l.type == L_CONV) {   // Layer_Conv2D.h:198-213: fan-in InC KnX KnY, fan-out KnC; biases zero, weights in memory order
-      const nnReal init = fInitFactor(l.func, l.cv.inpFeatures * l.cv.filterx * l.cv.filtery, l.cv.outFeatures);
+      const nnScalar init = fInitFactor(l.func, l.cv.inpFeatures * l.cv.filterx * l.cv.filtery, l.cv.outFeatures);
       for (int o = 0; o < l.size; ++o) Bv[o] = 0;
       for (int64_t w = 0; w < l.nW; ++w) W[w] = uniformFloat(h->gen, -init, init);
     }
@@ -949,7 +960,7 @@ void applyMoments(ol_learner* h, const std::vector<long double>& mom, bool bInit
   const Real annealLearnR = std::min((Real)1, rRateFac * learnR);
   const Real WS = bInit ? 1 : annealLearnR, WR = bInit ? 1 : annealLearnR;
   const long double count = mom[2 * dS];
-  const auto updateStats = [](nnReal& mean, nnReal& stdev, nnReal& invstdev, const Real learnRate,
+  const auto updateStats = [](nnScalar& mean, nnScalar& stdev, nnScalar& invstdev, const Real learnRate,
                               const long double Evar, const long double Evar2) {
     mean += learnRate * Evar;
     auto variance = Evar2 - Evar * Evar * (2 * learnRate - learnRate * learnRate);
@@ -1143,12 +1154,14 @@ void idToSeqStep(ol_learner* h, const std::vector<int64_t>& flat, std::vector<in
 void adamApply(ol_learner* h) {
   const Real factor = 1.0 / h->Bglobal;
   // Optimizer.h:52-53: nnReal eta = eta_init; annealRate<nnReal>(eta, nStep, epsAnneal)
-  const nnReal eta0 = (nnReal)h->cfg.learnrate;
-  const nnReal _eta = (nnReal)(eta0 / (1 + (nnReal)h->nStep * h->cfg.epsAnneal));
+  // (the scalars are float in the wide build too: `1 - 0.999f` alone is 1e-5 off `1 - 0.999`, and it is the former the
+  // reference and the device compute with)
+  const nnScalar eta0 = (nnScalar)h->cfg.learnrate;
+  const nnScalar _eta = (nnScalar)(eta0 / (1 + (nnScalar)h->nStep * h->cfg.epsAnneal));
   (void)h->gen.next();  // Saru seed draw of thread 0 (:139): the other threads draw from generators of their own
-  const nnReal betat1 = (nnReal)h->beta_t_1, betat2 = (nnReal)h->beta_t_2;
-  const nnReal eta = _eta * std::sqrt(1 - betat2) / (1 - betat1);
-  const nnReal B1 = (nnReal)0.9, B2 = (nnReal)0.999, lambda = (nnReal)h->cfg.nnLambda, fac = (nnReal)factor;
+  const nnScalar betat1 = (nnScalar)h->beta_t_1, betat2 = (nnScalar)h->beta_t_2;
+  const nnScalar eta = _eta * std::sqrt(1 - betat2) / (1 - betat1);
+  const nnScalar B1 = (nnScalar)0.9, B2 = (nnScalar)0.999, lambda = (nnScalar)h->cfg.nnLambda, fac = (nnScalar)factor;
   nnReal* Wp = h->W.data(); nnReal* M1 = h->M1.data(); nnReal* M2 = h->M2.data(); nnReal* Gp = h->G.data();
   for (int64_t i = 0; i < h->nParams; ++i) {
     const nnReal penal = -Wp[i] * lambda;
@@ -1249,6 +1262,14 @@ int ol_get_params(ol_learner* h, float* w, float* m1, float* m2) {
   if (m2) std::copy(h->M2.begin(), h->M2.end(), m2);
   return HL_OK;
 }
+int ol_get_params64(ol_learner* h, double* w, double* m1, double* m2) {      // the arrays as they are held (exact in both builds)
+  if (!h) return HL_ERR_BAD_ARG;
+  if (w) std::copy(h->W.begin(), h->W.end(), w);
+  if (m1) std::copy(h->M1.begin(), h->M1.end(), m1);
+  if (m2) std::copy(h->M2.begin(), h->M2.end(), m2);
+  return HL_OK;
+}
+int ol_real_bytes(void) { return (int)sizeof(nnReal); }
 int ol_set_rng_state(ol_learner* h, const uint32_t s[625]) {
   if (!h || !s) return HL_ERR_BAD_ARG;
   std::memcpy(h->gen.x, s, 624 * 4); h->gen.p = s[624]; return HL_OK;
@@ -1701,14 +1722,14 @@ int ol_readback(ol_learner* h, int32_t what, void* dst, int64_t bytes) {
     case HL_TAP_EPISODE: src = h->bEp.data(); n = h->bEp.size() * 8; break;
     case HL_TAP_TSTEP: src = h->bT.data(); n = h->bT.size() * 8; break;
     case HL_TAP_TAG: src = h->bTag.data(); n = h->bTag.size() * 8; break;
-    case HL_TAP_STATE: src = h->tState.data(); n = h->tState.size() * 4; break;
+    case HL_TAP_STATE: src = h->tState.data(); n = h->tState.size() * sizeof(h->tState[0]); break;
     case HL_TAP_OUTPUT: src = h->tO.data(); n = h->tO.size() * 8; break;
     case HL_TAP_OUTGRAD: src = h->tG.data(); n = h->tG.size() * 8; break;
     case HL_TAP_RHO: src = h->tRho.data(); n = h->tRho.size() * 8; break;
     case HL_TAP_DKL: src = h->tDkl.data(); n = h->tDkl.size() * 8; break;
     case HL_TAP_DELTAQ: src = h->tDq.data(); n = h->tDq.size() * 8; break;
     case HL_TAP_FAR: src = h->tFar.data(); n = h->tFar.size(); break;
-    case HL_TAP_GRADSUM: src = h->tGradSum.data(); n = h->tGradSum.size() * 4; break;
+    case HL_TAP_GRADSUM: src = h->tGradSum.data(); n = h->tGradSum.size() * sizeof(nnReal); break;
     default: return HL_ERR_BAD_ARG;
   }
   if (n == 0) return fail(h, HL_ERR_STATE, "tap not recorded (hl_set_tap before the step)");

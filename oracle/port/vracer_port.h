@@ -29,6 +29,13 @@ HL_API int ol_param_layout(const ol_learner* h, int64_t* indW, int64_t* nW, int6
 HL_API int ol_init_weights(ol_learner* h);
 HL_API int ol_set_params(ol_learner* h, const float* w, const float* m1, const float* m2);
 HL_API int ol_get_params(ol_learner* h, float* w, float* m1, float* m2);
+/* The wide build (-DOL_WIDE, liboracle_port64.so) holds weights, moments, gradients and activations in double; float
+ * scalars, the replay memory and the samplers are those of the default build.  ol_set_params takes float in both (the
+ * inputs are fp32 values); ol_get_params rounds to float; ol_get_params64 returns the arrays as held.  ol_readback
+ * returns HL_TAP_GRADSUM in the build's array type -- ol_real_bytes() bytes per element: 4 by default, 8 wide --, every
+ * other tap as in hl_readback.  Checkpoints and the wire format stay fp32 (the wide build rounds on the way out). */
+HL_API int ol_get_params64(ol_learner* h, double* w, double* m1, double* m2);
+HL_API int ol_real_bytes(void);
 HL_API int ol_set_rng_state(ol_learner* h, const uint32_t state[625]);
 HL_API int ol_get_rng_state(ol_learner* h, uint32_t state[625]);
 HL_API int ol_append_episode(ol_learner* h, int32_t nsteps, const float* states, const double* actions,

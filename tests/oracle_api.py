@@ -6,10 +6,11 @@ import subprocess
 
 import numpy as np
 
-from smarties_amd.capi import CApi, Learner
+from smarties_amd.capi import TAP_GRADSUM, CApi, Learner
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_LIB = os.path.join(ROOT, "oracle", "liboracle_port.so")
+ORACLE64_LIB = os.path.join(ROOT, "oracle", "liboracle_port64.so")      # the same restatement with its arrays in double (-DOL_WIDE)
 
 
 class SynthCfg(C.Structure):
@@ -45,6 +46,45 @@ def oracle_api():
 
 def oracle_learner(cfg):
     return Learner(oracle_api(), cfg)
+
+
+_api64 = None
+
+
+def oracle64_api():
+    global _api64
+    if _api64 is None:
+        if not os.path.exists(ORACLE64_LIB):
+            subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "port64"])
+        _api64 = CApi(ORACLE64_LIB, "ol_")
+        pd = C.POINTER(C.c_double)
+        _api64.lib.ol_get_params64.restype = C.c_int
+        _api64.lib.ol_get_params64.argtypes = [C.c_void_p, pd, pd, pd]
+        _api64.lib.ol_real_bytes.restype = C.c_int
+        assert _api64.lib.ol_real_bytes() == 8 and oracle_api().lib.ol_real_bytes() == 4
+    return _api64
+
+
+class Learner64(Learner):
+    """A learner of the wide restatement: weights, moments, gradients and activations in double.  set_params takes the
+    fp32 values a float learner holds; get_params rounds to float, get_params64 does not."""
+
+    def get_params64(self):
+        w, m1, m2 = [np.zeros(self.nParams, np.float64) for _ in range(3)]
+        pd = C.POINTER(C.c_double)
+        self._ck(self.api.lib.ol_get_params64(self.h, w.ctypes.data_as(pd), m1.ctypes.data_as(pd), m2.ctypes.data_as(pd)))
+        return w, m1, m2
+
+    def readback(self, what):
+        if what != TAP_GRADSUM:
+            return super().readback(what)
+        out = np.zeros(self.nParams, np.float64)      # ol_readback: the gradient sum in the build's array type
+        self._ck(self.api.fn("readback")(self.h, what, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+
+def oracle64_learner(cfg):
+    return Learner64(oracle64_api(), cfg)
 
 
 def synth_cfg(seed=7, dimS=17, dimA=6, lenMin=201, lenMax=201, pTerm=0.0, muSpread=0.5, actNoise=1.0):

@@ -252,3 +252,138 @@ def lines_agree(mine, ref, head, rel=0.0):
         if abs(float(a) - float(b)) > max(2 * ulp, rel * abs(float(b))):
             return False
     return True
+
+
+# ---- per-block deviations -----------------------------------------------------------------------------------------------
+# relinf() takes its scale from the largest element of the whole array: one large block (the first layer's weights, the policy
+# columns of a tap) sets the bar for all the others.  The helpers below take the scale per parameter block and per output column.
+
+def _layer_kinds(cfg):
+    """(kind, units) per layer in build order, as the port's buildNet lays them out (oracle/port/vracer_port.cpp); kind is one of
+    in, conv, join, dense, rnn, lstm, mgu, res, out, sigma"""
+    hidden = [int(cfg.encoder[j]) for j in range(cfg.n_encoder) if cfg.encoder[j] > 0]
+    nEnc = len(hidden)
+    hidden += [int(cfg.hidden[j]) for j in range(cfg.n_hidden)]
+    kinds = [("in", 0)] + [("conv", 0)] * cfg.n_conv
+    inAll = cfg.dimS * (1 + cfg.nAppendedObs)
+    inImg = cfg.conv[0].inpFeatures * cfg.conv[0].inpY * cfg.conv[0].inpX if cfg.n_conv else inAll
+    if inAll > inImg:
+        kinds += [("in", 0), ("join", 0)]
+    nHid = 0
+    for hsz in hidden:
+        if hsz <= 0:
+            continue
+        ID = len(kinds)
+        kind = {capi.NN_FFNN: "dense", capi.NN_LSTM: "lstm", capi.NN_MGU: "mgu", capi.NN_RNN: "rnn"}[cfg.nn_type]
+        if cfg.encoder_rnn and nHid < nEnc:
+            kind = "rnn"
+        nHid += 1
+        kinds.append((kind, hsz))
+        if ID != 1:
+            kinds.append(("res", hsz))
+    kinds.append(("out", 0))
+    if cfg.adv_kind != capi.ADV_DISCRETE:
+        kinds.append(("sigma", 0))
+    return kinds
+
+
+_GATES = {"lstm": ("cell", "in", "forget", "out"), "mgu": ("forget", "state")}
+
+
+def param_blocks(L):
+    """[(name, start, n)] over the parameter vector of learner L: one entry per non-empty weight block and per non-empty bias block
+    of L.layout().  The weights of a recurrent layer are split into input and recurrent weights (rows [0, nIn) and [nIn, nIn + cells)
+    of its matrix: forwardNet, packBlob of the port), those of LSTM / MGU layers per gate as well; a gate's weights are a column
+    range of every row, so for these entries `start` is the array of their n indices."""
+    lay, kinds = L.layout(), _layer_kinds(L.cfg)
+    assert len(kinds) == len(lay["nW"]), (kinds, lay)
+    out = []
+    for i, (kind, units) in enumerate(kinds):
+        iW, nW, iB, nB = [int(lay[k][i]) for k in ("indW", "nW", "indB", "nB")]
+        name = "L%d.%s" % (i, kind)
+        if nW > 0 and kind == "rnn":
+            ld = (units + 7) // 8 * 8                      # nOutSimd
+            assert nB == units and nW % ld == 0
+            nIn = nW // ld - units
+            out += [(name + ".Wx", iW, ld * nIn), (name + ".Wr", iW + ld * nIn, ld * units)]
+        elif nW > 0 and kind in _GATES:
+            g = len(_GATES[kind])
+            assert nB == g * units and nW % (g * units) == 0
+            nIn = nW // (g * units) - units
+            for part, rows in (("Wx", np.arange(nIn)), ("Wr", nIn + np.arange(units))):
+                for k, gate in enumerate(_GATES[kind]):
+                    idx = (iW + rows[:, None] * (g * units) + k * units + np.arange(units)[None, :]).ravel()
+                    if idx.size:
+                        out.append(("%s.%s.%s" % (name, part, gate), idx, idx.size))
+        elif nW > 0:
+            out.append((name + ".W", iW, nW))
+        if nB > 0:
+            out.append((name + ".B", iB, nB))
+    return out
+
+
+def _dev(a, ref, what):
+    a, ref = np.asarray(a, np.float64), np.asarray(ref, np.float64)
+    scale = np.abs(ref).max() if ref.size else 0.0
+    if scale == 0.0:
+        assert not np.any(a), "%s: the reference is identically zero, the array is not (max %g)" % (what, np.abs(a).max())
+        return "zero"
+    return float(np.abs(a - ref).max() / scale)
+
+
+def blockdev(blocks, a, ref):
+    """{name: max|a - ref| / max|ref|} over each block of param_blocks(); "zero" where the reference block is identically zero
+    (a must then be identically zero too)"""
+    a, ref = np.asarray(a), np.asarray(ref)
+    out = {}
+    for name, start, n in blocks:
+        sl = slice(start, start + n) if np.ndim(start) == 0 else start
+        out[name] = _dev(a[sl], ref[sl], name)
+    return out
+
+
+def coldev(a, ref):
+    """{"c<j>": max|a - ref| / max|ref|} per column j of a [B, nOut] array (a [B] vector is one column); "zero" as in blockdev"""
+    a, ref = np.asarray(a), np.asarray(ref)
+    assert a.shape == ref.shape, (a.shape, ref.shape)
+    a, ref = a.reshape(a.shape[0], -1), ref.reshape(ref.shape[0], -1)
+    return {"c%d" % j: _dev(a[:, j], ref[:, j], "column %d" % j) for j in range(a.shape[1])}
+
+
+def worst_dev(devs):
+    """(deviation, name) of the largest numeric entry of a {name: deviation} dict"""
+    num = [(v, k) for k, v in devs.items() if v != "zero"]
+    return max(num) if num else (0.0, "-")
+
+
+def twin64(L):
+    """The restatement with its arrays in double (oracle/liboracle_port64.so) holding learner L's weights and state scaling: the
+    reference of the acting calls (forward, forward_sequence), which read nothing else."""
+    from oracle_api import oracle64_learner
+    T = oracle64_learner(L.cfg)
+    T.set_params(*L.get_params())
+    T.set_scaling(*L.get_scaling())
+    return T
+
+
+def assert_columns(got, ref, tol, what=None, ref32=None, cpu_bar=False):
+    """Every output column of a batch on its own scale: max|got - ref| / max|ref| over the rows below tol.  The row-wise checks of
+    the acting tests take the scale from a row's largest output, which hides its value and advantage columns.  ref32 (the fp32
+    restatement's rows), where given, is printed beside the worst column.
+    cpu_bar: for a net whose columns are ill-conditioned -- outputs of 1e-3 behind sums of thousands of terms, where the fp32
+    restatement itself loses more than tol / 3 against ref -- the bar of such a column is 4 x what the fp32 restatement loses
+    in it, taken here from ref32 (the rule of tests/blocks.py for ill-conditioned blocks); every other column keeps tol."""
+    d = coldev(got, ref)
+    w, c = worst_dev(d)
+    e_cpu = None if ref32 is None else coldev(ref32, ref)
+    cpu = "" if e_cpu is None else ", fp32 restatement there %s" % (e_cpu[c],)
+    print("%s: worst column %s dev %.3g over %d rows%s" % (what, c, w, np.asarray(ref).shape[0], cpu))
+    if not cpu_bar:
+        assert w < tol, (what, c, w)
+        return
+    for c, v in d.items():
+        bar = tol if e_cpu[c] == "zero" or e_cpu[c] <= tol / 3 else 4 * e_cpu[c]
+        assert v == "zero" or v < bar, (what, c, v, bar, e_cpu[c])
+
+
+COL_ROWS = 16      # a column's scale is taken over a batch: calls of fewer rows are left to the row-wise checks

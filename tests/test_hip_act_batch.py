@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle_api import oracle_learner, fill_synth, synth_cfg
-from parity import relinf
+from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,19 +69,25 @@ def test_batched_acting_matches_oracle_per_agent(hip_api, kind, hidden, nApp):
     lengths = [1, 2, bptt + 1, 5] + ([bptt + 1 + nApp, bptt + 2] if nApp else [])
     wins = _ragged(rng, 300, 6, lengths)                    # 300 agents: more than the device has compute units
     ref = np.stack([O.forward_sequence(w) for w in wins])
+    T = twin64(O)
+    ref64 = np.stack([T.forward_sequence(w) for w in wins])
     one = np.stack([G.forward_sequence(w) for w in wins])
     for i in range(len(wins)):
         assert relinf(one[i], ref[i]) < TOL32, ("single-agent call", i, wins[i].shape[0])
+    assert_columns(one, ref64, TOL32, "single-agent calls", ref)
     for n in (1, 3, 64, 300):
         out = G.forward_sequences(wins[:n])
         assert out.shape == (n, G.nOut)
         for i in range(n):
             assert relinf(out[i], ref[i]) < TOL32, (n, i, wins[i].shape[0], out[i], ref[i])
+        if n >= COL_ROWS:
+            assert_columns(out, ref64[:n], TOL32, n, ref[:n])
     # windows in another order: an agent's result does not depend on its place in the batch
     perm = rng.permutation(300)
     out = G.forward_sequences([wins[i] for i in perm])
     for q, i in enumerate(perm):
         assert relinf(out[q], ref[i]) < TOL32, (q, i)
+    assert_columns(out, ref64[perm], TOL32, "permuted", ref[perm])
 
 
 # ---- 2. shapes that go through the single-agent routes ------------------------------------------------------------------------
@@ -203,6 +209,8 @@ def test_batched_acting_is_one_launch_per_chunk(hip_api):
     assert np.array_equal(out[:64], out64)
     for i in (0, capi.ACT_SEQ_CHUNK - 1, capi.ACT_SEQ_CHUNK, 2 * capi.ACT_SEQ_CHUNK, len(wins) - 1):      # both sides of the chunk borders
         assert relinf(out[i], O.forward_sequence(wins[i])) < TOL32, i
+    T = twin64(O)
+    assert_columns(out, np.stack([T.forward_sequence(w) for w in wins]), TOL32, "three chunks")
 
 
 # ---- 6. surface and resources (no GPU) ------------------------------------------------------------------------------------------

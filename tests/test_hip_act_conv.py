@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from oracle_api import oracle_learner, fill_synth, synth_cfg
-from parity import relinf
+from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +42,10 @@ NETS = {
                   nnFunc="SoftSign", batchSize=8, maxTotObsNum=400, randSeed=11),
 }
 N_EPS = {"atari": 14}
+# nets whose output columns the fp32 restatement itself does not resolve to TOL32 / 3 against its build in double (measured on the CPU after
+# the three steps of the row-by-row test, 17 rows: 6 of the 13 columns of "atari" between 3.5e-6 and 3.6e-5 -- outputs of 7e-4 .. 5e-2 behind
+# the 3136-term sums of its dense layer): parity.assert_columns holds those columns to 4 x the restatement's own loss
+ILL_COLUMNS = ("atari",)
 
 
 def _sc(kw, **over):
@@ -118,12 +122,15 @@ def test_conv_rows_match_oracle_row_by_row(hip_api, name, monkeypatch):
     ns = (1, 17) if name == "atari" else (1, 17, 81, capi.ACT_ROWS_CHUNK + 1)      # one row, ragged row blocks, walked rows, two chunks
     st = _rows(np.random.default_rng(11), max(ns), G.dIn)
     ref = O.forward(st)
+    ref64 = twin64(O).forward(st)
     G.timing_enable(True)
     for n in ns:
         n0 = _count(G, "act_conv")
         out = G.forward(st[:n])
         assert _count(G, "act_conv") - n0 == -(-n // _cap(G.dIn)), (name, n)      # (the route under test served the call)
         _check_rows(name, n, out, ref)
+        if n >= COL_ROWS:
+            assert_columns(out, ref64[:n], TOL32, (name, n), ref[:n], cpu_bar=name in ILL_COLUMNS)
     G.timing_enable(False)
 
 
@@ -143,6 +150,8 @@ def test_chunks_hold_no_more_rows_than_the_staging_bytes(hip_api, monkeypatch):
     G.timing_enable(False)
     for i in (0, cap - 1, cap):
         assert relinf(out[i], O.forward(st[i:i + 1])[0]) < TOL32, i
+    rows = np.r_[0:16, cap - 15:cap + 1]      # (the oracle's forward through this stack takes its time: both ends of the first chunk, the second's row)
+    assert_columns(out[rows], twin64(O).forward(st[rows]), TOL32, "two chunks", O.forward(st[rows]), cpu_bar=True)
 
 
 # ---- 3. row independence, bit for bit ----------------------------------------------------------------------------------------------

@@ -7,10 +7,10 @@ act -> simulate -> append -> step on tensors with stacked frames against the sam
 import numpy as np
 import pytest
 
-from parity import relinf
+from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 from test_act_dev_cpu import head_np
-from test_hip_act_conv import LDS_NETS, NETS, TOL32, _count, _pair, _row_bytes, _rows, _training_forwards
+from test_hip_act_conv import ILL_COLUMNS, LDS_NETS, NETS, TOL32, _count, _pair, _row_bytes, _rows, _training_forwards
 from test_hip_act_dev import N_AGENTS, _check_heads, _same_replay, _same_training_state
 from test_hip_act_seq_dev import _call_dev, _columns, _packed, _side_stream
 
@@ -51,6 +51,7 @@ def test_conv_windows_from_device_memory_equal_the_host_call_and_the_oracle(hip_
     ns = (1, 17) if name == "atari" else (1, 17, 300) + ((capi.ACT_ROWS_CHUNK + 1,) if name == "odd" else ())
     wins = _wins(np.random.default_rng(11), max(ns), kw)
     ref = O.forward(_stacked(wins, nApp))
+    ref64 = twin64(O).forward(_stacked(wins, nApp))
     want = host.forward_sequences(wins)
     side = _side_stream()
     for n in ns:
@@ -62,6 +63,8 @@ def test_conv_windows_from_device_memory_equal_the_host_call_and_the_oracle(hip_
             worst = int(np.argmax(err))
             print("%s n=%d stride %d: worst row %d relinf %.3g" % (name, n, layout[3], worst, err[worst]))
             assert err[worst] < TOL32, (name, layout[3], n, worst, got[worst], ref[worst])
+            if n >= COL_ROWS:
+                assert_columns(got, ref64[:n], TOL32, (name, layout[3], n), ref[:n], cpu_bar=name in ILL_COLUMNS)
 
 
 # ---- 2. alignment -------------------------------------------------------------------------------------------------------------------------
@@ -183,6 +186,7 @@ def test_given_weights_serve_device_windows_without_a_step(hip_api):
     got = _call_dev(G, _side_stream(), _columns(wins), np.arange(20))
     for i in range(20):
         assert relinf(got[i], ref[i]) < TOL32, (i, got[i], ref[i])
+    assert_columns(got, twin64(O).forward(_stacked(wins, 0)), TOL32, "given weights", ref)
 
 
 # ---- 7. refusals --------------------------------------------------------------------------------------------------------------------------

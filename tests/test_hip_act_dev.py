@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle_api import fill_synth, synth_cfg
+from parity import assert_columns, twin64
 from smarties_amd import capi
 from test_act_dev_cpu import CLIP, head_np
 
@@ -61,6 +62,7 @@ def test_forward_dev_equals_hl_forward_and_leaves_training_untouched(hip_api):
             got = out.cpu().numpy()                           # read in that stream's order, no other synchronisation
         assert got.shape == (n, A.nOut)
         assert np.array_equal(got, ref), n
+    assert_columns(got, twin64(A).forward(base), 1e-5, "forward_dev, %d rows" % len(base))      # (TOL32 of the acting tests, per output column)
     assert A.forward_dev(torch.empty((0, A.dIn), dtype=torch.float32, device="cuda")).shape == (0, A.nOut)
     A.step(3); B.step(3)
     _same_training_state(A, B)

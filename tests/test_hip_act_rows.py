@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from oracle_api import oracle_learner, fill_synth, synth_cfg
-from parity import relinf
+from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -91,6 +91,7 @@ def test_many_rows_match_oracle_row_by_row(hip_api, name):
     G.step(3); O.step(3)
     st = _rows(np.random.default_rng(11), capi.ACT_ROWS_CHUNK + 1, G.dIn)
     ref = O.forward(st)
+    ref64 = twin64(O).forward(st)
     for n in (65, 81, 300, capi.ACT_ROWS_CHUNK + 1):      # a block with one live row, ragged blocks, two chunks
         out = G.forward(st[:n])
         assert out.shape == (n, G.nOut)
@@ -98,6 +99,7 @@ def test_many_rows_match_oracle_row_by_row(hip_api, name):
         worst = int(np.argmax(err))
         print("%s n=%d: worst row %d relinf %.3g" % (name, n, worst, err[worst]))
         assert err[worst] < TOL32, (name, n, worst, out[worst], ref[worst])
+        assert_columns(out, ref64[:n], TOL32, (name, n), ref[:n])
 
 
 # ---- 2. the wide single-row call ---------------------------------------------------------------------------------------------------
@@ -115,6 +117,7 @@ def test_wide_nets_take_the_route_for_any_row_count(hip_api, name):
     G.step(3); O.step(3)
     st = _rows(np.random.default_rng(5), 70, G.dIn)
     ref = O.forward(st)
+    ref64 = twin64(O).forward(st)
     G.timing_enable(True)
     for n in (1, 3, 70):
         n0 = _launches(G)
@@ -123,6 +126,8 @@ def test_wide_nets_take_the_route_for_any_row_count(hip_api, name):
         err = [relinf(out[i], ref[i]) for i in range(n)]
         print("%s n=%d: worst relinf %.3g" % (name, n, max(err)))
         assert max(err) < TOL32, (name, n, int(np.argmax(err)))
+        if n >= COL_ROWS:
+            assert_columns(out, ref64[:n], TOL32, (name, n), ref[:n])
     G.timing_enable(False)
 
 
@@ -181,6 +186,7 @@ def test_many_rows_are_one_launch_per_chunk(hip_api):
     assert relinf(out64, out[:64]) < 2 * TOL32
     for i in (0, capi.ACT_ROWS_CHUNK - 1, capi.ACT_ROWS_CHUNK, 2 * capi.ACT_ROWS_CHUNK, len(st) - 1):      # both sides of the chunk borders
         assert relinf(out[i], O.forward(st[i:i + 1])[0]) < TOL32, i
+    assert_columns(out, twin64(O).forward(st), TOL32, "three chunks")
 
 
 # ---- 4b. the size switch: nets beyond HL_ACT_ROWS_SMALL_NET weights take the route only from HL_ACT_ROWS_WIDE_MIN_N rows and two rounds of Mmax on --
@@ -202,6 +208,7 @@ def test_size_switch_routes_and_both_routes_match_oracle(hip_api, name):
     G.step(3); O.step(3)
     st = _rows(np.random.default_rng(7), capi.ACT_ROWS_CHUNK + 1, G.dIn)
     ref = O.forward(st)
+    ref64 = twin64(O).forward(st)
     G.timing_enable(True)
     for n, want in ((70, at70), (capi.ACT_ROWS_CHUNK + 1, at1025)):
         n0 = _launches(G)
@@ -210,6 +217,7 @@ def test_size_switch_routes_and_both_routes_match_oracle(hip_api, name):
         err = [relinf(out[i], ref[i]) for i in range(n)]
         print("%s n=%d: worst relinf %.3g" % (name, n, max(err)))
         assert max(err) < TOL32, (name, n, int(np.argmax(err)))
+        assert_columns(out, ref64[:n], TOL32, (name, n), ref[:n])
     G.timing_enable(False)
 
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle_api import fill_synth, synth_cfg
-from parity import relinf
+from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 from test_act_dev_cpu import head_np
 from test_hip_act_batch import FALLBACK, TOL32, _pair, _ragged, _rec_cfg
@@ -84,6 +84,8 @@ def test_windows_from_device_memory_equal_the_host_call_bit_for_bit(hip_api, kin
     rng = np.random.default_rng(11)
     wins = _ragged(rng, 300, 6, [1, 2, 5, BPTT + 1] + ([BPTT + 1 + nApp] if nApp else []))      # 300 agents: more than compute units
     ref = np.stack([O.forward_sequence(w) for w in wins])
+    T = twin64(O)
+    ref64 = np.stack([T.forward_sequence(w) for w in wins])
     host = G.forward_sequences(wins)
     side = _side_stream()
     perm = rng.permutation(300)
@@ -95,11 +97,14 @@ def test_windows_from_device_memory_equal_the_host_call_bit_for_bit(hip_api, kin
             assert np.array_equal(got, host[:n]), (layout[3], n)
             for i in range(n):
                 assert relinf(got[i], ref[i]) < TOL32, (layout[3], n, i, wins[i].shape[0], got[i], ref[i])
+            if n >= COL_ROWS:
+                assert_columns(got, ref64[:n], TOL32, (layout[3], n), ref[:n])
         # the agents in another order: an agent's result does not depend on its place in the batch
         got = _call_dev(G, side, layout, perm)
         assert np.array_equal(got, host[perm]), layout[3]
         for q, i in enumerate(perm):
             assert relinf(got[q], ref[i]) < TOL32, (layout[3], q, i)
+        assert_columns(got, ref64[perm], TOL32, (layout[3], "permuted"), ref[perm])
     empty = torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty(0, dtype=torch.int32, device="cuda")
     assert G.forward_sequences_dev(torch.empty((0, 6), dtype=torch.float32, device="cuda"), empty[0], empty[1], 1).shape == (0, G.nOut)
 

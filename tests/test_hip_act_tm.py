@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from oracle_api import synth_cfg, fill_synth
-from parity import relinf
+from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 from test_hip_parity import _pair, _compare_step, TOL32
 
@@ -92,6 +92,9 @@ def test_every_agent_equals_the_single_agent_call_and_the_oracle(nets, name):
     for i, w in enumerate(wins):
         assert np.array_equal(out[i], one[i]), (name, i, w.shape[0], out[i], one[i])
         assert relinf(out[i], O.forward_sequence(w)) < TOL32, (name, i, w.shape[0])
+    if agents >= COL_ROWS:
+        T = twin64(O)
+        assert_columns(out, np.stack([T.forward_sequence(w) for w in wins]), TOL32, name)
     # the windows in another order: an agent's place, chunk and row block do not matter
     perm = rng.permutation(agents)
     out2 = G.forward_sequences([wins[i] for i in perm])

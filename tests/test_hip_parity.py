@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle_api import oracle_learner, fill_synth, synth_cfg, synth_episode
-from parity import (far_count_loop, storage_order, load_fixture, fixture_config, fixture_synth, fixture_arrival, setup_from_fixture, relinf,
+from parity import (COL_ROWS, assert_columns, twin64, far_count_loop, storage_order, load_fixture, fixture_config, fixture_synth, fixture_arrival, setup_from_fixture, relinf,
                     episode_arrays_by_tag, fixture_arrays_by_tag, stats_line, lines_agree, fx_vec_dev, flat_for)
 from smarties_amd import capi
 
@@ -1323,9 +1323,12 @@ def test_rollout_forward_matches_oracle(hip_api, cfg_kw, sc_kw):
         st = rng.standard_normal((n, cfg_kw["dimS"])).astype(np.float32) * 2 + 0.3
         og, oo = G.forward(st), O.forward(st)
         assert og.shape == (n, G.nOut) and relinf(og, oo) < TOL32
+        if n >= COL_ROWS:
+            assert_columns(og, twin64(O).forward(st), TOL32, ("initial weights", n), oo)
     G.step(20); O.step(20)
     st = rng.standard_normal((33, cfg_kw["dimS"])).astype(np.float32)
     assert relinf(G.forward(st), O.forward(st)) < TOL32
+    assert_columns(G.forward(st), twin64(O).forward(st), TOL32, "after 20 steps", O.forward(st))
     G.step(3); O.step(3)            # the forward pass in between leaves the training path untouched
     _compare_step(G, O)
 
@@ -1349,6 +1352,11 @@ def test_recurrent_acting_matches_oracle(hip_api, kind, hidden):
         S = rng.normal(size=(n, 6)).astype(np.float32)
         og, oo = G.forward_sequence(S), O.forward_sequence(S)
         assert relinf(og, oo) < TOL32, (n, og, oo)
+    # ... and per output column over a batch of such windows (a row's largest output hides its value and advantage columns)
+    wins = [rng.normal(size=(n, 6)).astype(np.float32) for n in (1, 2, 5, 9) * (COL_ROWS // 4)]
+    T = twin64(O)
+    assert_columns(np.stack([G.forward_sequence(S) for S in wins]), np.stack([T.forward_sequence(S) for S in wins]), TOL32, "windows",
+                   np.stack([O.forward_sequence(S) for S in wins]))
     with pytest.raises(capi.HlError):
         G.forward_sequence(rng.normal(size=(10, 6)).astype(np.float32))      # more than nnBPTTseq + 1 steps
     with pytest.raises(capi.HlError):
