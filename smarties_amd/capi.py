@@ -682,6 +682,13 @@ class Learner:
         self._ck(f(self.h, int(backward), buf, 256))
         return buf.value.decode()
 
+    def debug_conv_rows_kind(self):
+        """The form of the row-block kernels the first convolutional layer's training launches take: -1 none, 0 any geometry, 1 the
+        RACER_atari geometry at compile time (development entry hl_debug_conv_rows_kind)."""
+        f = self.api.lib.hl_debug_conv_rows_kind
+        f.restype, f.argtypes = C.c_int, [C.c_void_p]
+        return f(self.h)
+
     def kernel_profile(self, which, reps=200):
         """Average microseconds per launch of one kernel of the step (see hl_kernel_profile)."""
         us = C.c_double()

@@ -139,6 +139,17 @@ extern "C" HL_API int hl_debug_rec_route(hl_learner* h, int32_t backward, char* 
   std::snprintf(buf, (size_t)n, "%s", name.c_str());
   return HL_OK;
 }
+// which form of the row-block kernels (conv.hip) the first convolutional layer takes in this learner's training launches, as launchFront /
+// launchBackward decide it: -1 none (the gather kernels), 0 the any-geometry form, 1 the form with the RACER_atari geometry at compile
+// time (ConvGeo::rbKind; only with the windows read from the replay).  Read-only; tests pin the shapes that reach each form
+extern "C" HL_API int hl_debug_conv_rows_kind(hl_learner* h) {
+  if (!h) return -1;
+  HL_LOCK(h);
+  if (h->nConv == 0 || !h->cg[0].rbRows) return -1;
+  ConvArgs ca = convArgs(h, 0);
+  if (convFromReplay(h)) convSource(h, 0, &ca);
+  return ca.L[0].rbKind;
+}
 // sets every arrive counter of the in-kernel panel barriers to `value` (tests: the counters are monotonic and wrap; the barrier's
 // target arithmetic must survive that).  A barrier's group adds HT per launch to its counter, so only multiples of HT are states
 // the kernels can meet: anything else is refused.

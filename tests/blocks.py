@@ -1,5 +1,6 @@
-"""Shared by tests/test_blocks_cpu.py and tests/test_hip_blocks.py: the shapes (one per launch route of the training step), the
-fp32 / fp64 pair of the CPU restatement stepped side by side, and the per-block deviations.
+"""Shared by tests/test_blocks_cpu.py and tests/test_hip_blocks.py: the shapes (one per launch route of the training step: every
+counter of ROUTE_COUNTERS fires in a recorded route or is in EXCUSED, tests/test_blocks_cpu.py), the fp32 / fp64 pair of the CPU
+restatement stepped side by side, and the per-block deviations.
 
 O32 is oracle/liboracle_port.so, O64 its build with the arrays in double (oracle/liboracle_port64.so).  Both start from the
 same fp32 weights and the same synthetic replay and draw their own minibatches.  e_cpu(block) = dev(O32, O64) is what fp32
@@ -108,6 +109,51 @@ SHAPES = {
     "encoder-24-16x16-b20": dict(      # tests/golden/encoder_dense.bin: an encoder layer under the hidden layers
         kw=dict(dimS=5, dimA=2, bounded=[1, 0], encoder=[24], hidden=(16, 16), batchSize=20, maxTotObsNum=2000, randSeed=7),
         sc=dict(seed=7, dimS=5, dimA=2, lenMin=5, lenMax=40, pTerm=0.5), n_eps=30),
+    # ---- convolutional routes beside conv-small's: batches are the smallest that still fill a tile edge ----
+    "conv-atari-18opt-b8": dict(      # RACER_atari's stack: the first layer's row-block kernels with the geometry at compile time, windows
+        # read from the replay; layers 1 to 3 in one launch (convt.hip).  18 options: an ALE action count (and 133 blocks, 5 of them listed)
+        kw=dict(dimS=7056, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=18, nAppendedObs=3,
+                conv=[(84, 84, 4, 8, 8, 4), (20, 20, 8, 16, 6, 2), (8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)], hidden=(512,), nnFunc="Tanh",
+                batchSize=8, maxTotObsNum=600, randSeed=4),
+        sc=dict(seed=8, dimS=7056, dimA=1, lenMin=4, lenMax=12, pTerm=0.5), n_eps=14),
+    "conv-rows-32x32-b8": dict(      # the smallest first layer the any-geometry row-block kernels take (4 x 8 x 8 patches, 4096 inputs), from the replay
+        kw=dict(dimS=1024, dimA=2, bounded=[1, 0], nAppendedObs=3, conv=[(32, 32, 4, 8, 8, 4), (7, 7, 8, 16, 3, 1)], hidden=(32,), nnFunc="Tanh",
+                batchSize=8, maxTotObsNum=1500, randSeed=13),
+        sc=dict(seed=15, dimS=1024, dimA=2, lenMin=4, lenMax=20, pTerm=0.5), n_eps=30),
+    "conv-rows-stacked-extras3-b8": dict(      # the same layer on stacked rows: three state variables beside the image keep it off the replay
+        kw=dict(dimS=4099, dimA=2, bounded=[1, 0], nAppendedObs=0, conv=[(32, 32, 4, 8, 8, 4), (7, 7, 8, 16, 3, 1)], hidden=(32,), nnFunc="Tanh",
+                batchSize=8, maxTotObsNum=1500, randSeed=13),
+        sc=dict(seed=15, dimS=4099, dimA=2, lenMin=4, lenMax=20, pTerm=0.5), n_eps=30),
+    "conv-rows-single-b8": dict(      # that layer alone: no other filter-gradient block, so its filter gradient is a launch of its own
+        kw=dict(dimS=1024, dimA=2, bounded=[1, 0], nAppendedObs=3, conv=[(32, 32, 4, 8, 8, 4)], hidden=(32,), nnFunc="Tanh",
+                batchSize=8, maxTotObsNum=1500, randSeed=13),
+        sc=dict(seed=15, dimS=1024, dimA=2, lenMin=4, lenMax=20, pTerm=0.5), n_eps=30),
+    "conv-perlayer-strided-b10": dict(      # 12 channels: conv_tail_plan declines, the input gradient is a launch per layer (strided form)
+        kw=dict(dimS=576, dimA=2, nAppendedObs=0, conv=[(12, 12, 4, 8, 3, 1), (10, 10, 8, 12, 4, 2)], hidden=(32,), nnFunc="Tanh",
+                batchSize=10, maxTotObsNum=1500, randSeed=17),
+        sc=dict(seed=19, dimS=576, dimA=2, lenMin=4, lenMax=20, pTerm=0.5), n_eps=30),
+    "conv-perlayer-unstrided-b10": dict(      # ... and the unstrided form
+        kw=dict(dimS=576, dimA=2, nAppendedObs=0, conv=[(12, 12, 4, 8, 3, 1), (10, 10, 8, 12, 4, 1)], hidden=(32,), nnFunc="Tanh",
+                batchSize=10, maxTotObsNum=1500, randSeed=17),
+        sc=dict(seed=19, dimS=576, dimA=2, lenMin=4, lenMax=20, pTerm=0.5), n_eps=30),
+    "conv-extras6-b24": dict(      # the "6-extras" case of tests/test_hip_a22.py: six state variables beside the image
+        kw=dict(dimS=1030, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=5, conv=[(8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)],
+                hidden=(48,), nnFunc="Tanh", batchSize=24, maxTotObsNum=2000, randSeed=3),
+        sc=dict(seed=5, dimS=1030, dimA=1, lenMin=3, lenMax=9, pTerm=0.3), n_eps=60),
+    "conv-lstm32-bptt4": dict(      # convolutions under a recurrent layer: every window row passes through the conv stack
+        kw=dict(dimS=256, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=5, nAppendedObs=3, conv=[(8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)],
+                hidden=(32,), nnFunc="Tanh", batchSize=12, maxTotObsNum=2000, randSeed=3, nn_type=_LSTM, nnBPTTseq=4),
+        sc=dict(seed=5, dimS=256, dimA=1, lenMin=3, lenMax=12, pTerm=0.3), n_eps=50),
+    # ---- the prioritised samplers inside a training step ----
+    "per-rank-2x32-b16": dict(
+        kw=dict(dimS=5, dimA=2, bounded=[1, 0], hidden=(32, 32), batchSize=16, maxTotObsNum=2000, randSeed=42, dataSamplingAlgo="PERrank"),
+        sc=dict(seed=7, dimS=5, dimA=2, lenMin=5, lenMax=40, pTerm=0.5), n_eps=30),
+    "per-seq-2x32-b16": dict(
+        kw=dict(dimS=5, dimA=2, bounded=[1, 0], hidden=(32, 32), batchSize=16, maxTotObsNum=2000, randSeed=42, dataSamplingAlgo="PERseq"),
+        sc=dict(seed=7, dimS=5, dimA=2, lenMin=5, lenMax=40, pTerm=0.5), n_eps=30),
+    "per-err-lstm24": _rec(_LSTM, (24,), 6, 5, 20, dataSamplingAlgo="PERerr"),
+    # ---- a recurrent net's weight gradients over at least 1024 window rows: one launch ----
+    "lstm-2x32-bptt16-b64": _rec(_LSTM, (32, 32), 6, 16, 64),      # 64 x 17 = 1088 window rows
 }
 
 # every counter hl_timing_get knows for a launch of the training step (smarties_amd/csrc/step_exec.h)
@@ -115,7 +161,8 @@ ROUTE_COUNTERS = (["step_tail_kernel", "big_sample_ahead", "per_prepare", "stack
                    "fused_fwd_head_dx", "fused_wide", "step_chain", "fwd_chain", "head_kernel", "panel_head",
                    "dw_table_kernel", "gemm16_dw", "big_dw", "dw_wide", "dw_direct", "splitk_reduce", "adam_kernel", "post_kernel", "post_agg_chunks",
                    "rec_prepare", "rec_in_product", "rec_forward", "rec_backward", "rec_step_fused", "rec_forward_lower", "rec_backward_lower", "gemm16_dx_segment",
-                   "conv_back", "conv_dw_dense", "conv_dw_all", "conv_dw_rows", "conv_dw", "conv_reduce_adam", "conv_fwd_tail", "conv_prep"]
+                   "conv_back", "conv_dw_dense", "conv_dw_all", "conv_dw_rows", "conv_dw", "conv_reduce_adam", "conv_fwd_tail", "conv_prep",
+                   "moments_kernel", "xchg_allreduce"]
                   + ["gemm16_fwd%d" % j for j in range(8)] + ["gemm16_dx%d" % j for j in range(8)]
                   + ["conv_fwd%d" % j for j in range(8)] + ["conv_dx%d" % j for j in range(8)])
 
@@ -134,6 +181,15 @@ LISTED = {
     "mgu-80x80-tm": {("W", "L3.res.B"): 5.3e-06},
     "rnn-272-tm": {("W", "L1.rnn.B"): 3.9e-04},
     "conv-small": {("W", "L1.conv.B"): 8.8e-05, ("W", "L2.conv.B"): 6.4e-05},
+    "conv-atari-18opt-b8": {("W", "L1.conv.B"): 2.9e-05, ("W", "L2.conv.B"): 4.0e-05, ("W", "L3.conv.B"): 1.7e-05, ("W", "L4.conv.B"): 1.4e-05,
+                            ("W", "L6.res.B"): 1.1e-05},
+    "conv-rows-32x32-b8": {("W", "L1.conv.B"): 2.4e-04, ("W", "L2.conv.B"): 4.9e-06},
+    "conv-rows-stacked-extras3-b8": {("W", "L1.conv.B"): 2.9e-05, ("W", "L2.conv.B"): 2.7e-05},
+    "conv-rows-single-b8": {("W", "L1.conv.B"): 9.6e-05},
+    "conv-perlayer-strided-b10": {("W", "L1.conv.B"): 3.1e-05, ("W", "L2.conv.B"): 3.8e-05},
+    "conv-perlayer-unstrided-b10": {("W", "L1.conv.B"): 1.7e-05, ("W", "L2.conv.B"): 2.0e-04},
+    "conv-extras6-b24": {("W", "L1.conv.B"): 1.2e-05, ("W", "L2.conv.B"): 2.7e-05, ("W", "L5.dense.B"): 2.3e-05},
+    "conv-lstm32-bptt4": {("W", "L1.conv.B"): 1.8e-05, ("W", "L2.conv.B"): 1.3e-05},
 }
 for _n, _l in LISTED.items():
     SHAPES[_n]["listed"] = _l
@@ -167,9 +223,66 @@ ROUTES = {
     "fwdchain-64x288-b40": {'step_tail_kernel': 1, 'fwd_chain': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'gemm16_dx1': 1},
     "generic-288x64-b40": {'step_tail_kernel': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'gemm16_fwd0': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1},
     "rnn-encoder-mgu": {'step_tail_kernel': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'rec_forward': 1, 'rec_backward': 1, 'rec_forward_lower': 1, 'rec_backward_lower': 1, 'gemm16_dx_segment': 1},
+    # (conv_dw_dense, not conv_dw_all: the 3136 x 512 dense layer alone is 196 x 32 weight-gradient tiles of 16 x 16, above the 128 from which
+    #  the dense layers' tiles join the filter-gradient launch -- launchBackward: denseMerged -- so the step has no weight-gradient launch of its own)
+    "conv-atari-18opt-b8": {'step_tail_kernel': 1, 'head_kernel': 1, 'post_kernel': 1, 'conv_back': 1, 'conv_dw_dense': 1, 'conv_reduce_adam': 1, 'conv_fwd_tail': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1},
+    # (conv_dw_all: a 400 x 32 dense layer is 25 x 2 tiles, the net stays below 128: the dense layers keep their launch, gemm16_dw)
+    "conv-rows-32x32-b8": {'step_tail_kernel': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'conv_back': 1, 'conv_dw_all': 1, 'conv_reduce_adam': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1, 'conv_fwd1': 1},
+    "conv-rows-stacked-extras3-b8": {'step_tail_kernel': 1, 'stack_gather': 1, 'extras_copy': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'conv_back': 1, 'conv_dw_all': 1, 'conv_reduce_adam': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1, 'conv_fwd1': 1},
+    "conv-rows-single-b8": {'step_tail_kernel': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'conv_dw_rows': 1, 'conv_reduce_adam': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1},
+    "conv-perlayer-strided-b10": {'step_tail_kernel': 1, 'stack_gather': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'conv_dw': 1, 'conv_reduce_adam': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1, 'conv_fwd1': 1, 'conv_dx1': 1},
+    "conv-perlayer-unstrided-b10": {'step_tail_kernel': 1, 'stack_gather': 1, 'head_kernel': 1, 'dw_direct': 1, 'post_kernel': 1, 'conv_dw': 1, 'conv_reduce_adam': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1, 'conv_fwd1': 1, 'conv_dx1': 1},
+    "conv-extras6-b24": {'step_tail_kernel': 1, 'stack_gather': 1, 'extras_copy': 1, 'head_kernel': 1, 'dw_direct': 1, 'post_kernel': 1, 'conv_back': 1, 'conv_dw': 1, 'conv_reduce_adam': 1, 'gemm16_fwd1': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1, 'conv_fwd1': 1},
+    "conv-lstm32-bptt4": {'step_tail_kernel': 1, 'stack_gather': 1, 'window_rows': 1, 'panel_head': 1, 'dw_direct': 1, 'post_kernel': 1, 'rec_forward': 1, 'rec_backward': 1, 'conv_back': 1, 'conv_dw': 1, 'conv_reduce_adam': 1, 'gemm16_dx1': 1, 'conv_fwd0': 1, 'conv_fwd1': 1},
+    "per-rank-2x32-b16": {'step_tail_kernel': 1, 'per_prepare': 1, 'fused_fwd_head_dx': 1, 'dw_table_kernel': 1, 'post_kernel': 1},
+    "per-seq-2x32-b16": {'step_tail_kernel': 1, 'per_prepare': 1, 'fused_fwd_head_dx': 1, 'dw_table_kernel': 1, 'post_kernel': 1},
+    "per-err-lstm24": {'step_tail_kernel': 1, 'per_prepare': 1, 'head_kernel': 1, 'gemm16_dw': 1, 'post_kernel': 1, 'rec_forward': 1, 'rec_backward': 1},
+    "lstm-2x32-bptt16-b64": {'step_tail_kernel': 1, 'dw_wide': 1, 'post_kernel': 1, 'rec_step_fused': 1},
+}
+
+# the counters a shape is there for: (those that must fire, those that must not).  A shape whose recorded route lacks one is changed
+# until it fires, never the expectation (tests/test_blocks_cpu.py)
+REQUIRED = {
+    "conv-atari-18opt-b8": (["conv_fwd0", "conv_fwd_tail", "conv_back", "conv_dw_dense"], ["stack_gather"]),
+    "conv-rows-32x32-b8": (["conv_fwd0", "conv_dw_all"], ["stack_gather"]),
+    "conv-rows-stacked-extras3-b8": (["stack_gather", "extras_copy", "conv_dw_all"], []),
+    "conv-rows-single-b8": (["conv_fwd0", "conv_dw_rows"], ["stack_gather", "conv_dw"]),
+    "conv-perlayer-strided-b10": (["conv_dx1", "conv_dw"], ["conv_back"]),
+    "conv-perlayer-unstrided-b10": (["conv_dx1", "conv_dw"], ["conv_back"]),
+    "conv-extras6-b24": (["extras_copy"], []),
+    "conv-lstm32-bptt4": (["window_rows", "rec_forward", "rec_backward"], []),
+    "per-rank-2x32-b16": (["per_prepare"], []),
+    "per-seq-2x32-b16": (["per_prepare"], []),
+    "per-err-lstm24": (["per_prepare"], []),
+    "lstm-2x32-bptt16-b64": (["dw_wide"], []),
 }
 for _n, _r in ROUTES.items():
     SHAPES[_n]["route"] = _r
+
+
+# the counters of ROUTE_COUNTERS that no shape's route holds: {counter: (why, the test that runs the launch)}.  `why` is one of
+#   "exchange"     only a replica exchange reaches the launch (per-block parity of replica steps is tests/test_hip_r6.py's, bit-equal to host sums)
+#   "periodic"     a launch of every 1000th step, not of a training step's own launch list
+#   "repeat"       the same launch as a covered counter with another layer index as its argument (a deeper stack repeats it)
+#   "unreachable"  no configuration hl_create accepts reaches the name (the loops that print it start at layer 1)
+# tests/test_blocks_cpu.py holds this table to ROUTES (nothing here fires in a route, everything else does in one) and to the named tests
+_R6 = "tests/test_hip_r6.py::test_two_replicas_with_large_local_batches_and_other_layer_types"
+_DEEP_DENSE = "tests/test_hip_settings_r3.py::test_random_configurations_match_oracle"       # [wide-320x288x64-oneshot-gemm]: three layers, a launch each
+_DEEP_CONV = "tests/test_hip_r5.py::test_every_form_of_the_convolutional_backward_pass_follows_the_reference"      # four layers, per-layer launches (GENERIC & 8)
+EXCUSED = {
+    "adam_kernel": ("exchange", "tests/test_hip_r6.py::test_rccl_sequence_at_the_baseline_shapes_on_one_rank"),      # (RCCL: dW -> all-reduce -> Adam launch)
+    "conv_prep": ("exchange", _R6), "xchg_allreduce": ("exchange", _R6),
+    "moments_kernel": ("periodic", "tests/test_hip_parity.py::test_thousand_step_sweep_matches_oracle"),
+    "gemm16_dx0": ("unreachable", None), "conv_dx0": ("unreachable", None),
+}
+# (layers 2 and 3 run in the named tests; no test runs a stack deeper than four convolutions or four separately launched dense layers:
+#  counters 4 .. 7 are the same launch_* call with l = 4 .. 7)
+EXCUSED.update({"gemm16_%s%d" % (k, j): ("repeat", _DEEP_DENSE) for k in ("fwd", "dx") for j in range(2, 8)})
+EXCUSED.update({"conv_%s%d" % (k, j): ("repeat", _DEEP_CONV) for k in ("fwd", "dx") for j in range(2, 8)})
+
+# the form of the row-block kernels (conv.hip) the first convolutional layer takes, as hl_debug_conv_rows_kind states it: 1 the RACER_atari
+# geometry at compile time, 0 any geometry; every other shape: -1, no row-block kernels (conv_fwd0 and conv_dw_* count launches of either form)
+ROWS_KIND = {"conv-atari-18opt-b8": 1, "conv-rows-32x32-b8": 0, "conv-rows-single-b8": 0, "conv-rows-stacked-extras3-b8": 0}
 
 
 def make_learners(makers, name, params=None):

@@ -1,6 +1,9 @@
 """The yardstick of tests/test_hip_blocks.py, pinned on the CPU: the fp32 restatement (O32, oracle/liboracle_port.so) against its
 build with the arrays in double (O64, oracle/liboracle_port64.so) on every shape of tests/blocks.py, four steps from the same
-weights, each drawing its own minibatches."""
+weights, each drawing its own minibatches; and the claim "one shape per launch route" held to the names step_exec.h times."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -49,11 +52,64 @@ def test_fp32_loses_at_most_a_third_of_tol32_in_every_block(name):
 def test_replay_fields_of_both_builds_agree():
     """what four steps wrote back into the replay: per field over all episodes within TOL32 / 3 of its largest entry"""
     for name in SHAPES:
-        ref = cpu_reference(name) if name in ("fused-2x32-b16", "lstm-2x32-wave", "discrete18-2x128-b40") else None
+        ref = cpu_reference(name) if name in ("fused-2x32-b16", "lstm-2x32-wave", "discrete18-2x128-b40", "conv-atari-18opt-b8", "per-rank-2x32-b16") else None
         if ref is None:
             continue
         for f, v in ref["fields64"].items():
             assert relinf(ref["fields32"][f], v) <= TOL32 / 3, (name, f)
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def step_exec_counters():
+    """every name smarties_amd/csrc/step_exec.h passes to timed(h, ...): the literals, and the snprintf families with every layer index"""
+    src = open(os.path.join(ROOT, "smarties_amd", "csrc", "step_exec.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "smarties_hip.h")).read()
+    nMax = max(int(m) for m in re.findall(r"#define\s+HL_MAX_(?:HIDDEN|CONV)\s+(\d+)", hdr))
+    args = re.findall(r"\btimed\(h,\s*([^,]+),", src)
+    assert len(args) > 50 and set(a for a in args if not a.startswith('"')) == {"nm"}, sorted(set(args))      # (a literal, or the formatted buffer)
+    names = set(a.strip('"') for a in args if a.startswith('"'))
+    fmts = set(re.findall(r'snprintf\(nm,\s*sizeof\(nm\),\s*"([^"]+)"', src))
+    assert fmts and all(f.count("%d") == 1 and f.count("%") == 1 for f in fmts), fmts
+    for f in fmts:
+        names |= set(f % j for j in range(nMax))
+    return names
+
+
+def test_route_counters_are_the_names_step_exec_times():
+    """blocks.ROUTE_COUNTERS is what a route is read from: a launch timed under a name it lacks would fire unseen in every route"""
+    names = step_exec_counters()
+    for fam in ("gemm16_fwd", "gemm16_dx", "conv_fwd", "conv_dx"):
+        assert fam + "0" in names and fam + "7" in names, fam
+    assert len(set(blocks.ROUTE_COUNTERS)) == len(blocks.ROUTE_COUNTERS)
+    assert names - set(blocks.ROUTE_COUNTERS) == set()
+    assert set(blocks.ROUTE_COUNTERS) - names == set()      # (and no stale name that nothing can fire)
+
+
+def test_every_counter_fires_in_some_shape_or_is_excused():
+    """"one shape per launch route" kept honest: every counter is in the recorded route of at least one shape, or in blocks.EXCUSED with
+    an allowed reason and a test of the suite that runs the launch; the counters a shape is there for are in its recorded route"""
+    fired = set()
+    for name in SHAPES:
+        assert name in blocks.ROUTES, name      # (every shape has a recorded route)
+        assert set(blocks.ROUTES[name]) <= set(blocks.ROUTE_COUNTERS), name
+        fired |= set(blocks.ROUTES[name])
+    assert set(blocks.EXCUSED) <= set(blocks.ROUTE_COUNTERS)
+    assert fired & set(blocks.EXCUSED) == set()
+    assert set(blocks.ROUTE_COUNTERS) - fired - set(blocks.EXCUSED) == set()
+    for c, (why, by) in blocks.EXCUSED.items():
+        assert why in ("exchange", "periodic", "repeat", "unreachable"), c
+        if why == "unreachable":      # (the loops that format these names start at layer 1: nothing can run them)
+            assert by is None and c in ("gemm16_dx0", "conv_dx0"), c
+            continue
+        path, test = by.split("::")
+        assert re.search(r"^def %s\(" % re.escape(test), open(os.path.join(ROOT, path)).read(), re.M), (c, by)
+    for name, (must, must_not) in blocks.REQUIRED.items():
+        route = blocks.ROUTES[name]
+        assert must and all(c in route for c in must), (name, [c for c in must if c not in route])
+        assert not any(c in route for c in must_not), (name, [c for c in must_not if c in route])
+    assert set(blocks.ROWS_KIND) <= set(n for n in SHAPES if "conv_fwd0" in blocks.ROUTES[n])
 
 
 def test_blockdev_sees_a_zeroed_layer_that_relinf_does_not():

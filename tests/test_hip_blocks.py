@@ -5,7 +5,8 @@ and every tap column on its own scale (tests/blocks.py, tests/parity.py: blockde
 e_hip(b) = dev(G, O64) is held to TOL32 per block -- tests/test_blocks_cpu.py proves e_cpu(b) = dev(O32, O64) <= TOL32 / 3 for the
 same inputs -- or to 4 e_cpu(b) for the few blocks a shape lists as ill-conditioned.  The first two steps run as the suite's other
 tests run them (the captured single-step graph); the last two run with the launch timers on, which makes them eager launches
-and counts them: the counters that fire, and how often, are the shape's route, and a shape that takes another one fails."""
+and counts them: the counters that fire, and how often, are the shape's route, and a shape that takes another one fails; so does
+one whose first convolutional layer takes another form of the row-block kernels than blocks.ROWS_KIND states."""
 import numpy as np
 import pytest
 
@@ -53,6 +54,11 @@ def run_case(hip_api, name):
     report.append("route: %r" % ({c: (int(n) if n == int(n) else n) for c, n in route.items()},))
     if route != SHAPES[name].get("route"):
         problems.append("route %r, expected %r" % (route, SHAPES[name].get("route")))
+    # (conv_fwd0 / conv_dw_* count launches of either form of the row-block kernels: which one is the learner's to say)
+    kind = G.debug_conv_rows_kind()
+    report.append("row-block kernels of the first convolutional layer: %d" % kind)
+    if kind != blocks.ROWS_KIND.get(name, -1):
+        problems.append("row-block kernel form %d, expected %d" % (kind, blocks.ROWS_KIND.get(name, -1)))
     fields = blocks.episode_fields(G)
     for f, v in ref["fields64"].items():
         d = relinf(fields[f], v)
