@@ -12,7 +12,7 @@
  * DEVICE pointers (a torch tensor's data_ptr(): the library shares the process's HIP runtime) and never touch host copies of the data.
  * hl_forward_dev and hl_select_actions_dev act on rows (dense nets), hl_forward_sequences_dev and hl_select_actions_sequences_dev on
  * windows of a strided rollout buffer (recurrent nets, dense nets whose appended observations they stack, and feed-forward nets behind
- * convolutions, whose stacked frames they read from a one-frame-per-step buffer), hl_append_episodes_dev stores the finished episodes
+ * convolutions, the Nature-DQN stack among them, whose stacked frames they read from a one-frame-per-step buffer), hl_append_episodes_dev stores the finished episodes
  * of any net.
  *
  * Streams.  `stream` is the caller's hipStream_t passed as void*; NULL is the null stream.  Every call takes the learner's lock,
@@ -31,6 +31,9 @@
 extern "C" {
 #endif
 
+/* widest input row (dense nets) and feature row (behind convolutions) the calls below serve, floats */
+#define HL_ACT_DEV_MAX_ROW 8192
+
 /* hl_forward for rows in device memory.  dStates: [n][dimS (1 + nAppendedObs)] floats (appended observations stacked in the row by
  * the caller, as for hl_forward), dOutputs: [n][nOutputs] doubles, both device memory.
  *
@@ -40,12 +43,16 @@ extern "C" {
  * the row-block kernel in chunks of HL_ACT_ROWS_CHUNK rows.  Where hl_forward picks the same kernel the result is the same bit for bit;
  * that is every call except a net beyond HL_ACT_ROWS_SMALL_NET weights below HL_ACT_ROWS_WIDE_MIN_N or 4 x batchSize rows, which
  * hl_forward sends over the training buffers and this call does not (the two agree to rounding there).
+ * Served as well, input rows of 2049 .. HL_ACT_DEV_MAX_ROW floats (layers still at most 2048 wide): rows in device memory need not be
+ * resident in a workgroup's LDS, so act_rows_panel_kernel (smarties_amd/csrc/actband.hip) stages the first layer's input in panels of up
+ * to 1024 columns, its accumulators kept across the panels, and runs every other layer as the row-block kernel does.  Its sums run in
+ * the row-block kernel's order; hl_forward sends such rows over the training buffers, so the two calls agree to rounding there.
  * The minibatch buffers and a minibatch drawn ahead are not touched.
  *
  * Status: HL_ERR_UNSUPPORTED (with a message) for every other net -- recurrent layers (hl_forward_sequences_dev below),
  * convolutions in front (hl_forward_sequences_dev below as well, the message names it: the conv-stack kernel reads an agent's row from
- * the states of its window; a net without appended observations passes windows of one state), wider rows or layers,
- * SMARTIES_HIP_GENERIC bit 2.  HL_ERR_STATE between hl_step_begin and hl_step_end.  n == 0: HL_OK, nothing is enqueued. */
+ * the states of its window; a net without appended observations passes windows of one state), input rows beyond HL_ACT_DEV_MAX_ROW,
+ * layers beyond 2048, SMARTIES_HIP_GENERIC bit 2 (the message names the bound).  HL_ERR_STATE between hl_step_begin and hl_step_end.  n == 0: HL_OK, nothing is enqueued. */
 HL_API int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream);
 
 /* RACER::selectAction (Learners/RACER.cpp:30-47) for n agents without leaving the device: the forward pass of hl_forward_dev into a
@@ -105,11 +112,20 @@ HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates,
  * From the standardised row on the arithmetic and its order are act_conv_kernel's: an agent's outputs equal hl_forward's on the same
  * stacked row bit for bit wherever hl_forward takes the conv-stack route (rows up to HL_ACT_CONV_MAX_ROW_BYTES; beyond them hl_forward
  * runs the training launches, which agree to rounding).
+ * Served, feed-forward nets behind convolutions beyond that plan (smarties_amd/csrc/actband.hip; the Nature-DQN stack of
+ * Network/Builder.cpp:189-194 -- conv 32 / 64 / 64 on 84 x 84 x 4, a feature row of 3136 -- takes both kernels):
+ *   an image that does not fit the LDS beside the maps (above about 150 KB, or the Nature stack's 110 KB beside maps of 70 KB) runs
+ *   act_conv_band_dev_kernel in place of act_conv_dev_kernel: the FIRST layer in the smallest number of bands of output rows, from 2 on,
+ *   whose input rows fit -- a band's rows of every channel are loaded from the agent's window into LDS, rows two bands share are read
+ *   again from device memory --, every other layer as before; refused only where a MAP exceeds the LDS at any band count;
+ *   a feature row of 2049 .. HL_ACT_DEV_MAX_ROW floats runs act_rows_panel_kernel in place of the row-block kernel (see hl_forward_dev).
+ * Both keep the order of every sum of the kernels they stand in for (tests: equal bits on every net both forms can run); hl_forward
+ * sends these nets over the training buffers, so the device and the host calls agree to rounding there.
  *
  * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other recurrent net -- layers beyond 256 cells (the
  * time-step-major nets), inputs beyond 1024, convolutions in front, encoder_rnn layers: they act on windows in host memory -- and, with
- * a message naming hl_forward, for feed-forward nets behind convolutions beyond the conv-stack kernel's plan (image plus maps beyond
- * 160 KB of LDS; feature rows beyond 2048, the Nature-DQN stack among them; SMARTIES_HIP_GENERIC bit 2).
+ * a message naming hl_forward and the bound, for feed-forward nets behind convolutions beyond the plans above (a map beyond 160 KB of
+ * LDS at any band count; feature rows beyond HL_ACT_DEV_MAX_ROW; dense layers beyond 2048; SMARTIES_HIP_GENERIC bit 2).
  * HL_ERR_BAD_ARG for a null handle or array, n < 0 or row_stride < 1.  HL_ERR_STATE between hl_step_begin and hl_step_end.
  * n == 0: HL_OK, nothing is enqueued.  The minibatch buffers and a minibatch drawn ahead are not touched. */
 HL_API int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride,

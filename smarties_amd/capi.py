@@ -27,6 +27,7 @@ ORDER_STABLE, ORDER_REFERENCE = 0, 1
 RDX_CURRENT, RDX_ONE_BEHIND = 0, 1      # hl_config::reduction_timing (include/smarties_hip.h)
 ACT_SEQ_CHUNK = 512                     # HL_ACT_SEQ_CHUNK (include/smarties_hip_act.h): agents per launch of hl_forward_sequences
 ACT_ROWS_CHUNK = 1024                   # HL_ACT_ROWS_CHUNK (include/smarties_hip_act.h): rows per launch of hl_forward's many-row route
+ACT_DEV_MAX_ROW = 8192                  # HL_ACT_DEV_MAX_ROW (include/smarties_hip_dev.h): widest input / feature row of the device acting calls
 ACT_CONV_MAX_ROW_BYTES = 6 << 10         # HL_ACT_CONV_MAX_ROW_BYTES: raw rows beyond this keep hl_forward's route over the training buffers
 ACT_CONV_STAGE_BYTES = 32 << 20         # HL_ACT_CONV_STAGE_BYTES (include/smarties_hip_act.h): staged raw rows per chunk of hl_forward behind convolutions
 RDX = {"current": RDX_CURRENT, "one_behind": RDX_ONE_BEHIND}

@@ -407,6 +407,9 @@ struct ActRowsArgs {
   int outFunc;
   int ld, ldO, ng; size_t ldsBytes;       // act_rows_plan: row pitch of the activations / of the output values in LDS, column groups per wavefront, dynamic LDS
   ActLayer L[HL_MAX_HIDDEN];
+  // act_rows_panel_plan (act_plan.h; 0: the resident form above): the first layer's input row, up to ACT_DEV_MAX_ROW wide, is staged in panels
+  // of pn columns [16][pn + 4] at float offset panOff of the LDS; ld then covers the layers only
+  int pn, panOff;
 };
 bool act_rows_plan(ActRowsArgs* a);       // the kernel serves this net (every width and the input row <= 2048): LDS layout filled in
 int act_rows_blocks(int n);               // row blocks (= stamps) of a launch over n rows
@@ -427,10 +430,19 @@ struct ActConvArgs {
   // windows in the caller's device memory (launch_act_conv_dev; behind everything the host launch reads, whose offsets stay): `in` is the
   // [rows][dS] array of states then, agent i's row [dIn] the states firstRow[i] + max(max(nSteps[i], 1) - 1 - j, 0) * rowStride, j = 0 .. nAppendedObs
   const long long* firstRow; const int* nSteps; long long rowStride;
+  // act_conv_band_plan (act_plan.h; nb == 0: the resident form above): the first layer runs in nb bands of bandR output rows; a band's input
+  // rows of every channel lie in an LDS buffer [InC][bandRows][InX] at float offset bandOff (imgOff is not used then), loaded 16 bytes at a
+  // time where bandVec says every band's channel slices start and end on multiples of 4 floats
+  int nb, bandR, bandRows, bandOff, bandVec;
 };
 bool act_conv_plan(ActConvArgs* a);       // the kernel serves this net (feed-forward behind the stack, image + maps + offset tables within 160 KB of LDS, feature row <= ACT_ROWS_MAXW): layout filled in
 hipError_t launch_act_conv(const ActConvArgs& a, int nBlocks, hipStream_t s);
 hipError_t launch_act_conv_dev(const ActConvArgs& a, int nBlocks, hipStream_t s);      // 16-byte row loads only where a.vec and `in` is 16-byte aligned
+// the device calls beyond those two plans (actband.hip; the plans: act_plan.h): the first conv layer's image in bands of output rows
+// (act_conv_band_dev_kernel), the first dense layer's input row in panels (act_rows_panel_kernel)
+constexpr int ACT_DEV_MAX_ROW = 8192;     // widest feature / input row of the device calls (HL_ACT_DEV_MAX_ROW of include/smarties_hip_dev.h)
+hipError_t launch_act_conv_band_dev(const ActConvArgs& a, int nBlocks, hipStream_t s);      // 16-byte band loads only where a.bandVec and `in` is 16-byte aligned
+hipError_t launch_act_rows_panel(const ActRowsArgs& a, hipStream_t s);
 // rollout inference of recurrent nets for many agents (actseq.hip: act_seq_kernel): a workgroup stages the recurrent stack once and
 // walks its agents' windows; states, window offsets, outputs and per-agent stamps in pinned host memory
 constexpr int ACT_SEQ_CHUNK = 512;      // agents per launch (HL_ACT_SEQ_CHUNK of include/smarties_hip_act.h)

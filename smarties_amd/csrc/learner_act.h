@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/smarties_hip_act.h"
 #include "act_host.h"
+#include "act_plan.h"
 static_assert(ACT_SEQ_CHUNK == HL_ACT_SEQ_CHUNK, "the chunk capacity the header states");
 static_assert(ACT_ROWS_CHUNK == HL_ACT_ROWS_CHUNK, "the chunk capacity the header states");
 static_assert(ACT_ROWS_SMALL_NET == HL_ACT_ROWS_SMALL_NET && ACT_ROWS_WIDE_MIN_N == HL_ACT_ROWS_WIDE_MIN_N, "the switch the header states");
@@ -149,6 +150,85 @@ static bool act_conv_ok(hl_learner* h) {
   const size_t fit = (size_t)HL_ACT_CONV_STAGE_BYTES / ((size_t)h->dIn * sizeof(float));
   h->act.convCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, fit) & ~(size_t)15));
   h->act.convOk = 1;
+  return true;
+}
+// ---- the device calls (learner_dev.h) beyond the three predicates above, which they leave as they are: rows in device memory can be streamed,
+// so neither the whole image nor the whole input row has to fit a workgroup's LDS (actband.hip, the plans of act_plan.h).
+// SMARTIES_HIP_GENERIC bit 8192 sends every net those kernels can run through them -- three bands, panels of 64 columns --, nets the
+// resident kernels serve among them (tests: the two forms give the same bits)
+constexpr int ACT_DEV_FORCE_NB = 3, ACT_DEV_FORCE_PN = 64;
+static bool actDevRefuse(hl_learner* h, const char* why) { h->act.devWhy = why; return false; }
+// dense nets on rows in device memory: act_rows_kernel where act_rows_ok serves the net, act_rows_panel_kernel on input rows up to
+// ACT_DEV_MAX_ROW wide otherwise
+static bool act_dev_rows_ok(hl_learner* h) {
+  if (h->act.devRowsOk) return h->act.devRowsOk > 0;
+  h->act.devRowsOk = -1;
+  if (h->recurrent || h->nConv > 0) return actDevRefuse(h, "a recurrent net or convolutions in front");
+  if (h->generic & 2) return actDevRefuse(h, "SMARTIES_HIP_GENERIC bit 2");
+  const bool force = (h->generic & 8192) != 0;
+  ActRowsArgs& a = h->act.devRowsArgs;
+  auto panels = [&] {
+    a = ActRowsArgs{}; actFillShared(h, a);
+    a.dS = h->dS; a.dIn = h->dIn; a.nL = actFillLayers(h, 0, a.L);
+    return act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0);
+  };
+  if (force && panels()) h->act.devRowsPanel = true;
+  else if (act_rows_ok(h)) { a = h->act.rowsArgs; h->act.devRowsPanel = false; }
+  else if (!force && panels()) h->act.devRowsPanel = true;
+  else {
+    if (h->dIn > ACT_DEV_MAX_ROW) return actDevRefuse(h, "an input row beyond HL_ACT_DEV_MAX_ROW = 8192");
+    for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) return actDevRefuse(h, "a layer beyond 2048");
+    return actDevRefuse(h, "the layers' activations beyond 160 KB of LDS");
+  }
+  h->act.devRowsOk = 1;
+  return true;
+}
+// feed-forward nets behind convolutions on windows in device memory: today's two launches wherever act_conv_plan_ok serves the net; otherwise
+// act_conv_band_dev_kernel where the image does not fit beside the maps, act_rows_panel_kernel where the feature row is beyond ACT_ROWS_MAXW
+static bool act_dev_conv_ok(hl_learner* h) {
+  if (h->act.devConvOk) return h->act.devConvOk > 0;
+  h->act.devConvOk = -1;
+  if (h->recurrent || h->nConv < 1 || h->nHidden < 2) return actDevRefuse(h, "a recurrent net, or no convolutions in front of dense layers");
+  if (h->generic & 2) return actDevRefuse(h, "SMARTIES_HIP_GENERIC bit 2");
+  const bool force = (h->generic & 8192) != 0;
+  ActConvArgs& c = h->act.devConvArgs; ActRowsArgs& a = h->act.devConvRowsArgs;
+  if (!force && act_conv_plan_ok(h)) {
+    c = h->act.convArgs; a = h->act.convRowsArgs; h->act.devConvBand = h->act.devConvPanel = false;
+    h->act.devConvOk = 1;
+    return true;
+  }
+  auto conv = [&](bool bands) {
+    c = ActConvArgs{};
+    c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
+    c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = 0;
+    for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
+      c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
+    if (!(bands ? act_conv_band_plan(&c, force ? ACT_DEV_FORCE_NB : 0) : act_conv_wide_plan(&c))) return false;
+    if (c.extras != h->extras || c.nF != h->hid[1].nIn) return false;
+    c.ldF = c.nF;
+    return true;
+  };
+  if (conv(force)) h->act.devConvBand = force;
+  else if (conv(!force)) h->act.devConvBand = !force;
+  else {
+    long long tab, buf[2];
+    if (act_conv_geometry(&c, &tab, buf)) return actDevRefuse(h, "a map of the conv stack beyond 160 KB of LDS at any band count");
+    return actDevRefuse(h, "a feature row beyond HL_ACT_DEV_MAX_ROW = 8192, or the stack's geometry");
+  }
+  // the dense layers behind: hid[1 ..] on feature rows [extras | last map], standardised already
+  auto dense = [&](bool panels) {
+    a = ActRowsArgs{}; actFillShared(h, a); a.stMean = nullptr; a.stScale = nullptr;
+    a.dS = c.nF; a.dIn = c.nF; a.nL = actFillLayers(h, 1, a.L);
+    return panels ? act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0) : act_rows_plan(&a);
+  };
+  if (dense(force)) h->act.devConvPanel = force;
+  else if (dense(!force)) h->act.devConvPanel = !force;
+  else {
+    for (int j = 1; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) return actDevRefuse(h, "a layer beyond 2048");
+    return actDevRefuse(h, "the dense layers' activations beyond 160 KB of LDS");
+  }
+  if (actCus(h) < 1) return actDevRefuse(h, "the device does not say its compute units");
+  h->act.devConvOk = 1;
   return true;
 }
 // agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the chains of the other two routes borrow

@@ -1,6 +1,7 @@
 // smarties_amd/csrc/learner_dev.h -- part of learner.cpp's ONE translation unit (included there, behind learner_act.h): acting and episode ingestion from device memory: hl_forward_dev, hl_select_actions_dev, hl_forward_sequences_dev, hl_select_actions_sequences_dev, hl_append_episodes_dev
 #pragma once
 #include "../../include/smarties_hip_dev.h"
+static_assert(ACT_DEV_MAX_ROW == HL_ACT_DEV_MAX_ROW, "the row bound of the device calls the header states");
 static_assert(HL_MAX_DIMA <= 64, "ActHeadArgs::bounded holds one bit per action component");
 
 extern "C++" {
@@ -35,11 +36,12 @@ static int devActEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets act on windows in host memory (hl_forward_sequences)");
   if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act on windows in device memory (hl_forward_sequences_dev; without appended observations: windows of one state)");
-  if (!act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2");
+  if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row beyond 8192 or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2 -- here: " + h->act.devWhy);
   return devStampsEnsure(h);
 }
 // ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk), the dense nets above, the feed-forward nets behind
-// convolutions of the conv-stack kernel's plan (act_conv_plan_ok: whatever the row size -- the rows lie in device memory)
+// convolutions of the conv-stack kernel's plan (act_conv_plan_ok: whatever the row size -- the rows lie in device memory) and, beyond it, of the
+// banded and panelled kernels' (act_dev_conv_ok, act_dev_rows_ok: neither the image nor the input row has to be resident in LDS)
 static int devSeqEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
@@ -48,32 +50,39 @@ static int devSeqEnsure(hl_learner* h, const char* who) {
     return HL_OK;
   }
   if (h->nConv > 0) {
-    if (!act_conv_plan_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": this net acts on rows in host memory (hl_forward); served here behind convolutions: image and maps within 160 KB of LDS, feature rows and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear");
+    if (!act_dev_conv_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + h->act.devWhy);
     return devStampsEnsure(h);
   }
-  if (!act_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets with input row and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear");
+  if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets with input rows up to 8192 and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + h->act.devWhy);
   return devStampsEnsure(h);
 }
 // the library's buffer between the window calls' two launches: the stacked rows of a dense net, the feature rows of a net behind convolutions
 static int devSeqRowsEnsure(hl_learner* h, int n) {
   if (h->recurrent) return HL_OK;
-  if (h->nConv > 0) return devEnsure(h, &h->act.devFeat, &h->act.devFeatCap, (size_t)n * h->act.convArgs.nF);
+  if (h->nConv > 0) return devEnsure(h, &h->act.devFeat, &h->act.devFeatCap, (size_t)n * h->act.devConvArgs.nF);
   return devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn);
 }
+// the row-block kernel per chunk of ACT_ROWS_CHUNK rows [n][ldIn] in device memory: act_rows_kernel, or (panel) act_rows_panel_kernel, which
+// stages the first layer's input row in panels
+static int devRows(hl_learner* h, const ActRowsArgs& plan, bool panel, int n, const float* in, size_t ldIn, double* out) {
+  for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
+    ActRowsArgs a = plan;
+    a.in = in + (size_t)r0 * ldIn; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
+    if (panel) HIPCK(timed(h, "act_rows_panel_dev", h->stream, [&] { return launch_act_rows_panel(a, h->stream); }));
+    else HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+  }
+  return HL_OK;
+}
 // hl_forward's kernels on device rows, enqueued on the learner's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
-// bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows
+// bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows (input
+// rows beyond ACT_ROWS_MAXW: its panelled form)
 static int devForward(hl_learner* h, int n, const float* in, double* out) {
   if (n <= ACT_MAXROWS && actFewOk(h)) {
     const ActArgs aa = actFewArgs(h, in, out, h->act.devStamps, actNextTag(h));
     HIPCK(timed(h, "act_forward_dev", h->stream, [&] { return launch_act_forward(aa, n, h->stream); }));
     return HL_OK;
   }
-  for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
-    ActRowsArgs a = h->act.rowsArgs;
-    a.in = in + (size_t)r0 * h->dIn; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
-    HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
-  }
-  return HL_OK;
+  return devRows(h, h->act.devRowsArgs, h->act.devRowsPanel, n, in, h->dIn, out);
 }
 // n windows of the caller's device arrays, enqueued on the learner's stream.  Recurrent nets: ONE launch of the batched window kernel, which
 // gathers and truncates the windows itself (no staging, so no chunks).  Behind convolutions: ONE launch of the conv-stack kernel, which reads
@@ -88,15 +97,11 @@ static int devSeqForward(hl_learner* h, int n, const int64_t* firstRow, const in
     return HL_OK;
   }
   if (h->nConv > 0) {
-    ActConvArgs c = h->act.convArgs;
+    ActConvArgs c = h->act.devConvArgs;
     c.in = states; c.firstRow = reinterpret_cast<const long long*>(firstRow); c.nSteps = nSteps; c.rowStride = rowStride; c.feat = h->act.devFeat; c.n = n;
-    HIPCK(timed(h, "act_conv_dev", h->stream, [&] { return launch_act_conv_dev(c, h->act.cus, h->stream); }));
-    for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
-      ActRowsArgs a = h->act.convRowsArgs;
-      a.in = h->act.devFeat + (size_t)r0 * c.nF; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
-      HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
-    }
-    return HL_OK;
+    if (h->act.devConvBand) HIPCK(timed(h, "act_conv_band_dev", h->stream, [&] { return launch_act_conv_band_dev(c, h->act.cus, h->stream); }));
+    else HIPCK(timed(h, "act_conv_dev", h->stream, [&] { return launch_act_conv_dev(c, h->act.cus, h->stream); }));
+    return devRows(h, h->act.devConvRowsArgs, h->act.devConvPanel, n, h->act.devFeat, (size_t)c.nF, out);
   }
   ActStackDevArgs sa{states, reinterpret_cast<const long long*>(firstRow), nSteps, rowStride, h->act.devRows, n, h->dS, h->nApp};
   HIPCK(timed(h, "act_stack_dev", h->stream, [&] { return launch_act_stack_dev(sa, h->stream); }));

@@ -42,6 +42,12 @@ struct ActState {
   double* devOut = nullptr; size_t devOutCap = 0; double* devSums = nullptr; size_t devSumsCap = 0;
   float* devRows = nullptr; size_t devRowsCap = 0;      // hl_forward_sequences_dev, dense nets with appended observations: the stacked rows
   float* devFeat = nullptr; size_t devFeatCap = 0;      // ... nets behind convolutions: the agents' feature rows [n][nF] between the two launches
+  // what the device calls launch (learner_act.h: act_dev_rows_ok, act_dev_conv_ok): the resident kernels on the arguments above wherever their
+  // plans serve the net, otherwise the first conv layer in bands (devConvBand) and / or the first dense layer's input row in panels
+  // (devRowsPanel, devConvPanel) on plans of act_plan.h (actband.hip); devWhy: the bound that refuses the net
+  int devRowsOk = 0; bool devRowsPanel = false; ActRowsArgs devRowsArgs{};
+  int devConvOk = 0; bool devConvBand = false, devConvPanel = false; ActConvArgs devConvArgs{}; ActRowsArgs devConvRowsArgs{};
+  const char* devWhy = "";
 };
 }  // namespace
 
