@@ -92,6 +92,19 @@ HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates,
  * ONE launch for any n (there is no staging, so HL_ACT_SEQ_CHUNK does not apply), min(n, compute units) workgroups walking the agents,
  * outputs written to dOutputs, no stamps and no system-scope fence -- completion is stream order.  From the standardised window on the
  * arithmetic and its order are the host route's: an agent's outputs equal hl_forward_sequences' on the same window bit for bit.
+ * Served, recurrent nets on wide inputs: every net hl_create admits on a state beyond 256 components or a stacked input
+ * dimS (1 + nAppendedObs) beyond 1024, up to 8192 -- LSTM / MGU / RNN layers of one type in multiples of 16 cells up to 1024, no
+ * convolutions or encoder layers in front.  The route is hl_forward_sequences' for these nets, the time-step-major launches
+ * (smarties_amd/csrc/rectm.hip) with the agents as the samples of one chain, behind a prepare launch of its own
+ * (lstm_tm_prepare_acts_dev_kernel) that forms every agent's window by the rule above and gathers, truncates and standardises its states
+ * from the caller's array into the first layer's input rows (16-byte loads where dimS is a multiple of 4 and dStates is 16-byte aligned,
+ * scalar loads of the same values otherwise).  The agents go in chunks of min(local batch, HL_ACT_SEQ_CHUNK): a chain borrows the training
+ * rows of that many samples between steps, as hl_forward_sequences does; nothing is staged, so HL_ACT_WIN_STAGE_BYTES does not apply, and
+ * all chunks are enqueued back to back, chunk i0 reading the tables at offset i0.  The host never reads the tables, so it cannot know a
+ * chunk's longest window: the chain always runs nnBPTTseq + 1 steps -- nnBPTTseq + number of layers diagonals, twice as many launches for
+ * MGU -- whatever the windows are; an agent whose window has ended is left out by the forward tiles, and its outputs come from its own
+ * last step.  The output layer writes straight to dOutputs, no stamps.  The input rows are the host route's bit for bit and the launches
+ * behind them are the same: an agent's outputs equal hl_forward_sequences' on the same window bit for bit.
  * Served, dense nets: those hl_forward_dev serves.  One small launch (smarties_amd/csrc/actdev.hip: act_stack_dev_kernel) builds the
  * agents' rows [n][dimS (1 + nAppendedObs)] -- the last state, then the ones before it, steps before the first given state repeating
  * it -- into a buffer of the library, then hl_forward_dev's kernels run on those rows (no truncation: a dense net reads
@@ -122,8 +135,8 @@ HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates,
  * Both keep the order of every sum of the kernels they stand in for (tests: equal bits on every net both forms can run); hl_forward
  * sends these nets over the training buffers, so the device and the host calls agree to rounding there.
  *
- * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other recurrent net -- layers beyond 256 cells (the
- * time-step-major nets), inputs beyond 1024, convolutions in front, encoder_rnn layers: they act on windows in host memory -- and, with
+ * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other recurrent net -- layers beyond 256 cells on
+ * narrow inputs (the other time-step-major nets), convolutions in front, encoder_rnn layers: they act on windows in host memory -- and, with
  * a message naming hl_forward and the bound, for feed-forward nets behind convolutions beyond the plans above (a map beyond 160 KB of
  * LDS at any band count; feature rows beyond HL_ACT_DEV_MAX_ROW; dense layers beyond 2048; SMARTIES_HIP_GENERIC bit 2).
  * HL_ERR_BAD_ARG for a null handle or array, n < 0 or row_stride < 1.  HL_ERR_STATE between hl_step_begin and hl_step_end.

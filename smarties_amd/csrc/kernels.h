@@ -113,6 +113,13 @@ bool rec_win_act_ok(const RecArgs& a);                                // rec.hip
 std::string rec_route_name(const RecArgs& a, bool backward);          // the kernel launch_rec_forward / launch_rec_backward take for this net, template arguments included
 hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s, int parts = TM_PART_ALL);
 hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s);
+// acting for a.B agents whose windows lie in the CALLER's device memory (hl_forward_sequences_dev, wide inputs): agent b gives nSteps[b]
+// states from row firstRow[b] of a.actStates [rows][dS] on, rowStride rows apart; its window is act_win_geo's (act_win_geo.h).  Beside
+// RecArgs, not inside it: the argument block of every other kernel stays as it is
+struct TmActDev { const long long* firstRow; const int* nSteps; long long rowStride; };
+// lstm_tm_prepare_acts_dev_kernel, the input product and the chain over a.actSteps = nBPTT + 1 steps (the host does not know the windows);
+// a.actOff / a.actCnt != nullptr mark the many-agent form as for launch_rec_tm_forward and are never read
+hipError_t launch_rec_tm_act_dev(const RecArgs& a, const TmActDev& t, hipStream_t s);
 // window forward + output layer + head + back-propagation through time of a sample as ONE launch (rec.hip: lstm32_step_wave_kernel)
 struct ExtraArgs;
 bool rec_step_fused_ok(const RecArgs& a, const HeadArgs& ha);

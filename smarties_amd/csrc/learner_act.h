@@ -231,6 +231,9 @@ static bool act_dev_conv_ok(hl_learner* h) {
   h->act.devConvOk = 1;
   return true;
 }
+// recurrent nets on wide inputs on windows in device memory: the time-step-major chain of actTmChain behind a prepare launch that gathers
+// the windows from the caller's array itself (rectm.hip: lstm_tm_prepare_acts_dev_kernel) -- every wide-input net hl_create admits
+static bool act_dev_tm_ok(hl_learner* h) { return h->wideIn && actTmOk(h) && actCus(h) >= 1; }
 // agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the chains of the other two routes borrow
 // the training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples -- and, behind
 // convolutions, no more than whose stacked window rows fit HL_ACT_WIN_STAGE_BYTES of pinned staging (never fewer than one)

@@ -39,14 +39,15 @@ static int devActEnsure(hl_learner* h, const char* who) {
   if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row beyond 8192 or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2 -- here: " + h->act.devWhy);
   return devStampsEnsure(h);
 }
-// ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk), the dense nets above, the feed-forward nets behind
+// ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk) and those on wide inputs (act_dev_tm_ok), the dense nets above, the feed-forward nets behind
 // convolutions of the conv-stack kernel's plan (act_conv_plan_ok: whatever the row size -- the rows lie in device memory) and, beyond it, of the
 // banded and panelled kernels' (act_dev_conv_ok, act_dev_rows_ok: neither the image nor the input row has to be resident in LDS)
 static int devSeqEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
   if (h->recurrent) {
-    if (!actSeqOk(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs");
+    if (act_dev_tm_ok(h)) return HL_OK;      // wide inputs: the time-step-major chain on windows gathered from the caller's array
+    if (!actSeqOk(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs or wide inputs");
     return HL_OK;
   }
   if (h->nConv > 0) {
@@ -84,12 +85,35 @@ static int devForward(hl_learner* h, int n, const float* in, double* out) {
   }
   return devRows(h, h->act.devRowsArgs, h->act.devRowsPanel, n, in, h->dIn, out);
 }
-// n windows of the caller's device arrays, enqueued on the learner's stream.  Recurrent nets: ONE launch of the batched window kernel, which
-// gathers and truncates the windows itself (no staging, so no chunks).  Behind convolutions: ONE launch of the conv-stack kernel, which reads
-// every agent's stacked row from its window's states, then the row-block kernel on the feature rows per chunk of ACT_ROWS_CHUNK (hl_forward's
-// two launches without the staging).  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
 static_assert(sizeof(long long) == sizeof(int64_t), "the row tables are passed on as they come");
+// n windows of a recurrent net on wide inputs: agents in chunks of min(local batch, ACT_SEQ_CHUNK) -- the chain borrows the training rows of that many samples between
+// steps, as actTmChain does; nothing is staged, so no stage-bytes cap -- each chunk the prepare launch on the tables at its offset, the input
+// product and the chain over all recWin steps (the host does not know the windows: an agent whose window has ended is left out by the
+// forward tiles), the output layer on the chunk's rows of Yout straight into `out`.  All chunks back to back in ONE timed bracket
+static int devSeqTmForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
+  const int cap = std::min(h->B, ACT_SEQ_CHUNK);
+  for (int m : {std::min(cap, n), n % cap})      // the two chunk sizes of the call
+    if (m > 0 && !rec_tm_act_ok(actRecArgs(h, -1, m, states, nSteps, nSteps, h->recWin, 0)))
+      return fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences_dev: the time-step-major launches refuse the chunk");
+  HIPCK(timed(h, "act_tm_dev", h->stream, [&] {
+    for (int i0 = 0; i0 < n; i0 += cap) {
+      const int m = std::min(cap, n - i0);
+      // (actOff / actCnt: the many-agent form's marks for the host side of the launches; the kernels read the tables of TmActDev)
+      const RecArgs ra = actRecArgs(h, -1, m, states, nSteps + i0, nSteps + i0, h->recWin, 0);
+      const TmActDev t{reinterpret_cast<const long long*>(firstRow) + i0, nSteps + i0, rowStride};
+      hipError_t e = launch_rec_tm_act_dev(ra, t, h->stream); if (e != hipSuccess) return e;
+      e = actOutput(h, m, out + (size_t)i0 * h->nOut, nullptr, 0); if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }));
+  return HL_OK;
+}
+// n windows of the caller's device arrays, enqueued on the learner's stream.  Recurrent nets: ONE launch of the batched window kernel, which
+// gathers and truncates the windows itself (no staging, so no chunks); on wide inputs the chain above.  Behind convolutions: ONE launch of the
+// conv-stack kernel, which reads every agent's stacked row from its window's states, then the row-block kernel on the feature rows per chunk of
+// ACT_ROWS_CHUNK (hl_forward's two launches without the staging).  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
 static int devSeqForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
+  if (h->recurrent && act_dev_tm_ok(h)) return devSeqTmForward(h, n, firstRow, nSteps, rowStride, states, out);
   if (h->recurrent) {
     ActSeqArgs a = h->act.seqArgs;
     a.states = states; a.firstRow = reinterpret_cast<const long long*>(firstRow); a.nSteps = nSteps; a.rowStride = rowStride; a.out = out; a.n = n;

@@ -10,7 +10,8 @@
 //     gates[b][o] = bias[o] + sum_i A[r][i] W[i][o],        A[r] = [input of the step | previous output]   (the dW operand row itself)
 // a [B x (nIn + nC)] x [(nIn + nC) x 4 nC] product per layer and step: the weights are read once per step, not once per sample.
 //   forward   lstm_tm_prepare_kernel (window geometry per sample, the first layer's input rows; acting: lstm_tm_prepare_act_kernel for one
-//             agent's window, lstm_tm_prepare_acts_kernel for many agents as the samples), then per step and layer
+//             agent's window, lstm_tm_prepare_acts_kernel for many agents as the samples, lstm_tm_prepare_acts_dev_kernel
+//             for their windows in the caller's device memory), then per step and layer
 //             lstm_tm_fwd_kernel: workgroup = 16 samples x 16 cells, its four wavefronts the four gates (16 x 16 x K on
 //             v_mfma_f32_16x16x4_f32: A tile staged in LDS with 16-byte loads, W columns as 64-byte runs from the L2); epilogue =
 //             the cell (Layer_LSTM.h:77-125), the rows kept for the backward pass and the dW launch, this step's block output into the
@@ -28,7 +29,9 @@
 //   backward  tmDeltaProduct (a wavefront's part of D W^T), tmJoinPartials, tmFinishTile (whose cell deltas the tile completes, and the
 //             hand-off between the two producers of a tile at the arrival counter -- the protocol and its reasoning stand there)
 // A kernel keeps what is its own: how its wavefronts split columns and reduction, the loads it requests early, its cell.
+#include <type_traits>
 #include "rec_dev.h"
+#include "act_win_geo.h"
 
 namespace hl {
 
@@ -105,6 +108,56 @@ __global__ __launch_bounds__(256) void lstm_tm_prepare_acts_kernel(RecArgs a) {
     const float* states = a.actStates + (size_t)a.actOff[b] * a.dS;
     for (int i = tid; i < L0.nIn; i += 256) L0.A[r * L0.ldA + i] = recActInputAt(a, states, ctx, k, i);
   }
+}
+
+// ... and its twin for windows in the CALLER's device memory (hl_forward_sequences_dev): agent b's states are rows of a strided rollout
+// buffer, t.nSteps[b] of them from row t.firstRow[b] on; the kernel forms the window itself (act_win_geo: the newest nBPTT + 1 + nApp
+// states, one where the count is below 1) and reads, truncates and standardises it on the way into L0.A -- recActInputAt's expression on
+// the same values, so the rows are the host route's bit for bit.  The host does not know the windows, so the grid and the chain behind it
+// cover nBPTT + 1 steps whatever they are; rows k >= win are left as they are: the product multiplies them row by row into rows of P that
+// no epilogue reads, the chain's tiles mask them (tmActiveMask).
+// VEC: dS is a multiple of 4 and the states, the mean and the scale are 16-byte aligned -- every state row then starts on a 16-byte
+// boundary, as every row of L0.A does.  TM_PD pieces per lane are requested before the first is used: a row of 8192 floats is 32 pieces
+// of 16 bytes per lane, one dependent round trip each otherwise
+constexpr int TM_PD = 4;
+template <bool VEC>
+__device__ __forceinline__ void tmPrepareActsDev(const RecArgs& a, const TmActDev& t) {
+  using V = typename std::conditional<VEC, f32x4, float>::type;
+  constexpr int W = VEC ? 4 : 1;
+  const int b = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+  const ActWinGeo g = act_win_geo(t.nSteps[b], a.nBPTT + 1, a.nApp);
+  const long long r = (long long)b * a.K + k;
+  if (k == 0) {
+    if (tid == 0) { a.tmT[b] = g.win - 1; a.tmSteps[b] = g.win; a.tmNext[b] = -1; }
+    for (int j = 0; j < a.nL; ++j) {
+      const RecLayer& L = a.L[j];
+      for (int c = tid; c < L.nC; c += 256) L.A[r * L.ldA + L.nIn + c] = 0.f;
+    }
+  }
+  if (k >= g.win) return;
+  const RecLayer& L0 = a.L[0];
+  const long long first = t.firstRow[b];
+  const int dS = a.dS, nP = L0.nIn / W;      // (VEC: dS and with it nIn = dS (1 + nApp) are multiples of 4, a piece lies inside one state)
+  float* dst = L0.A + r * L0.ldA;
+  for (int p0 = tid; p0 < nP; p0 += TM_PD * 256) {
+    V x[TM_PD], m[TM_PD], s[TM_PD];
+#pragma unroll
+    for (int u = 0; u < TM_PD; ++u) {
+      const int e = min(p0 + 256 * u, nP - 1) * W, i = e % dS;
+      const float* src = a.actStates + act_win_row(g, first, t.rowStride, act_win_state(g, k, e, dS)) * dS + i;
+      x[u] = *reinterpret_cast<const V*>(src);
+      m[u] = *reinterpret_cast<const V*>(a.rp.stMean + i);
+      s[u] = *reinterpret_cast<const V*>(a.rp.stScale + i);
+    }
+#pragma unroll
+    for (int u = 0; u < TM_PD; ++u) {
+      const int p = p0 + 256 * u;
+      if (p < nP) *reinterpret_cast<V*>(dst + p * W) = (x[u] - m[u]) * s[u];
+    }
+  }
+}
+__global__ __launch_bounds__(256) void lstm_tm_prepare_acts_dev_kernel(RecArgs a, TmActDev t, int vec) {
+  if (vec) tmPrepareActsDev<true>(a, t); else tmPrepareActsDev<false>(a, t);
 }
 
 // ---- what the three forward kernels share --------------------------------------------------------------------------------------------
@@ -795,6 +848,15 @@ hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s, int parts) {
   return tmForwardDiagonals(a, kLast, reinterpret_cast<const void*>(lstm_tm_fwd_kernel), 1, [&](dim3 g, size_t lds, int jLo, int k0) {
     hipLaunchKernelGGL(lstm_tm_fwd_kernel, g, dim3(TM_FNT), lds, s, a, jLo, k0);
   });
+}
+// the windows of a.B agents from the caller's device memory: the prepare launch that gathers them, then the product and the chain over
+// all nBPTT + 1 steps -- after the prepare launch they read tmT / tmSteps / tmNext and the rows of L.A only
+hipError_t launch_rec_tm_act_dev(const RecArgs& a, const TmActDev& t, hipStream_t s) {
+  if (!a.actStates || !a.actOff || !a.actCnt || !a.tmP || a.actSteps != a.nBPTT + 1 || !t.firstRow || !t.nSteps || t.rowStride < 1) return hipErrorInvalidValue;
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const int vec = a.dS % 4 == 0 && aligned(a.actStates) && aligned(a.rp.stMean) && aligned(a.rp.stScale) ? 1 : 0;
+  hipLaunchKernelGGL(lstm_tm_prepare_acts_dev_kernel, dim3(a.B, a.actSteps), dim3(256), 0, s, a, t, vec);
+  return launch_rec_tm_forward(a, s, TM_PART_PRODUCT | TM_PART_CHAIN);
 }
 // anti-diagonal j + k = e of the backward chain: its members are layers jLo .. jLo + nz - 1 at steps e - j (behind the windows, k = nBPTT + 1,
 // the last layer only); gx1 = grid width of the D W^T launches over the members' rows of W, gx0 = that of MGU's phase 0 over their cells
