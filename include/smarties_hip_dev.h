@@ -170,6 +170,46 @@ HL_API int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nst
                                   const int64_t* first_row, int64_t row_stride, const float* dStates, const double* dActions,
                                   const double* dMu, const double* dRewards, const float* dValues, const float* dAdvantages, void* stream);
 
+/* ---- acting on a policy snapshot while gradient steps run -------------------------------------------------------------------------
+ * The four acting calls above are enqueued on the learner's stream: behind hl_step(2000) an answer of tens of microseconds waits for every
+ * queued step, and it cannot be had earlier from the live weights, which Adam rewrites in every weight-gradient launch.  The calls below let
+ * the learner publish a SNAPSHOT of what acting reads, in stream order, and switch the acting calls to read it on a stream of their own,
+ * concurrently with the queued steps.  The default is unchanged; the training launches are not touched; results are bit for bit those of live
+ * acting at the moment the snapshot was taken. */
+enum { HL_ACT_LIVE = 0, HL_ACT_SNAPSHOT = 1 };
+
+/* Enqueues on the learner's stream, behind every step queued so far, a copy of everything the acting kernels read of the learner's mutable
+ * state: the parameter blob (hl_num_params floats) and the state standardisation (means and scales, dimS floats each; the head kernel
+ * reads network outputs, noise and the configuration only).  ONE launch (smarties_amd/csrc/actdev.hip: policy_snapshot_kernel, 16-byte
+ * accesses; timed label policy_snapshot); returns without waiting.  Two buffers, allocated at the first call; the copy goes to the one that
+ * is not current: the learner's stream first waits for an event recorded on the acting stream behind the last acting call that read that
+ * buffer, after the copy it records the buffer's "ready" event, and the host marks the buffer current -- acting calls from here on read it,
+ * calls enqueued before keep the other one.  Stream order and events are the only synchronisation: no device-side protocol, no wait inside a
+ * kernel.  A snapshot is not changed by later steps, hl_set_params, hl_set_scaling or hl_restart.
+ * Status: HL_ERR_BAD_ARG for a null handle. */
+HL_API int hl_policy_snapshot(hl_learner* h);
+
+/* Two host-side numbers, no device wait: the snapshots taken so far, and nGradSteps as queued when the current one was taken (-1 before the
+ * first) -- hl_get_counts' nGradSteps minus this is the policy lag of the actions being produced.  Either pointer may be NULL. */
+HL_API int hl_policy_snapshot_info(hl_learner* h, int64_t* n_snapshots, int64_t* nGradSteps);
+
+/* What hl_forward_dev, hl_select_actions_dev, hl_forward_sequences_dev and hl_select_actions_sequences_dev read and where they run.
+ * HL_ACT_LIVE (the default): as described above -- every code path, launch, label and buffer as without this call.
+ * HL_ACT_SNAPSHOT: the calls run on an acting stream the learner owns (created at first use, default priority).  The handshake with the
+ * caller's `stream` is the same, against the acting stream; the acting stream also waits for the current snapshot's "ready" event and for
+ * nothing else of the learner's stream, so a call completes while gradient steps queued before it still run.  The kernels are the ones the
+ * live source picks for the same net and n, on arguments that differ in the three pointers to the blob, the means and the scales only; the
+ * scratch (stamps, network outputs, stacked rows, feature rows, the stamps' tag) is a set of its own, grown behind a wait for the acting
+ * stream only.  Nothing writable is shared between the two streams, and nothing the acting stream runs waits inside a kernel: the step
+ * kernels' bounded waits for peer workgroups can be delayed by one acting launch at most, never held.
+ * hl_append_episodes_dev and every host-pointer call are unaffected by the source.
+ * Status: HL_ERR_BAD_ARG for a null handle or an unknown source.  From the acting calls under HL_ACT_SNAPSHOT: HL_ERR_STATE before any
+ * snapshot exists (the message names hl_policy_snapshot) and between hl_step_begin and hl_step_end; HL_ERR_UNSUPPORTED, with a message
+ * naming HL_ACT_LIVE, from the window calls for recurrent nets on wide inputs -- their chain borrows training rows, the step tables and the
+ * last hidden layer's activations, so it cannot run beside a step --; every net a live call refuses is refused alike.
+ * hl_destroy waits for the acting stream and releases the stream, the events and the buffers. */
+HL_API int hl_act_dev_source(hl_learner* h, int32_t source);
+
 #ifdef __cplusplus
 }
 #endif

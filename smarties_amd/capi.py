@@ -27,6 +27,7 @@ ORDER_STABLE, ORDER_REFERENCE = 0, 1
 RDX_CURRENT, RDX_ONE_BEHIND = 0, 1      # hl_config::reduction_timing (include/smarties_hip.h)
 ACT_SEQ_CHUNK = 512                     # HL_ACT_SEQ_CHUNK (include/smarties_hip_act.h): agents per launch of hl_forward_sequences
 ACT_ROWS_CHUNK = 1024                   # HL_ACT_ROWS_CHUNK (include/smarties_hip_act.h): rows per launch of hl_forward's many-row route
+ACT_LIVE, ACT_SNAPSHOT = 0, 1           # HL_ACT_LIVE, HL_ACT_SNAPSHOT (include/smarties_hip_dev.h): what the device acting calls read
 ACT_DEV_MAX_ROW = 8192                  # HL_ACT_DEV_MAX_ROW (include/smarties_hip_dev.h): widest input / feature row of the device acting calls
 ACT_CONV_MAX_ROW_BYTES = 6 << 10         # HL_ACT_CONV_MAX_ROW_BYTES: raw rows beyond this keep hl_forward's route over the training buffers
 ACT_CONV_STAGE_BYTES = 32 << 20         # HL_ACT_CONV_STAGE_BYTES (include/smarties_hip_act.h): staged raw rows per chunk of hl_forward behind convolutions
@@ -222,6 +223,9 @@ class CApi:
             "append_episodes_dev": (C.c_int, [P, I32, pi32, pi32, pi64, pi64, I64, P, P, P, P, P, P, P]),
             "forward_sequences_dev": (C.c_int, [P, I32, P, P, I64, P, P, P]),
             "select_actions_sequences_dev": (C.c_int, [P, I32, P, P, I64, P, P, P, P, P, P, P]),
+            "policy_snapshot": (C.c_int, [P]),
+            "policy_snapshot_info": (C.c_int, [P, pi64, pi64]),
+            "act_dev_source": (C.c_int, [P, I32]),
             "save": (C.c_int, [P, C.c_char_p]),
             "metrics": (C.c_int, [P, C.c_char_p, I32, C.c_char_p, I32]),
             "grad_stats": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -601,6 +605,26 @@ class Learner:
             self._dev(mu, "f64", rows * self.polDim, "mu"), self._dev(rewards, "f64", rows, "rewards"),
             self._dev(values, "f32", rows, "values"), self._dev(advantages, "f32", rows, "advantages", optional=True),
             self._stream(stream)))
+
+    # -- acting on a policy snapshot while gradient steps run (include/smarties_hip_dev.h) ----
+    def policy_snapshot(self):
+        """hl_policy_snapshot: behind every step queued so far, copy what the acting kernels read (parameters, state standardisation)
+        into the snapshot buffer that is not current, and make it current.  No host wait."""
+        self._ck(self.api.fn("policy_snapshot")(self.h))
+
+    def policy_snapshot_info(self):
+        """(snapshots taken, nGradSteps as queued when the current one was taken; -1 before the first): host-side, no device wait"""
+        n, g = C.c_int64(), C.c_int64()
+        self._ck(self.api.fn("policy_snapshot_info")(self.h, C.byref(n), C.byref(g)))
+        return int(n.value), int(g.value)
+
+    def act_source(self, source):
+        """hl_act_dev_source: "live" (the default: the four _dev acting calls on the learner's stream and weights) or "snapshot" (on the
+        learner's acting stream and the current snapshot, beside queued gradient steps).  An integer is passed on as it is."""
+        code = {"live": ACT_LIVE, "snapshot": ACT_SNAPSHOT}.get(source, source)
+        if not isinstance(code, int):
+            raise ValueError('act_source: "live" or "snapshot", not %r' % (source,))
+        self._ck(self.api.fn("act_dev_source")(self.h, code))
 
     def set_episode_log(self, path):
         self._ck(self.api.fn("set_episode_log")(self.h, str(path).encode() if path else None))

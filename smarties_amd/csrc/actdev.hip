@@ -10,6 +10,8 @@
 //                      episodes whose steps are rows of the caller's device arrays: ingest_kernel (misc.hip) with a strided gather in
 //                      place of the pinned host block, the same insertion values for the derived fields, the reward sum formed on the
 //                      device in step order.
+//   policy_snapshot_kernel  hl_policy_snapshot: the parameter blob and the state standardisation copied into one of the learner's two
+//                      snapshot buffers, which the acting calls read on a stream of their own while gradient steps run.
 #include "dev_common.h"
 
 #pragma clang fp contract(off)
@@ -104,6 +106,37 @@ hipError_t launch_act_stack_dev(const ActStackDevArgs& a, hipStream_t s) {
   if (!a.states || !a.firstRow || !a.nSteps || !a.rows || a.rowStride < 1 || a.dS < 1 || a.nApp < 0) return hipErrorInvalidValue;
   const long long blocks = ((long long)a.n * a.dS * (1 + a.nApp) + 255) / 256;
   hipLaunchKernelGGL(act_stack_dev_kernel, dim3((unsigned)std::min(blocks, 4096ll)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// hl_policy_snapshot: everything the acting kernels read of the learner's mutable state -- the blob, the states' means and scales -- into a
+// snapshot buffer, ONE launch.  16 bytes per access, four loads in flight per thread, workgroups striding over the blob; the last workgroup
+// also takes the two small arrays (whole quads as 16 bytes, the up to three values behind them one by one).  Waits for nothing in the kernel
+__global__ __launch_bounds__(256) void policy_snapshot_kernel(PolicySnapshotArgs a) {
+  const long long n4 = a.nW >> 2, nT = (long long)gridDim.x * 256;
+  const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(a.W);
+  f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(a.dW);
+  for (long long i0 = (long long)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += 4 * nT) {
+    f32x4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const long long i = i0 + q * nT; v[q] = i < n4 ? src[i] : f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const long long i = i0 + q * nT; if (i < n4) dst[i] = v[q]; }
+  }
+  if (blockIdx.x != gridDim.x - 1) return;
+  const int dS = a.dS, q4 = dS >> 2;
+  for (int i = threadIdx.x; i < 2 * q4; i += 256) {
+    const bool sc = i >= q4; const int k = sc ? i - q4 : i;
+    reinterpret_cast<f32x4*>(sc ? a.dScale : a.dMean)[k] = reinterpret_cast<const f32x4*>(sc ? a.stScale : a.stMean)[k];
+  }
+  for (int i = 4 * q4 + (int)threadIdx.x; i < dS; i += 256) { a.dMean[i] = a.stMean[i]; a.dScale[i] = a.stScale[i]; }
+}
+hipError_t launch_policy_snapshot(const PolicySnapshotArgs& a, hipStream_t s) {
+  if (!a.W || !a.stMean || !a.stScale || !a.dW || !a.dMean || !a.dScale || a.nW < 0 || (a.nW & 3) || a.dS < 1) return hipErrorInvalidValue;
+  for (const void* p : {(const void*)a.W, (const void*)a.stMean, (const void*)a.stScale, (const void*)a.dW, (const void*)a.dMean, (const void*)a.dScale})
+    if (reinterpret_cast<uintptr_t>(p) & 15) return hipErrorInvalidValue;
+  const long long blocks = ((a.nW >> 2) + 1023) / 1024;      // four quads per thread and pass
+  hipLaunchKernelGGL(policy_snapshot_kernel, dim3((unsigned)std::max(1ll, std::min(blocks, 1024ll))), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -363,6 +363,14 @@ struct ActHeadArgs {
   unsigned long long bounded;                // bit i: action component i is bounded (dA <= HL_MAX_DIMA = 64)
 };
 hipError_t launch_act_head(const ActHeadArgs& a, hipStream_t s);
+// hl_policy_snapshot (actdev.hip: policy_snapshot_kernel): what the acting kernels read of the learner's mutable state -- the blob W [nW]
+// (a multiple of 8 floats), the states' means and scales [dS] -- copied into a snapshot buffer in ONE launch.  All six arrays 16-byte aligned
+struct PolicySnapshotArgs {
+  const float* W; const float* stMean; const float* stScale;
+  float* dW; float* dMean; float* dScale;
+  long long nW; int dS;
+};
+hipError_t launch_policy_snapshot(const PolicySnapshotArgs& a, hipStream_t s);
 // forward / dX tile with the whole reduction in flight at once (gemm16.hip: gemm_os_kernel), 256 < K <= 640
 bool gemm_oneshot_ok(int flavor, int K);
 // all dense forward layers in one launch (gemm16.hip: fwd_chain_kernel)

@@ -421,7 +421,9 @@ int hl_destroy(hl_learner* h) {
   h->mu.lock();      // (released before the handle goes away; no other thread may still be using it)
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->sideStream) hipStreamSynchronize(h->sideStream);
+  actSnapSync(h);      // the acting stream of the snapshot source (learner_dev.h)
   timerFlush(h);
+  actSnapRelease(h);
   invalidateGraphs(h);
   if (h->comm) ncclCommDestroy(h->comm);
   for (unsigned char* q : {h->act.pin, h->act.rowsPin, h->act.convPin}) if (q) hipHostFree(q);

@@ -1,34 +1,74 @@
-// smarties_amd/csrc/learner_dev.h -- part of learner.cpp's ONE translation unit (included there, behind learner_act.h): acting and episode ingestion from device memory: hl_forward_dev, hl_select_actions_dev, hl_forward_sequences_dev, hl_select_actions_sequences_dev, hl_append_episodes_dev
+// smarties_amd/csrc/learner_dev.h -- part of learner.cpp's ONE translation unit (included there, behind learner_act.h): acting and episode ingestion from device memory: hl_forward_dev, hl_select_actions_dev, hl_forward_sequences_dev, hl_select_actions_sequences_dev, hl_append_episodes_dev; acting on a policy snapshot beside queued gradient steps: hl_policy_snapshot, hl_policy_snapshot_info, hl_act_dev_source
 #pragma once
 #include "../../include/smarties_hip_dev.h"
 static_assert(ACT_DEV_MAX_ROW == HL_ACT_DEV_MAX_ROW, "the row bound of the device calls the header states");
 static_assert(HL_MAX_DIMA <= 64, "ActHeadArgs::bounded holds one bit per action component");
 
 extern "C++" {
-// the handshake with the caller's stream: the learner's stream waits for what the caller queued so far ...
-static int devEnter(hl_learner* h, void* stream) {
-  if (!h->act.devIn) HIPCK(hipEventCreateWithFlags(&h->act.devIn, hipEventDisableTiming));
-  if (!h->act.devDone) HIPCK(hipEventCreateWithFlags(&h->act.devDone, hipEventDisableTiming));
-  HIPCK(hipEventRecord(h->act.devIn, static_cast<hipStream_t>(stream)));
-  HIPCK(hipStreamWaitEvent(h->stream, h->act.devIn, 0));
+// Where an acting call runs and what it reads (hl_act_dev_source).  HL_ACT_LIVE: the learner's stream, the live blob and standardisation, the
+// scratch of ActState -- everything as it was before the sources existed.  HL_ACT_SNAPSHOT: the acting stream, the current snapshot buffer,
+// the scratch set ActState::snap; nothing the two streams share is writable
+struct DevCtx {
+  hipStream_t st; bool snap;
+  const float *W, *stMean, *stScale;
+  hipEvent_t *in, *done;
+  unsigned* tag; unsigned** stamps;
+  double** out; size_t* outCap; float** rows; size_t* rowsCap; float** feat; size_t* featCap;
+};
+static size_t snapMeanOff(const hl_learner* h) { return (size_t)h->nParams; }
+static size_t snapScaleOff(const hl_learner* h) { return (size_t)h->nParams + (size_t)roundUp(h->dS, 4); }
+static DevCtx devCtx(hl_learner* h, int source) {
+  ActState& s = h->act;
+  if (source == HL_ACT_SNAPSHOT) {
+    const float* b = s.snapCur >= 0 ? s.snapBuf[s.snapCur] : nullptr;
+    return DevCtx{s.snapStream, true, b, b ? b + snapMeanOff(h) : nullptr, b ? b + snapScaleOff(h) : nullptr, &s.snapIn, &s.snapDone,
+                  &s.snap.tag, &s.snap.stamps, &s.snap.out, &s.snap.outCap, &s.snap.rows, &s.snap.rowsCap, &s.snap.feat, &s.snap.featCap};
+  }
+  return DevCtx{h->stream, false, h->W, h->rp.stMean, h->rp.stScale, &s.devIn, &s.devDone,
+                &s.tag, &s.devStamps, &s.devOut, &s.devOutCap, &s.devRows, &s.devRowsCap, &s.devFeat, &s.devFeatCap};
+}
+// a cached plan's three pointers into the learner's mutable state, as actFillShared sets them (rows standardised already keep their nullptr)
+template <typename A> static void devSource(const DevCtx& d, A& a) {
+  a.W = d.W;
+  if (a.stMean) { a.stMean = d.stMean; a.stScale = d.stScale; }
+}
+static unsigned devNextTag(const DevCtx& d) { if (++*d.tag == 0) ++*d.tag; return *d.tag; }      // (actNextTag on the source's own counter)
+// the handshake with the caller's stream: the source's stream waits for what the caller queued so far -- and, under the snapshot source, for
+// the copy into the current buffer (nothing else of the learner's stream) ...
+static int devEnter(hl_learner* h, const DevCtx& d, void* stream) {
+  if (!*d.in) HIPCK(hipEventCreateWithFlags(d.in, hipEventDisableTiming));
+  if (!*d.done) HIPCK(hipEventCreateWithFlags(d.done, hipEventDisableTiming));
+  HIPCK(hipEventRecord(*d.in, static_cast<hipStream_t>(stream)));
+  HIPCK(hipStreamWaitEvent(d.st, *d.in, 0));
+  if (d.snap) HIPCK(hipStreamWaitEvent(d.st, h->act.snapReady[h->act.snapCur], 0));
   return HL_OK;
 }
-// ... and what the caller queues from here on waits for the learner's work; the host waits for neither
-static int devLeave(hl_learner* h, void* stream) {
-  HIPCK(hipEventRecord(h->act.devDone, h->stream));
-  HIPCK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->act.devDone, 0));
+// ... and what the caller queues from here on waits for the call's work; the host waits for neither.  Snapshot source: the event the next
+// copy into the buffer just read waits for
+static int devLeave(hl_learner* h, const DevCtx& d, void* stream) {
+  HIPCK(hipEventRecord(*d.done, d.st));
+  HIPCK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), *d.done, 0));
+  if (d.snap) { HIPCK(hipEventRecord(h->act.snapRead[h->act.snapCur], d.st)); h->act.snapReadSet[h->act.snapCur] = true; }
   return HL_OK;
 }
-// a device buffer of at least `need` elements (a larger one replaces it once the stream is done with the old one)
-template <typename T> static int devEnsure(hl_learner* h, T** p, size_t* cap, size_t need) {
+// a device buffer of at least `need` elements (a larger one replaces it once the stream that uses it is done with the old one: the acting
+// stream for the snapshot source's set, so that a growing call does not wait for the gradient steps queued on the learner's)
+template <typename T> static int devEnsure(hl_learner* h, hipStream_t user, T** p, size_t* cap, size_t need) {
   if (need <= *cap) return HL_OK;
-  if (*p) { HIPCK(hipStreamSynchronize(h->stream)); hipFree(*p); *p = nullptr; *cap = 0; }
+  if (*p) { HIPCK(hipStreamSynchronize(user)); hipFree(*p); *p = nullptr; *cap = 0; }
   HIPCK(devAlloc(p, need)); *cap = need;
   return HL_OK;
 }
-// the scratch block the dense acting kernels stamp, allocated once
-static int devStampsEnsure(hl_learner* h) {
-  if (!h->act.devStamps) HIPCK(devAlloc(&h->act.devStamps, (size_t)std::max(ACT_MAXROWS, act_rows_blocks(ACT_ROWS_CHUNK))));
+// the scratch block the dense acting kernels stamp, allocated once per source
+static int devStampsEnsure(hl_learner* h, const DevCtx& d) {
+  if (!*d.stamps) HIPCK(devAlloc(d.stamps, (size_t)std::max(ACT_MAXROWS, act_rows_blocks(ACT_ROWS_CHUNK))));
+  return HL_OK;
+}
+// the snapshot source serves a call once a snapshot exists; its stream is created at first use, with default priority
+static int devSnapEnsure(hl_learner* h, const DevCtx& d, const char* who) {
+  if (!d.snap) return HL_OK;
+  if (h->act.snapCur < 0) return fail(h, HL_ERR_STATE, std::string(who) + ": the snapshot source before any snapshot was taken (hl_policy_snapshot)");
+  if (!h->act.snapStream) HIPCK(hipStreamCreateWithFlags(&h->act.snapStream, hipStreamNonBlocking));
   return HL_OK;
 }
 // which nets the row calls serve
@@ -37,59 +77,70 @@ static int devActEnsure(hl_learner* h, const char* who) {
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets act on windows in host memory (hl_forward_sequences)");
   if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act on windows in device memory (hl_forward_sequences_dev; without appended observations: windows of one state)");
   if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row beyond 8192 or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2 -- here: " + h->act.devWhy);
-  return devStampsEnsure(h);
+  const DevCtx d = devCtx(h, h->act.source);
+  { int rc = devSnapEnsure(h, d, who); if (rc) return rc; }
+  return devStampsEnsure(h, d);
 }
 // ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk) and those on wide inputs (act_dev_tm_ok), the dense nets above, the feed-forward nets behind
 // convolutions of the conv-stack kernel's plan (act_conv_plan_ok: whatever the row size -- the rows lie in device memory) and, beyond it, of the
-// banded and panelled kernels' (act_dev_conv_ok, act_dev_rows_ok: neither the image nor the input row has to be resident in LDS)
+// banded and panelled kernels' (act_dev_conv_ok, act_dev_rows_ok: neither the image nor the input row has to be resident in LDS).
+// Snapshot source: recurrent nets on wide inputs are refused -- their chain borrows training rows, tmT / tmSteps and the last hidden layer's
+// activations (devSeqTmForward, actOutput), which the step queued beside it writes
 static int devSeqEnsure(hl_learner* h, const char* who) {
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
+  const DevCtx d = devCtx(h, h->act.source);
   if (h->recurrent) {
-    if (act_dev_tm_ok(h)) return HL_OK;      // wide inputs: the time-step-major chain on windows gathered from the caller's array
+    if (act_dev_tm_ok(h)) {      // wide inputs: the time-step-major chain on windows gathered from the caller's array
+      if (d.snap) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets on wide inputs act over the training buffers, which cannot run beside a gradient step: they are served by the source HL_ACT_LIVE only");
+      return HL_OK;
+    }
     if (!actSeqOk(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs or wide inputs");
-    return HL_OK;
+    return devSnapEnsure(h, d, who);
   }
   if (h->nConv > 0) {
     if (!act_dev_conv_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + h->act.devWhy);
-    return devStampsEnsure(h);
+    { int rc = devSnapEnsure(h, d, who); if (rc) return rc; }
+    return devStampsEnsure(h, d);
   }
   if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets with input rows up to 8192 and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + h->act.devWhy);
-  return devStampsEnsure(h);
+  { int rc = devSnapEnsure(h, d, who); if (rc) return rc; }
+  return devStampsEnsure(h, d);
 }
 // the library's buffer between the window calls' two launches: the stacked rows of a dense net, the feature rows of a net behind convolutions
-static int devSeqRowsEnsure(hl_learner* h, int n) {
+static int devSeqRowsEnsure(hl_learner* h, const DevCtx& d, int n) {
   if (h->recurrent) return HL_OK;
-  if (h->nConv > 0) return devEnsure(h, &h->act.devFeat, &h->act.devFeatCap, (size_t)n * h->act.devConvArgs.nF);
-  return devEnsure(h, &h->act.devRows, &h->act.devRowsCap, (size_t)n * h->dIn);
+  if (h->nConv > 0) return devEnsure(h, d.st, d.feat, d.featCap, (size_t)n * h->act.devConvArgs.nF);
+  return devEnsure(h, d.st, d.rows, d.rowsCap, (size_t)n * h->dIn);
 }
 // the row-block kernel per chunk of ACT_ROWS_CHUNK rows [n][ldIn] in device memory: act_rows_kernel, or (panel) act_rows_panel_kernel, which
 // stages the first layer's input row in panels
-static int devRows(hl_learner* h, const ActRowsArgs& plan, bool panel, int n, const float* in, size_t ldIn, double* out) {
+static int devRows(hl_learner* h, const DevCtx& d, const ActRowsArgs& plan, bool panel, int n, const float* in, size_t ldIn, double* out) {
   for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
-    ActRowsArgs a = plan;
-    a.in = in + (size_t)r0 * ldIn; a.out = out + (size_t)r0 * h->nOut; a.done = h->act.devStamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = actNextTag(h);
-    if (panel) HIPCK(timed(h, "act_rows_panel_dev", h->stream, [&] { return launch_act_rows_panel(a, h->stream); }));
-    else HIPCK(timed(h, "act_rows_dev", h->stream, [&] { return launch_act_rows(a, h->stream); }));
+    ActRowsArgs a = plan; devSource(d, a);
+    a.in = in + (size_t)r0 * ldIn; a.out = out + (size_t)r0 * h->nOut; a.done = *d.stamps; a.n = std::min(ACT_ROWS_CHUNK, n - r0); a.tag = devNextTag(d);
+    if (panel) HIPCK(timed(h, "act_rows_panel_dev", d.st, [&] { return launch_act_rows_panel(a, d.st); }));
+    else HIPCK(timed(h, "act_rows_dev", d.st, [&] { return launch_act_rows(a, d.st); }));
   }
   return HL_OK;
 }
-// hl_forward's kernels on device rows, enqueued on the learner's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
+// hl_forward's kernels on device rows, enqueued on the source's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
 // bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows (input
 // rows beyond ACT_ROWS_MAXW: its panelled form)
-static int devForward(hl_learner* h, int n, const float* in, double* out) {
+static int devForward(hl_learner* h, const DevCtx& d, int n, const float* in, double* out) {
   if (n <= ACT_MAXROWS && actFewOk(h)) {
-    const ActArgs aa = actFewArgs(h, in, out, h->act.devStamps, actNextTag(h));
-    HIPCK(timed(h, "act_forward_dev", h->stream, [&] { return launch_act_forward(aa, n, h->stream); }));
+    ActArgs aa = actFewArgs(h, in, out, *d.stamps, devNextTag(d)); devSource(d, aa);
+    HIPCK(timed(h, "act_forward_dev", d.st, [&] { return launch_act_forward(aa, n, d.st); }));
     return HL_OK;
   }
-  return devRows(h, h->act.devRowsArgs, h->act.devRowsPanel, n, in, h->dIn, out);
+  return devRows(h, d, h->act.devRowsArgs, h->act.devRowsPanel, n, in, h->dIn, out);
 }
 static_assert(sizeof(long long) == sizeof(int64_t), "the row tables are passed on as they come");
 // n windows of a recurrent net on wide inputs: agents in chunks of min(local batch, ACT_SEQ_CHUNK) -- the chain borrows the training rows of that many samples between
 // steps, as actTmChain does; nothing is staged, so no stage-bytes cap -- each chunk the prepare launch on the tables at its offset, the input
 // product and the chain over all recWin steps (the host does not know the windows: an agent whose window has ended is left out by the
-// forward tiles), the output layer on the chunk's rows of Yout straight into `out`.  All chunks back to back in ONE timed bracket
+// forward tiles), the output layer on the chunk's rows of Yout straight into `out`.  All chunks back to back in ONE timed bracket.
+// Live source only (devSeqEnsure)
 static int devSeqTmForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
   const int cap = std::min(h->B, ACT_SEQ_CHUNK);
   for (int m : {std::min(cap, n), n % cap})      // the two chunk sizes of the call
@@ -108,48 +159,88 @@ static int devSeqTmForward(hl_learner* h, int n, const int64_t* firstRow, const 
   }));
   return HL_OK;
 }
-// n windows of the caller's device arrays, enqueued on the learner's stream.  Recurrent nets: ONE launch of the batched window kernel, which
+// n windows of the caller's device arrays, enqueued on the source's stream.  Recurrent nets: ONE launch of the batched window kernel, which
 // gathers and truncates the windows itself (no staging, so no chunks); on wide inputs the chain above.  Behind convolutions: ONE launch of the
 // conv-stack kernel, which reads every agent's stacked row from its window's states, then the row-block kernel on the feature rows per chunk of
 // ACT_ROWS_CHUNK (hl_forward's two launches without the staging).  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
-static int devSeqForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
+static int devSeqForward(hl_learner* h, const DevCtx& d, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
   if (h->recurrent && act_dev_tm_ok(h)) return devSeqTmForward(h, n, firstRow, nSteps, rowStride, states, out);
   if (h->recurrent) {
-    ActSeqArgs a = h->act.seqArgs;
+    ActSeqArgs a = h->act.seqArgs; devSource(d, a);
     a.states = states; a.firstRow = reinterpret_cast<const long long*>(firstRow); a.nSteps = nSteps; a.rowStride = rowStride; a.out = out; a.n = n;
-    HIPCK(timed(h, "act_seq_dev", h->stream, [&] { return launch_act_seq_dev(a, std::min(n, h->act.cus), h->stream); }));
+    HIPCK(timed(h, "act_seq_dev", d.st, [&] { return launch_act_seq_dev(a, std::min(n, h->act.cus), d.st); }));
     return HL_OK;
   }
   if (h->nConv > 0) {
-    ActConvArgs c = h->act.devConvArgs;
-    c.in = states; c.firstRow = reinterpret_cast<const long long*>(firstRow); c.nSteps = nSteps; c.rowStride = rowStride; c.feat = h->act.devFeat; c.n = n;
-    if (h->act.devConvBand) HIPCK(timed(h, "act_conv_band_dev", h->stream, [&] { return launch_act_conv_band_dev(c, h->act.cus, h->stream); }));
-    else HIPCK(timed(h, "act_conv_dev", h->stream, [&] { return launch_act_conv_dev(c, h->act.cus, h->stream); }));
-    return devRows(h, h->act.devConvRowsArgs, h->act.devConvPanel, n, h->act.devFeat, (size_t)c.nF, out);
+    ActConvArgs c = h->act.devConvArgs; devSource(d, c);
+    c.in = states; c.firstRow = reinterpret_cast<const long long*>(firstRow); c.nSteps = nSteps; c.rowStride = rowStride; c.feat = *d.feat; c.n = n;
+    if (h->act.devConvBand) HIPCK(timed(h, "act_conv_band_dev", d.st, [&] { return launch_act_conv_band_dev(c, h->act.cus, d.st); }));
+    else HIPCK(timed(h, "act_conv_dev", d.st, [&] { return launch_act_conv_dev(c, h->act.cus, d.st); }));
+    return devRows(h, d, h->act.devConvRowsArgs, h->act.devConvPanel, n, *d.feat, (size_t)c.nF, out);
   }
-  ActStackDevArgs sa{states, reinterpret_cast<const long long*>(firstRow), nSteps, rowStride, h->act.devRows, n, h->dS, h->nApp};
-  HIPCK(timed(h, "act_stack_dev", h->stream, [&] { return launch_act_stack_dev(sa, h->stream); }));
-  return devForward(h, n, h->act.devRows, out);
+  ActStackDevArgs sa{states, reinterpret_cast<const long long*>(firstRow), nSteps, rowStride, *d.rows, n, h->dS, h->nApp};
+  HIPCK(timed(h, "act_stack_dev", d.st, [&] { return launch_act_stack_dev(sa, d.st); }));
+  return devForward(h, d, n, *d.rows, out);
 }
-// RACER::selectAction's head on n rows of network outputs (actdev.hip: act_head_kernel)
-static int devHead(hl_learner* h, int n, const double* O, const double* dNoise, double* dActions, double* dMu, float* dValues, float* dAdvantages) {
+// RACER::selectAction's head on n rows of network outputs (actdev.hip: act_head_kernel): it reads those, the noise and the configuration
+// only, so it is the same launch under either source
+static int devHead(hl_learner* h, const DevCtx& d, int n, const double* O, const double* dNoise, double* dActions, double* dMu, float* dValues, float* dAdvantages) {
   ActHeadArgs a{};
   a.O = O; a.noise = dNoise; a.act = dActions; a.mu = dMu; a.V = dValues; a.ADV = dAdvantages;
   a.n = n; a.dA = h->dA; a.nOut = h->nOut; a.nDense = h->nDense; a.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; a.nOpt = h->nOpt;
   for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) a.bounded |= 1ull << i;
-  HIPCK(timed(h, "act_head_kernel", h->stream, [&] { return launch_act_head(a, h->stream); }));
+  HIPCK(timed(h, "act_head_kernel", d.st, [&] { return launch_act_head(a, d.st); }));
   return HL_OK;
 }
 }  // extern "C++"
+
+int hl_act_dev_source(hl_learner* h, int32_t source) {
+  if (!h) return HL_ERR_BAD_ARG;
+  HL_LOCK_RAW(h);      // (nothing is enqueued)
+  if (source != HL_ACT_LIVE && source != HL_ACT_SNAPSHOT) return fail(h, HL_ERR_BAD_ARG, "hl_act_dev_source: neither HL_ACT_LIVE nor HL_ACT_SNAPSHOT");
+  h->act.source = source;
+  return HL_OK;
+}
+
+int hl_policy_snapshot(hl_learner* h) {
+  if (!h) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  ActState& s = h->act;
+  if (!s.snapBuf[0]) {      // the two buffers and their events, once
+    if (h->nParams % 8) return fail(h, HL_ERR_STATE, "hl_policy_snapshot: the blob is no multiple of 8 floats");
+    const size_t len = snapScaleOff(h) + (size_t)roundUp(h->dS, 4);
+    for (int b = 0; b < 2; ++b) {
+      HIPCK(hipEventCreateWithFlags(&s.snapReady[b], hipEventDisableTiming));
+      HIPCK(hipEventCreateWithFlags(&s.snapRead[b], hipEventDisableTiming));
+    }
+    HIPCK(devAlloc(&s.snapBuf[1], len)); HIPCK(devAlloc(&s.snapBuf[0], len));
+  }
+  const int b = s.snapCur < 0 ? 0 : s.snapCur ^ 1;      // the buffer that is not current
+  if (s.snapReadSet[b]) HIPCK(hipStreamWaitEvent(h->stream, s.snapRead[b], 0));      // the last acting call that read it
+  PolicySnapshotArgs a{h->W, h->rp.stMean, h->rp.stScale, s.snapBuf[b], s.snapBuf[b] + snapMeanOff(h), s.snapBuf[b] + snapScaleOff(h), h->nParams, h->dS};
+  HIPCK(timed(h, "policy_snapshot", h->stream, [&] { return launch_policy_snapshot(a, h->stream); }));
+  HIPCK(hipEventRecord(s.snapReady[b], h->stream));
+  s.snapCur = b; s.snapGrad[b] = h->nGradSteps; ++s.nSnap;
+  return HL_OK;
+}
+
+int hl_policy_snapshot_info(hl_learner* h, int64_t* n_snapshots, int64_t* nGradSteps) {
+  if (!h) return HL_ERR_BAD_ARG;
+  HL_LOCK_RAW(h);
+  if (n_snapshots) *n_snapshots = h->act.nSnap;
+  if (nGradSteps) *nGradSteps = h->act.snapCur >= 0 ? h->act.snapGrad[h->act.snapCur] : -1;
+  return HL_OK;
+}
 
 int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream) {
   if (!h || n < 0 || (n > 0 && (!dStates || !dOutputs))) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   { int rc = devActEnsure(h, "hl_forward_dev"); if (rc) return rc; }
   if (n == 0) return HL_OK;
-  { int rc = devEnter(h, stream); if (rc) return rc; }
-  { int rc = devForward(h, n, dStates, dOutputs); if (rc) return rc; }
-  return devLeave(h, stream);
+  const DevCtx d = devCtx(h, h->act.source);
+  { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  { int rc = devForward(h, d, n, dStates, dOutputs); if (rc) return rc; }
+  return devLeave(h, d, stream);
 }
 
 int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const double* dNoise, double* dActions, double* dMu,
@@ -158,11 +249,12 @@ int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const 
   HL_LOCK(h);
   { int rc = devActEnsure(h, "hl_select_actions_dev"); if (rc) return rc; }
   if (n == 0) return HL_OK;
-  { int rc = devEnsure(h, &h->act.devOut, &h->act.devOutCap, (size_t)n * h->nOut); if (rc) return rc; }
-  { int rc = devEnter(h, stream); if (rc) return rc; }
-  { int rc = devForward(h, n, dStates, h->act.devOut); if (rc) return rc; }
-  { int rc = devHead(h, n, h->act.devOut, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
-  return devLeave(h, stream);
+  const DevCtx d = devCtx(h, h->act.source);
+  { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; }
+  { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  { int rc = devForward(h, d, n, dStates, *d.out); if (rc) return rc; }
+  { int rc = devHead(h, d, n, *d.out, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
+  return devLeave(h, d, stream);
 }
 
 int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride, const float* dStates,
@@ -172,10 +264,11 @@ int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow,
   { int rc = devSeqEnsure(h, "hl_forward_sequences_dev"); if (rc) return rc; }
   if (n == 0) return HL_OK;
   if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_forward_sequences_dev: row_stride below 1");
-  { int rc = devSeqRowsEnsure(h, n); if (rc) return rc; }
-  { int rc = devEnter(h, stream); if (rc) return rc; }
-  { int rc = devSeqForward(h, n, dFirstRow, dNSteps, row_stride, dStates, dOutputs); if (rc) return rc; }
-  return devLeave(h, stream);
+  const DevCtx d = devCtx(h, h->act.source);
+  { int rc = devSeqRowsEnsure(h, d, n); if (rc) return rc; }
+  { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  { int rc = devSeqForward(h, d, n, dFirstRow, dNSteps, row_stride, dStates, dOutputs); if (rc) return rc; }
+  return devLeave(h, d, stream);
 }
 
 int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride, const float* dStates,
@@ -185,12 +278,13 @@ int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFi
   { int rc = devSeqEnsure(h, "hl_select_actions_sequences_dev"); if (rc) return rc; }
   if (n == 0) return HL_OK;
   if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_select_actions_sequences_dev: row_stride below 1");
-  { int rc = devSeqRowsEnsure(h, n); if (rc) return rc; }
-  { int rc = devEnsure(h, &h->act.devOut, &h->act.devOutCap, (size_t)n * h->nOut); if (rc) return rc; }
-  { int rc = devEnter(h, stream); if (rc) return rc; }
-  { int rc = devSeqForward(h, n, dFirstRow, dNSteps, row_stride, dStates, h->act.devOut); if (rc) return rc; }
-  { int rc = devHead(h, n, h->act.devOut, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
-  return devLeave(h, stream);
+  const DevCtx d = devCtx(h, h->act.source);
+  { int rc = devSeqRowsEnsure(h, d, n); if (rc) return rc; }
+  { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; }
+  { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  { int rc = devSeqForward(h, d, n, dFirstRow, dNSteps, row_stride, dStates, *d.out); if (rc) return rc; }
+  { int rc = devHead(h, d, n, *d.out, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
+  return devLeave(h, d, stream);
 }
 
 int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, const int32_t* terminated, const int64_t* tags,
@@ -208,8 +302,9 @@ int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, co
   if (nEp == 0) return HL_OK;
   { int rc = flushStaging(h); if (rc) return rc; }      // episodes staged by hl_append_episode go first
   const bool log = !h->episodeLog.empty();
-  if (log) { int rc = devEnsure(h, &h->act.devSums, &h->act.devSumsCap, (size_t)2 * nEp); if (rc) return rc; }
-  { int rc = devEnter(h, stream); if (rc) return rc; }
+  const DevCtx d = devCtx(h, HL_ACT_LIVE);      // (ingestion writes the replay the steps read: the learner's stream whatever the acting source)
+  if (log) { int rc = devEnsure(h, h->stream, &h->act.devSums, &h->act.devSumsCap, (size_t)2 * nEp); if (rc) return rc; }
+  { int rc = devEnter(h, d, stream); if (rc) return rc; }
   // the bookkeeping of hl_append_episode, episode by episode; an episode that finds no room ends the batch, the ones before it are stored
   std::vector<long long> ids((size_t)nEp);
   int booked = 0, rcBook = HL_OK;
@@ -232,7 +327,7 @@ int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, co
     }
     HIPCK(timed(h, "ingest_dev_kernel", h->stream, [&] { return launch_ingest_dev(ia, h->stream); }));
   }
-  { int rc = devLeave(h, stream); if (rc) return rc; }
+  { int rc = devLeave(h, d, stream); if (rc) return rc; }
   if (log && booked > 0) {
     std::vector<double> sums((size_t)2 * booked);
     HIPCK(hipMemcpyAsync(sums.data(), h->act.devSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));

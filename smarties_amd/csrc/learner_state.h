@@ -22,6 +22,15 @@ struct StepBuf {
   DwTable dwTable{}, dwTableAdam{};        // the dW problems by value (kernel-argument table of dw_table_kernel)
 };
 struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int steps = 0; };
+// the scratch of the device acting calls under the snapshot source (learner_dev.h): a set of its own, so that the acting stream and the
+// learner's stream share nothing writable -- the stamps' block and the tag handed out last, the network outputs in front of the head
+// kernel, the stacked rows of a dense net, the feature rows behind convolutions
+struct ActDevScratch {
+  unsigned tag = 0; unsigned* stamps = nullptr;
+  double* out = nullptr; size_t outCap = 0;
+  float* rows = nullptr; size_t rowsCap = 0;
+  float* feat = nullptr; size_t featCap = 0;
+};
 // rollout inference (learner_act.h).  Every route's predicate is looked at once: 0 not looked at yet / 1 the route serves the net / -1 not
 struct ActState {
   unsigned tag = 0; int cus = 0;      // the last completion stamp handed out (actNextTag); compute units of the device, asked once (actCus)
@@ -48,6 +57,16 @@ struct ActState {
   int devRowsOk = 0; bool devRowsPanel = false; ActRowsArgs devRowsArgs{};
   int devConvOk = 0; bool devConvBand = false, devConvPanel = false; ActConvArgs devConvArgs{}; ActRowsArgs devConvRowsArgs{};
   const char* devWhy = "";
+  // acting on a policy snapshot (learner_dev.h: hl_policy_snapshot, hl_act_dev_source).  source: HL_ACT_LIVE / HL_ACT_SNAPSHOT.  Two
+  // buffers [W nParams | stMean | stScale], the small arrays each on a multiple of 4 floats; snapCur the one the acting calls read (-1:
+  // none yet).  snapReady[b]: recorded on the learner's stream behind the copy into b; snapRead[b]: recorded on the acting stream behind
+  // the last acting call that read b (snapReadSet) -- the next copy into b waits for it.  snapGrad[b]: nGradSteps as queued when b was taken
+  int source = 0;
+  hipStream_t snapStream = nullptr; hipEvent_t snapIn = nullptr, snapDone = nullptr;
+  float* snapBuf[2] = {nullptr, nullptr}; hipEvent_t snapReady[2] = {nullptr, nullptr}, snapRead[2] = {nullptr, nullptr};
+  bool snapReadSet[2] = {false, false};
+  int snapCur = -1; long long nSnap = 0, snapGrad[2] = {0, 0};
+  ActDevScratch snap;
 };
 }  // namespace
 
@@ -265,12 +284,23 @@ int timerId(hl_learner* h, const char* name) {
 void timerFlush(hl_learner* h) {
   if (h->trecs.empty()) return;
   hipStreamSynchronize(h->stream);
+  if (h->act.snapStream) hipStreamSynchronize(h->act.snapStream);      // (the acting calls under the snapshot source bracket their launches there)
   for (auto& r : h->trecs) {
     float ms = 0; hipEventElapsedTime(&ms, r.a, r.b);
     h->tsum[r.name] += ms; h->tcnt[r.name] += 1;
     hipEventDestroy(r.a); hipEventDestroy(r.b);
   }
   h->trecs.clear();
+}
+// hl_destroy: the acting stream drained (call before timerFlush), then its events, the snapshot buffers, the scratch set and the stream
+void actSnapSync(hl_learner* h) { if (h->act.snapStream) hipStreamSynchronize(h->act.snapStream); }
+void actSnapRelease(hl_learner* h) {
+  ActState& s = h->act;
+  actSnapSync(h);
+  for (hipEvent_t ev : {s.snapIn, s.snapDone, s.snapReady[0], s.snapReady[1], s.snapRead[0], s.snapRead[1]}) if (ev) hipEventDestroy(ev);
+  for (void* q : {(void*)s.snapBuf[0], (void*)s.snapBuf[1], (void*)s.snap.stamps, (void*)s.snap.out, (void*)s.snap.rows, (void*)s.snap.feat}) if (q) hipFree(q);
+  if (s.snapStream) hipStreamDestroy(s.snapStream);
+  s.snapStream = nullptr; s.snapCur = -1; s.snap = ActDevScratch{};
 }
 // run a launch, optionally bracketed by HIP events on the library's own stream
 template <typename F> hipError_t timed(hl_learner* h, const char* name, hipStream_t st, F&& f) {
