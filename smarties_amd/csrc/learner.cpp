@@ -204,7 +204,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     HIPCK(hipStreamCreateWithFlags(&h->sideStream, hipStreamNonBlocking));
     HIPCK(hipEventCreateWithFlags(&h->evMain, hipEventDisableTiming)); HIPCK(hipEventCreateWithFlags(&h->evSide, hipEventDisableTiming));
   }
-  // (+ PARAM_TAIL unused floats: scratch "bias" rows of weight-gradient problems that have no bias, step_exec.h; allocated ONCE: the acting predicates cache W, learner_act.h: actFillShared)
+  // (+ PARAM_TAIL unused floats: scratch "bias" rows of weight-gradient problems that have no bias, step_exec.h; allocated ONCE: the resolved acting records cache W, learner_act.h: actFillShared)
   HIPCK(devAlloc(&h->W, (size_t)h->nParams + PARAM_TAIL)); HIPCK(devAlloc(&h->M1, (size_t)h->nParams + PARAM_TAIL));
   HIPCK(devAlloc(&h->M2, (size_t)h->nParams + PARAM_TAIL)); HIPCK(devAlloc(&h->G, (size_t)h->nParams + PARAM_TAIL));
   HIPCK(devAlloc(&h->sc, 1));
@@ -384,7 +384,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   }
   HIPCK(devAlloc(&h->dFlatGiven, B));
   HIPCK(devAlloc(&h->dMoments, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dMomentsPrev, (size_t)2 * h->dS + 3)); HIPCK(devAlloc(&h->dStatsOut, 16)); HIPCK(devAlloc(&h->dStatsIns, 16));
-  HIPCK(devAlloc(&h->rp.stMean, h->dS)); HIPCK(devAlloc(&h->rp.stScale, h->dS)); HIPCK(devAlloc(&h->rp.stStd, h->dS));      // (ONCE: cached by the acting predicates, as W)
+  HIPCK(devAlloc(&h->rp.stMean, h->dS)); HIPCK(devAlloc(&h->rp.stScale, h->dS)); HIPCK(devAlloc(&h->rp.stStd, h->dS));      // (ONCE: cached by the resolved acting records, as W)
   HIPCK(devAlloc(&h->rp.farStart, 4 * 256));
   {   // ring slack: an eighth of the budget plus room for the episodes in flight (bounded in bytes for image-sized states)
     const long long slack = std::max<long long>(512, std::min<long long>(8192, (64ll << 20) / ((long long)h->dS * 4)));

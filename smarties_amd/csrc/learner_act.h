@@ -56,190 +56,164 @@ static ActArgs actFewArgs(const hl_learner* h, const float* in, double* out, vol
   aa.dS = h->dS; aa.dIn = h->dIn; aa.nL = actFillLayers(h, 0, aa.L);
   return aa;
 }
-static const float actNoState = 0.f;      // (a predicate asks for given states, it does not read them)
-// a few rows of a dense net, one workgroup per row (misc.hip: act_forward_kernel): layers and input rows within its bounds;
-// SMARTIES_HIP_GENERIC bit 2 keeps the route over the training buffers
-static bool actFewOk(hl_learner* h) {
-  if (h->act.fewOk) return h->act.fewOk > 0;
-  bool ok = !h->recurrent && h->nConv == 0 && !(h->generic & 2) && h->dIn <= ACT_MAXW;
-  for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_MAXW || h->hid[j].nIn > ACT_MAXW) ok = false;
-  h->act.fewOk = ok ? 1 : -1;
-  return ok;
-}
-// the batched window kernel (actseq.hip) serves this net: one recurrent layer type, no convolutions in front, layers within its bounds
-static bool actSeqOk(hl_learner* h) {
-  if (h->act.seqOk) return h->act.seqOk > 0;
-  h->act.seqOk = -1;
-  if (!h->recurrent || h->nConv > 0 || h->recSplit || h->wideIn) return false;      // (wide inputs: the time-step-major chain, as hl_forward_sequence)
-  const RecArgs ra = recArgs(h, 0);
-  ActSeqArgs& a = h->act.seqArgs; a = ActSeqArgs{};
-  actFillShared(h, a);
-  a.dS = h->dS; a.nApp = h->nApp; a.recWin = h->recWin; a.nL = ra.nL; a.gates = ra.gates; a.func = ra.func;
-  for (int j = 0; j < ra.nL; ++j) { const RecLayer& L = ra.L[j]; a.L[j] = ActSeqLayer{L.nIn, L.nC, L.hasRes, L.resW, L.indW, L.indB, L.indWr, L.indBr, 0, 0}; }
-  if (!act_seq_plan(&a) || actCus(h) < 1) return false;
-  h->act.seqOk = 1;
-  return true;
-}
-// the time-step-major launches (rectm.hip) serve this net's acting window -- hl_forward_sequence's route where a layer is wider than 256
-// cells --: many agents' windows then run as the samples of one chain of those launches
-static bool actTmOk(hl_learner* h) {
-  if (h->act.tmOk) return h->act.tmOk > 0;
-  const bool ok = h->recurrent && h->nConv == 0 && !h->recSplit && rec_tm_act_ok(actRecArgs(h, -1, 1, &actNoState, nullptr, nullptr, 1, 0));
-  h->act.tmOk = ok ? 1 : -1;
-  return ok;
-}
-// the workgroup-per-sample window kernels (rec.hip) serve this net's acting window -- hl_forward_sequence's route for every net the two
-// predicates above leave: convolutions in front, RNN encoder layers under MGU layers, a window beyond the batched kernel's LDS --: many
-// agents' windows then run as the samples of hl_forward_sequence's own launches, workgroup b on agent b's window
-static bool actWinOk(hl_learner* h) {
-  if (h->act.winOk) return h->act.winOk > 0;
-  bool ok = h->recurrent;
-  for (int seg = h->recSplit ? 0 : -1; ok && seg < (h->recSplit ? 2 : 0); ++seg) ok = rec_win_act_ok(actRecArgs(h, seg, 1, &actNoState, nullptr, nullptr, 1, 0));
-  h->act.winOk = ok ? 1 : -1;
-  return ok;
-}
-// the row-block kernel (actrows.hip) serves this net: dense, no convolutions in front, input rows and layers within its bounds;
-// SMARTIES_HIP_GENERIC bit 2 keeps the route over the training buffers
-static bool act_rows_ok(hl_learner* h) {
-  if (h->act.rowsOk) return h->act.rowsOk > 0;
-  h->act.rowsOk = -1;
-  if (h->recurrent || h->nConv > 0 || h->dIn > ACT_ROWS_MAXW || (h->generic & 2)) return false;
-  ActRowsArgs& a = h->act.rowsArgs; a = ActRowsArgs{};
-  actFillShared(h, a);
-  a.dS = h->dS; a.dIn = h->dIn; a.nL = actFillLayers(h, 0, a.L);
-  if (!act_rows_plan(&a)) return false;
-  long long nW = (long long)h->hid[h->nHidden - 1].size * h->ldWo;
-  for (int j = 0; j < h->nHidden; ++j) nW += (long long)h->hid[j].nIn * h->hid[j].ldW;
-  h->act.rowsSmall = nW <= ACT_ROWS_SMALL_NET;
-  h->act.rowsOk = 1;
-  return true;
-}
-// the conv-stack kernels (actconv.hip) and the row-block kernel behind them serve this net: feed-forward, convolutions in front, image and maps
-// within a workgroup's LDS, feature rows and dense layers within the row-block kernel's bounds; SMARTIES_HIP_GENERIC bit 2 keeps the route
-// over the training buffers.  Depends on the net only, never on n or on where the rows lie: hl_forward's route (act_conv_ok) and the
-// window calls on device memory (learner_dev.h: devSeqEnsure) both ask it
-static bool act_conv_plan_ok(hl_learner* h) {
-  if (h->act.convPlanOk) return h->act.convPlanOk > 0;
-  h->act.convPlanOk = -1;
-  if (h->nConv < 1 || h->nHidden < 2 || (h->generic & 2)) return false;
-  ActConvArgs& c = h->act.convArgs; c = ActConvArgs{};
+// ---- the two builders of the argument records (no plan yet: the plans of kernels.h and act_plan.h fill in the LDS layout) ----
+// the conv stack, from h->cg[]
+static ActConvArgs actConvRecord(const hl_learner* h) {
+  ActConvArgs c{};
   c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
   c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = h->recurrent ? 1 : 0;
   for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
     c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
-  if (!act_conv_plan(&c) || c.extras != h->extras || c.nF != h->hid[1].nIn) return false;
-  c.ldF = c.nF;
-  // the dense layers behind: hid[1 ..] on feature rows [extras | last map], standardised already
-  ActRowsArgs& a = h->act.convRowsArgs; a = ActRowsArgs{};
-  actFillShared(h, a); a.stMean = nullptr; a.stScale = nullptr;
-  a.dS = c.nF; a.dIn = c.nF; a.nL = actFillLayers(h, 1, a.L);
-  if (!act_rows_plan(&a) || actCus(h) < 1) return false;
-  h->act.convPlanOk = 1;
-  return true;
+  return c;
 }
-// ... and hl_forward takes that route: rows in HOST memory go through pinned staging, so on top of the plan the row-size switch.
-// A row's result is the same alone, among others and through the window calls
-static bool act_conv_ok(hl_learner* h) {
-  if (h->act.convOk) return h->act.convOk > 0;
-  h->act.convOk = -1;
-  // raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES: the copy into pinned staging costs more than the route saves (the header's figures);
-  // SMARTIES_HIP_GENERIC bit 4096 holds the switch open (tests, tools/act_conv_timing.py)
-  if ((size_t)h->dIn * sizeof(float) > (size_t)HL_ACT_CONV_MAX_ROW_BYTES && !(h->generic & 4096)) return false;
-  if (!act_conv_plan_ok(h)) return false;
-  // rows per chunk: no more than HL_ACT_CONV_STAGE_BYTES of staged raw rows, whole blocks of 16 rows, at least one
-  const size_t fit = (size_t)HL_ACT_CONV_STAGE_BYTES / ((size_t)h->dIn * sizeof(float));
-  h->act.convCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, fit) & ~(size_t)15));
-  h->act.convOk = 1;
-  return true;
+// the dense layers hid[first ..]: on raw rows, standardised on load (nF = 0), or on feature rows [extras | last map] of nF columns, standardised already
+static ActRowsArgs actDenseRecord(const hl_learner* h, int first, int nF) {
+  ActRowsArgs a{}; actFillShared(h, a);
+  if (nF) a.stMean = a.stScale = nullptr;
+  a.dS = nF ? nF : h->dS; a.dIn = nF ? nF : h->dIn; a.nL = actFillLayers(h, first, a.L);
+  return a;
 }
-// ---- the device calls (learner_dev.h) beyond the three predicates above, which they leave as they are: rows in device memory can be streamed,
-// so neither the whole image nor the whole input row has to fit a workgroup's LDS (actband.hip, the plans of act_plan.h).
-// SMARTIES_HIP_GENERIC bit 8192 sends every net those kernels can run through them -- three bands, panels of 64 columns --, nets the
-// resident kernels serve among them (tests: the two forms give the same bits)
+// ---- the resolved table (ActRoutes, learner_state.h).  SMARTIES_HIP_GENERIC bit 2 refuses every LDS route (the training buffers serve);
+// bit 4096 holds the host conv row-size switch open; bit 8192 sends every net the banded / panelled kernels of actband.hip can run through
+// them -- three bands, panels of 64 columns --, nets the resident kernels serve among them (tests: the two forms give the same bits):
+// the forced form is tried first, then the other one
 constexpr int ACT_DEV_FORCE_NB = 3, ACT_DEV_FORCE_PN = 64;
-static bool actDevRefuse(hl_learner* h, const char* why) { h->act.devWhy = why; return false; }
-// dense nets on rows in device memory: act_rows_kernel where act_rows_ok serves the net, act_rows_panel_kernel on input rows up to
-// ACT_DEV_MAX_ROW wide otherwise
-static bool act_dev_rows_ok(hl_learner* h) {
-  if (h->act.devRowsOk) return h->act.devRowsOk > 0;
-  h->act.devRowsOk = -1;
-  if (h->recurrent || h->nConv > 0) return actDevRefuse(h, "a recurrent net or convolutions in front");
-  if (h->generic & 2) return actDevRefuse(h, "SMARTIES_HIP_GENERIC bit 2");
-  const bool force = (h->generic & 8192) != 0;
-  ActRowsArgs& a = h->act.devRowsArgs;
-  auto panels = [&] {
-    a = ActRowsArgs{}; actFillShared(h, a);
-    a.dS = h->dS; a.dIn = h->dIn; a.nL = actFillLayers(h, 0, a.L);
-    return act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0);
-  };
-  if (force && panels()) h->act.devRowsPanel = true;
-  else if (act_rows_ok(h)) { a = h->act.rowsArgs; h->act.devRowsPanel = false; }
-  else if (!force && panels()) h->act.devRowsPanel = true;
-  else {
-    if (h->dIn > ACT_DEV_MAX_ROW) return actDevRefuse(h, "an input row beyond HL_ACT_DEV_MAX_ROW = 8192");
-    for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) return actDevRefuse(h, "a layer beyond 2048");
-    return actDevRefuse(h, "the layers' activations beyond 160 KB of LDS");
+static const ActRoutes& actResolve(hl_learner* h) {
+  ActRoutes& r = h->act.routes;
+  if (r.resolved) return r;
+  static const float noState = 0.f;      // (rec_tm_act_ok and rec_win_act_ok ask for given states, they do not read them)
+  const bool lds = !(h->generic & 2), force = (h->generic & 8192) != 0, dense = !h->recurrent && h->nConv == 0;
+  // a conv stack's plan serves the net: the geometry hl_create built, the feature row the first dense layer reads
+  auto convFits = [&](ActConvArgs& c, bool planned) { if (!planned || c.extras != h->extras || c.nF != h->hid[1].nIn) return false; c.ldF = c.nF; return true; };
+  // 1. a few rows of a dense net, one workgroup per row (misc.hip: act_forward_kernel): layers and input rows within its bounds
+  r.few = dense && lds && h->dIn <= ACT_MAXW;
+  for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_MAXW || h->hid[j].nIn > ACT_MAXW) r.few = false;
+  // 2. the row-block kernel (actrows.hip): dense, input rows and layers within its bounds
+  if (dense && lds && h->dIn <= ACT_ROWS_MAXW) {
+    ActRowsArgs a = actDenseRecord(h, 0, 0);
+    if (act_rows_plan(&a)) {
+      long long nW = (long long)h->hid[h->nHidden - 1].size * h->ldWo;
+      for (int j = 0; j < h->nHidden; ++j) nW += (long long)h->hid[j].nIn * h->hid[j].ldW;
+      r.rowsArgs = a; r.rows = true; r.rowsSmall = nW <= ACT_ROWS_SMALL_NET;
+    }
   }
-  h->act.devRowsOk = 1;
-  return true;
+  // 3. the conv-stack kernel (actconv.hip) and the row-block kernel on hid[1 ..] behind it: feed-forward, image and maps within a workgroup's
+  // LDS, feature rows and dense layers within the row-block kernel's bounds.  Wherever the rows lie: hl_forward and the device window calls
+  // (resolved with everything else at the first acting call of any family, under bit 8192 too: actCus is then asked at calls that did not
+  // ask it before the table existed -- hl_forward on rows beyond the row-size switch, for one; a device attribute, no result depends on when)
+  if (h->nConv >= 1 && h->nHidden >= 2 && lds) {
+    ActConvArgs c = actConvRecord(h);
+    if (convFits(c, act_conv_plan(&c))) {
+      ActRowsArgs a = actDenseRecord(h, 1, c.nF);
+      if (act_rows_plan(&a) && actCus(h) >= 1) { r.convArgs = c; r.convRowsArgs = a; r.convPlan = true; }
+    }
+  }
+  // 4. ... and hl_forward takes that route: rows in HOST memory go through pinned staging, and beyond HL_ACT_CONV_MAX_ROW_BYTES the copy costs
+  // more than the route saves (the header's figures).  Rows per chunk: no more than HL_ACT_CONV_STAGE_BYTES of staged raw rows, whole
+  // blocks of 16 rows, at least one
+  r.conv = r.convPlan && ((size_t)h->dIn * sizeof(float) <= (size_t)HL_ACT_CONV_MAX_ROW_BYTES || (h->generic & 4096));
+  if (r.conv) r.convCap = std::max(16, (int)(std::min((size_t)ACT_ROWS_CHUNK, (size_t)HL_ACT_CONV_STAGE_BYTES / ((size_t)h->dIn * sizeof(float))) & ~(size_t)15));
+  // 5. the batched window kernel (actseq.hip): one recurrent layer type, no convolutions in front, layers within its bounds (wide inputs: 6.)
+  if (h->recurrent && h->nConv == 0 && !h->recSplit && !h->wideIn) {
+    const RecArgs ra = recArgs(h, 0);
+    ActSeqArgs a{}; actFillShared(h, a);
+    a.dS = h->dS; a.nApp = h->nApp; a.recWin = h->recWin; a.nL = ra.nL; a.gates = ra.gates; a.func = ra.func;
+    for (int j = 0; j < ra.nL; ++j) { const RecLayer& L = ra.L[j]; a.L[j] = ActSeqLayer{L.nIn, L.nC, L.hasRes, L.resW, L.indW, L.indB, L.indWr, L.indBr, 0, 0}; }
+    if (act_seq_plan(&a) && actCus(h) >= 1) { r.seqArgs = a; r.seq = true; }
+  }
+  // 6. the time-step-major launches (rectm.hip) serve the net's acting window -- hl_forward_sequence's route where a layer is wider than 256
+  // cells or the input wide --: many agents' windows then run as the samples of one chain of those launches
+  r.tm = h->recurrent && h->nConv == 0 && !h->recSplit && rec_tm_act_ok(actRecArgs(h, -1, 1, &noState, nullptr, nullptr, 1, 0));
+  // 7. the workgroup-per-sample window kernels (rec.hip) serve it -- hl_forward_sequence's route for every net 5. and 6. leave: convolutions in
+  // front, RNN encoder layers under MGU layers, a window beyond the batched kernel's LDS --: workgroup b on agent b's window
+  r.win = h->recurrent;
+  for (int seg = h->recSplit ? 0 : -1; r.win && seg < (h->recSplit ? 2 : 0); ++seg) r.win = rec_win_act_ok(actRecArgs(h, seg, 1, &noState, nullptr, nullptr, 1, 0));
+  // 8. dense nets on rows in device memory, which can be streamed: the row-block kernel where 2. serves the net, act_rows_panel_kernel on
+  // input rows up to ACT_DEV_MAX_ROW wide otherwise
+  const char* why = nullptr;
+  if (!dense) why = "a recurrent net or convolutions in front";
+  else if (!lds) why = "SMARTIES_HIP_GENERIC bit 2";
+  else {
+    auto panels = [&] {
+      ActRowsArgs a = actDenseRecord(h, 0, 0);
+      if (!act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0)) return false;
+      r.panelArgs = a; r.devRows = &r.panelArgs; r.devRowsPanel = true;
+      return true;
+    };
+    bool served = force && panels();                                         // the forced form first
+    if (!served && r.rows) { r.devRows = &r.rowsArgs; served = true; }       // the resident plan of 2.
+    if (!served && !force) served = panels();                                // beyond it: panels
+    if (!served) {
+      why = "the layers' activations beyond 160 KB of LDS";
+      for (int j = 0; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) why = "a layer beyond 2048";
+      if (h->dIn > ACT_DEV_MAX_ROW) why = "an input row beyond HL_ACT_DEV_MAX_ROW = 8192";
+    }
+  }
+  if (h->recurrent) r.devRowsNo = ": recurrent nets act on windows in host memory (hl_forward_sequences)";
+  else if (h->nConv > 0) r.devRowsNo = ": nets with convolutional layers in front act on windows in device memory (hl_forward_sequences_dev; without appended observations: windows of one state)";
+  else if (why) r.devRowsNo = std::string(": an input row beyond 8192 or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2 -- here: ") + why;
+  // 9. windows in device memory.  Recurrent nets: on wide inputs the time-step-major chain behind a prepare launch that gathers the windows
+  // itself (rectm.hip: lstm_tm_prepare_acts_dev_kernel; live source only: the chain borrows training rows, tmT / tmSteps and the last hidden
+  // layer's activations, which a step queued beside it writes), otherwise the batched window kernel of 5.  Dense nets: 8. behind a stacking
+  // launch.  Feed-forward nets behind convolutions: the two launches of 3. whatever the row size; beyond that plan act_conv_band_dev_kernel
+  // where the image does not fit beside the maps, act_rows_panel_kernel where the feature row is beyond ACT_ROWS_MAXW
+  const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
+  if (h->recurrent) {
+    if (h->wideIn && r.tm && actCus(h) >= 1) r.devSeq = ACT_DEV_SEQ_TM;
+    else if (r.seq) { r.devSeq = ACT_DEV_SEQ_BATCHED; r.devSeqSnap = true; }
+    else r.devSeqNo = std::string(host) + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs or wide inputs";
+  } else if (h->nConv > 0) {
+    why = nullptr;
+    if (h->nHidden < 2) why = "a recurrent net, or no convolutions in front of dense layers";
+    else if (!lds) why = "SMARTIES_HIP_GENERIC bit 2";
+    else if (!force && r.convPlan) { r.devConv = &r.convArgs; r.devConvRows = &r.convRowsArgs; }
+    else {      // (both records are planned on locals and committed together, once nothing refuses the net any more)
+      ActConvArgs c{}; ActRowsArgs a{}; bool bands = force, panels = force;
+      auto conv = [&](bool b) { c = actConvRecord(h); bands = b; return convFits(c, b ? act_conv_band_plan(&c, force ? ACT_DEV_FORCE_NB : 0) : act_conv_wide_plan(&c)); };
+      auto denseBehind = [&](bool p) { a = actDenseRecord(h, 1, c.nF); panels = p; return p ? act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0) : act_rows_plan(&a); };
+      if (!conv(force) && !conv(!force)) {
+        c = actConvRecord(h); long long tab, buf[2];
+        why = act_conv_geometry(&c, &tab, buf) ? "a map of the conv stack beyond 160 KB of LDS at any band count" : "a feature row beyond HL_ACT_DEV_MAX_ROW = 8192, or the stack's geometry";
+      } else if (!denseBehind(force) && !denseBehind(!force)) {
+        why = "the dense layers' activations beyond 160 KB of LDS";
+        for (int j = 1; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) why = "a layer beyond 2048";
+      } else if (actCus(h) < 1) why = "the device does not say its compute units";
+      else { r.bandArgs = c; r.panelArgs = a; r.devConv = &r.bandArgs; r.devConvRows = &r.panelArgs; r.devConvBand = bands; r.devConvPanel = panels; }
+    }
+    if (why) r.devSeqNo = std::string(": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: ") + why;
+    else { r.devSeq = ACT_DEV_SEQ_CONV; r.devSeqSnap = true; }
+  } else if (r.devRows) { r.devSeq = ACT_DEV_SEQ_ROWS; r.devSeqSnap = true; }
+  else r.devSeqNo = std::string(host) + "dense nets with input rows up to 8192 and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + why;
+  r.resolved = true;
+  return r;
 }
-// feed-forward nets behind convolutions on windows in device memory: today's two launches wherever act_conv_plan_ok serves the net; otherwise
-// act_conv_band_dev_kernel where the image does not fit beside the maps, act_rows_panel_kernel where the feature row is beyond ACT_ROWS_MAXW
-static bool act_dev_conv_ok(hl_learner* h) {
-  if (h->act.devConvOk) return h->act.devConvOk > 0;
-  h->act.devConvOk = -1;
-  if (h->recurrent || h->nConv < 1 || h->nHidden < 2) return actDevRefuse(h, "a recurrent net, or no convolutions in front of dense layers");
-  if (h->generic & 2) return actDevRefuse(h, "SMARTIES_HIP_GENERIC bit 2");
-  const bool force = (h->generic & 8192) != 0;
-  ActConvArgs& c = h->act.devConvArgs; ActRowsArgs& a = h->act.devConvRowsArgs;
-  if (!force && act_conv_plan_ok(h)) {
-    c = h->act.convArgs; a = h->act.convRowsArgs; h->act.devConvBand = h->act.devConvPanel = false;
-    h->act.devConvOk = 1;
-    return true;
-  }
-  auto conv = [&](bool bands) {
-    c = ActConvArgs{};
-    c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
-    c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = 0;
-    for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
-      c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
-    if (!(bands ? act_conv_band_plan(&c, force ? ACT_DEV_FORCE_NB : 0) : act_conv_wide_plan(&c))) return false;
-    if (c.extras != h->extras || c.nF != h->hid[1].nIn) return false;
-    c.ldF = c.nF;
-    return true;
-  };
-  if (conv(force)) h->act.devConvBand = force;
-  else if (conv(!force)) h->act.devConvBand = !force;
-  else {
-    long long tab, buf[2];
-    if (act_conv_geometry(&c, &tab, buf)) return actDevRefuse(h, "a map of the conv stack beyond 160 KB of LDS at any band count");
-    return actDevRefuse(h, "a feature row beyond HL_ACT_DEV_MAX_ROW = 8192, or the stack's geometry");
-  }
-  // the dense layers behind: hid[1 ..] on feature rows [extras | last map], standardised already
-  auto dense = [&](bool panels) {
-    a = ActRowsArgs{}; actFillShared(h, a); a.stMean = nullptr; a.stScale = nullptr;
-    a.dS = c.nF; a.dIn = c.nF; a.nL = actFillLayers(h, 1, a.L);
-    return panels ? act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0) : act_rows_plan(&a);
-  };
-  if (dense(force)) h->act.devConvPanel = force;
-  else if (dense(!force)) h->act.devConvPanel = !force;
-  else {
-    for (int j = 1; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) return actDevRefuse(h, "a layer beyond 2048");
-    return actDevRefuse(h, "the dense layers' activations beyond 160 KB of LDS");
-  }
-  if (actCus(h) < 1) return actDevRefuse(h, "the device does not say its compute units");
-  h->act.devConvOk = 1;
-  return true;
+// ---- the choice per call, on the resolved table and n.  Rows in host memory: a few rows the one-kernel route; the row-block route (a net
+// beyond ACT_ROWS_SMALL_NET weights: only from ACT_ROWS_WIDE_MIN_N rows on and where the launches over the training buffers would need two
+// rounds of Mmax rows or more -- below, one workgroup per 16 rows streaming all weights takes longer than they do); behind convolutions
+// the conv-stack route; the forward pass over the training buffers
+enum ActRowsRoute { ACT_ROWS_FEW, ACT_ROWS_BLOCK, ACT_ROWS_CONV, ACT_ROWS_TRAIN };
+static ActRowsRoute actRowsRoute(const hl_learner* h, const ActRoutes& r, int n) {
+  if (n <= ACT_MAXROWS && r.few) return ACT_ROWS_FEW;
+  if (r.rows && (r.rowsSmall || (n >= ACT_ROWS_WIDE_MIN_N && n >= 2 * h->Mmax))) return ACT_ROWS_BLOCK;
+  return r.conv ? ACT_ROWS_CONV : ACT_ROWS_TRAIN;
 }
-// recurrent nets on wide inputs on windows in device memory: the time-step-major chain of actTmChain behind a prepare launch that gathers
-// the windows from the caller's array itself (rectm.hip: lstm_tm_prepare_acts_dev_kernel) -- every wide-input net hl_create admits
-static bool act_dev_tm_ok(hl_learner* h) { return h->wideIn && actTmOk(h) && actCus(h) >= 1; }
-// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the chains of the other two routes borrow
-// the training rows of the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples -- and, behind
-// convolutions, no more than whose stacked window rows fit HL_ACT_WIN_STAGE_BYTES of pinned staging (never fewer than one)
+// windows in host memory: a dense net's through hl_forward, then the first of 5., 6., 7. that serves the net, else agent by agent
+enum ActWindowsRoute { ACT_WIN_DENSE, ACT_WIN_BATCHED, ACT_WIN_TM, ACT_WIN_CHAIN, ACT_WIN_EACH };
+static ActWindowsRoute actWindowsRoute(const hl_learner* h, const ActRoutes& r) {
+  return !h->recurrent ? ACT_WIN_DENSE : r.seq ? ACT_WIN_BATCHED : r.tm ? ACT_WIN_TM : r.win ? ACT_WIN_CHAIN : ACT_WIN_EACH;
+}
+// rows in device memory of a net 8. serves: as hl_forward picks the one-kernel route (the same bits), else the row-block kernel or its panelled form
+enum ActDevRowsRoute { ACT_DEV_ROWS_FEW, ACT_DEV_ROWS_BLOCK, ACT_DEV_ROWS_PANEL };
+static ActDevRowsRoute actDevRowsRoute(const ActRoutes& r, int n) {
+  return n <= ACT_MAXROWS && r.few ? ACT_DEV_ROWS_FEW : r.devRowsPanel ? ACT_DEV_ROWS_PANEL : ACT_DEV_ROWS_BLOCK;
+}
+// agents per chunk of hl_forward_sequences: ACT_SEQ_CHUNK windows of the batched window kernel; the two chains borrow the training rows of
+// the first agents-many samples, so a chunk holds no more agents than the local minibatch has samples -- and, behind convolutions, no more
+// than whose stacked window rows fit HL_ACT_WIN_STAGE_BYTES of pinned staging (never fewer than one)
 static int actChunkCap(hl_learner* h) {
-  if (actSeqOk(h)) return ACT_SEQ_CHUNK;
-  if (!actTmOk(h) && !actWinOk(h)) return 0;
+  const ActWindowsRoute route = actWindowsRoute(h, actResolve(h));
+  if (route == ACT_WIN_BATCHED) return ACT_SEQ_CHUNK;
+  if (route != ACT_WIN_TM && route != ACT_WIN_CHAIN) return 0;
   size_t cap = (size_t)std::min(h->B, ACT_SEQ_CHUNK);
   if (h->nConv > 0) cap = std::min(cap, (size_t)HL_ACT_WIN_STAGE_BYTES / ((size_t)h->recK * h->dIn * sizeof(float)));
   // (wide inputs: a window of nnBPTTseq + 1 + nAppendedObs states of up to 8192 floats -- the same bound on the staged states)
@@ -356,8 +330,10 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   if (h->inStep) return fail(h, HL_ERR_STATE, "hl_forward between hl_step_begin and hl_step_end");
   if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, "forward of a recurrent net needs the agent's history");
   if (n == 0) return HL_OK;
+  const ActRoutes& r = actResolve(h);
+  switch (actRowsRoute(h, r, n)) {
   // a few agents, dense network: one kernel, states and outputs through pinned host memory (misc.hip: act_forward_kernel)
-  if (n <= ACT_MAXROWS && actFewOk(h)) {
+  case ACT_ROWS_FEW: {
     { int rc = actPinEnsure(h); if (rc) return rc; }
     const ActStage& s = h->act.few;
     return actRowChunks(h, s, ACT_MAXROWS, [](int m) { return m; }, n, states, outputs, [&](int m, unsigned tag) -> int {
@@ -367,13 +343,11 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   }
   // more rows than that, or a layer / an input row wider: the whole net per block of 16 rows on the MFMA (actrows.hip: act_rows_kernel),
   // one launch per chunk of ACT_ROWS_CHUNK rows
-  // (a net beyond ACT_ROWS_SMALL_NET weights: only from ACT_ROWS_WIDE_MIN_N rows on and where the launches over the training buffers would
-  // need two rounds of Mmax rows or more -- below, one workgroup per 16 rows streaming all weights takes longer than they do)
-  if (act_rows_ok(h) && (h->act.rowsSmall || (n >= ACT_ROWS_WIDE_MIN_N && n >= 2 * h->Mmax))) {
+  case ACT_ROWS_BLOCK: {
     { int rc = actRowsPinEnsure(h, &h->act.rowsPin, &h->act.rows, ACT_ROWS_CHUNK); if (rc) return rc; }
     const ActStage& s = h->act.rows;
     return actRowChunks(h, s, ACT_ROWS_CHUNK, act_rows_blocks, n, states, outputs, [&](int m, unsigned tag) -> int {
-      ActRowsArgs a = h->act.rowsArgs; a.in = s.in; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
+      ActRowsArgs a = r.rowsArgs; a.in = s.in; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
       HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
       return HL_OK;
     });
@@ -382,18 +356,20 @@ int hl_forward(hl_learner* h, int32_t n, const float* states, double* outputs) {
   // workgroup per row up to the number of compute units, which reads the raw rows from the mapped staging itself (a device copy ahead of the
   // launch was slower in development, include/smarties_hip_act.h) and writes the chunk's feature rows; the dense layers on those.  The
   // training activations and the prepared filter layouts are not touched either
-  if (act_conv_ok(h)) {
-    const int cap = h->act.convCap;
-    if (!h->act.convFeat) HIPCK(devAlloc(&h->act.convFeat, (size_t)cap * h->act.convArgs.nF));      // (kept if the pinned block fails: the next call tries that again)
+  case ACT_ROWS_CONV: {
+    const int cap = r.convCap;
+    if (!h->act.convFeat) HIPCK(devAlloc(&h->act.convFeat, (size_t)cap * r.convArgs.nF));      // (kept if the pinned block fails: the next call tries that again)
     { int rc = actRowsPinEnsure(h, &h->act.convPin, &h->act.conv, cap); if (rc) return rc; }
     const ActStage& s = h->act.conv;
     return actRowChunks(h, s, cap, act_rows_blocks, n, states, outputs, [&](int m, unsigned tag) -> int {
-      ActConvArgs c = h->act.convArgs; c.in = s.in; c.feat = h->act.convFeat; c.n = m;
-      ActRowsArgs a = h->act.convRowsArgs; a.in = h->act.convFeat; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
+      ActConvArgs c = r.convArgs; c.in = s.in; c.feat = h->act.convFeat; c.n = m;
+      ActRowsArgs a = r.convRowsArgs; a.in = h->act.convFeat; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
       HIPCK(timed(h, "act_conv", h->stream, [&] { return launch_act_conv(c, h->act.cus, h->stream); }));
       HIPCK(timed(h, "act_rows", h->stream, [&] { return launch_act_rows(a, h->stream); }));
       return HL_OK;
     });
+  }
+  case ACT_ROWS_TRAIN: break;
   }
   { int rc = actTrainEnsure(h); if (rc) return rc; }      // the forward pass borrows minibatch buffer 0
   // (with appended observations a row holds the raw state of step t followed by those of t-1 .. t-nAppendedObs)
@@ -445,7 +421,7 @@ int hl_forward_sequence(hl_learner* h, int32_t nSteps, const float* states, doub
   return HL_OK;
 }
 
-// n checked windows of a net whose layers run time-step-major (actTmOk): agent i of a chunk is sample row i of ONE chain of launches --
+// n checked windows of a net whose layers run time-step-major (ActRoutes::tm): agent i of a chunk is sample row i of ONE chain of launches --
 // prepare, the forward diagonals up to the chunk's longest window, the output layer on the chunk's rows of Yout.  The chain borrows rows
 // 0 .. m - 1 of the training buffers between steps, as hl_forward_sequence borrows row 0: every training step writes its rows anew
 static int actTmChain(hl_learner* h, int n, const int32_t* nSteps, const float* states, double* outputs) {
@@ -459,7 +435,7 @@ static int actTmChain(hl_learner* h, int n, const int32_t* nSteps, const float* 
     return e == hipSuccess ? actOutput(h, m, s.out, s.done, tag) : e;
   });
 }
-// n checked windows of a net whose windows the workgroup-per-sample kernels run (actWinOk): agent i of a chunk is sample i of ONE chain of
+// n checked windows of a net whose windows the workgroup-per-sample kernels run (ActRoutes::win): agent i of a chunk is sample i of ONE chain of
 // hl_forward_sequence's own launches -- behind convolutions the chunk's stacked rows through the front; the window launch (two for a
 // stack of two layer types) with the per-agent tables, workgroup i walking agent i's window alone; the output layer on the chunk's rows
 // of Yout.  The chain borrows the training rows of the first m samples between steps, as hl_forward_sequence borrows those of the first
@@ -489,25 +465,28 @@ int hl_forward_sequences(hl_learner* h, int32_t n, const int32_t* nSteps, const 
     if (nSteps[i] < 1) return fail(h, HL_ERR_BAD_ARG, "hl_forward_sequences: a window without a state");
     if (h->recurrent && nSteps[i] > maxSteps) return fail(h, HL_ERR_BAD_ARG, "more steps than nnBPTTseq + 1 (+ nAppendedObs)");
   }
-  if (!h->recurrent) {
+  const ActRoutes& r = actResolve(h);
+  size_t off = 0;
+  switch (actWindowsRoute(h, r)) {
+  case ACT_WIN_DENSE: {
     // dense net: the rows hl_forward reads -- that of every agent's last step -- then ONE call for all agents
     std::vector<float> rows((size_t)n * h->dIn);
-    size_t off = 0;
     for (int i = 0; i < n; ++i) { act_stack_row(rows.data() + (size_t)i * h->dIn, states + off * h->dS, nSteps[i] - 1, h->nApp, h->dS); off += nSteps[i]; }
     return hl_forward(h, n, rows.data(), outputs);
   }
-  if (actSeqOk(h)) {      // one launch per chunk: a workgroup per agent up to the number of compute units
+  case ACT_WIN_BATCHED: {      // one launch per chunk: a workgroup per agent up to the number of compute units
     const ActStage& s = h->act.chunk;
     return actWindowChunks(h, "act_seq", false, n, nSteps, states, outputs, [](int, int) { return HL_OK; }, [&](int m, unsigned tag, int*) {
-      ActSeqArgs a = h->act.seqArgs; a.states = s.in; a.offset = s.off; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
+      ActSeqArgs a = r.seqArgs; a.states = s.in; a.offset = s.off; a.out = s.out; a.done = s.done; a.n = m; a.tag = tag;
       return launch_act_seq(a, std::min(m, h->act.cus), h->stream);
     });
   }
-  if (actTmOk(h)) return actTmChain(h, n, nSteps, states, outputs);       // layers wider than 256 cells
-  if (actWinOk(h)) return actWinChain(h, n, nSteps, states, outputs);     // convolutions in front, two layer types, a window beyond the batched kernel's LDS
-  // a net all three predicates refuse -- layers or inputs beyond the bounds the window kernels state (256 cells, 1024 inputs) that the
+  case ACT_WIN_TM: return actTmChain(h, n, nSteps, states, outputs);         // layers wider than 256 cells, wide inputs
+  case ACT_WIN_CHAIN: return actWinChain(h, n, nSteps, states, outputs);     // convolutions in front, two layer types, a window beyond the batched kernel's LDS
+  // a net all three refuse -- layers or inputs beyond the bounds the window kernels state (256 cells, 1024 inputs) that the
   // time-step-major launches do not take either --: hl_forward_sequence's own route, agent by agent, as before
-  size_t off = 0;
+  case ACT_WIN_EACH: break;
+  }
   for (int i = 0; i < n; ++i) {
     const int rc = hl_forward_sequence(h, nSteps[i], states + off * h->dS, outputs + (size_t)i * h->nOut); if (rc) return rc;
     off += nSteps[i];

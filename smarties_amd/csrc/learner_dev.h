@@ -65,54 +65,15 @@ static int devStampsEnsure(hl_learner* h, const DevCtx& d) {
   return HL_OK;
 }
 // the snapshot source serves a call once a snapshot exists; its stream is created at first use, with default priority
-static int devSnapEnsure(hl_learner* h, const DevCtx& d, const char* who) {
-  if (!d.snap) return HL_OK;
+// -- BEFORE the call's DevCtx is built, which copies the stream
+static int devSnapEnsure(hl_learner* h, const char* who) {
+  if (h->act.source != HL_ACT_SNAPSHOT) return HL_OK;
   if (h->act.snapCur < 0) return fail(h, HL_ERR_STATE, std::string(who) + ": the snapshot source before any snapshot was taken (hl_policy_snapshot)");
   if (!h->act.snapStream) HIPCK(hipStreamCreateWithFlags(&h->act.snapStream, hipStreamNonBlocking));
   return HL_OK;
 }
-// which nets the row calls serve
-static int devActEnsure(hl_learner* h, const char* who) {
-  if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
-  if (h->recurrent) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets act on windows in host memory (hl_forward_sequences)");
-  if (h->nConv > 0) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": nets with convolutional layers in front act on windows in device memory (hl_forward_sequences_dev; without appended observations: windows of one state)");
-  if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": an input row beyond 8192 or a layer beyond 2048, or SMARTIES_HIP_GENERIC bit 2 -- here: " + h->act.devWhy);
-  const DevCtx d = devCtx(h, h->act.source);
-  { int rc = devSnapEnsure(h, d, who); if (rc) return rc; }
-  return devStampsEnsure(h, d);
-}
-// ... and the window calls: the recurrent nets of the one-launch batched kernel (actSeqOk) and those on wide inputs (act_dev_tm_ok), the dense nets above, the feed-forward nets behind
-// convolutions of the conv-stack kernel's plan (act_conv_plan_ok: whatever the row size -- the rows lie in device memory) and, beyond it, of the
-// banded and panelled kernels' (act_dev_conv_ok, act_dev_rows_ok: neither the image nor the input row has to be resident in LDS).
-// Snapshot source: recurrent nets on wide inputs are refused -- their chain borrows training rows, tmT / tmSteps and the last hidden layer's
-// activations (devSeqTmForward, actOutput), which the step queued beside it writes
-static int devSeqEnsure(hl_learner* h, const char* who) {
-  if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
-  const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
-  const DevCtx d = devCtx(h, h->act.source);
-  if (h->recurrent) {
-    if (act_dev_tm_ok(h)) {      // wide inputs: the time-step-major chain on windows gathered from the caller's array
-      if (d.snap) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets on wide inputs act over the training buffers, which cannot run beside a gradient step: they are served by the source HL_ACT_LIVE only");
-      return HL_OK;
-    }
-    if (!actSeqOk(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "one recurrent layer type without convolutions or encoder_rnn, layers up to 256 cells and 1024 inputs or wide inputs");
-    return devSnapEnsure(h, d, who);
-  }
-  if (h->nConv > 0) {
-    if (!act_dev_conv_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + h->act.devWhy);
-    { int rc = devSnapEnsure(h, d, who); if (rc) return rc; }
-    return devStampsEnsure(h, d);
-  }
-  if (!act_dev_rows_ok(h)) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + host + "dense nets with input rows up to 8192 and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + h->act.devWhy);
-  { int rc = devSnapEnsure(h, d, who); if (rc) return rc; }
-  return devStampsEnsure(h, d);
-}
-// the library's buffer between the window calls' two launches: the stacked rows of a dense net, the feature rows of a net behind convolutions
-static int devSeqRowsEnsure(hl_learner* h, const DevCtx& d, int n) {
-  if (h->recurrent) return HL_OK;
-  if (h->nConv > 0) return devEnsure(h, d.st, d.feat, d.featCap, (size_t)n * h->act.devConvArgs.nF);
-  return devEnsure(h, d.st, d.rows, d.rowsCap, (size_t)n * h->dIn);
-}
+// the windows of a device window call: agent i's newest states from row firstRow[i] on, rowStride rows apart (nullptr in their place: a row call)
+struct DevWindows { const int64_t* firstRow; const int32_t* nSteps; int64_t rowStride; };
 // the row-block kernel per chunk of ACT_ROWS_CHUNK rows [n][ldIn] in device memory: act_rows_kernel, or (panel) act_rows_panel_kernel, which
 // stages the first layer's input row in panels
 static int devRows(hl_learner* h, const DevCtx& d, const ActRowsArgs& plan, bool panel, int n, const float* in, size_t ldIn, double* out) {
@@ -127,20 +88,21 @@ static int devRows(hl_learner* h, const DevCtx& d, const ActRowsArgs& plan, bool
 // hl_forward's kernels on device rows, enqueued on the source's stream: up to ACT_MAXROWS rows of a net within the one-kernel route's
 // bounds that kernel (as hl_forward picks it: the same bits), everything else the row-block kernel per chunk of ACT_ROWS_CHUNK rows (input
 // rows beyond ACT_ROWS_MAXW: its panelled form)
-static int devForward(hl_learner* h, const DevCtx& d, int n, const float* in, double* out) {
-  if (n <= ACT_MAXROWS && actFewOk(h)) {
+static int devForward(hl_learner* h, const ActRoutes& r, const DevCtx& d, int n, const float* in, double* out) {
+  const ActDevRowsRoute route = actDevRowsRoute(r, n);
+  if (route == ACT_DEV_ROWS_FEW) {
     ActArgs aa = actFewArgs(h, in, out, *d.stamps, devNextTag(d)); devSource(d, aa);
     HIPCK(timed(h, "act_forward_dev", d.st, [&] { return launch_act_forward(aa, n, d.st); }));
     return HL_OK;
   }
-  return devRows(h, d, h->act.devRowsArgs, h->act.devRowsPanel, n, in, h->dIn, out);
+  return devRows(h, d, *r.devRows, route == ACT_DEV_ROWS_PANEL, n, in, h->dIn, out);
 }
 static_assert(sizeof(long long) == sizeof(int64_t), "the row tables are passed on as they come");
 // n windows of a recurrent net on wide inputs: agents in chunks of min(local batch, ACT_SEQ_CHUNK) -- the chain borrows the training rows of that many samples between
 // steps, as actTmChain does; nothing is staged, so no stage-bytes cap -- each chunk the prepare launch on the tables at its offset, the input
 // product and the chain over all recWin steps (the host does not know the windows: an agent whose window has ended is left out by the
 // forward tiles), the output layer on the chunk's rows of Yout straight into `out`.  All chunks back to back in ONE timed bracket.
-// Live source only (devSeqEnsure)
+// Live source only (devAct)
 static int devSeqTmForward(hl_learner* h, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
   const int cap = std::min(h->B, ACT_SEQ_CHUNK);
   for (int m : {std::min(cap, n), n % cap})      // the two chunk sizes of the call
@@ -163,34 +125,68 @@ static int devSeqTmForward(hl_learner* h, int n, const int64_t* firstRow, const 
 // gathers and truncates the windows itself (no staging, so no chunks); on wide inputs the chain above.  Behind convolutions: ONE launch of the
 // conv-stack kernel, which reads every agent's stacked row from its window's states, then the row-block kernel on the feature rows per chunk of
 // ACT_ROWS_CHUNK (hl_forward's two launches without the staging).  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
-static int devSeqForward(hl_learner* h, const DevCtx& d, int n, const int64_t* firstRow, const int32_t* nSteps, int64_t rowStride, const float* states, double* out) {
-  if (h->recurrent && act_dev_tm_ok(h)) return devSeqTmForward(h, n, firstRow, nSteps, rowStride, states, out);
-  if (h->recurrent) {
-    ActSeqArgs a = h->act.seqArgs; devSource(d, a);
-    a.states = states; a.firstRow = reinterpret_cast<const long long*>(firstRow); a.nSteps = nSteps; a.rowStride = rowStride; a.out = out; a.n = n;
+static int devSeqForward(hl_learner* h, const ActRoutes& r, const DevCtx& d, int n, const DevWindows& w, const float* states, double* out) {
+  const long long* firstRow = reinterpret_cast<const long long*>(w.firstRow);
+  switch (r.devSeq) {
+  case ACT_DEV_SEQ_TM: return devSeqTmForward(h, n, w.firstRow, w.nSteps, w.rowStride, states, out);
+  case ACT_DEV_SEQ_BATCHED: {
+    ActSeqArgs a = r.seqArgs; devSource(d, a);
+    a.states = states; a.firstRow = firstRow; a.nSteps = w.nSteps; a.rowStride = w.rowStride; a.out = out; a.n = n;
     HIPCK(timed(h, "act_seq_dev", d.st, [&] { return launch_act_seq_dev(a, std::min(n, h->act.cus), d.st); }));
     return HL_OK;
   }
-  if (h->nConv > 0) {
-    ActConvArgs c = h->act.devConvArgs; devSource(d, c);
-    c.in = states; c.firstRow = reinterpret_cast<const long long*>(firstRow); c.nSteps = nSteps; c.rowStride = rowStride; c.feat = *d.feat; c.n = n;
-    if (h->act.devConvBand) HIPCK(timed(h, "act_conv_band_dev", d.st, [&] { return launch_act_conv_band_dev(c, h->act.cus, d.st); }));
+  case ACT_DEV_SEQ_CONV: {
+    ActConvArgs c = *r.devConv; devSource(d, c);
+    c.in = states; c.firstRow = firstRow; c.nSteps = w.nSteps; c.rowStride = w.rowStride; c.feat = *d.feat; c.n = n;
+    if (r.devConvBand) HIPCK(timed(h, "act_conv_band_dev", d.st, [&] { return launch_act_conv_band_dev(c, h->act.cus, d.st); }));
     else HIPCK(timed(h, "act_conv_dev", d.st, [&] { return launch_act_conv_dev(c, h->act.cus, d.st); }));
-    return devRows(h, d, h->act.devConvRowsArgs, h->act.devConvPanel, n, *d.feat, (size_t)c.nF, out);
+    return devRows(h, d, *r.devConvRows, r.devConvPanel, n, *d.feat, (size_t)c.nF, out);
   }
-  ActStackDevArgs sa{states, reinterpret_cast<const long long*>(firstRow), nSteps, rowStride, *d.rows, n, h->dS, h->nApp};
-  HIPCK(timed(h, "act_stack_dev", d.st, [&] { return launch_act_stack_dev(sa, d.st); }));
-  return devForward(h, d, n, *d.rows, out);
+  case ACT_DEV_SEQ_ROWS: {
+    ActStackDevArgs sa{states, firstRow, w.nSteps, w.rowStride, *d.rows, n, h->dS, h->nApp};
+    HIPCK(timed(h, "act_stack_dev", d.st, [&] { return launch_act_stack_dev(sa, d.st); }));
+    return devForward(h, r, d, n, *d.rows, out);
+  }
+  case ACT_DEV_SEQ_NONE: break;      // (devAct refused the call before)
+  }
+  return HL_ERR_UNSUPPORTED;
 }
 // RACER::selectAction's head on n rows of network outputs (actdev.hip: act_head_kernel): it reads those, the noise and the configuration
 // only, so it is the same launch under either source
-static int devHead(hl_learner* h, const DevCtx& d, int n, const double* O, const double* dNoise, double* dActions, double* dMu, float* dValues, float* dAdvantages) {
+struct DevHeadIo { const double* noise; double *act, *mu; float *V, *ADV; };
+static int devHead(hl_learner* h, const DevCtx& d, int n, const double* O, const DevHeadIo& io) {
   ActHeadArgs a{};
-  a.O = O; a.noise = dNoise; a.act = dActions; a.mu = dMu; a.V = dValues; a.ADV = dAdvantages;
+  a.O = O; a.noise = io.noise; a.act = io.act; a.mu = io.mu; a.V = io.V; a.ADV = io.ADV;
   a.n = n; a.dA = h->dA; a.nOut = h->nOut; a.nDense = h->nDense; a.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; a.nOpt = h->nOpt;
   for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) a.bounded |= 1ull << i;
   HIPCK(timed(h, "act_head_kernel", d.st, [&] { return launch_act_head(a, d.st); }));
   return HL_OK;
+}
+// The one body of the four _dev acting calls, behind their argument checks: n rows [n][dIn] at `in` (w == nullptr), or n windows w of the
+// states array `in`; the network outputs into `out`, or (head != nullptr) into the source's scratch and RACER::selectAction's head on them.
+// In this order: the call between the two halves of a step; a net the resolved table (learner_act.h: actResolve) refuses -- the snapshot
+// source on a route that acts over the training buffers included --; the snapshot source before any snapshot, whose stream is created
+// here; the stamp block of the dense kernels; n == 0; row_stride; the library's buffers -- between a window call's two launches the
+// stacked rows of a dense net or the feature rows behind convolutions, in front of the head the outputs --; the handshake with the
+// caller's stream around the launches
+static int devAct(hl_learner* h, const char* who, int n, const float* in, const DevWindows* w, double* out, const DevHeadIo* head, void* stream) {
+  HL_LOCK(h);
+  if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
+  const ActRoutes& r = actResolve(h);
+  if (w ? r.devSeq == ACT_DEV_SEQ_NONE : !r.devRows) return fail(h, HL_ERR_UNSUPPORTED, who + (w ? r.devSeqNo : r.devRowsNo));
+  if (w && h->act.source == HL_ACT_SNAPSHOT && !r.devSeqSnap) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets on wide inputs act over the training buffers, which cannot run beside a gradient step: they are served by the source HL_ACT_LIVE only");
+  { int rc = devSnapEnsure(h, who); if (rc) return rc; }
+  const DevCtx d = devCtx(h, h->act.source);
+  if (!w || r.devSeq == ACT_DEV_SEQ_CONV || r.devSeq == ACT_DEV_SEQ_ROWS) { int rc = devStampsEnsure(h, d); if (rc) return rc; }
+  if (n == 0) return HL_OK;
+  if (w && w->rowStride < 1) return fail(h, HL_ERR_BAD_ARG, std::string(who) + ": row_stride below 1");
+  if (w && r.devSeq == ACT_DEV_SEQ_CONV) { int rc = devEnsure(h, d.st, d.feat, d.featCap, (size_t)n * r.devConv->nF); if (rc) return rc; }
+  if (w && r.devSeq == ACT_DEV_SEQ_ROWS) { int rc = devEnsure(h, d.st, d.rows, d.rowsCap, (size_t)n * h->dIn); if (rc) return rc; }
+  if (head) { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; out = *d.out; }
+  { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  { int rc = w ? devSeqForward(h, r, d, n, *w, in, out) : devForward(h, r, d, n, in, out); if (rc) return rc; }
+  if (head) { int rc = devHead(h, d, n, out, *head); if (rc) return rc; }
+  return devLeave(h, d, stream);
 }
 }  // extern "C++"
 
@@ -234,57 +230,29 @@ int hl_policy_snapshot_info(hl_learner* h, int64_t* n_snapshots, int64_t* nGradS
 
 int hl_forward_dev(hl_learner* h, int32_t n, const float* dStates, double* dOutputs, void* stream) {
   if (!h || n < 0 || (n > 0 && (!dStates || !dOutputs))) return HL_ERR_BAD_ARG;
-  HL_LOCK(h);
-  { int rc = devActEnsure(h, "hl_forward_dev"); if (rc) return rc; }
-  if (n == 0) return HL_OK;
-  const DevCtx d = devCtx(h, h->act.source);
-  { int rc = devEnter(h, d, stream); if (rc) return rc; }
-  { int rc = devForward(h, d, n, dStates, dOutputs); if (rc) return rc; }
-  return devLeave(h, d, stream);
+  return devAct(h, "hl_forward_dev", n, dStates, nullptr, dOutputs, nullptr, stream);
 }
 
 int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates, const double* dNoise, double* dActions, double* dMu,
                           float* dValues, float* dAdvantages, void* stream) {
   if (!h || n < 0 || (n > 0 && (!dStates || !dActions || !dMu || !dValues || !dAdvantages))) return HL_ERR_BAD_ARG;
-  HL_LOCK(h);
-  { int rc = devActEnsure(h, "hl_select_actions_dev"); if (rc) return rc; }
-  if (n == 0) return HL_OK;
-  const DevCtx d = devCtx(h, h->act.source);
-  { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; }
-  { int rc = devEnter(h, d, stream); if (rc) return rc; }
-  { int rc = devForward(h, d, n, dStates, *d.out); if (rc) return rc; }
-  { int rc = devHead(h, d, n, *d.out, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
-  return devLeave(h, d, stream);
+  const DevHeadIo head{dNoise, dActions, dMu, dValues, dAdvantages};
+  return devAct(h, "hl_select_actions_dev", n, dStates, nullptr, nullptr, &head, stream);
 }
 
 int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride, const float* dStates,
                              double* dOutputs, void* stream) {
   if (!h || n < 0 || (n > 0 && (!dFirstRow || !dNSteps || !dStates || !dOutputs))) return HL_ERR_BAD_ARG;
-  HL_LOCK(h);
-  { int rc = devSeqEnsure(h, "hl_forward_sequences_dev"); if (rc) return rc; }
-  if (n == 0) return HL_OK;
-  if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_forward_sequences_dev: row_stride below 1");
-  const DevCtx d = devCtx(h, h->act.source);
-  { int rc = devSeqRowsEnsure(h, d, n); if (rc) return rc; }
-  { int rc = devEnter(h, d, stream); if (rc) return rc; }
-  { int rc = devSeqForward(h, d, n, dFirstRow, dNSteps, row_stride, dStates, dOutputs); if (rc) return rc; }
-  return devLeave(h, d, stream);
+  const DevWindows w{dFirstRow, dNSteps, row_stride};
+  return devAct(h, "hl_forward_sequences_dev", n, dStates, &w, dOutputs, nullptr, stream);
 }
 
 int hl_select_actions_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride, const float* dStates,
                                     const double* dNoise, double* dActions, double* dMu, float* dValues, float* dAdvantages, void* stream) {
   if (!h || n < 0 || (n > 0 && (!dFirstRow || !dNSteps || !dStates || !dActions || !dMu || !dValues || !dAdvantages))) return HL_ERR_BAD_ARG;
-  HL_LOCK(h);
-  { int rc = devSeqEnsure(h, "hl_select_actions_sequences_dev"); if (rc) return rc; }
-  if (n == 0) return HL_OK;
-  if (row_stride < 1) return fail(h, HL_ERR_BAD_ARG, "hl_select_actions_sequences_dev: row_stride below 1");
-  const DevCtx d = devCtx(h, h->act.source);
-  { int rc = devSeqRowsEnsure(h, d, n); if (rc) return rc; }
-  { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; }
-  { int rc = devEnter(h, d, stream); if (rc) return rc; }
-  { int rc = devSeqForward(h, d, n, dFirstRow, dNSteps, row_stride, dStates, *d.out); if (rc) return rc; }
-  { int rc = devHead(h, d, n, *d.out, dNoise, dActions, dMu, dValues, dAdvantages); if (rc) return rc; }
-  return devLeave(h, d, stream);
+  const DevWindows w{dFirstRow, dNSteps, row_stride};
+  const DevHeadIo head{dNoise, dActions, dMu, dValues, dAdvantages};
+  return devAct(h, "hl_select_actions_sequences_dev", n, dStates, &w, nullptr, &head, stream);
 }
 
 int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, const int32_t* terminated, const int64_t* tags,

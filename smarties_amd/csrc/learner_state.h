@@ -31,15 +31,35 @@ struct ActDevScratch {
   float* rows = nullptr; size_t rowsCap = 0;
   float* feat = nullptr; size_t featCap = 0;
 };
-// rollout inference (learner_act.h).  Every route's predicate is looked at once: 0 not looked at yet / 1 the route serves the net / -1 not
+// What serves a learner's acting calls, resolved ONCE by actResolve (learner_act.h) at the first acting call and read-only from then on: it
+// depends on the net and on SMARTIES_HIP_GENERIC only, never on n or on a call.  The n-dependent choice is made per call by one small
+// function per call family on these facts (actRowsRoute, actWindowsRoute, actDevRowsRoute; the device window calls switch on devSeq).
+// Every argument record is stored once; the device routes point at the resident record wherever they run the resident plan
+enum ActDevSeq { ACT_DEV_SEQ_NONE, ACT_DEV_SEQ_TM, ACT_DEV_SEQ_BATCHED, ACT_DEV_SEQ_CONV, ACT_DEV_SEQ_ROWS };
+struct ActRoutes {
+  bool resolved = false;
+  // rows in host memory (hl_forward)
+  bool few = false;                                      // a few rows of a dense net, a workgroup per row (misc.hip: act_forward_kernel)
+  bool rows = false, rowsSmall = false; ActRowsArgs rowsArgs{};      // many rows of a dense net (actrows.hip); the net takes the route at any row count (ACT_ROWS_SMALL_NET)
+  bool convPlan = false; ActConvArgs convArgs{}; ActRowsArgs convRowsArgs{};      // a feed-forward net behind convolutions (actconv.hip + actrows.hip): the plan serves it
+  bool conv = false; int convCap = 0;                    // ... and hl_forward takes that route for rows in host memory (the row-size switch); rows per chunk
+  // windows in host memory (hl_forward_sequences)
+  bool seq = false; ActSeqArgs seqArgs{};                // the batched window kernel (actseq.hip)
+  bool tm = false, win = false;                          // one chain of the time-step-major launches (rectm.hip) / of the workgroup-per-sample window kernels (rec.hip)
+  // rows in device memory (hl_forward_dev, hl_select_actions_dev): devRows the dense layers' record (nullptr: refused, devRowsNo says why
+  // behind the caller's name), devRowsPanel: act_rows_panel_kernel on it
+  const ActRowsArgs* devRows = nullptr; bool devRowsPanel = false; std::string devRowsNo;
+  // windows in device memory: the route (ACT_DEV_SEQ_NONE: refused, devSeqNo says why), whether the snapshot source may serve it; behind
+  // convolutions the conv stack's record (devConvBand: act_conv_band_dev_kernel on it) and the dense layers' (devConvPanel)
+  ActDevSeq devSeq = ACT_DEV_SEQ_NONE; bool devSeqSnap = false; std::string devSeqNo;
+  const ActConvArgs* devConv = nullptr; const ActRowsArgs* devConvRows = nullptr; bool devConvBand = false, devConvPanel = false;
+  // the device routes' own records, filled only where the banded / panelled plan (act_plan.h, actband.hip) serves instead of the resident one
+  ActConvArgs bandArgs{}; ActRowsArgs panelArgs{};
+};
+// rollout inference (learner_act.h)
 struct ActState {
   unsigned tag = 0; int cus = 0;      // the last completion stamp handed out (actNextTag); compute units of the device, asked once (actCus)
-  int fewOk = 0;                      // a few rows of a dense net, a workgroup per row (misc.hip: act_forward_kernel)
-  int rowsOk = 0; bool rowsSmall = false; ActRowsArgs rowsArgs{};      // many rows of a dense net (actrows.hip); the net takes the route at any row count (ACT_ROWS_SMALL_NET)
-  int convPlanOk = 0; ActConvArgs convArgs{}; ActRowsArgs convRowsArgs{};      // a feed-forward net behind convolutions (actconv.hip + actrows.hip): the plan serves it
-  int convOk = 0, convCap = 0;        // ... and hl_forward takes that route for rows in host memory (the row-size switch); rows per chunk
-  int seqOk = 0; ActSeqArgs seqArgs{};      // many agents' windows: the batched window kernel (actseq.hip)
-  int tmOk = 0, winOk = 0;            // ... as one chain of the time-step-major launches (rectm.hip) / of the workgroup-per-sample window kernels (rec.hip)
+  ActRoutes routes;                   // (the learner is never copied: the table points into itself)
   // three pinned, device-mapped blocks, each allocated at the first call that takes a route through it, and their carves (act_host.h):
   // [a few rows or one window | a chunk of chunkCap agents' windows], a chunk of many rows, a chunk of rows behind convolutions
   unsigned char *pin = nullptr, *rowsPin = nullptr, *convPin = nullptr; ActStage few{}, chunk{}, rows{}, conv{}; int chunkCap = 0;
@@ -51,12 +71,6 @@ struct ActState {
   double* devOut = nullptr; size_t devOutCap = 0; double* devSums = nullptr; size_t devSumsCap = 0;
   float* devRows = nullptr; size_t devRowsCap = 0;      // hl_forward_sequences_dev, dense nets with appended observations: the stacked rows
   float* devFeat = nullptr; size_t devFeatCap = 0;      // ... nets behind convolutions: the agents' feature rows [n][nF] between the two launches
-  // what the device calls launch (learner_act.h: act_dev_rows_ok, act_dev_conv_ok): the resident kernels on the arguments above wherever their
-  // plans serve the net, otherwise the first conv layer in bands (devConvBand) and / or the first dense layer's input row in panels
-  // (devRowsPanel, devConvPanel) on plans of act_plan.h (actband.hip); devWhy: the bound that refuses the net
-  int devRowsOk = 0; bool devRowsPanel = false; ActRowsArgs devRowsArgs{};
-  int devConvOk = 0; bool devConvBand = false, devConvPanel = false; ActConvArgs devConvArgs{}; ActRowsArgs devConvRowsArgs{};
-  const char* devWhy = "";
   // acting on a policy snapshot (learner_dev.h: hl_policy_snapshot, hl_act_dev_source).  source: HL_ACT_LIVE / HL_ACT_SNAPSHOT.  Two
   // buffers [W nParams | stMean | stScale], the small arrays each on a multiple of 4 floats; snapCur the one the acting calls read (-1:
   // none yet).  snapReady[b]: recorded on the learner's stream behind the copy into b; snapRead[b]: recorded on the acting stream behind

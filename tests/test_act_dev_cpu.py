@@ -1,6 +1,6 @@
 """Acting and episode ingestion from device memory (include/smarties_hip_dev.h), the part that needs no GPU: the header and the
 exported symbols, the null-handle refusals, the resource remarks of the two new kernels (smarties_amd/csrc/actdev.hip), and the numpy
-fp64 restatement of RACER::selectAction's three heads that tests/test_hip_act_dev.py holds the device head to -- pinned here against
+fp64 restatement of RACER::selectAction's three heads (tests/acting.py: head_np) that tests/test_hip_act_dev.py holds the device head to -- pinned here against
 values worked out by hand for one agent per head."""
 import ctypes as C
 import os
@@ -9,75 +9,11 @@ import sys
 
 import numpy as np
 
+from acting import CLIP, _net2v, head_np
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("hl_forward_dev", "hl_select_actions_dev", "hl_append_episodes_dev")
-CLIP = 8.31776613503286      # SquashedNormalPolicy::sample (Continuous_policy.h:356-360)
-
-
-# ---- the checker: smarties_amd/host/vracer_hip.h:209-258 in numpy fp64, one agent per call -------------------------------------------
-def _softplus(x):
-    return (x + np.sqrt(1 + x * x)) / 2
-
-
-def _net2v(x):      # Learners/RACER_common.cpp:23-27
-    return 100 * (x + 51) - 100 * np.sqrt(2601 + 100 * x) if x > 0 else 100 * (x - 51) + 100 * np.sqrt(2601 - 100 * x)
-
-
-def _clip(v):
-    return CLIP if v > CLIP else (-CLIP if v < -CLIP else v)
-
-
-def _store(V, A):
-    """(values, advantages) as MB.appendValues keeps them: (Fval)V, (Fval)((Fval)(V + A) - (Fval)V)"""
-    return np.float32(V), np.float32(np.float32(V + A) - np.float32(V))
-
-
-def head_np(out, noise, dA, bounded=(), gaussian=False, n_options=0):
-    """One agent: network outputs (float64) -> (action [dA], mu [polDim], value f32, advantage f32).  noise None: the evaluation action."""
-    out = np.asarray(out, np.float64)
-    V = _net2v(out[0])
-    if n_options:
-        probs = np.array([_softplus(out[1 + n_options + j]) for j in range(n_options)])
-        norm = 0.0
-        for p in probs:
-            norm += p
-        probs = probs / max(norm, np.finfo(np.float64).eps)
-        if noise is None:
-            label = int(np.argmax(probs))
-        else:
-            cdf, label = 0.0, n_options - 1
-            for j in range(n_options):
-                cdf += probs[j]
-                if cdf > float(noise):
-                    label = j
-                    break
-        expA = 0.0
-        for j in range(n_options):
-            expA += probs[j] * out[1 + j]
-        v, a = _store(V, out[1 + label] - expA)
-        return np.array([label + 0.1]), probs, v, a
-    nAdv = 1 + 2 * dA if gaussian else 0
-    nDense = 1 + nAdv + dA
-    mean = out[1 + nAdv:1 + nAdv + dA].copy()
-    stdev = np.array([_softplus(out[nDense + i]) for i in range(dA)])
-    act = mean.copy()
-    if noise is not None:
-        for i in range(dA):
-            a = mean[i] + stdev[i] * noise[i]
-            act[i] = _clip(a) if (i < len(bounded) and bounded[i]) else a
-    A = 0.0
-    if gaussian:
-        quad, ratio = 0.0, 1.0
-        for i in range(dA):
-            m = _clip(mean[i]) if (i < len(bounded) and bounded[i]) else mean[i]
-            p1, p2, Sv = _softplus(out[2 + i]), _softplus(out[2 + dA + i]), stdev[i] * stdev[i]
-            quad += (act[i] - m) * (act[i] - m) / (p1 if act[i] > m else p2)
-            ratio *= np.sqrt(p1 / (p1 + Sv)) / 2 + np.sqrt(p2 / (p2 + Sv)) / 2
-        A = _softplus(out[1]) * (np.exp(-quad / 2) - ratio)
-    v, a = _store(V, A)
-    return act, np.concatenate([mean, stdev]), v, a
 
 
 # ---- 1. the checker against hand-computed values -----------------------------------------------------------------------------------

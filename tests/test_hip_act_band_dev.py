@@ -8,29 +8,10 @@ refusals that remain; a closed loop act -> simulate -> append -> step on tensors
 import numpy as np
 import pytest
 
+from acting import (BAND_NETS as NEW, FALLBACK, LDS_NETS, N_EPS, NETS, PARITY, TOL32, _BASE, _bare, _call_dev, _columns, _conv_pair as _pair, _count,
+                    _packed, _rows, _same_replay, _same_training_state, _side_stream, _stacked, _synth_learner as _learner, _window_args, head_np)
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
-from test_act_dev_cpu import head_np
-from test_hip_act_batch import FALLBACK
-from test_hip_act_conv import LDS_NETS, N_EPS, NETS, TOL32, _BASE, _count, _pair, _rows
-from test_hip_act_conv_dev import PARITY, _bare, _stacked, _window_args
-from test_hip_act_dev import _same_replay, _same_training_state
-from test_hip_act_seq_dev import _call_dev, _columns, _learner, _packed, _side_stream
-
-NATURE = [(84, 84, 4, 32, 8, 4), (20, 20, 32, 64, 4, 2), (9, 9, 64, 64, 3, 1)]      # Network/Builder.cpp:189-194
-# name -> (configuration, row counts, window lengths, band launches per call, the dense layers run panelled, cpu_bar of assert_columns)
-NEW = {
-    # two bands of 10 output rows (44 input rows x 84 x 4 channels), a feature row of 3136 in panels of 1024 and one of 64
-    "nature": (dict(dimS=7056, dimA=1, bounded=[0], adv_kind=capi.ADV_DISCRETE, n_options=6, nAppendedObs=3, conv=NATURE, hidden=(512,),
-                    nnFunc="Tanh", batchSize=8, maxTotObsNum=400, randSeed=11), (1, 17), (1, 2, 3, 4, 9), 1, True, True),
-    # ONE conv layer: every band's part of the map goes straight behind the (zero) extras of the feature vector
-    "image-176K": (LDS_NETS["image-176K"], (1, 17, 300), (1, 2), 1, False, False),
-    # 5 extras, a row that is no multiple of 4 floats, a feature row of 2357, the residual of 48 columns over a panelled input
-    "feat-2357": (dict(_BASE, dimS=517, conv=[(16, 16, 2, 12, 3, 1)], hidden=(48, 24), nnFunc="SoftSign"), (1, 17, 300), (1, 2, 9), 0, True, False),
-    "dense-2500": (dict(_BASE, dimS=2500, hidden=(48, 24)), (1, 17, 300), None, 0, True, False),
-    # a stacked row of 3090 through act_stack_dev_kernel
-    "dense-1030x3": (dict(_BASE, dimS=1030, nAppendedObs=2, hidden=(64,)), (1, 17, 300), (1, 2, 3, 9), 0, True, True),
-}
 
 
 def _new_pair(hip_api, name, monkeypatch, oracle=True):

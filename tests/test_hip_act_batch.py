@@ -11,46 +11,12 @@ import sys
 import numpy as np
 import pytest
 
-from oracle_api import oracle_learner, fill_synth, synth_cfg
+from acting import FALLBACK, TOL32, _compare_step, _pair, _ragged, _rec_cfg
+from oracle_api import synth_cfg
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL32 = 1e-5     # the bound test_recurrent_acting_matches_oracle holds the single-agent call to
-
-
-def _pair(hip_api, cfg_kw, sc, n_eps):
-    G = capi.Learner(hip_api, capi.make_config(**cfg_kw))
-    O = oracle_learner(capi.make_config(**cfg_kw))
-    for L in (G, O):
-        L.init_weights()
-        fill_synth(L, sc, n_eps)
-        L.initialize()
-        L.set_tap(True)
-    return G, O
-
-
-def _compare_step(G, O):
-    assert np.array_equal(G.readback(capi.TAP_FLAT), O.readback(capi.TAP_FLAT))
-    assert np.array_equal(G.readback(capi.TAP_TAG), O.readback(capi.TAP_TAG))
-    assert np.array_equal(G.readback(capi.TAP_TSTEP), O.readback(capi.TAP_TSTEP))
-    assert np.array_equal(G.readback(capi.TAP_STATE), O.readback(capi.TAP_STATE))
-    assert relinf(G.readback(capi.TAP_OUTPUT), O.readback(capi.TAP_OUTPUT)) < TOL32
-    assert relinf(G.readback(capi.TAP_RHO), O.readback(capi.TAP_RHO)) < TOL32
-    assert relinf(G.readback(capi.TAP_DKL), O.readback(capi.TAP_DKL)) < TOL32
-    assert relinf(G.readback(capi.TAP_OUTGRAD), O.readback(capi.TAP_OUTGRAD)) < TOL32
-    assert np.array_equal(G.readback(capi.TAP_FAR), O.readback(capi.TAP_FAR))
-    assert relinf(G.readback(capi.TAP_GRADSUM), O.readback(capi.TAP_GRADSUM)) < TOL32
-
-
-def _ragged(rng, n, dS, lengths):
-    """n windows whose lengths go round `lengths` (so that the first few cover all of them)"""
-    return [(rng.normal(size=(lengths[i % len(lengths)], dS)) * 1.5 + 0.2).astype(np.float32) for i in range(n)]
-
-
-def _rec_cfg(kind, hidden, nApp=0, bptt=8):
-    return dict(dimS=6, dimA=2, bounded=[1, 0], hidden=hidden, nnFunc="Tanh", batchSize=16, maxTotObsNum=5000, randSeed=51,
-                adv_kind=capi.ADV_GAUSSIAN, nn_type=kind, nnBPTTseq=bptt, nAppendedObs=nApp)
 
 
 BATCHED = [(capi.NN_LSTM, (32, 32), 0), (capi.NN_MGU, (32, 32), 0), (capi.NN_LSTM, (24, 16), 0), (capi.NN_MGU, (24, 16, 8), 0),
@@ -91,21 +57,6 @@ def test_batched_acting_matches_oracle_per_agent(hip_api, kind, hidden, nApp):
 
 
 # ---- 2. shapes that go through the single-agent routes ------------------------------------------------------------------------
-CONV = [(8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)]
-FALLBACK = {
-    "conv-lstm": (dict(dimS=256, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=4, nAppendedObs=3, conv=CONV, hidden=(32,), nnFunc="Tanh",
-                       batchSize=16, maxTotObsNum=2000, randSeed=3, nn_type=capi.NN_LSTM, nnBPTTseq=4),
-                  dict(seed=5, dimS=256, dimA=1, lenMin=10, lenMax=40, pTerm=0.5)),
-    "rnn-encoder-mgu": (dict(dimS=5, dimA=2, bounded=[1, 0], hidden=(16, 16), encoder=[24], encoder_rnn=1, nn_type=capi.NN_MGU, nnFunc="Tanh",
-                             batchSize=16, maxTotObsNum=2000, randSeed=5, adv_kind=capi.ADV_GAUSSIAN, nnBPTTseq=5),
-                        dict(seed=21, dimS=5, dimA=2, lenMin=5, lenMax=40, pTerm=0.5)),
-    "lstm-512": (dict(dimS=7, dimA=2, bounded=[1, 0], hidden=(512,), nnFunc="Tanh", batchSize=6, maxTotObsNum=8000, randSeed=5,
-                      nn_type=capi.NN_LSTM, adv_kind=capi.ADV_GAUSSIAN, nnBPTTseq=3),
-                 dict(seed=21, dimS=7, dimA=2, lenMin=2, lenMax=30, pTerm=0.5)),
-    "dense-app3": (dict(dimS=9, dimA=3, bounded=[0, 0, 0], hidden=(24, 16, 8), nnFunc="Tanh", batchSize=8, maxTotObsNum=1000, randSeed=5,
-                        nAppendedObs=3),
-                   dict(seed=3, dimS=9, dimA=3, lenMin=5, lenMax=30, pTerm=0.3)),
-}
 
 
 @pytest.mark.gpu

@@ -15,88 +15,11 @@ import sys
 import numpy as np
 import pytest
 
-from oracle_api import oracle_learner, fill_synth, synth_cfg
+from acting import ILL_COLUMNS, LDS_NETS, NETS, TOL32, _compare_step, _conv_pair as _pair, _count, _row_bytes, _rows, _training_forwards
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL32 = 1e-5     # the bound the existing tests hold hl_forward and the conv training outputs to against the oracle
-
-CONV_ATARI = [(84, 84, 4, 8, 8, 4), (20, 20, 8, 16, 6, 2), (8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)]      # RACER_atari.json
-_BASE = dict(dimA=2, bounded=[1, 0], batchSize=8, maxTotObsNum=1500, randSeed=5)
-NETS = {
-    # 8 channels (half a channel tile), stride 2
-    "strided": dict(_BASE, dimS=576, conv=[(12, 12, 4, 8, 3, 1), (10, 10, 8, 16, 4, 2)], hidden=(32,), nnFunc="Tanh"),
-    # non-square image, 5 channels, K = 27 (no multiple of 4), 35 positions
-    "odd": dict(_BASE, dimS=189, conv=[(9, 7, 3, 5, 3, 1)], hidden=(32, 24), nnFunc="SoftSign"),
-    # stMean[c % dS] over stacked frames
-    "app3": dict(_BASE, dimS=200, nAppendedObs=3, conv=[(10, 10, 8, 16, 6, 2)], hidden=(40,)),
-    # 6 extras, a row that is no multiple of 4 floats
-    "extras6": dict(_BASE, dimS=1030, dimA=1, bounded=[0], adv_kind=capi.ADV_DISCRETE, n_options=5,
-                    conv=[(8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)], hidden=(48,)),
-    # one extra per frame, feature rows 1028 wide
-    "app3-extra": dict(_BASE, dimS=801, nAppendedObs=3, conv=[(20, 20, 8, 16, 6, 2)], hidden=(40, 24)),
-    # more extras (40) than the first dense layer is wide: its residual reads extras only
-    "extras40": dict(_BASE, dimS=229, conv=[(9, 7, 3, 5, 3, 1)], hidden=(32, 32), nnFunc="SoftSign"),
-    "atari": dict(dimS=7056, dimA=1, bounded=[0], adv_kind=capi.ADV_DISCRETE, n_options=6, nAppendedObs=3, conv=CONV_ATARI, hidden=(64,),
-                  nnFunc="SoftSign", batchSize=8, maxTotObsNum=400, randSeed=11),
-}
-N_EPS = {"atari": 14}
-# nets whose output columns the fp32 restatement itself does not resolve to TOL32 / 3 against its build in double (measured on the CPU after
-# the three steps of the row-by-row test, 17 rows: 6 of the 13 columns of "atari" between 3.5e-6 and 3.6e-5 -- outputs of 7e-4 .. 5e-2 behind
-# the 3136-term sums of its dense layer): parity.assert_columns holds those columns to 4 x the restatement's own loss
-ILL_COLUMNS = ("atari",)
-
-
-def _sc(kw, **over):
-    d = dict(seed=21, dimS=kw["dimS"], dimA=kw["dimA"], lenMin=4, lenMax=12, pTerm=0.5)
-    d.update(over)
-    return synth_cfg(**d)
-
-
-def _pair(hip_api, name, oracle=True, weights=None):
-    kw = NETS[name] if isinstance(name, str) else name
-    Ls = [capi.Learner(hip_api, capi.make_config(**kw))] + ([oracle_learner(capi.make_config(**kw))] if oracle else [])
-    for L in Ls:
-        if weights is None:
-            L.init_weights()
-        else:
-            w = weights(L)
-            L.set_params(w, np.zeros_like(w), np.zeros_like(w))
-        fill_synth(L, _sc(kw), N_EPS.get(name, 30) if isinstance(name, str) else 30)
-        L.initialize()
-        L.set_tap(True)
-    return Ls if oracle else Ls[0]
-
-
-def _compare_step(G, O):
-    assert np.array_equal(G.readback(capi.TAP_FLAT), O.readback(capi.TAP_FLAT))
-    assert np.array_equal(G.readback(capi.TAP_TAG), O.readback(capi.TAP_TAG))
-    assert np.array_equal(G.readback(capi.TAP_TSTEP), O.readback(capi.TAP_TSTEP))
-    assert np.array_equal(G.readback(capi.TAP_STATE), O.readback(capi.TAP_STATE))
-    assert relinf(G.readback(capi.TAP_OUTPUT), O.readback(capi.TAP_OUTPUT)) < TOL32
-    assert relinf(G.readback(capi.TAP_RHO), O.readback(capi.TAP_RHO)) < TOL32
-    assert relinf(G.readback(capi.TAP_DKL), O.readback(capi.TAP_DKL)) < TOL32
-    assert relinf(G.readback(capi.TAP_OUTGRAD), O.readback(capi.TAP_OUTGRAD)) < TOL32
-    assert np.array_equal(G.readback(capi.TAP_FAR), O.readback(capi.TAP_FAR))
-    assert relinf(G.readback(capi.TAP_GRADSUM), O.readback(capi.TAP_GRADSUM)) < TOL32
-
-
-def _rows(rng, n, dIn):
-    return (rng.normal(size=(n, dIn)) * 1.5 + 0.2).astype(np.float32)
-
-
-def _count(G, name):
-    return G.timing_get(name)[1]
-
-
-def _training_forwards(G):
-    """launches of the training forward path: the first conv layer and whichever name the dense layers behind run under"""
-    return _count(G, "conv_fwd0"), _count(G, "fwd_chain") + sum(_count(G, "gemm16_fwd%d" % j) for j in range(8))
-
-
-def _row_bytes(kw):
-    return 4 * kw["dimS"] * (1 + kw.get("nAppendedObs", 0))
 
 
 def _cap(dIn):
@@ -285,14 +208,6 @@ def test_generic_bit_2_keeps_the_training_buffer_route(hip_api, monkeypatch):
         G.timing_enable(False)
     for i in range(40):
         assert relinf(outs["2"][i], outs[None][i]) < 2 * TOL32, i
-
-
-LDS_NETS = {
-    # 176 KB of image (rows beyond HL_ACT_CONV_MAX_ROW_BYTES as well: the switch is held open, so the plan is what refuses)
-    "image-176K": dict(_BASE, dimS=44100, conv=[(210, 210, 1, 2, 10, 8)], hidden=(32,), maxTotObsNum=300),
-    # rows of 5.6 KB, within the switch as shipped: the first map, 32 x 36 x 36 floats = 162 KB, is what exceeds the LDS
-    "map-162K": dict(_BASE, dimS=1444, conv=[(38, 38, 1, 32, 3, 1), (36, 36, 32, 2, 4, 4)], hidden=(32,), maxTotObsNum=300),
-}
 
 
 @pytest.mark.gpu

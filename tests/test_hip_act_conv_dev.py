@@ -7,14 +7,11 @@ act -> simulate -> append -> step on tensors with stacked frames against the sam
 import numpy as np
 import pytest
 
+from acting import (ILL_COLUMNS, LDS_NETS, N_AGENTS, NETS, PARITY, TOL32, _bare, _call_dev, _check_heads, _columns, _conv_pair as _pair, _count,
+                    _packed, _row_bytes, _rows, _same_replay, _same_training_state, _side_stream, _stacked, _training_forwards, _window_args,
+                    head_np)
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
-from test_act_dev_cpu import head_np
-from test_hip_act_conv import ILL_COLUMNS, LDS_NETS, NETS, TOL32, _count, _pair, _row_bytes, _rows, _training_forwards
-from test_hip_act_dev import N_AGENTS, _check_heads, _same_replay, _same_training_state
-from test_hip_act_seq_dev import _call_dev, _columns, _packed, _side_stream
-
-PARITY = ["strided", "odd", "app3", "app3-extra", "extras6", "atari"]
 
 
 def _lengths(nApp):
@@ -25,11 +22,6 @@ def _lengths(nApp):
 def _wins(rng, n, kw):
     lengths = _lengths(kw.get("nAppendedObs", 0))
     return [_rows(rng, lengths[i % len(lengths)], kw["dimS"]) for i in range(n)]
-
-
-def _stacked(wins, nApp):
-    """the rows hl_forward reads: the last state, then the ones before it, steps before the first given state repeating it"""
-    return np.stack([np.concatenate([w[max(len(w) - 1 - j, 0)] for j in range(1 + nApp)]) for w in wins])
 
 
 # ---- 1. bit identity with the host call, parity with the oracle -------------------------------------------------------------------------
@@ -190,16 +182,6 @@ def test_given_weights_serve_device_windows_without_a_step(hip_api):
 
 
 # ---- 7. refusals --------------------------------------------------------------------------------------------------------------------------
-def _bare(hip_api, kw):
-    L = capi.Learner(hip_api, capi.make_config(**kw))
-    L.init_weights()
-    return L
-
-
-def _window_args(L, n=3):
-    import torch
-    return (torch.zeros((n + 1, L.dS), dtype=torch.float32, device="cuda"), torch.arange(n, dtype=torch.int64, device="cuda"),
-            torch.ones(n, dtype=torch.int32, device="cuda"))
 
 
 @pytest.mark.gpu

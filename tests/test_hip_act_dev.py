@@ -1,17 +1,15 @@
 """Acting and episode ingestion from device memory (include/smarties_hip_dev.h; smarties_amd/csrc/learner_dev.h, actdev.hip), on the GPU:
 hl_forward_dev against hl_forward bit for bit with the rows written on a side stream right before the call; the fp64 head kernel against
-the numpy restatement of tests/test_act_dev_cpu.py; hl_append_episodes_dev against hl_append_episode for a strided rollout buffer --
+the numpy restatement of tests/acting.py; hl_append_episodes_dev against hl_append_episode for a strided rollout buffer --
 fields, statistics, training after it, eviction, the episode log --; and a closed loop act -> simulate -> append -> step on tensors against
 the same loop through the host-pointer calls."""
 import numpy as np
 import pytest
 
+from acting import CLIP, DENSE_BASE as BASE, N_AGENTS, _check_heads, _same_replay, _same_training_state, head_np
 from oracle_api import fill_synth, synth_cfg
 from parity import assert_columns, twin64
 from smarties_amd import capi
-from test_act_dev_cpu import CLIP, head_np
-
-BASE = dict(dimS=6, dimA=2, bounded=[1, 0], hidden=(32, 32), nnFunc="Tanh", batchSize=8, maxTotObsNum=4000, randSeed=5)
 
 
 def _learner(hip_api, kw, n_eps=20, weights=None):
@@ -25,24 +23,6 @@ def _learner(hip_api, kw, n_eps=20, weights=None):
         fill_synth(L, synth_cfg(seed=21, dimS=kw["dimS"], dimA=kw["dimA"], lenMin=5, lenMax=30, pTerm=0.5), n_eps)
         L.initialize()
     return L
-
-
-def _same_training_state(A, B):
-    for a, b in zip(A.get_params(), B.get_params()):      # weights and both moments
-        assert np.array_equal(a, b)
-    assert np.array_equal(A.get_rng_state(), B.get_rng_state())
-    assert A.scalars().beta == B.scalars().beta
-
-
-def _same_replay(A, B):
-    assert A.counts() == B.counts()
-    for pos in range(A.counts()[1]):
-        assert A.episode_info(pos) == B.episode_info(pos), pos
-        assert np.array_equal(A.episode_stats(pos), B.episode_stats(pos)), pos
-        for field in range(6):
-            assert np.array_equal(A.episode_field(pos, field), B.episode_field(pos, field)), (pos, field)
-        # states, actions, policies and rewards as stored (bytes: the wire format's trailer holds integers that read as NaN)
-        assert A.pack_episode(pos).tobytes() == B.pack_episode(pos).tobytes(), pos
 
 
 # ---- 1. forward -------------------------------------------------------------------------------------------------------------------------
@@ -104,28 +84,6 @@ HEADS = {
     "gaussian": dict(BASE, dimA=2, bounded=[1, 0], adv_kind=capi.ADV_GAUSSIAN),
     "discrete": dict(BASE, dimA=1, bounded=[0], adv_kind=capi.ADV_DISCRETE, n_options=5),
 }
-N_AGENTS = 37
-
-
-def _ulp32(x):
-    return float(np.spacing(np.float32(abs(x))))
-
-
-def _check_heads(kw, O, noise, got):
-    """device results against head_np, agent by agent: f64 outputs within 1e-12 relative, f32 within one float ulp of the larger operand"""
-    act, mu, val, adv = [t.cpu().numpy() for t in got]
-    gauss, nOpt = kw.get("adv_kind") == capi.ADV_GAUSSIAN, kw.get("n_options", 0)
-    for i in range(N_AGENTS):
-        ra, rm, rv, radv = head_np(O[i], None if noise is None else noise[i], kw["dimA"], kw["bounded"], gauss, nOpt)
-        if nOpt:
-            assert act[i, 0] == ra[0], (i, act[i], ra)       # the label is exact by construction
-        assert np.all(np.abs(act[i] - ra) <= 1e-12 * np.abs(ra)), (i, act[i], ra)
-        assert np.all(np.abs(mu[i] - rm) <= 1e-12 * np.abs(rm)), (i, mu[i], rm)
-        V = float(rv)
-        assert abs(float(val[i]) - V) <= _ulp32(V), (i, val[i], rv)
-        # advantage = (Fval)((Fval)(V + A) - (Fval)V): the larger operand is V + A or V
-        big = max(abs(V), abs(V + float(radv)))
-        assert abs(float(adv[i]) - float(radv)) <= _ulp32(big), (i, adv[i], radv, V)
 
 
 @pytest.mark.gpu

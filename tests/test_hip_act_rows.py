@@ -12,48 +12,12 @@ import sys
 import numpy as np
 import pytest
 
-from oracle_api import oracle_learner, fill_synth, synth_cfg
+from acting import ROWS_WIDE as WIDE, TOL32, _compare_step, _pair, _rows
+from oracle_api import fill_synth, synth_cfg
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL32 = 1e-5     # the bound the existing tests hold hl_forward to against ol_forward (test_hip_r5: up to 2048-wide layers)
-
-
-def _pair(hip_api, cfg_kw, sc, n_eps, given=False):
-    """given: both start from the same given weights instead of hl_init_weights -- which refuses a Tanh output layer under the Gaussian
-    advantage, whose initial outputs of -1 / +1 have no finite pre-image (test_output_functions_without_a_finite_start_are_refused)"""
-    G = capi.Learner(hip_api, capi.make_config(**cfg_kw))
-    O = oracle_learner(capi.make_config(**cfg_kw))
-    w = None
-    for L in (G, O):
-        if given:
-            if w is None:
-                w = np.random.default_rng(1).uniform(-0.1, 0.1, L.get_params()[0].shape).astype(np.float32)
-            L.set_params(w, np.zeros_like(w), np.zeros_like(w))
-        else:
-            L.init_weights()
-        fill_synth(L, sc, n_eps)
-        L.initialize()
-        L.set_tap(True)
-    return G, O
-
-
-def _compare_step(G, O):
-    assert np.array_equal(G.readback(capi.TAP_FLAT), O.readback(capi.TAP_FLAT))
-    assert np.array_equal(G.readback(capi.TAP_TAG), O.readback(capi.TAP_TAG))
-    assert np.array_equal(G.readback(capi.TAP_TSTEP), O.readback(capi.TAP_TSTEP))
-    assert np.array_equal(G.readback(capi.TAP_STATE), O.readback(capi.TAP_STATE))
-    assert relinf(G.readback(capi.TAP_OUTPUT), O.readback(capi.TAP_OUTPUT)) < TOL32
-    assert relinf(G.readback(capi.TAP_RHO), O.readback(capi.TAP_RHO)) < TOL32
-    assert relinf(G.readback(capi.TAP_DKL), O.readback(capi.TAP_DKL)) < TOL32
-    assert relinf(G.readback(capi.TAP_OUTGRAD), O.readback(capi.TAP_OUTGRAD)) < TOL32
-    assert np.array_equal(G.readback(capi.TAP_FAR), O.readback(capi.TAP_FAR))
-    assert relinf(G.readback(capi.TAP_GRADSUM), O.readback(capi.TAP_GRADSUM)) < TOL32
-
-
-def _rows(rng, n, dIn):
-    return (rng.normal(size=(n, dIn)) * 1.5 + 0.2).astype(np.float32)
 
 
 def _sc(kw, **over):
@@ -103,10 +67,6 @@ def test_many_rows_match_oracle_row_by_row(hip_api, name):
 
 
 # ---- 2. the wide single-row call ---------------------------------------------------------------------------------------------------
-WIDE = {
-    "h1040": dict(dimS=9, dimA=3, bounded=[1, 0, 0], hidden=(1040,), nnFunc="Tanh", batchSize=8, maxTotObsNum=2000, randSeed=17),
-    "in1030": dict(dimS=1030, dimA=2, bounded=[1, 0], hidden=(32,), nnFunc="Tanh", batchSize=8, maxTotObsNum=2000, randSeed=17),
-}
 
 
 @pytest.mark.gpu

@@ -6,72 +6,17 @@ refusals; and a closed loop act -> simulate -> append -> step of an LSTM on tens
 import numpy as np
 import pytest
 
-from oracle_api import fill_synth, synth_cfg
+from acting import (FALLBACK, TOL32, _call_dev, _columns, _packed, _pair, _ragged, _rec_cfg, _same_replay, _same_training_state, _side_stream,
+                    _synth_learner as _learner, head_np)
+from oracle_api import synth_cfg
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
-from test_act_dev_cpu import head_np
-from test_hip_act_batch import FALLBACK, TOL32, _pair, _ragged, _rec_cfg
-from test_hip_act_dev import _same_replay, _same_training_state
 
 BPTT = 8
 SYNTH = dict(seed=43, dimS=6, dimA=2, lenMin=5, lenMax=40, pTerm=0.5)
 SHAPES = [(capi.NN_LSTM, (32, 32), 0), (capi.NN_MGU, (24, 16, 8), 0), (capi.NN_RNN, (24, 16), 0), (capi.NN_LSTM, (32, 32), 2),
           (capi.NN_LSTM, (128, 32), 0)]      # the last: the weights-through-L2 variant
 IDS = ["lstm-2x32", "mgu-24x16x8", "rnn-24x16", "lstm-2x32-app2", "lstm-128x32"]
-
-
-def _learner(hip_api, kw, sc_kw, n_eps=40):
-    L = capi.Learner(hip_api, capi.make_config(**kw))
-    L.init_weights()
-    if n_eps:
-        fill_synth(L, synth_cfg(**sc_kw), n_eps)
-        L.initialize()
-    return L
-
-
-_SIDE = []
-
-
-def _side_stream():
-    """ONE side stream for the whole file: every stream torch hands out and that is used keeps a hardware queue of the process for
-    good, and the tests of several replicas in one process (test_hip_parity.py, test_hip_r6.py) need a queue per replica"""
-    import torch
-    if not _SIDE:
-        _SIDE.append(torch.cuda.Stream())
-    return _SIDE[0]
-
-
-def _packed(wins):
-    """the windows back to back: (states [rows][dS], first_row, n_steps, row_stride 1)"""
-    n_steps = np.array([w.shape[0] for w in wins], np.int32)
-    first = np.concatenate([[0], np.cumsum(n_steps[:-1])]).astype(np.int64)
-    return np.concatenate(wins, axis=0), first, n_steps, 1
-
-
-def _columns(wins):
-    """the windows as columns of a [T][nEnv] rollout buffer, agent e in column e from row e % 3 on; cells no window owns hold NaN, so a
-    row read from the wrong place shows in the outputs: (states [T nEnv][dS], first_row, n_steps, row_stride nEnv)"""
-    n_env, dS = len(wins), wins[0].shape[1]
-    T = max(w.shape[0] for w in wins) + 2
-    buf = np.full((T, n_env, dS), np.nan, np.float32)
-    for e, w in enumerate(wins):
-        buf[e % 3:e % 3 + w.shape[0], e] = w
-    first = np.array([(e % 3) * n_env + e for e in range(n_env)], np.int64)
-    return buf.reshape(T * n_env, dS), first, np.array([w.shape[0] for w in wins], np.int32), n_env
-
-
-def _call_dev(G, side, layout, order, select=None):
-    """the device call on agents `order` of a layout, the buffer written on the side stream right before it and the outputs read in that
-    stream's order, no other synchronisation"""
-    import torch
-    states, first, n_steps, stride = layout
-    with torch.cuda.stream(side):
-        tables = (torch.from_numpy(first[order]).to("cuda", non_blocking=True), torch.from_numpy(n_steps[order]).to("cuda", non_blocking=True))
-        half = torch.from_numpy(states * np.float32(0.5)).to("cuda", non_blocking=True)
-        st = half + half
-        if select is None:
-            return G.forward_sequences_dev(st, tables[0], tables[1], stride, stream=side).cpu().numpy()
-        return [t.cpu().numpy() for t in G.select_actions_sequences_dev(st, tables[0], tables[1], stride, select, stream=side)]
 
 
 # ---- 1. bit identity with the host call, parity with the oracle -------------------------------------------------------------------------

@@ -9,10 +9,9 @@ import time
 import numpy as np
 import pytest
 
+from acting import _same_replay, _same_training_state, _side_stream
 from oracle_api import fill_synth, synth_cfg
 from smarties_amd import capi
-from test_hip_act_dev import _same_replay, _same_training_state
-from test_hip_act_seq_dev import _side_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -300,6 +299,45 @@ def test_snapshot_acting_does_not_queue_behind_a_backlog_of_steps(hip_api, capsy
     t1, t2 = stamps["live"]
     assert t1 >= t2 / 2, stamps      # the test discriminates, and a backlog existed
     L.scalars()                      # no device-side failure code
+
+
+def test_the_first_snapshot_call_runs_on_the_acting_stream(hip_api):
+    """The acting stream is created inside the first call under the snapshot source, and that call's launches must already run on it --
+    not on the legacy default stream, which a context built before the stream existed would name.  The default stream waits for the
+    work of every BLOCKING stream of the process; torch's and the library's streams are all non-blocking, so the test makes one through
+    the HIP runtime the process holds, queues about half a second of products on it, and the first call must be done while they run.
+    An LSTM's window call: it allocates nothing (an allocation waits for the default stream whatever stream the launches take)."""
+    import ctypes as C
+    import torch
+    kw, _, calls = NETS["lstm"]
+    L = _learner(hip_api, kw)
+    side, inputs = _side_stream(), _inputs(L, calls)
+    stride, (st, first, n_steps) = inputs[0][1], inputs[0][2]
+    out = torch.empty((n_steps.numel(), L.nOut), dtype=torch.float64, device="cuda")
+    L.step(2)
+    want = L.forward_sequences_dev(st, first, n_steps, stride).cpu().numpy()
+    L.policy_snapshot()
+    L.act_source("snapshot")
+    hip = C.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line))      # (the copy already mapped)
+    raw = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(raw)) == 0
+    blocking = torch.cuda.ExternalStream(raw.value)
+    a = torch.randn((4096, 4096), device="cuda")
+    b, c = torch.eye(4096, device="cuda"), torch.empty_like(a)
+    with torch.cuda.stream(blocking):
+        torch.mm(a, b, out=c)
+    L.sync(); torch.cuda.synchronize()
+    with torch.cuda.stream(blocking):
+        for _ in range(400):
+            torch.mm(a, b, out=c)
+    with torch.cuda.stream(side):
+        L.forward_sequences_dev(st, first, n_steps, stride, out=out, stream=side)      # the FIRST call under the snapshot source
+    side.synchronize()
+    busy = not blocking.query()
+    blocking.synchronize()
+    assert hip.hipStreamDestroy(raw) == 0
+    assert np.array_equal(out.cpu().numpy(), want)
+    assert busy, "the first snapshot call waited for a blocking stream's work: it ran on the default stream"
 
 
 # ---- 6. refusals -----------------------------------------------------------------------------------------------------------------------

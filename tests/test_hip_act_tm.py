@@ -14,10 +14,10 @@ import sys
 import numpy as np
 import pytest
 
+from acting import TOL32, _compare_step, _pair, _ragged as _windows
 from oracle_api import synth_cfg, fill_synth
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
-from test_hip_parity import _pair, _compare_step, TOL32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PREPARE_KERNEL = "lstm_tm_prepare_acts_kernel"
@@ -44,11 +44,6 @@ def _cfg(name):
 
 def _synth(name):
     return synth_cfg(seed=21, dimS=SHAPES[name][2], dimA=2, lenMin=2, lenMax=30, pTerm=0.5)
-
-
-def _windows(rng, n, dS, lengths):
-    """n windows whose lengths go round `lengths`"""
-    return [(rng.normal(size=(lengths[i % len(lengths)], dS)) * 1.5 + 0.2).astype(np.float32) for i in range(n)]
 
 
 def _ragged_lengths(name):

@@ -8,34 +8,15 @@ the host-pointer calls; the refusals of bad arguments."""
 import numpy as np
 import pytest
 
+from acting import (N_AGENTS, TOL32, WIDE_IDS as _IDS, WIDE_SHAPES as SHAPES, _call_dev, _check_heads, _columns, _packed, _pair, _ragged,
+                    _same_replay, _same_training_state, _side_stream, _wide_cfg as _cfg, head_np)
 from oracle_api import fill_synth, synth_cfg
 from parity import COL_ROWS, assert_columns, relinf, twin64
 from smarties_amd import capi
-from test_act_dev_cpu import head_np
-from test_hip_act_batch import TOL32, _pair, _ragged
-from test_hip_act_dev import N_AGENTS, _check_heads, _same_replay, _same_training_state
-from test_hip_act_seq_dev import _call_dev, _columns, _packed, _side_stream
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"lstm": capi.NN_LSTM, "mgu": capi.NN_MGU, "rnn": capi.NN_RNN}
-SHAPES = [  # (layer type, hidden, dimS, nAppendedObs, bptt, batch)
-    ("lstm", (32, 16), 257, 0, 3, 6),       # one component above the old bound; dimS % 4 != 0: scalar loads; a chunk below a 16-row tile
-    ("mgu", (64, 32), 300, 4, 4, 20),       # context states, windows that begin before the episode's start, both MGU phases, a partial second row block, 16-byte loads
-    ("rnn", (272,), 1027, 0, 3, 6),         # an odd reduction length, 17 cell tiles
-    ("lstm", (512,), 260, 0, 2, 8),         # wide inputs and a layer beyond 256 cells together
-    ("lstm", (16,), 8192, 0, 2, 4),         # the upper bound
-]
-_IDS = ["%s-%s-dS%d-app%d" % (sh[0], "x".join(map(str, sh[1])), sh[2], sh[3]) for sh in SHAPES]
 MGU = SHAPES[1]
-
-
-def _cfg(shape, **over):
-    kind, hidden, dS, nApp, bptt, batch = shape
-    kw = dict(dimS=dS, dimA=2, bounded=[1, 0], hidden=hidden, nnFunc="Tanh", batchSize=batch, maxTotObsNum=8000, randSeed=5,
-              nn_type=KINDS[kind], adv_kind=capi.ADV_GAUSSIAN, nnBPTTseq=bptt, nAppendedObs=nApp)
-    kw.update(over)
-    return kw
 
 
 def _synth(dS, dA=2):

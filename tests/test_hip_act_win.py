@@ -16,11 +16,10 @@ import sys
 import numpy as np
 import pytest
 
+from acting import FALLBACK, TOL32, _compare_step, _pair, _ragged as _windows
 from oracle_api import synth_cfg, fill_synth
 from parity import relinf
 from smarties_amd import capi
-from test_hip_act_batch import FALLBACK
-from test_hip_parity import _pair, _compare_step, TOL32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WINDOW_KERNELS = ("rnn_forward_kernel", "mgu_forward_kernel", "rec_forward_kernel", "lstm_forward_lds_kernel")
@@ -61,11 +60,6 @@ def _synth(name):
         return synth_cfg(**FALLBACK[name][1])
     kw = SHAPES[name][0]
     return synth_cfg(seed=21, dimS=kw["dimS"], dimA=kw["dimA"], lenMin=5, lenMax=40, pTerm=0.5)
-
-
-def _windows(rng, n, dS, lengths):
-    """n windows whose lengths go round `lengths`"""
-    return [(rng.normal(size=(lengths[i % len(lengths)], dS)) * 1.5 + 0.2).astype(np.float32) for i in range(n)]
 
 
 def _ragged_lengths(name):
