@@ -95,7 +95,23 @@ enum { HL_NN_FFNN = 0, HL_NN_LSTM = 1, HL_NN_MGU = 2 /* Layer_GRU.h: what a part
  * nAppendedObs 3, replayed graphs of 20 steps, median of 240 steps): 1024 inputs, the route as before, 583 us per step; 1040 inputs, the
  * product launch, 449 us (device time of the forward pass: 349 us against 11 + 53 + 149 for prepare, product and chain); 2048 inputs
  * 548 us; 8192 inputs 1066 us.  Nothing else about the speed of these nets has been measured: other cell counts, batches and window
- * lengths, and where the product launch would start to win below 1024 inputs, are open. */
+ * lengths, and where the product launch would start to win below 1024 inputs, are open.
+ *
+ * Recurrent nets BEHIND convolutional layers (n_conv > 0).  HL_NN_RNN: up to 256 cells on a feature row of up to 1024 floats, as before.
+ * HL_NN_LSTM, HL_NN_MGU: the first recurrent layer's input is the feature row: the state variables
+ * beside the first convolution's image, then the last map.  Layers up to 256 cells on a feature row of up to 1024 floats: the per-sample
+ * kernels of rec.hip, as before (also behind encoder layers and with encoder_rnn).  Beyond either, without encoder layers and without
+ * encoder_rnn: every layer a multiple of 16 cells, 16 to 1024, a feature row of up to 8192 floats; the conv stack runs over the
+ * batch x (nnBPTTseq + 2) window rows, its feature rows are the wide input rows of the route above (one copy launch joins them to the
+ * first layer's operand rows, then tm_win_product_kernel and the time-step-major chain), the gradient into them comes from the table's
+ * GEMM_X problem up to 1024 inputs and from rectm.hip: tm_conv_dx_kernel beyond; steps are eager launches.  hl_forward_sequence and
+ * hl_forward_sequences serve these nets (the windows' rows through the conv stack, then the product and the acting chain, agents as
+ * samples, in chunks of min(local batch, HL_ACT_SEQ_CHUNK)); the device-memory window calls and hl_forward refuse them as they refuse
+ * every recurrent net behind convolutions.  Refused by hl_create with HL_ERR_UNSUPPORTED (without a device the bare status, no handle; with one
+ * a handle that holds the message alone is left for hl_last_error / hl_destroy): a layer above 256 cells that is no multiple of 16, a layer above
+ * 1024 cells, any layer that is no multiple of 16 cells on a feature row beyond 1024 floats, a feature row beyond 8192 floats;
+ * SMARTIES_HIP_GENERIC bit 4 (no time-step-major launches); the 2^31 / 2^30 bounds above on the operand rows and the partials.
+ * Encoder layers in front of layers above 256 cells stay refused.  Measured times: DESIGN.md 4.4, profiles/conv_rec_wide_timing.json. */
 
 /* settings key returnsEstimator (Settings/HyperParameters.cpp:135; MemoryProcessing::createReturnEstimator,
  * ReplayMemory/MemoryProcessing.cpp:391-450): how the per-step return estimates are swept backwards over an episode */

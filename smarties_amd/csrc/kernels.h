@@ -113,6 +113,10 @@ bool rec_win_act_ok(const RecArgs& a);                                // rec.hip
 std::string rec_route_name(const RecArgs& a, bool backward);          // the kernel launch_rec_forward / launch_rec_backward take for this net, template arguments included
 hipError_t launch_rec_tm_forward(const RecArgs& a, hipStream_t s, int parts = TM_PART_ALL);
 hipError_t launch_rec_tm_backward(const RecArgs& a, hipStream_t s);
+// convolutions in front of time-step-major layers: a GEMM_X / EPI_DX problem (the gradient into the feature rows) in slices of the gate
+// columns, 64 x 64 tiles on the MFMA (rectm.hip: tm_conv_dx_kernel) -- whatever the number of inputs
+bool tm_conv_dx_ok(const GemmProblem& p);
+hipError_t launch_tm_conv_dx(const GemmProblem& p, hipStream_t s);
 // acting for a.B agents whose windows lie in the CALLER's device memory (hl_forward_sequences_dev, wide inputs): agent b gives nSteps[b]
 // states from row firstRow[b] of a.actStates [rows][dS] on, rowStride rows apart; its window is act_win_geo's (act_win_geo.h).  Beside
 // RecArgs, not inside it: the argument block of every other kernel stays as it is

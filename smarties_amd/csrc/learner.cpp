@@ -86,10 +86,14 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] < 16 || cfg->hidden[j] % 16 != 0 || cfg->hidden[j] > 1024) return HL_ERR_UNSUPPORTED;
     }
     // (encoder layers are hidden layers of the same network, Learner_approximator.cpp:149-166: the same limits hold for them)
-    // (LSTM / MGU / RNN layers of up to 1024 cells, all multiples of 16, without encoder layers or convolutions in front: the time-step-major
-    //  launches -- rectm.hip -- serve their training windows and their acting windows; checked again where recTm is decided)
-    const bool tmKind = cfg->n_encoder == 0 && cfg->n_conv <= 0;      // (every recurrent type)
-    for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] > (tmKind && cfg->hidden[j] % 16 == 0 ? 1024 : 256)) return HL_ERR_UNSUPPORTED;
+    // (LSTM / MGU / RNN layers of up to 1024 cells, all multiples of 16, without encoder layers in front: the time-step-major
+    //  launches -- rectm.hip -- serve their training windows and their acting windows; checked again where recTm is decided.
+    //  LSTM and MGU layers behind convolutions as well -- convRec; what those nets are held to follows the convolutions' own checks
+    //  below.  Plain RNN layers behind convolutions stay with the per-sample kernels' 256 cells)
+    const bool convRec = convRecTmKind(cfg);
+    const bool tmKind = cfg->n_encoder == 0 && (cfg->n_conv <= 0 || convRec);      // (without convolutions: every recurrent type)
+    for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] > (tmKind && cfg->hidden[j] % 16 == 0 ? 1024 : 256))
+      return convRec ? refuse(out, "recurrent layer behind convolutions wider than 256 cells: every LSTM / MGU layer must be a multiple of 16 cells, 16 to 1024 (time-step-major launches)") : HL_ERR_UNSUPPORTED;
     for (int j = 0; j < cfg->n_encoder; ++j) if (cfg->encoder[j] > 256) return HL_ERR_UNSUPPORTED;
   }
   if (cfg->nAppendedObs < 0 || cfg->n_conv < 0 || cfg->n_conv > HL_MAX_CONV) return HL_ERR_BAD_ARG;
@@ -106,6 +110,16 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     // conv.hip: zero padding, one power-of-two stride, <= 64 channels per layer, filters <= 32 wide
     if (d.paddinx || d.paddiny || d.stridex != d.stridey || (d.stridex & (d.stridex - 1)) || d.stridex > 8) return HL_ERR_UNSUPPORTED;
     if (d.outFeatures > 64 || d.inpFeatures > 64 || d.filterx > 31 || d.filtery > 63 || (long long)d.outFeatures * d.outY * d.outX >= (1 << 20)) return HL_ERR_UNSUPPORTED;
+  }
+  if (convRecTmKind(cfg)) {
+    // LSTM / MGU layers behind convolutions: a layer beyond the 256 cells, or a feature row -- the state variables beside the image, then the
+    // last map (Builder.cpp:26-46) -- beyond the 1024 floats the per-sample kernels hold takes the time-step-major launches, the feature
+    // rows as the wide input rows of tm_win_product_kernel: every layer a multiple of 16 cells, rows of up to TM_WIN_MAX_IN floats
+    const long long row = convRecFeatureRow(cfg);
+    bool wide = row > 1024, ok = true;
+    for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] > 0) { wide = wide || cfg->hidden[j] > 256; ok = ok && cfg->hidden[j] >= 16 && cfg->hidden[j] % 16 == 0; }
+    if (wide && row > TM_WIN_MAX_IN) return refuse(out, "recurrent layer behind convolutions: a feature row (state variables beside the image + the last map) beyond 8192 floats");
+    if (wide && !ok) return refuse(out, "recurrent layers behind convolutions beyond 256 cells or on a feature row beyond 1024 floats: every LSTM / MGU layer must be a multiple of 16 cells, 16 to 1024 (time-step-major launches)");
   }
   int nDev = 0;
   if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return HL_ERR_NO_DEVICE;
@@ -179,22 +193,37 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     // 4 x as often)
     if (h->recTm && !(h->generic & 128)) h->bigMm |= 2;
   }
+  // ... and LSTM / MGU layers behind convolutions (no encoder layers): nets within the per-sample kernels' limits -- layers up to 256 cells on a feature row
+  // of up to 1024 floats -- keep those kernels whatever their cell count; beyond either limit the conv stack's feature rows, one per
+  // (sample, window step), are the wide input rows of the route above: the prepare launch copies them into the first layer's operand
+  // rows, tm_win_product_kernel and the chain follow, the gradient into the rows is tm_conv_dx_kernel's or the table's GEMM_X problem
+  // (step_exec.h: convRecWideDx in launchBackward).  Sizes were checked at the top; their steps are eager launches
+  if (h->recurrent && convRecTmKind(cfg) && h->nHidden >= 2) {
+    bool wide = h->hid[1].nIn > 1024;
+    for (int j = 1; j < h->nHidden; ++j) wide = wide || h->hid[j].size > 256;
+    if (wide && (h->generic & 4)) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layers behind convolutions beyond 256 cells or on a feature row beyond 1024 floats: served by the time-step-major launches only (SMARTIES_HIP_GENERIC bit 4 switches them off)");
+    if (wide) {
+      h->recTm = h->wideIn = h->convTm = true; h->recK += 1; h->useGraph = false;
+      if (!(h->generic & 128)) h->bigMm |= 2;
+    }
+  }
   if (h->recurrent && h->nConv == 0 && (cfg->dimS > 256 || h->dIn > 1024) && !(h->recTm && h->wideIn))
     return fail(h, HL_ERR_UNSUPPORTED, "recurrent net on a state beyond 256 components or a stacked input beyond 1024: served by the time-step-major launches only (SMARTIES_HIP_GENERIC bit 4 switches them off)");
   if (h->recurrent && h->wideIn) {
     // what the launches index with 32-bit row offsets and what the partial buffers hold: the operand rows [B recK][input + cells + 1] of
     // the first layer below 2^31 floats (its weight-gradient partials are bounded where they are sized: buildProblems)
-    const long long rows = (long long)B * h->recK, pitch = roundUp((long long)h->dIn + h->cfg.hidden[0] + 1, 16);
+    const DevHidden& f = h->hid[h->nConv > 0 ? 1 : 0];      // (behind convolutions: on the feature rows)
+    const long long rows = (long long)B * h->recK, pitch = roundUp((long long)f.nIn + f.size + 1, 16);
     if (rows * pitch >= (1ll << 31)) return fail(h, HL_ERR_UNSUPPORTED, "wide recurrent input: batch x (nnBPTTseq + 2) window rows of input + cells + 1 floats reach 2^31 floats");
   }
   if (h->recurrent && !h->recTm)
-    for (int j = 0; j < h->cfg.n_hidden; ++j) if (h->cfg.hidden[j] > 256) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer wider than 256 cells: every LSTM / MGU / RNN layer must be a multiple of 16 cells, without encoder layers or convolutions in front (time-step-major launches)");
+    for (int j = 0; j < h->cfg.n_hidden; ++j) if (h->cfg.hidden[j] > 256) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer wider than 256 cells: every LSTM / MGU / RNN layer must be a multiple of 16 cells, without encoder layers in front (time-step-major launches)");
   h->convB = B; h->convMmax = h->Mmax;
   if (h->recurrent && h->nConv > 0) {
     if (h->nHidden < 2) return fail(h, HL_ERR_UNSUPPORTED, "recurrent network type behind convolutions without a recurrent layer (nnLayerSizes is empty)");
     // (the input gradient of the first recurrent layer is a GEMM over its gate deltas with 16-byte row loads; its input rows are staged in LDS)
     if ((std::max(h->hid[1].lstm, 1) * h->hid[1].size) % 4 != 0) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer behind convolutions: gates x cells must be a multiple of 4");
-    if (h->hid[1].nIn > 1024) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer behind convolutions: more than 1024 inputs");
+    if (h->hid[1].nIn > 1024 && !h->convTm) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layer behind convolutions: more than 1024 inputs (LSTM / MGU layers without encoder layers: up to 8192, every layer a multiple of 16 cells)");
     h->convB = B * h->recK; h->convMmax = (int)roundUp((long long)h->convB + B, 16);
     HIPCK(devAlloc(&h->winSlot, (size_t)h->convB)); HIPCK(devAlloc(&h->winT, (size_t)h->convB)); HIPCK(devAlloc(&h->winNextSrc, (size_t)B));
     HIPCK(devAlloc(&h->scW, 1));
@@ -276,9 +305,9 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     if (h->recTm) {
       HIPCK(devAlloc(&h->tmT, (size_t)B)); HIPCK(devAlloc(&h->tmSteps, (size_t)B)); HIPCK(devAlloc(&h->tmNext, (size_t)B));
       int nCtr = 0;
-      for (int j = 0; j < h->nHidden; ++j) { h->tmCtrOff[j] = nCtr; nCtr += (h->hid[j].size / 16) * ((B + 15) / 16); }      // (recTm: no convolutions in front)
+      for (int j = h->nConv > 0 ? 1 : 0; j < h->nHidden; ++j) { h->tmCtrOff[j] = nCtr; nCtr += (h->hid[j].size / 16) * ((B + 15) / 16); }      // (hid[0] of a convolutional net is its last convolution)
       HIPCK(devAlloc(&h->tmCtr, (size_t)nCtr)); h->tmCtrN = nCtr;
-      if (h->wideIn) HIPCK(devAlloc(&h->tmP, R * (size_t)h->hid[0].lstm * h->hid[0].size));      // (a row per window row, as the layer's X)
+      if (h->wideIn) { const DevHidden& f = h->hid[h->nConv > 0 ? 1 : 0]; HIPCK(devAlloc(&h->tmP, R * (size_t)f.lstm * f.size)); }      // (a row per window row, as the layer's X)
     }
   }
   {   // fused forward + head + dX kernel: two equal hidden blocks of width H <= 256, small state / action spaces
@@ -411,6 +440,7 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   rc = buildProblems(h); if (rc) return rc;
   // (wide inputs have no other route: the per-sample kernels stage an input row of at most 1024 floats)
   if (h->wideIn && !rec_tm_ok(recArgs(h, 0))) return fail(h, HL_ERR_UNSUPPORTED, "wide recurrent input: the time-step-major launches refuse this net");
+  if (h->convTm && !tm_conv_dx_ok(h->hostProbs[h->buf[0].dxIdx[0]])) return fail(h, HL_ERR_UNSUPPORTED, "recurrent layers behind convolutions: the input-gradient launch refuses this net");
   if (const char* e = getenv("SMARTIES_HIP_NO_GRAPH")) { if (e[0] == '1') h->useGraph = false; }
   if (const char* e = getenv("SMARTIES_HIP_XCHG_TIMEOUT_MS")) h->xchgTimeoutTicks = std::max(1LL, atoll(e)) * 100000LL;
   return HL_OK;

@@ -128,6 +128,9 @@ static const ActRoutes& actResolve(hl_learner* h) {
   // front, RNN encoder layers under MGU layers, a window beyond the batched kernel's LDS --: workgroup b on agent b's window
   r.win = h->recurrent;
   for (int seg = h->recSplit ? 0 : -1; r.win && seg < (h->recSplit ? 2 : 0); ++seg) r.win = rec_win_act_ok(actRecArgs(h, seg, 1, &noState, nullptr, nullptr, 1, 0));
+  // ... and behind convolutions the nets beyond those kernels (hl_learner::convTm) keep the shape of that chain -- the chunk's stacked rows through
+  // the front -- with the time-step-major launches behind it, the agents as their samples, the feature rows as their wide input rows
+  if (h->convTm) r.win = rec_tm_act_ok(actRecArgs(h, -1, 1, &noState, nullptr, nullptr, 1, 0));
   // 8. dense nets on rows in device memory, which can be streamed: the row-block kernel where 2. serves the net, act_rows_panel_kernel on
   // input rows up to ACT_DEV_MAX_ROW wide otherwise
   const char* why = nullptr;
@@ -446,6 +449,7 @@ static int actWinChain(hl_learner* h, int n, const int32_t* nSteps, const float*
   ActRecPair rec;
   return actWindowChunks(h, "act_win_chain", conv, n, nSteps, states, outputs, [&](int m, int winMax) {
     actRecPair(h, rec, m, conv ? h->act.dS : s.in, s.off, s.cnt, winMax, 0);
+    if (h->convTm) return rec_tm_act_ok(rec.lo) ? HL_OK : fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the time-step-major launches refuse the chunk");
     return rec_win_act_ok(rec.lo) && (!rec.split || rec_win_act_ok(rec.up)) ? HL_OK : fail(h, HL_ERR_UNSUPPORTED, "hl_forward_sequences: the window kernels refuse the chunk");
   }, [&](int m, unsigned tag, int* rc) {
     if (conv) return actTrainTail(h, s.in, m * h->recK, &rec, m, s.out, s.done, tag, rc);

@@ -150,6 +150,27 @@ extern "C" HL_API int hl_debug_conv_rows_kind(hl_learner* h) {
   if (convFromReplay(h)) convSource(h, 0, &ca);
   return ca.L[0].rbKind;
 }
+// recurrent layers behind convolutions: the operands and the result of the gradient into the feature rows as the last step left them
+// (tests: tm_conv_dx_kernel and the GEMM_X problem against the same product in double, column by column).  which = 0 the first recurrent
+// layer's gate deltas [rows][gates x cells], 1 its residual deltas [rows][ldR], 2 Dres of the last convolution's rows [rows][ldA], 3 their
+// D; dims = {rows, floats per row}; out may be nullptr (dims only), else cap >= rows x floats per row.  which = 4: nothing is copied,
+// dims = {the launch that forms Dres: 0 the GEMM_X problem (gemm16.hip), 1 tm_conv_dx_kernel; 1 where the net runs time-step-major}
+extern "C" HL_API int hl_debug_conv_rec_dx(hl_learner* h, int which, float* out, int64_t cap, int32_t dims[2]) {
+  if (!h || !dims || which < 0 || which > 4) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  if (!h->recurrent || h->nConv == 0 || h->nHidden < 2) return fail(h, HL_ERR_UNSUPPORTED, "no recurrent layer behind convolutions");
+  if (which == 4) { dims[0] = convRecWideDx(h) ? 1 : 0; dims[1] = h->convTm ? 1 : 0; return HL_OK; }
+  const RecLayer& L = h->rec[1]; const DevHidden& q = h->hid[0];
+  if (which == 1 && !L.hasRes) return fail(h, HL_ERR_UNSUPPORTED, "the first recurrent layer has no residual");
+  const float* src = which == 0 ? L.D : which == 1 ? L.Rd : which == 2 ? q.Dres : q.D;
+  dims[0] = h->convB; dims[1] = which == 0 ? std::max(h->hid[1].lstm, 1) * h->hid[1].size : which == 1 ? L.ldR : q.ldA;
+  if (!out) return HL_OK;
+  const int64_t n = (int64_t)dims[0] * dims[1];
+  if (cap < n) return HL_ERR_BAD_ARG;
+  HIPCK(hipStreamSynchronize(h->stream));
+  HIPCK(hipMemcpy(out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return HL_OK;
+}
 // sets every arrive counter of the in-kernel panel barriers to `value` (tests: the counters are monotonic and wrap; the barrier's
 // target arithmetic must survive that).  A barrier's group adds HT per launch to its counter, so only multiples of HT are states
 // the kernels can meet: anything else is refused.

@@ -117,6 +117,10 @@ struct hl_learner {
   // wide inputs (dimS > 256 or a stacked input beyond 1024, no convolutions in front): time-step-major whatever the cell count, the first
   // layer's input product of all window rows from one launch into tmP [B recK][gates x cells] (rectm.hip: tm_win_product_kernel)
   bool wideIn = false; float* tmP = nullptr;
+  // ... and LSTM / MGU layers behind convolutions beyond 256 cells or on a feature row beyond 1024 floats (no encoder layers): the same
+  // route, the feature rows [extras | last map] of the B recK window rows as its wide input rows; the gradient into them from
+  // tm_conv_dx_kernel where the row is beyond 1024 floats (SMARTIES_HIP_GENERIC & 2048: wherever the route is taken), else the GEMM_X problem
+  bool convTm = false;
   bool recurrent = false; int recK = 0;    // LSTM hidden layers: rows per sample of the per-step buffers (nnBPTTseq + 1; one more for the time-step-major launches)
   int recWin = 0;                          // ... steps of a window: nnBPTTseq + 1
   // hl_config::encoder_rnn: the first recSplit recurrent layers are plain recurrent ("RNN") ones under MGU layers.  The window kernels
@@ -192,6 +196,7 @@ struct hl_learner {
   //   1 no two-kernel fused step            2 no forward chain / activation kernel / deferred beta      4 recurrent: unfused launches, chunked dW
   //   8 conv: per-layer launches behind the first layer       16 conv: any-geometry kernels       32 conv: gather-form filter gradients
   //  64 conv: stacked rows, no row-block kernels              128 large batches: the common tile launches      256 weight-gradient tiles in launches of their own
+  // 2048 recurrent layers behind convolutions, time-step-major: the gradient into the feature rows from tm_conv_dx_kernel also where GEMM_X serves (tests, tools/conv_rec_wide_timing.py)
   // 4096 acting behind convolutions: the route of actconv.hip also for raw rows beyond HL_ACT_CONV_MAX_ROW_BYTES (tests, tools/act_conv_timing.py)
   int generic = 0;
   bool plainGraph = false;      // the replayed steps of this net are stepEager's launches as graph nodes (the next minibatch's sampler in front): nets none of the rider forms serves
@@ -260,6 +265,26 @@ void windowPoolPut(int dev, size_t bytes, unsigned char* q) {
 }
 
 int fail(hl_learner* h, int code, const std::string& m) { if (h) h->err = m; return code; }
+// hl_create refuses a configuration by its sizes alone.  Without a device the bare status, *out untouched, as every size check in front
+// of the device query answers; with one a handle that holds the message alone (the caller reads hl_last_error and calls hl_destroy, as
+// after any failure of hl_create behind the device query)
+int refuse(hl_learner** out, const std::string& m) {
+  int nDev = 0;
+  if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return HL_ERR_UNSUPPORTED;
+  hl_learner* h = new hl_learner(); *out = h; return fail(h, HL_ERR_UNSUPPORTED, m);
+}
+// the nets behind convolutions that may take the time-step-major launches: LSTM or MGU layers, no encoder layers, no encoder_rnn (plain
+// RNN layers behind convolutions keep the per-sample kernels and their 256 cells)
+bool convRecTmKind(const hl_config* c) {
+  return (c->nn_type == HL_NN_LSTM || c->nn_type == HL_NN_MGU) && c->n_conv > 0 && c->n_conv <= HL_MAX_CONV && c->n_encoder == 0 && !c->encoder_rnn;
+}
+// recurrent layers behind convolutions: floats of the first recurrent layer's input row -- the state variables beside the first
+// convolution's image, then the last map (buildNet: extras, prev); the geometry has passed hl_create's checks
+long long convRecFeatureRow(const hl_config* c) {
+  const hl_conv2d& f = c->conv[0]; const hl_conv2d& l = c->conv[c->n_conv - 1];
+  const long long inAll = (long long)c->dimS * (1 + c->nAppendedObs), inImg = (long long)f.inpFeatures * f.inpY * f.inpX;
+  return std::max(0ll, inAll - inImg) + (long long)l.outFeatures * l.outY * l.outX;
+}
 int hipFail(hl_learner* h, hipError_t e, const char* what) {
   return fail(h, HL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }

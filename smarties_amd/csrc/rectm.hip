@@ -106,6 +106,9 @@ __global__ __launch_bounds__(256) void lstm_tm_prepare_acts_kernel(RecArgs a) {
   if (k < win) {
     const RecLayer& L0 = a.L[0];
     const float* states = a.actStates + (size_t)a.actOff[b] * a.dS;
+    // (behind convolutions: the agents' feature rows, step k of agent b at row b K + k, written by the launches in front)
+    if (a.Xin) { for (int i = tid; i < L0.nIn; i += 256) L0.A[r * L0.ldA + i] = a.Xin[r * a.ldXin + i]; }
+    else
     for (int i = tid; i < L0.nIn; i += 256) L0.A[r * L0.ldA + i] = recActInputAt(a, states, ctx, k, i);
   }
 }
@@ -425,7 +428,8 @@ __device__ __forceinline__ void tmLstmForward(const RecArgs& a, int j0, int k0) 
   const float out = og * co;
   L.X[r * NO + c] = ci; L.X[r * NO + nC + c] = ig; L.X[r * NO + 2 * nC + c] = fg; L.X[r * NO + 3 * nC + c] = og;
   L.Y[r * NO + c] = out; L.Y[r * NO + nC + c] = st; L.Y[r * NO + 2 * nC + c] = co;
-  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wrE, brE, stepsE, TE);      // (the first layer has no residual: its staged row is read above it only)
+  // (the product route stages the recurrent part alone: a first layer with a residual -- behind convolutions -- reads its input from the operand row)
+  tmHandOn(a, L, j, k, b, c, r, out, win ? L.A + r * L.ldA : sA + row * lds, wrE, brE, stepsE, TE);
   TMSTMP(5);
 }
 __global__ __launch_bounds__(TM_FNT) void lstm_tm_fwd_kernel(RecArgs a, int j0, int k0) { tmLstmForward<false>(a, j0, k0); }
@@ -532,7 +536,7 @@ __device__ __forceinline__ void tmMguForward(const RecArgs& a, int j0, int k0, i
   L.Y[r * NO + c] = out;
   float wr = 0.f, br = 0.f;
   if (L.hasRes && c < L.resW) { wr = a.W[L.indWr + c]; br = a.W[L.indBr + c]; }
-  tmHandOn(a, L, j, k, b, c, r, out, sA + row * lds, wr, br, a.tmSteps[b], a.tmT[b]);
+  tmHandOn(a, L, j, k, b, c, r, out, win ? L.A + r * L.ldA : sA + row * lds, wr, br, a.tmSteps[b], a.tmT[b]);
 }
 __global__ __launch_bounds__(TM_FNT) void mgu_tm_fwd_kernel(RecArgs a, int j0, int k0, int phase) { tmMguForward<false>(a, j0, k0, phase); }
 __global__ __launch_bounds__(TM_FNT) void tm_win_mgu_fwd_kernel(RecArgs a, int j0, int k0, int phase) { tmMguForward<true>(a, j0, k0, phase); }
@@ -769,6 +773,86 @@ __global__ __launch_bounds__(256) void tm_win_product_kernel(RecArgs a, int nB, 
   }
 }
 
+// ---- convolutions in front: the gradient into the feature rows, the mirror of the product above ---------------------------------------
+//   Dres[r][i] = sum_{o < gates nC} D[r][o] W_in[i][o]  (+ Rd[r][i] w_res[i], i < resN),   D2[r][i] = Dres[r][i] act'(X[r][i], Y[r][i])
+// for every window row r < M and input i < N: the GEMM_X / EPI_DX problem of the step's table (step_exec.h: buildProblems), whose record
+// this kernel reads as it stands -- A = the first recurrent layer's gate deltas [M][K], B = W_in [N][ldb], C / C2 = Dres / D of the last
+// convolution's rows, resIn / resW the parametric-residual path, actX / actY / func the convolution's activation.  gemm16.hip's form of
+// it stages an operand row per sample; here both operands come in slices of 32 gate columns: a workgroup = 64 rows x 64 inputs, a slice =
+// 64 x 32 of D and 64 x 32 of W_in (both read along the gate columns, 16 bytes per load: K and both pitches are multiples of 4), wavefront
+// w its rows 16 w .. 16 w + 15 over the four input tiles, the next slice in registers while this one's products run.  An element is one
+// chain of MFMAs over o = 0 .. K - 1 whatever its row's place in the launch.  Rows past M and inputs past N are clamped on the way in and
+// masked on the way out; rows of steps a sample does not have hold zero deltas (lstm_tm_prepare_kernel) and come out zero.
+constexpr int WX_T = 64, WX_KC = 32, WX_P = WX_KC + 4;
+__global__ __launch_bounds__(256) void tm_conv_dx_kernel(GemmProblem P) {
+  __shared__ __attribute__((aligned(16))) float sD[WX_T * WX_P], sW[WX_T * WX_P];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lc = lane >> 4;
+  const int n0 = blockIdx.x * WX_T, m0 = blockIdx.y * WX_T;
+  // a slice: rows tid / 8 and + 32 of either operand, four gate columns from 4 (tid % 8)
+  const int r0 = tid >> 3, oc = (tid & 7) * 4;
+  const float* dRow[2]; const float* wRow[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    dRow[q] = P.A + (size_t)min(m0 + r0 + 32 * q, P.M - 1) * P.lda;
+    wRow[q] = P.B + (size_t)min(n0 + r0 + 32 * q, P.N - 1) * P.ldb;
+  }
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 vd[2], vw[2];
+  auto loadSlice = [&](int o0) {
+    const bool in = o0 + oc < P.K;      // (K is a multiple of 4: a 16-byte piece is inside the row or behind it)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      vd[q] = in ? *reinterpret_cast<const f32x4*>(dRow[q] + o0 + oc) : z4;
+      vw[q] = in ? *reinterpret_cast<const f32x4*>(wRow[q] + o0 + oc) : z4;
+    }
+  };
+  f32x4 acc[4] = {z4, z4, z4, z4};
+  const float* ar = sD + (16 * wave + li) * WX_P + lc;      // A element = (row li of the wavefront's 16, k = 4 s + lc)
+  const float* br = sW + li * WX_P + lc;                    // B element = (k = 4 s + lc, input li of tile t): W_in's row read along its columns
+  loadSlice(0);
+  for (int o0 = 0; o0 < P.K; o0 += WX_KC) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      *reinterpret_cast<f32x4*>(sD + (r0 + 32 * q) * WX_P + oc) = vd[q];
+      *reinterpret_cast<f32x4*>(sW + (r0 + 32 * q) * WX_P + oc) = vw[q];
+    }
+    __syncthreads();
+    if (o0 + WX_KC < P.K) loadSlice(o0 + WX_KC);
+#pragma unroll
+    for (int s = 0; s < WX_KC / 4; ++s) {
+      const float av = ar[4 * s];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, br[16 * t * WX_P + 4 * s], acc[t], 0, 0, 0);
+    }
+    __syncthreads();      // (the slice's readers are through before the next one is stored)
+  }
+  // result element q = (row 4 lc + q, input li of tile t): EPI_DX (gemm_tile.h) on it
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int m = m0 + 16 * wave + 4 * lc + q;
+    if (m >= P.M) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int n = n0 + 16 * t + li;
+      if (n >= P.N) continue;
+      float dres = acc[t][q];
+      if (n < P.resN) dres += P.resIn[(size_t)m * P.ldRes + n] * P.resW[n];
+      P.C[(size_t)m * P.ldc + n] = dres;
+      P.C2[(size_t)m * P.ldc + n] = dres * actDiff(P.func, P.actX[(size_t)m * P.ldAct + n], P.actY[(size_t)m * P.ldAct + n]);
+    }
+  }
+}
+bool tm_conv_dx_ok(const GemmProblem& p) {
+  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  return p.flavor == GEMM_X && p.epi == EPI_DX && p.M >= 1 && p.N >= 1 && p.K >= 4 && (p.K & 3) == 0 && (p.lda & 3) == 0 && (p.ldb & 3) == 0 &&
+         p.lda >= p.K && p.ldb >= p.K && aligned(p.A) && aligned(p.B) && p.C && p.C2 && p.actX && p.actY && (p.resN == 0 || (p.resIn && p.resW));
+}
+hipError_t launch_tm_conv_dx(const GemmProblem& p, hipStream_t s) {
+  if (!tm_conv_dx_ok(p)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tm_conv_dx_kernel, dim3((p.N + WX_T - 1) / WX_T, (p.M + WX_T - 1) / WX_T), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 static bool tmGatesOk(const RecArgs& a) { return a.gates == 4 || a.gates == 2 || a.gates == 1; }
 // (wide inputs -- RecArgs::tmP --: the first layer's tile is the recurrent part of the row alone)
@@ -780,9 +864,11 @@ static bool tmLayersOk(const RecArgs& a) {
     if (a.gates == 2 && a.tmFP[j] == nullptr) return false;
     if (tmFwdLds(a, j) > 150 * 1024) return false;
   }
-  // the input product: raw states as the first layer's input (no rows from launches in front), no residual on it (its epilogue would read
-  // the input part of a staged row), 16-byte pieces of the operand rows, nothing wider than the bound hl_create states
-  if (a.tmP && (a.Xin != nullptr || a.L[0].hasRes || (a.L[0].ldA & 15) || a.L[0].nIn > TM_WIN_MAX_IN || a.L[0].nC > 1024)) return false;
+  // the input product: 16-byte pieces of the operand rows, nothing wider than the bound hl_create states.  The first layer's input is the
+  // raw states or (Xin, convolutions in front) the feature rows the prepare launch copies into the operand rows; a residual on it -- it
+  // has one behind convolutions only -- reads its input from the operand row (the forward kernels' hand-off)
+  if (a.tmP && ((a.L[0].ldA & 15) || a.L[0].nIn > TM_WIN_MAX_IN || a.L[0].nC > 1024)) return false;
+  if (a.Xin != nullptr && a.tmP == nullptr) return false;      // (rows from launches in front: the product route only)
   return true;
 }
 // acting (one window of a.actSteps given states, or with the per-agent tables a.B windows of up to a.actSteps) through the same launches:
@@ -790,7 +876,7 @@ static bool tmLayersOk(const RecArgs& a) {
 bool rec_tm_act_ok(const RecArgs& a) {
   const bool many = a.actOff != nullptr && a.actCnt != nullptr;
   if ((a.actOff != nullptr) != (a.actCnt != nullptr) || (many ? a.B < 1 || a.actSteps > a.nBPTT + 1 : a.B != 1)) return false;
-  if (!tmGatesOk(a) || a.actStates == nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.Xin != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;
+  if (!tmGatesOk(a) || a.actStates == nullptr || a.tmSteps == nullptr || a.YoutRows != nullptr || a.actSteps < 1 || a.actSteps > a.K) return false;      // (Xin: tmLayersOk)
   bool wide = a.tmP != nullptr;
   for (int j = 0; j < a.nL; ++j) wide = wide || a.L[j].nC > 256;
   return wide && tmLayersOk(a);

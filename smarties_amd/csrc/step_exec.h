@@ -546,6 +546,9 @@ int launchWeightGrad(hl_learner* h, int parity, bool fuseAdam, hipStream_t s, bo
                        nextSampleC ? &exC : nullptr, s, fusePost ? &exP : nullptr); }));
   return HL_OK;
 }
+// recurrent layers behind convolutions on the time-step-major route: the gradient into the feature rows from tm_conv_dx_kernel -- a row beyond
+// the 1024 floats GEMM_X serves, or wherever SMARTIES_HIP_GENERIC bit 2048 asks for it (tests, tools/conv_rec_wide_timing.py)
+bool convRecWideDx(const hl_learner* h) { return h->convTm && (h->hid[1].nIn > 1024 || (h->generic & 2048)); }
 // `sampleC`: the index search of the NEXT minibatch (sampler phase C; recurrent nets) rides the weight-gradient launch
 // `skipDx`: the input gradients were taken by the launch in front (gemm16.hip: step_chain_kernel): the weight gradients and their riders only
 int launchBackward(hl_learner* h, int parity, bool fuseAdam, hipStream_t s, bool fusePost = false, int postMode = POST_AGG | POST_BETA, bool sampleC = false, bool skipDx = false) {
@@ -574,6 +577,12 @@ int launchBackward(hl_learner* h, int parity, bool fuseAdam, hipStream_t s, bool
     snprintf(nm, sizeof(nm), "gemm16_dx%d", h->nHidden - 1 - (int)i);
     const int jx = h->recurrent ? 1 : h->nHidden - 1 - (int)i;          // problem i back-propagates through block jx: reduction over its outputs
     const int Kx = h->recurrent ? std::max(h->hid[jx].lstm, 1) * h->hid[jx].size : h->hid[jx].size;      // (recurrent layer under a conv stack: over its gates)
+    // recurrent layers behind convolutions on the time-step-major route: a feature row beyond the 1024 floats GEMM_X serves (or bit 2048)
+    // (these nets step eagerly: the launch takes no rider)
+    if (convRecWideDx(h)) {
+      if (pex) return fail(h, HL_ERR_STATE, "no rider slot on the input-gradient launch of recurrent layers behind convolutions");
+      HIPCK(timed(h, nm, s, [&] { return launch_tm_conv_dx(h->hostProbs[sb.dxIdx[i]], s); }));      // (the same problem under the same counter)
+    } else
     if ((h->bigMm & 4) && !pex && big_mm_ok(h->hostProbs[sb.dxIdx[i]]))
       HIPCK(timed(h, nm, s, [&] { return launch_big_mm(h->hostProbs[sb.dxIdx[i]], h->sc, parity, s); }));
     else
@@ -873,6 +882,7 @@ int launchMlp(hl_learner* h, int parity, bool fuseAdam, hipStream_t s) {
       }
     }
     if (ra.tmP && rec_tm_ok(ra)) {      // wide inputs: the same launches in the same order, the product timed apart from the chain (tools/wide_in_timing.py)
+      // (behind convolutions the prepare launch is the join: it copies the feature rows into the first layer's operand rows)
       HIPCK(timed(h, "rec_prepare", s, [&] { return launch_rec_tm_forward(ra, s, TM_PART_PREPARE); }));
       HIPCK(timed(h, "rec_in_product", s, [&] { return launch_rec_tm_forward(ra, s, TM_PART_PRODUCT); }));
       HIPCK(timed(h, "rec_forward", s, [&] { return launch_rec_tm_forward(ra, s, TM_PART_CHAIN); }));
