@@ -386,4 +386,20 @@ def assert_columns(got, ref, tol, what=None, ref32=None, cpu_bar=False):
         assert v == "zero" or v < bar, (what, c, v, bar, e_cpu[c])
 
 
+def conv_rec_dx_call(L):
+    """the development entry hl_debug_conv_rec_dx of learner L's library, with its argument types"""
+    import ctypes as C
+    f = L.api.lib.hl_debug_conv_rec_dx
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    return f
+
+
+def conv_rec_dx_form(L):
+    """(1 where tm_conv_dx_kernel forms the gradient into the feature rows, 0 where the GEMM_X problem does; 1 where the net runs time-step-major)"""
+    import ctypes as C
+    dims = (C.c_int32 * 2)()
+    L._ck(conv_rec_dx_call(L)(L.h, 4, None, 0, dims))
+    return dims[0], dims[1]
+
+
 COL_ROWS = 16      # a column's scale is taken over a batch: calls of fewer rows are left to the row-wise checks

@@ -15,38 +15,23 @@ import pytest
 
 from smarties_amd import capi
 from oracle_api import synth_cfg, fill_synth
+from blocks import CONV2, CONV2_EXTRA, CONV_1331, conv_rec_kw      # (the geometries and the configuration: tests/blocks.py steps them per block)
 from parity import COL_ROWS, assert_columns, relinf
+from parity import conv_rec_dx_call as _dx_call, conv_rec_dx_form as _dx_form
 from test_hip_parity import hip_learner, _pair, _compare_step, TOL32
 
 pytestmark = pytest.mark.gpu
 
 NN = {"lstm": capi.NN_LSTM, "mgu": capi.NN_MGU, "rnn": capi.NN_RNN}
-CONV2 = [(8, 8, 16, 32, 4, 1), (5, 5, 32, 64, 3, 1)]           # 1 + 3 stacked frames of 256 as 16 channels of 8 x 8: a feature row of 576
-CONV2_EXTRA = [(8, 8, 12, 32, 4, 1), (5, 5, 32, 64, 3, 1)]     # 1 + 2 stacked frames of 258: 768 for the image, 6 state variables beside it
-CONV_1331 = [(13, 13, 2, 11, 3, 1)]                            # 338 = 2 x 13 x 13 -> 11 maps of 11 x 11: 1331 floats, odd, no multiple of 32
 BPTT, BATCH = 4, 12
 
 
 def _config(kind, hidden, conv, dS, nApp):
-    return dict(dimS=dS, dimA=1, adv_kind=capi.ADV_DISCRETE, n_options=5, nAppendedObs=nApp, conv=conv, hidden=hidden, nnFunc="Tanh",
-                batchSize=BATCH, maxTotObsNum=2000, randSeed=3, nn_type=NN[kind], nnBPTTseq=BPTT)
+    return conv_rec_kw(NN[kind], hidden, conv, dS, nApp, batch=BATCH, bptt=BPTT)
 
 
 def _counts(G, names):
     return {n: G.timing_get(n)[1] for n in names}
-
-
-def _dx_call(L):
-    f = L.api.lib.hl_debug_conv_rec_dx
-    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
-    return f
-
-
-def _dx_form(L):
-    """(1 where tm_conv_dx_kernel forms the gradient into the feature rows, 0 where the GEMM_X problem does; 1 where the net runs time-step-major)"""
-    dims = (C.c_int32 * 2)()
-    L._ck(_dx_call(L)(L.h, 4, None, 0, dims))
-    return dims[0], dims[1]
 
 
 def _steps_and_acting_match_the_restatement(hip_api, kind, hidden, conv, dS, nApp, wide_dx):
