@@ -84,6 +84,14 @@ class HlStats(C.Structure):
                 ("sumReturnsEstimateErrors", C.c_double)]
 
 
+class RolloutCounts(C.Structure):      # hl_rollout_counts (include/smarties_hip_rollout.h)
+    _fields_ = [("calls", C.c_int64), ("episodes", C.c_int64), ("steps", C.c_int64), ("capped", C.c_int64), ("no_room", C.c_int64)]
+
+
+ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2      # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
+ROLLOUT_MAX_ENV = 65536
+
+
 def make_config(dimS=17, dimA=6, bounded=None, hidden=(256, 256), nnFunc="SoftSign", batchSize=256,
                 maxTotObsNum=1000000, minTotObsNum=0, gamma=0.995, lambda_=1.0, clipImpWeight=4.0,
                 penalTol=0.1, epsAnneal=0.0, learnrate=1e-4, nnLambda=0.0, explNoise=0.4472135955,
@@ -226,6 +234,13 @@ class CApi:
             "policy_snapshot": (C.c_int, [P]),
             "policy_snapshot_info": (C.c_int, [P, pi64, pi64]),
             "act_dev_source": (C.c_int, [P, I32]),
+            # include/smarties_hip_rollout.h (product library only)
+            "rollout_create": (C.c_int, [P, I32, I32, C.c_uint64, I64, C.POINTER(P)]),
+            "rollout_destroy": (C.c_int, [P]),
+            "rollout_step": (C.c_int, [P, P, P, P, P, I32, P, P]),
+            "rollout_info": (C.c_int, [P, C.POINTER(RolloutCounts)]),
+            "rollout_read": (C.c_int, [P, I32, pi32, pf, pd, pd, pd, pf, pf]),
+            "rollout_noise": (C.c_int, [C.c_uint64, I32, I64, I32, I32, I32, pd]),
             "save": (C.c_int, [P, C.c_char_p]),
             "metrics": (C.c_int, [P, C.c_char_p, I32, C.c_char_p, I32]),
             "grad_stats": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -284,6 +299,8 @@ class Learner:
 
     def close(self):
         if self.h:
+            for r in list(getattr(self, "_rollouts", ())):      # hl_destroy destroys the rollouts still open: their handles are dead
+                r.h = C.c_void_p()
             self.api.fn("destroy")(self.h)
             self.h = C.c_void_p()
 
@@ -626,6 +643,12 @@ class Learner:
             raise ValueError('act_source: "live" or "snapshot", not %r' % (source,))
         self._ck(self.api.fn("act_dev_source")(self.h, code))
 
+    # -- a vectorised simulator on the learner's GPU (include/smarties_hip_rollout.h) ----------
+    def rollout(self, n_env, max_steps, seed=0, tag_base=0):
+        """hl_rollout_create: a rollout buffer of n_env environments with episodes of at most max_steps states, driven by one
+        Rollout.step per simulator step.  Closing the learner closes it."""
+        return Rollout(self, n_env, max_steps, seed, tag_base)
+
     def set_episode_log(self, path):
         self._ck(self.api.fn("set_episode_log")(self.h, str(path).encode() if path else None))
 
@@ -721,8 +744,80 @@ class Learner:
         return us.value
 
 
+class Rollout:
+    """One hl_rollout handle (include/smarties_hip_rollout.h): the episodes in flight of n_env environments in device memory."""
+
+    def __init__(self, learner, n_env, max_steps, seed=0, tag_base=0):
+        self.L, self.api, self.n_env, self.max_steps = learner, learner.api, int(n_env), int(max_steps)
+        self.h = C.c_void_p()
+        learner._ck(self.api.fn("rollout_create")(learner.h, self.n_env, self.max_steps, int(seed), int(tag_base), C.byref(self.h)))
+        if not hasattr(learner, "_rollouts"):
+            learner._rollouts = weakref.WeakSet()
+        learner._rollouts.add(self)
+
+    def _open(self):
+        if not self.h:
+            raise ValueError("the rollout is closed")
+
+    def close(self):
+        if self.h:
+            self.api.fn("rollout_destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, states, rewards, end, noise=None, evaluate=False, store=True, out=None, stream=None):
+        """hl_rollout_step: `states` [n_env][dimS] float32, `rewards` [n_env] float64, `end` [n_env] int32 (0 running, 1 terminal,
+        2 truncated) on the GPU; `noise` None (the library's generator) or [n_env][dimA] float64 clipped normal deviates ([n_env] uniforms
+        for the discrete head); evaluate: the evaluation action, no noise; store=False: finished episodes are not ingested.  Returns (or
+        fills `out` with) the actions [n_env][dimA] float64 on the GPU, valid in `stream`'s order."""
+        self._open()
+        L, n = self.L, self.n_env
+        if out is None:
+            import torch
+            out = torch.empty((n, L.dA), dtype=torch.float64, device=states.device)
+        n_noise = n if L.nOptions else n * L.dA
+        flags = (ROLLOUT_EVALUATE if evaluate else 0) | (0 if store else ROLLOUT_NO_STORE)
+        L._ck(self.api.fn("rollout_step")(
+            self.h, L._dev(states, "f32", n * L.dS, "states"), L._dev(rewards, "f64", n, "rewards"), L._dev(end, "i32", n, "end"),
+            L._dev(noise, "f64", n_noise, "noise", optional=True), flags, L._dev(out, "f64", n * L.dA, "out"), L._stream(stream)))
+        return out
+
+    def info(self):
+        """hl_rollout_info as a dict: calls, episodes, steps, capped, no_room (host-side, no device wait)"""
+        self._open()
+        c = RolloutCounts()
+        self.L._ck(self.api.fn("rollout_info")(self.h, C.byref(c)))
+        return {k: int(getattr(c, k)) for k, _ in RolloutCounts._fields_}
+
+    def read(self, env):
+        """hl_rollout_read (waits for the stream): (states of the episode in flight, the slab's max_steps rows of states, actions, mu,
+        rewards, values, advantages)"""
+        self._open()
+        L, T = self.L, self.max_steps
+        n = C.c_int32()
+        S, A, MU = np.zeros((T, L.dS), np.float32), np.zeros((T, L.dA), np.float64), np.zeros((T, L.polDim), np.float64)
+        R, V, ADV = np.zeros(T, np.float64), np.zeros(T, np.float32), np.zeros(T, np.float32)
+        L._ck(self.api.fn("rollout_read")(self.h, int(env), C.byref(n), _ptr(S, C.c_float), _ptr(A, C.c_double), _ptr(MU, C.c_double),
+                                          _ptr(R, C.c_double), _ptr(V, C.c_float), _ptr(ADV, C.c_float)))
+        return int(n.value), S, A, MU, R, V, ADV
+
+
+def rollout_noise(api, seed, env, episode, t, component, discrete=False):
+    """hl_rollout_noise: the library's draw for (seed, env, episode, t, component), evaluated on the host"""
+    out = C.c_double()
+    rc = api.fn("rollout_noise")(int(seed), int(env), int(episode), int(t), int(component), 1 if discrete else 0, C.byref(out))
+    if rc:
+        raise HlError(rc, "hl_rollout_noise")
+    return out.value
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-HIP_LIB = os.path.join(_HERE, "libsmarties_hip.so")
+HIP_LIB =os.path.join(_HERE, "libsmarties_hip.so")
 
 
 _hip_api = None

@@ -514,5 +514,32 @@ struct HistArgs { DevReplay rp; int nEpisodes; float bounds[82]; unsigned long l
 hipError_t launch_impw_hist(const HistArgs& a, hipStream_t s);
 int sweep_blocks(int count);
 int moments_blocks(int nEpisodes);
+// the rollout buffer of hl_rollout_step (rollout.hip; include/smarties_hip_rollout.h): one slab of maxSteps rows per environment, row
+// env * maxSteps + t state t of its episode in flight, in the types hl_append_episodes_dev takes.
+// rollout_book_kernel: the state and reward row at t = len[env], the two window tables, the environments that ended compacted in ascending
+// order into the mapped pinned block `host`: [0] the call's stamp, [1] episodes in the table, [2] of them closed by the cap, [3] unused, then
+// (env, states, kind) per episode.  kind: 1 terminal, 2 truncated by the environment, 3 closed by the cap
+constexpr int ROLLOUT_MAX_ENV = 65536, ROLLOUT_HOST_HEAD = 4, ROLLOUT_BLOCK = 1024;
+struct RolloutBookArgs {
+  const float* states; const double* rewards; const int* end;      // the caller's [nEnv][dS], [nEnv], [nEnv]
+  float* S; double* R; const int* len;
+  long long* firstRow; int* nSteps; int* kind;                     // [nEnv] each: the window tables, what the state did to the episode
+  int* host; unsigned tag;
+  int nEnv, maxSteps, dS;
+};
+hipError_t launch_rollout_book(const RolloutBookArgs& a, hipStream_t s);
+// rollout_noise_kernel: the library's action noise (rollout_rng.h) of every environment's current (episode, step): [nEnv][dA] clipped normal
+// deviates, or (discrete) [nEnv] uniforms
+struct RolloutNoiseArgs { double* noise; const int* nSteps; const int* episode; unsigned long long seed; int nEnv, dA, discrete; };
+hipError_t launch_rollout_noise(const RolloutNoiseArgs& a, hipStream_t s);
+// rollout_store_kernel: the head's results [nEnv] rows into row t of the slabs and the action to the caller; an environment whose state
+// ended its episode gets the terminal row, zeros as its action, len = 0 and its episode count advanced; every other one len = t + 1
+struct RolloutStoreArgs {
+  const double* act; const double* mu; const float* v; const float* adv;      // the head's outputs, contiguous
+  double* A; double* MU; float* V; float* ADV; double* outAct;
+  int* len; int* episode; const int* nSteps; const int* kind;
+  int nEnv, maxSteps, dA, polDim;
+};
+hipError_t launch_rollout_store(const RolloutStoreArgs& a, hipStream_t s);
 
 }  // namespace hl

@@ -452,6 +452,7 @@ int hl_destroy(hl_learner* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->sideStream) hipStreamSynchronize(h->sideStream);
   actSnapSync(h);      // the acting stream of the snapshot source (learner_dev.h)
+  rolloutReleaseAll(h);      // the rollout buffers still open (learner_rollout.h)
   timerFlush(h);
   actSnapRelease(h);
   invalidateGraphs(h);
@@ -964,6 +965,7 @@ int hl_step_end(hl_learner* h) {
 #include "learner_io.h"
 #include "learner_act.h"
 #include "learner_dev.h"
+#include "learner_rollout.h"
 
 int hl_sync(hl_learner* h) {
   if (!h) return HL_ERR_BAD_ARG;

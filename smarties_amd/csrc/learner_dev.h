@@ -169,7 +169,8 @@ static int devHead(hl_learner* h, const DevCtx& d, int n, const double* O, const
 // here; the stamp block of the dense kernels; n == 0; row_stride; the library's buffers -- between a window call's two launches the
 // stacked rows of a dense net or the feature rows behind convolutions, in front of the head the outputs --; the handshake with the
 // caller's stream around the launches
-static int devAct(hl_learner* h, const char* who, int n, const float* in, const DevWindows* w, double* out, const DevHeadIo* head, void* stream) {
+// `handshake` false (learner_rollout.h): the caller has done devEnter on the live source and does devLeave behind its own launches
+static int devAct(hl_learner* h, const char* who, int n, const float* in, const DevWindows* w, double* out, const DevHeadIo* head, void* stream, bool handshake = true) {
   HL_LOCK(h);
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   const ActRoutes& r = actResolve(h);
@@ -183,10 +184,52 @@ static int devAct(hl_learner* h, const char* who, int n, const float* in, const 
   if (w && r.devSeq == ACT_DEV_SEQ_CONV) { int rc = devEnsure(h, d.st, d.feat, d.featCap, (size_t)n * r.devConv->nF); if (rc) return rc; }
   if (w && r.devSeq == ACT_DEV_SEQ_ROWS) { int rc = devEnsure(h, d.st, d.rows, d.rowsCap, (size_t)n * h->dIn); if (rc) return rc; }
   if (head) { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; out = *d.out; }
-  { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  if (handshake) { int rc = devEnter(h, d, stream); if (rc) return rc; }
   { int rc = w ? devSeqForward(h, r, d, n, *w, in, out) : devForward(h, r, d, n, in, out); if (rc) return rc; }
   if (head) { int rc = devHead(h, d, n, out, *head); if (rc) return rc; }
-  return devLeave(h, d, stream);
+  return handshake ? devLeave(h, d, stream) : HL_OK;
+}
+// The one body of hl_append_episodes_dev and of hl_rollout_step's ingestion, behind their argument checks: nEp > 0 episodes, every one of
+// at least 2 steps.  *nBooked (where given) is set once the launches are out: the episodes stored, the ones behind them found no room
+static int devIngest(hl_learner* h, int nEp, const int32_t* nsteps, const int32_t* terminated, const int64_t* tags, const int64_t* first_row,
+                     int64_t row_stride, const float* dStates, const double* dActions, const double* dMu, const double* dRewards,
+                     const float* dValues, const float* dAdvantages, void* stream, bool handshake = true, int* nBooked = nullptr) {
+  { int rc = flushStaging(h); if (rc) return rc; }      // episodes staged by hl_append_episode go first
+  const bool log = !h->episodeLog.empty();
+  const DevCtx d = devCtx(h, HL_ACT_LIVE);      // (ingestion writes the replay the steps read: the learner's stream whatever the acting source)
+  if (log) { int rc = devEnsure(h, h->stream, &h->act.devSums, &h->act.devSumsCap, (size_t)2 * nEp); if (rc) return rc; }
+  if (handshake) { int rc = devEnter(h, d, stream); if (rc) return rc; }
+  // the bookkeeping of hl_append_episode, episode by episode; an episode that finds no room ends the batch, the ones before it are stored
+  std::vector<long long> ids((size_t)nEp);
+  int booked = 0, rcBook = HL_OK;
+  for (; booked < nEp; ++booked) {
+    long long off = 0; int eid = 0;
+    rcBook = appendAlloc(h, nsteps[booked], &off, &eid); if (rcBook) break;
+    ids[(size_t)booked] = appendBook(h, eid, off, nsteps[booked], terminated[booked] != 0, tags[booked]);
+  }
+  // (a later episode's allocation may have re-packed the replay: the slot offsets are read from the order now; episode e sits at position booked - 1 - e)
+  { int rc = refreshInsertionStats(h); if (rc) return rc; }
+  for (int e0 = 0; e0 < booked; e0 += INGEST_DEV_MAX_EP) {
+    IngestDevArgs ia{};
+    ia.rp = h->rp; ia.S = dStates; ia.A = dActions; ia.MU = dMu; ia.R = dRewards; ia.V = dValues; ia.ADV = dAdvantages;
+    ia.rowStride = row_stride; ia.nEp = std::min(INGEST_DEV_MAX_EP, booked - e0); ia.dS = h->dS; ia.dA = h->dA; ia.polDim = h->polDim;
+    ia.stats = h->dStatsIns; ia.nEpTable = h->anyStep ? h->tableCount : 0;
+    ia.sums = log ? h->act.devSums + (size_t)2 * e0 : nullptr;
+    for (int k = 0; k < ia.nEp; ++k) {
+      const EpMeta& m = h->order[(size_t)(booked - 1 - (e0 + k))];
+      ia.d[k] = IngestDevDesc{m.off, m.tag, first_row[e0 + k], m.N, m.eid, m.term ? 1 : 0, 0};
+    }
+    HIPCK(timed(h, "ingest_dev_kernel", h->stream, [&] { return launch_ingest_dev(ia, h->stream); }));
+  }
+  if (handshake) { int rc = devLeave(h, d, stream); if (rc) return rc; }
+  if (log && booked > 0) {
+    std::vector<double> sums((size_t)2 * booked);
+    HIPCK(hipMemcpyAsync(sums.data(), h->act.devSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    for (int e = 0; e < booked && !h->episodeLog.empty(); ++e) appendLogLine(h, ids[(size_t)e], nsteps[e], (float)sums[(size_t)2 * e + 1]);
+  }
+  if (nBooked) *nBooked = booked;
+  return rcBook;
 }
 }  // extern "C++"
 
@@ -268,39 +311,5 @@ int hl_append_episodes_dev(hl_learner* h, int32_t nEp, const int32_t* nsteps, co
     if (first_row[e] < 0) return fail(h, HL_ERR_BAD_ARG, "hl_append_episodes_dev: a negative first row");
   }
   if (nEp == 0) return HL_OK;
-  { int rc = flushStaging(h); if (rc) return rc; }      // episodes staged by hl_append_episode go first
-  const bool log = !h->episodeLog.empty();
-  const DevCtx d = devCtx(h, HL_ACT_LIVE);      // (ingestion writes the replay the steps read: the learner's stream whatever the acting source)
-  if (log) { int rc = devEnsure(h, h->stream, &h->act.devSums, &h->act.devSumsCap, (size_t)2 * nEp); if (rc) return rc; }
-  { int rc = devEnter(h, d, stream); if (rc) return rc; }
-  // the bookkeeping of hl_append_episode, episode by episode; an episode that finds no room ends the batch, the ones before it are stored
-  std::vector<long long> ids((size_t)nEp);
-  int booked = 0, rcBook = HL_OK;
-  for (; booked < nEp; ++booked) {
-    long long off = 0; int eid = 0;
-    rcBook = appendAlloc(h, nsteps[booked], &off, &eid); if (rcBook) break;
-    ids[(size_t)booked] = appendBook(h, eid, off, nsteps[booked], terminated[booked] != 0, tags[booked]);
-  }
-  // (a later episode's allocation may have re-packed the replay: the slot offsets are read from the order now; episode e sits at position booked - 1 - e)
-  { int rc = refreshInsertionStats(h); if (rc) return rc; }
-  for (int e0 = 0; e0 < booked; e0 += INGEST_DEV_MAX_EP) {
-    IngestDevArgs ia{};
-    ia.rp = h->rp; ia.S = dStates; ia.A = dActions; ia.MU = dMu; ia.R = dRewards; ia.V = dValues; ia.ADV = dAdvantages;
-    ia.rowStride = row_stride; ia.nEp = std::min(INGEST_DEV_MAX_EP, booked - e0); ia.dS = h->dS; ia.dA = h->dA; ia.polDim = h->polDim;
-    ia.stats = h->dStatsIns; ia.nEpTable = h->anyStep ? h->tableCount : 0;
-    ia.sums = log ? h->act.devSums + (size_t)2 * e0 : nullptr;
-    for (int k = 0; k < ia.nEp; ++k) {
-      const EpMeta& m = h->order[(size_t)(booked - 1 - (e0 + k))];
-      ia.d[k] = IngestDevDesc{m.off, m.tag, first_row[e0 + k], m.N, m.eid, m.term ? 1 : 0, 0};
-    }
-    HIPCK(timed(h, "ingest_dev_kernel", h->stream, [&] { return launch_ingest_dev(ia, h->stream); }));
-  }
-  { int rc = devLeave(h, d, stream); if (rc) return rc; }
-  if (log && booked > 0) {
-    std::vector<double> sums((size_t)2 * booked);
-    HIPCK(hipMemcpyAsync(sums.data(), h->act.devSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    for (int e = 0; e < booked && !h->episodeLog.empty(); ++e) appendLogLine(h, ids[(size_t)e], nsteps[e], (float)sums[(size_t)2 * e + 1]);
-  }
-  return rcBook;
+  return devIngest(h, nEp, nsteps, terminated, tags, first_row, row_stride, dStates, dActions, dMu, dRewards, dValues, dAdvantages, stream);
 }

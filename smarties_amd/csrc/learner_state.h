@@ -174,6 +174,7 @@ struct hl_learner {
   // 0 before the first step.  Computed on the device when needed (dStatsIns), at most once per step.
   double* dStatsIns = nullptr; bool statsFresh = false, anyStep = false;
   ActState act;      // rollout inference (learner_act.h)
+  std::vector<struct hl_rollout*> rollouts;      // the rollout buffers still open (learner_rollout.h): hl_destroy destroys them
   // prioritised samplers (per.hip): probabilities / cumulative table of the stored transitions, rebuilt before every minibatch
   float *perProb = nullptr, *perKey = nullptr, *perKeyS = nullptr; double* perCp = nullptr; unsigned *perIdx = nullptr, *perIdxS = nullptr; void* perScan = nullptr; size_t perScanBytes = 0;
   void* perTemp = nullptr; size_t perTempBytes = 0; long long perCap = 0;
@@ -332,6 +333,7 @@ void timerFlush(hl_learner* h) {
   h->trecs.clear();
 }
 // hl_destroy: the acting stream drained (call before timerFlush), then its events, the snapshot buffers, the scratch set and the stream
+void rolloutReleaseAll(hl_learner* h);      // (learner_rollout.h; hl_destroy, behind its wait for the learner's stream)
 void actSnapSync(hl_learner* h) { if (h->act.snapStream) hipStreamSynchronize(h->act.snapStream); }
 void actSnapRelease(hl_learner* h) {
   ActState& s = h->act;
