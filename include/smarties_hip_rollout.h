@@ -89,7 +89,7 @@ enum { HL_ROLLOUT_EVALUATE = 1, HL_ROLLOUT_NO_STORE = 2 };
  * ones left are dropped and counted (hl_rollout_counts::no_room), hl_last_error keeps the reason, the call returns HL_OK.
  * Status: HL_ERR_BAD_ARG for a null handle or array; HL_ERR_STATE between hl_step_begin and hl_step_end; HL_ERR_UNSUPPORTED, with a
  * message naming HL_ACT_LIVE, while the acting source is HL_ACT_SNAPSHOT: the rollout writes the buffer the ingestion reads on the
- * learner's stream.
+ * learner's stream.  (A rollout given a staging ring, hl_rollout_staging below, is served under that source.)
  *
  * Timing (tools/rollout_timing.py, profiles/rollout_timing.json): see DESIGN.md 4.4 for the figures of that file. */
 HL_API int hl_rollout_step(hl_rollout* r, const float* dStates, const double* dRewards, const int32_t* dEnd, const double* dNoise,
@@ -97,6 +97,47 @@ HL_API int hl_rollout_step(hl_rollout* r, const float* dStates, const double* dR
 
 /* the host-side numbers so far; no device wait */
 HL_API int hl_rollout_info(hl_rollout* r, hl_rollout_counts* out);
+
+/* ---- hl_rollout_step beside queued gradient steps: the staging ring ----
+ * Gives the rollout a staging ring of `rows` rows in device memory (states f32, actions and policies f64, rewards f64, values and
+ * advantages f32: the slab's types).  From then on hl_rollout_step serves HL_ACT_SNAPSHOT too.
+ *
+ * Under HL_ACT_SNAPSHOT the call runs on the acting stream (include/smarties_hip_dev.h: hl_act_dev_source) from the current snapshot: the
+ * bookkeeping kernel, the noise, the acting launches and the store kernel are enqueued there, the caller's stream waits for exactly
+ * these, and the one host poll waits for the acting stream only -- not for the gradient steps queued on the learner's.  The episodes
+ * that ended leave their slabs on the acting stream, before the slabs are reused: rollout_stage_kernel copies them into the ring, in
+ * batches of at most 64 episodes (one ingest launch) and at most rows / 2 rows, each batch one contiguous region; a batch that does not
+ * fit between the head and the ring's end starts again at row 0.  The learner's stream waits for the batch's copy, runs
+ * hl_append_episodes_dev's launch on the ring's rows -- whenever the steps queued there let it -- and records the region's `consumed`
+ * event.  A region is written again only behind that event: the host QUERIES it and, where it has not completed, makes the acting
+ * stream wait for it (a stall; it delays the next call's bookkeeping kernel -- and so that call's host poll: the ring bounds how far the
+ * rollout runs ahead of a backlog --, never this call's actions).  The host never blocks on the ring.  Order, tags, the terminal row and hl_rollout_counts are the live call's; an episode that finds no room ends the call's
+ * hand-off, later batches of that call are not staged, the rest is counted in no_room.
+ * A ring that holds the episodes ending between two bursts of queued steps never stalls: rows >= (episodes per burst) * maxSteps.
+ * Under HL_ACT_LIVE a rollout with a ring behaves like one without: direct ingestion from the slabs, no staging launch, the counters
+ * below untouched.  A rollout without a ring is refused under HL_ACT_SNAPSHOT as before.  The source may change with episodes in flight:
+ * the first call on the other stream waits for an event behind everything the last call enqueued.
+ * Known limits: hl_step after new episodes still waits for the learner's stream when it uploads the episode table; with
+ * hl_set_episode_log on, the ingestion reads the episodes' sums back behind the queued steps; a replay memory that has to grow for an
+ * episode waits for the learner's stream as it does in every appending call.
+ * Status: HL_ERR_BAD_ARG for a null handle (checked without a device), rows < 2 * maxSteps or rows >= 2^31; HL_ERR_STATE if the rollout
+ * already has a ring; HL_ERR_UNSUPPORTED, with a message naming HL_ACT_LIVE, for a net whose window route the snapshot source refuses
+ * (recurrent nets on wide inputs); HL_ERR_HIP, with the byte count in the message, if the ring cannot be allocated.
+ * hl_rollout_step under HL_ACT_SNAPSHOT, before its first launch: HL_ERR_STATE naming hl_policy_snapshot before any snapshot exists;
+ * HL_ERR_STATE between hl_step_begin and hl_step_end.
+ * hl_rollout_read and hl_rollout_destroy of a rollout with a ring wait for both streams.
+ * Timing (tools/rollout_snapshot_timing.py, profiles/rollout_snapshot_timing.json): see DESIGN.md 4.4. */
+HL_API int hl_rollout_staging(hl_rollout* r, int64_t rows);
+
+typedef struct hl_rollout_stage_counts {
+  int64_t capacity;   /* rows of the ring (0: none) */
+  int64_t batches;    /* staging launches so far */
+  int64_t episodes;   /* episodes copied into the ring */
+  int64_t rows;       /* ... and their rows */
+  int64_t wraps;      /* batches that started again at row 0 */
+  int64_t stalls;     /* batches whose region was not yet consumed when the host queried its event: the acting stream was made to wait */
+} hl_rollout_stage_counts;
+HL_API int hl_rollout_stage_info(hl_rollout* r, hl_rollout_stage_counts* out);   /* host numbers, no device wait */
 
 /* Diagnostics and tests (waits for the learner's stream): environment env's slab as it is.  *nStates: states of its episode in flight;
  * every array, each optional (NULL), receives ALL maxSteps rows of the slab -- rows below *nStates belong to the episode in flight, the

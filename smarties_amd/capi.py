@@ -88,7 +88,12 @@ class RolloutCounts(C.Structure):      # hl_rollout_counts (include/smarties_hip
     _fields_ = [("calls", C.c_int64), ("episodes", C.c_int64), ("steps", C.c_int64), ("capped", C.c_int64), ("no_room", C.c_int64)]
 
 
-ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2      # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
+class RolloutStageCounts(C.Structure):      # hl_rollout_stage_counts (include/smarties_hip_rollout.h)
+    _fields_ = [("capacity", C.c_int64), ("batches", C.c_int64), ("episodes", C.c_int64), ("rows", C.c_int64), ("wraps", C.c_int64),
+                ("stalls", C.c_int64)]
+
+
+ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2     # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
 ROLLOUT_MAX_ENV = 65536
 
 
@@ -241,6 +246,8 @@ class CApi:
             "rollout_info": (C.c_int, [P, C.POINTER(RolloutCounts)]),
             "rollout_read": (C.c_int, [P, I32, pi32, pf, pd, pd, pd, pf, pf]),
             "rollout_noise": (C.c_int, [C.c_uint64, I32, I64, I32, I32, I32, pd]),
+            "rollout_staging": (C.c_int, [P, I64]),
+            "rollout_stage_info": (C.c_int, [P, C.POINTER(RolloutStageCounts)]),
             "save": (C.c_int, [P, C.c_char_p]),
             "metrics": (C.c_int, [P, C.c_char_p, I32, C.c_char_p, I32]),
             "grad_stats": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -644,10 +651,14 @@ class Learner:
         self._ck(self.api.fn("act_dev_source")(self.h, code))
 
     # -- a vectorised simulator on the learner's GPU (include/smarties_hip_rollout.h) ----------
-    def rollout(self, n_env, max_steps, seed=0, tag_base=0):
+    def rollout(self, n_env, max_steps, seed=0, tag_base=0, staging_rows=None):
         """hl_rollout_create: a rollout buffer of n_env environments with episodes of at most max_steps states, driven by one
-        Rollout.step per simulator step.  Closing the learner closes it."""
-        return Rollout(self, n_env, max_steps, seed, tag_base)
+        Rollout.step per simulator step.  staging_rows: hl_rollout_staging with that many rows, so that the rollout runs under the
+        snapshot source too.  Closing the learner closes it."""
+        r = Rollout(self, n_env, max_steps, seed, tag_base)
+        if staging_rows is not None:
+            r.staging(staging_rows)
+        return r
 
     def set_episode_log(self, path):
         self._ck(self.api.fn("set_episode_log")(self.h, str(path).encode() if path else None))
@@ -761,7 +772,10 @@ class Rollout:
 
     def close(self):
         if self.h:
-            self.api.fn("rollout_destroy")(self.h)
+            # (hl_destroy of the learner has destroyed the rollouts still open.  Learner.close clears their handles through a weak set, which
+            # the garbage collector empties BEFORE it finalises a learner and its rollouts found unreachable together: ask the learner itself)
+            if self.L.h:
+                self.api.fn("rollout_destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -793,6 +807,18 @@ class Rollout:
         c = RolloutCounts()
         self.L._ck(self.api.fn("rollout_info")(self.h, C.byref(c)))
         return {k: int(getattr(c, k)) for k, _ in RolloutCounts._fields_}
+
+    def staging(self, rows):
+        """hl_rollout_staging: a staging ring of `rows` rows (at least 2 max_steps); from then on step() serves act_source("snapshot")"""
+        self._open()
+        self.L._ck(self.api.fn("rollout_staging")(self.h, int(rows)))
+
+    def stage_info(self):
+        """hl_rollout_stage_info as a dict: capacity, batches, episodes, rows, wraps, stalls (host-side, no device wait)"""
+        self._open()
+        c = RolloutStageCounts()
+        self.L._ck(self.api.fn("rollout_stage_info")(self.h, C.byref(c)))
+        return {k: int(getattr(c, k)) for k, _ in RolloutStageCounts._fields_}
 
     def read(self, env):
         """hl_rollout_read (waits for the stream): (states of the episode in flight, the slab's max_steps rows of states, actions, mu,

@@ -541,5 +541,18 @@ struct RolloutStoreArgs {
   int nEnv, maxSteps, dA, polDim;
 };
 hipError_t launch_rollout_store(const RolloutStoreArgs& a, hipStream_t s);
+// rollout_stage_kernel: the ended episodes of one batch out of their slabs into the staging ring (hl_rollout_staging): rows
+// env * maxSteps + t, t < nsteps, of the six slabs into rows dst + t of the ring's six arrays.  The batch table travels BY VALUE in the
+// kernel arguments: a launch the acting stream holds back behind a region's `consumed` event reads it after the host has gone on
+constexpr int ROLLOUT_STAGE_MAX_EP = 64;
+struct RolloutStageEp { int env, nsteps; long long dst; };
+struct RolloutStageArgs {
+  const float* S; const double* A; const double* MU; const double* R; const float* V; const float* ADV;      // the slabs
+  float* rS; double* rA; double* rMU; double* rR; float* rV; float* rADV;                                    // the ring
+  long long ringRows;
+  int nEnv, maxSteps, dS, dA, polDim, nEp;
+  RolloutStageEp ep[ROLLOUT_STAGE_MAX_EP];
+};
+hipError_t launch_rollout_stage(const RolloutStageArgs& a, hipStream_t s);
 
 }  // namespace hl

@@ -16,16 +16,17 @@ static int actCus(hl_learner* h) {
   return h->act.cus;
 }
 // the kernel stamps a row once its outputs are in host memory: poll the stamps (a stream synchronisation costs ~10 us more),
-// give up after 2 s and fall back to it
-static int actWait(hl_learner* h, volatile unsigned* pDone, int n, unsigned tag) {
+// give up after 2 s and fall back to it.  `st`: the stream the stamping kernel runs on
+static int actWaitOn(hl_learner* h, hipStream_t st, volatile unsigned* pDone, int n, unsigned tag) {
   const auto t0 = std::chrono::steady_clock::now();
   for (int r = 0; r < n; ++r)
     while (pDone[r] != tag) {
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { HIPCK(hipStreamSynchronize(h->stream)); break; }
+      if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { HIPCK(hipStreamSynchronize(st)); break; }
     }
   std::atomic_thread_fence(std::memory_order_acquire);
   return HL_OK;
 }
+static int actWait(hl_learner* h, volatile unsigned* pDone, int n, unsigned tag) { return actWaitOn(h, h->stream, pDone, n, tag); }
 // the output layer on the first `rows` rows of the last hidden layer's activations; done != nullptr: the rows' stamps
 static hipError_t actOutput(hl_learner* h, int rows, double* out, volatile unsigned* done, unsigned tag) {
   const DevHidden& q = h->hid[h->nHidden - 1];

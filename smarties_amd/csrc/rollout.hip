@@ -1,5 +1,5 @@
 // smarties_amd/csrc/rollout.hip -- the bookkeeping of a vectorised simulator's rollouts on the device (include/smarties_hip_rollout.h:
-// hl_rollout_step).  The forward pass, the action head and the ingestion are the existing launches (learner_dev.h); the three kernels here
+// hl_rollout_step).  The forward pass, the action head and the ingestion are the existing launches (learner_dev.h); the four kernels here
 // keep the episodes in flight around them.
 //
 //   rollout_book_kernel   in front of the forward pass: every environment's state and reward into row t = len[env] of its slab, the window
@@ -8,6 +8,8 @@
 //   rollout_noise_kernel  the library's action noise: Philox4x32-10 on (seed; env, episode, step, component) -- rollout_rng.h.
 //   rollout_store_kernel  behind the head: action, policy, V and advantage into row t; the terminal row of RACER::processTerminal
 //                         (Learners/RACER.cpp) where the episode ended; the action out to the caller; len and the episode count.
+//   rollout_stage_kernel  behind the store kernel, for a rollout with a staging ring under the snapshot source: the ended episodes out of
+//                         their slabs into the ring, from where the ingestion reads them on the learner's stream.
 //
 // No kernel waits for another workgroup.  len is read by every workgroup of the book kernel and written by the store kernel only, so
 // that the copy of the states needs no order against the bookkeeping.
@@ -114,6 +116,39 @@ hipError_t launch_rollout_store(const RolloutStoreArgs& a, hipStream_t s) {
   if (!a.act || !a.mu || !a.v || !a.adv || !a.A || !a.MU || !a.V || !a.ADV || !a.outAct || !a.len || !a.episode || !a.nSteps || !a.kind) return hipErrorInvalidValue;
   if (a.nEnv < 1 || a.nEnv > ROLLOUT_MAX_ENV || a.maxSteps < 2 || a.dA < 1 || a.polDim < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rollout_store_kernel, dim3((a.nEnv + 255) / 256), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// Workgroups (x, y): episode y of the batch, its rows walked by the gridDim.x workgroups of its column.  An episode's rows are contiguous
+// in the slab and in the ring, so each array is one flat copy of nsteps rows; the states 16 bytes per access where VEC.  Plain loads and
+// stores: the kernel waits for nothing and shares no word with another workgroup
+template <bool VEC> __global__ __launch_bounds__(256) void rollout_stage_kernel(RolloutStageArgs a) {
+  const RolloutStageEp q = a.ep[blockIdx.y];
+  const long long src = (long long)q.env * a.maxSteps, dst = q.dst, n = q.nsteps;
+  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+  const long long w = VEC ? a.dS >> 2 : a.dS, dA = a.dA, pD = a.polDim;
+  for (long long i = i0; i < n * w; i += step) {
+    if (VEC) reinterpret_cast<f32x4*>(a.rS)[dst * w + i] = reinterpret_cast<const f32x4*>(a.S)[src * w + i];
+    else a.rS[dst * w + i] = a.S[src * w + i];
+  }
+  for (long long i = i0; i < n * dA; i += step) a.rA[dst * dA + i] = a.A[src * dA + i];
+  for (long long i = i0; i < n * pD; i += step) a.rMU[dst * pD + i] = a.MU[src * pD + i];
+  for (long long i = i0; i < n; i += step) { a.rR[dst + i] = a.R[src + i]; a.rV[dst + i] = a.V[src + i]; a.rADV[dst + i] = a.ADV[src + i]; }
+}
+hipError_t launch_rollout_stage(const RolloutStageArgs& a, hipStream_t s) {
+  if (!a.S || !a.A || !a.MU || !a.R || !a.V || !a.ADV || !a.rS || !a.rA || !a.rMU || !a.rR || !a.rV || !a.rADV) return hipErrorInvalidValue;
+  if (a.nEnv < 1 || a.nEnv > ROLLOUT_MAX_ENV || a.maxSteps < 2 || a.dS < 1 || a.dA < 1 || a.polDim < 1) return hipErrorInvalidValue;
+  if (a.nEp < 1 || a.nEp > ROLLOUT_STAGE_MAX_EP || a.ringRows < 1) return hipErrorInvalidValue;
+  long long most = 0;      // the widest array of the longest episode, in accesses
+  const bool vec = a.dS % 4 == 0 && !((reinterpret_cast<uintptr_t>(a.S) | reinterpret_cast<uintptr_t>(a.rS)) & 15);
+  for (int k = 0; k < a.nEp; ++k) {      // every row read lies in its slab, every row written in the ring
+    const RolloutStageEp& q = a.ep[k];
+    if (q.env < 0 || q.env >= a.nEnv || q.nsteps < 2 || q.nsteps > a.maxSteps || q.dst < 0 || q.dst + q.nsteps > a.ringRows) return hipErrorInvalidValue;
+    most = std::max(most, (long long)q.nsteps * std::max<long long>(vec ? a.dS / 4 : a.dS, std::max(a.dA, a.polDim)));
+  }
+  const dim3 grid((unsigned)std::min((most + 255) / 256, 64ll), (unsigned)a.nEp);
+  if (vec) hipLaunchKernelGGL(rollout_stage_kernel<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(rollout_stage_kernel<false>, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
