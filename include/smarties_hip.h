@@ -149,7 +149,9 @@ enum { HL_ORDER_STABLE = 0,     /* stable sort by ID, newest first (product sema
  * Communicator::setPreprocessingConv2d, Communicator.cpp:136-162): image [inpFeatures][inpY][inpX] -> SoftSign
  * convolution -> [outFeatures][outY][outX], filter [outFeatures][inpFeatures][filtery][filterx], one bias per OUTPUT
  * ELEMENT (Network/Layers/Layer_Conv2D.h:37-40).  The reference instantiates seven shapes (Network/Builder.cpp:189-203);
- * the library takes any stride / filter with zero padding. */
+ * the library takes any filter up to 31 x 63, a stride of 1 .. 8 per axis and zero padding smaller than the filter on its axis, up to 256
+ * channels in and out; outY / outX = (inp - filter + 2 paddin) / stride + 1, rounded down (trailing rows or columns that no tap reaches are
+ * legal).  Recurrent network types behind convolutions: no padding, one power-of-two stride, up to 64 channels. */
 typedef struct hl_conv2d {
   int32_t inpFeatures, inpY, inpX, outFeatures, outY, outX, filterx, filtery, stridex, stridey, paddinx, paddiny;
 } hl_conv2d;

@@ -130,14 +130,18 @@ def make_config(dimS=17, dimA=6, bounded=None, hidden=(256, 256), nnFunc="SoftSi
     for i, hsz in enumerate(encoder):
         c.encoder[i] = int(hsz)
     c.nAppendedObs, c.n_conv = nAppendedObs, len(conv)
-    for i, (iw, ih, ic, kn, fs, st) in enumerate(conv):
+    # ... or (input_width, input_height, input_features, kernels_num, (fx, fy), (sx, sy), (px, py)): a filter, a stride and a zero
+    # padding per axis
+    for i, entry in enumerate(conv):
         d = c.conv[i]
+        iw, ih, ic, kn, fs, st = entry[:6]
+        pad = entry[6] if len(entry) > 6 else (0, 0)
         d.inpFeatures, d.inpY, d.inpX, d.outFeatures = ic, ih, iw, kn
-        d.filterx = d.filtery = fs
-        d.stridex = d.stridey = st
-        d.paddinx = d.paddiny = 0
-        d.outY = (d.inpY - d.filterx + 2 * d.paddinx) // d.stridex + 1
-        d.outX = (d.inpX - d.filtery + 2 * d.paddiny) // d.stridey + 1
+        d.filterx, d.filtery = fs if isinstance(fs, (tuple, list)) else (fs, fs)
+        d.stridex, d.stridey = st if isinstance(st, (tuple, list)) else (st, st)
+        d.paddinx, d.paddiny = pad
+        d.outY = (d.inpY - d.filtery + 2 * d.paddiny) // d.stridey + 1
+        d.outX = (d.inpX - d.filterx + 2 * d.paddinx) // d.stridex + 1
     c.batchSize = batchSize
     c.maxTotObsNum, c.minTotObsNum = int(maxTotObsNum), int(minTotObsNum)
     c.gamma, c.lambda_, c.clipImpWeight, c.penalTol = gamma, lambda_, clipImpWeight, penalTol

@@ -20,6 +20,7 @@ inline bool act_conv_geometry(ActConvArgs* a, long long* tab, long long (&buf)[2
   *tab = 0; buf[0] = buf[1] = 0;
   for (int l = 0; l < a->nL; ++l) {
     ActConvLayer& L = a->L[l];
+    // (S = 0: a layer of general geometry -- padding, two strides, beyond 64 channels: the record's builder marks it, the kernels know one stride and no padding)
     if (L.InC < 1 || L.InY < 1 || L.InX < 1 || L.KnC < 1 || L.KnY < 1 || L.KnX < 1 || L.S < 1 || L.OpY < 1 || L.OpX < 1) return false;
     if ((long long)(L.OpY - 1) * L.S + L.KnY > L.InY || (long long)(L.OpX - 1) * L.S + L.KnX > L.InX) return false;      // zero padding
     const long long inSize = (long long)L.InC * L.InY * L.InX, outSize = (long long)L.KnC * L.OpY * L.OpX;

@@ -158,7 +158,7 @@ hipError_t launch_conv_prep(const ConvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(conv_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
-long long conv_prep_floats(const ConvGeo& g, int which) { return which == 0 ? convWfFloats(g) : convWxFloats(g); }
+long long conv_prep_floats(const ConvGeo& g, int which) { return which == 0 ? convWfFloats(g) : (which == 1 ? convWxFloats(g) : convg_prep_floats(g)); }      // (2: Wg, convg.hip)
 
 // flat 16-byte copy global -> LDS, every load of the thread issued before its first store
 template <int MAXQ> __device__ __forceinline__ void stageFlat(float* dst, const float* src, int nFloats) {

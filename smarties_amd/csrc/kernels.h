@@ -148,6 +148,12 @@ struct ConvGeo {
   // filter gradient with the operands staged in LDS (conv.hip: convDwStaged; layers behind the first): a workgroup owns dwG rows
   // (samples) x one tile of 16 channels and leaves one partial per group of rows.  0: the gather workgroups (tile, chunk) above.
   int dwG;
+  // general geometry (convg.hip): padding, two strides, a stride that is no power of two, more than 64 channels.  gen = 0: the kernels
+  // of conv.hip serve the layer and S is both strides; gen = 1: S = stridex is read by nobody but the filter layouts of conv_prep_kernel
+  short gen, Sx, Sy, Px, Py;
+  short gF[3], gX[3], gW[3];   // band plans (convg_plan) of the forward / input-gradient / filter-gradient kernels: output rows and columns of a band, reduction channels per chunk
+  int gSamples;                // samples per reduction chunk of the filter gradient (nChunks of them)
+  float* Wg;                   // the input gradient's filter slices, one per residue class of the input position (convg_prep_kernel; conv_prep_floats(g, 2))
 };
 // where the row-block kernels of the first layer take their input rows from when no stacked minibatch rows X0 were written
 // (training steps: the replay itself, standardised on the way -- stack_gather_kernel's mapping, conv.hip)
@@ -183,6 +189,15 @@ hipError_t launch_conv_forward_rows(const ConvArgs& a, int l, int maxRows, hipSt
 hipError_t launch_conv_dw_all(const ConvArgs& a, int l, int dwBlocks, hipStream_t s);      // launch_conv_dw_rows(l) and launch_conv_dw as one launch
 hipError_t launch_conv_dw_rows(const ConvArgs& a, int l, hipStream_t s);
 hipError_t launch_conv_reduce_adam(const ConvArgs& a, const AdamHyper& hyp, int fuseAdam, hipStream_t s);
+
+// convg.hip: the same three passes for layers of general geometry (ConvGeo::gen), operands from zero-filled LDS windows
+bool convg_needed(int sx, int sy, int px, int py, int inC, int knC);          // the layer is beyond conv.hip's kernels
+bool convg_plan(ConvGeo* g, int rows);                                        // band plans + reduction chunks (host arithmetic only); false: one channel's window and filter exceed the LDS
+long long convg_prep_floats(const ConvGeo& g);                                // floats of Wg
+hipError_t launch_convg_prep(const ConvArgs& a, int l, hipStream_t s);       // Wg of layer l from the weights (in front of its input gradient)
+hipError_t launch_convg_forward(const ConvArgs& a, int l, int maxRows, hipStream_t s);
+hipError_t launch_convg_dx(const ConvArgs& a, int l, hipStream_t s);         // D of layer l-1 from D of layer l
+hipError_t launch_convg_dw(const ConvArgs& a, int l, hipStream_t s);         // partial filter gradients of layer l -> ConvGeo::part
 
 // convt.hip: the layers behind the first one by workgroups that keep a sample's maps and deltas in LDS
 struct ConvTailPlan {

@@ -36,6 +36,7 @@
 using namespace hl;
 
 #include "learner_state.h"
+#include "convg_exec.h"
 #include "step_exec.h"
 
 // =================================================================================================
@@ -105,11 +106,23 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
     const long long inSize = (long long)d.inpFeatures * d.inpY * d.inpX;
     const long long prev = j == 0 ? (long long)cfg->dimS * (1 + cfg->nAppendedObs)
                                   : (long long)cfg->conv[j - 1].outFeatures * cfg->conv[j - 1].outY * cfg->conv[j - 1].outX;
-    if ((j == 0 ? inSize > prev : inSize != prev) || d.outFeatures < 1 || d.outY < 1 || d.outX < 1 || d.stridex < 1 || d.filterx < 1 || d.filtery < 1) return HL_ERR_BAD_ARG;
+    if ((j == 0 ? inSize > prev : inSize != prev) || d.outFeatures < 1 || d.outY < 1 || d.outX < 1 || d.stridex < 1 || d.stridey < 1 || d.filterx < 1 || d.filtery < 1
+        || d.paddinx < 0 || d.paddiny < 0) return HL_ERR_BAD_ARG;
     if (d.outY != (d.inpY - d.filtery + 2 * d.paddiny) / d.stridey + 1 || d.outX != (d.inpX - d.filterx + 2 * d.paddinx) / d.stridex + 1) return HL_ERR_BAD_ARG;
-    // conv.hip: zero padding, one power-of-two stride, <= 64 channels per layer, filters <= 32 wide
-    if (d.paddinx || d.paddiny || d.stridex != d.stridey || (d.stridex & (d.stridex - 1)) || d.stridex > 8) return HL_ERR_UNSUPPORTED;
-    if (d.outFeatures > 64 || d.inpFeatures > 64 || d.filterx > 31 || d.filtery > 63 || (long long)d.outFeatures * d.outY * d.outX >= (1 << 20)) return HL_ERR_UNSUPPORTED;
+    // conv.hip: zero padding, one power-of-two stride, <= 64 channels per layer; convg.hip: every other layer -- strides 1 .. 8 per axis,
+    // padding smaller than the filter, <= 256 channels; both: filters <= 31 x 63, fewer than 2^20 outputs
+    if (d.stridex > 8 || d.stridey > 8) return refuse(out, "convolution: a stride beyond 8");
+    if (d.paddinx >= d.filterx || d.paddiny >= d.filtery) return refuse(out, "convolution: padding must be smaller than the filter on its axis");
+    if (d.outFeatures > 256 || d.inpFeatures > 256) return refuse(out, "convolution: more than 256 channels in or out of a layer");
+    if (d.filterx > 31 || d.filtery > 63 || (long long)d.outFeatures * d.outY * d.outX >= (1 << 20)) return HL_ERR_UNSUPPORTED;
+    if (convg_needed(d.stridex, d.stridey, d.paddinx, d.paddiny, d.inpFeatures, d.outFeatures)) {
+      // (the recurrent routes behind convolutions -- rec*.hip, tm_conv_dx_kernel -- read the one stride of conv.hip's layers)
+      if (cfg->nn_type != HL_NN_FFNN || cfg->encoder_rnn)
+        return refuse(out, "recurrent layers behind a convolution with padding, two strides, a stride that is no power of two or more than 64 channels: feed-forward nets only");
+      ConvGeo g{}; g.InC = d.inpFeatures; g.InY = d.inpY; g.InX = d.inpX; g.KnC = d.outFeatures; g.KnY = d.filtery; g.KnX = d.filterx; g.OpY = d.outY; g.OpX = d.outX;
+      g.K = g.InC * g.KnY * g.KnX; g.P = g.OpY * g.OpX; g.Sx = (short)d.stridex; g.Sy = (short)d.stridey; g.Px = (short)d.paddinx; g.Py = (short)d.paddiny;
+      if (!convg_plan(&g, 1)) return refuse(out, "convolution: the window of one input channel under a band of 16 outputs and its filter slice exceed 144 KB of LDS (convg.hip)");
+    }
   }
   if (convRecTmKind(cfg)) {
     // LSTM / MGU layers behind convolutions: a layer beyond the 256 cells, or a feature row -- the state variables beside the image, then the
@@ -262,20 +275,27 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       rowsPer = std::min<long long>(roundUp(rowsPer, 16), 2048);
       g.chunkRows = (int)rowsPer; g.nChunks = (int)((R + rowsPer - 1) / rowsPer);
       // layers with a large input image (the first one of the Atari stacks): row-block kernels, one partial per (sample, row block)
-      { int win = 0; const int rb = (h->generic & 64) ? 0 : conv_row_block(g, &win);
+      { int win = 0; const int rb = ((h->generic & 64) || g.gen) ? 0 : conv_row_block(g, &win);
         g.rbRows = 0; g.rbCount = 0; g.rbWin = 0;
         if (l == 0 && rb > 0 && conv_rows_ok(g)) { g.rbRows = rb; g.rbCount = (g.OpY + rb - 1) / rb; g.rbWin = win; g.nChunks = h->convB * g.rbCount; } }
       // layers behind the first: both operands staged in LDS, one workgroup per (group of rows, 16 channels)
-      g.dwG = (l > 0 && !g.rbRows && !(h->generic & 32)) ? conv_dw_staged_group(g, h->convB) : 0;
+      g.dwG = (l > 0 && !g.rbRows && !g.gen && !(h->generic & 32)) ? conv_dw_staged_group(g, h->convB) : 0;
       if (g.dwG && (((uintptr_t)g.D | (uintptr_t)h->cg[l - 1].Y) & 15)) g.dwG = 0;      // (16-byte copies: the last layer's rows may start behind extra state variables)
       if (g.dwG) { g.nChunks = (h->convB + g.dwG - 1) / g.dwG; g.chunkRows = g.dwG * g.P; }
-      g.dwBlock0 = blk; blk += g.rbRows ? 0 : (g.dwG ? g.nChunks * (g.KnC / 16) : g.nChunks * tiles);
+      // general geometry (convg.hip): launches of its own per layer -- band plans, one partial per chunk of samples, no workgroup in conv_dw_kernel
+      if (g.gen) {
+        if (!convg_plan(&g, h->convB)) return fail(h, HL_ERR_UNSUPPORTED, "convolution: no LDS plan for this layer (convg.hip)");
+        if (l > 0) HIPCK(devAlloc(&g.Wg, (size_t)conv_prep_floats(g, 2)));
+      }
+      g.dwBlock0 = blk; blk += (g.rbRows || g.gen) ? 0 : (g.dwG ? g.nChunks * (g.KnC / 16) : g.nChunks * tiles);
       HIPCK(devAlloc(&g.part, (size_t)g.nChunks * g.KnC * g.K));
       HIPCK(devAlloc(&g.Wf, (size_t)conv_prep_floats(g, 0))); HIPCK(devAlloc(&g.Wx, (size_t)conv_prep_floats(g, 1)));
       if ((long long)h->convMmax * g.P >= (1ll << 31) || (long long)h->convMmax * g.InY * g.InX >= (1ll << 31)) return fail(h, HL_ERR_UNSUPPORTED, "convolution: rows x positions >= 2^31");
     }
     h->convDwBlocks = blk;
-    if (h->nConv > 1 && !(h->generic & 8)) conv_tail_plan(h->cg, h->nConv, &h->convTail);
+    for (int l = 0; l < h->nConv; ++l) h->convGen = h->convGen || h->cg[l].gen;
+    // (a stack with a layer of general geometry: per-layer launches throughout -- convt.hip and the merged launches are written for conv.hip's layers)
+    if (h->nConv > 1 && !(h->generic & 8) && !h->convGen) conv_tail_plan(h->cg, h->nConv, &h->convTail);
     if (h->generic & 16) { h->convTail.atari = 0; h->convRowsAtari = false; }
   }
   if (h->recurrent && cfg->encoder_rnn && h->nEncLayers > 0 && h->nEncLayers < h->nHidden - (h->nConv > 0 ? 1 : 0)) {
@@ -483,7 +503,7 @@ int hl_destroy(hl_learner* h) {
   for (void* p : ptrs) if (p) hipFree(p);
   for (int l = 0; l < h->nConv; ++l) { ConvGeo& g = h->cg[l];
     if (l != h->nConv - 1) for (float* p : {g.X, g.Y, g.D}) if (p) hipFree(p);
-    for (float* p : {g.part, g.Wf, g.Wx}) if (p) hipFree(p); }
+    for (float* p : {g.part, g.Wf, g.Wx, g.Wg}) if (p) hipFree(p); }
   for (int j = 0; j < h->nHidden; ++j) { DevHidden& d = h->hid[j];
     for (float* p : {d.X, d.Y, d.Rr, d.D, d.Dres}) if (p) hipFree(p); }
   if (h->pinned) hipHostFree(h->pinned);

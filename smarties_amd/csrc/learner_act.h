@@ -64,7 +64,8 @@ static ActConvArgs actConvRecord(const hl_learner* h) {
   c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
   c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = h->recurrent ? 1 : 0;
   for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
-    c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
+    // (S = 0: a layer of general geometry, ConvGeo::gen -- every plan declines the net, which then acts through the training forward launches)
+    c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.gen ? 0 : g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
   return c;
 }
 // the dense layers hid[first ..]: on raw rows, standardised on load (nF = 0), or on feature rows [extras | last map] of nF columns, standardised already
@@ -169,6 +170,7 @@ static const ActRoutes& actResolve(hl_learner* h) {
   } else if (h->nConv > 0) {
     why = nullptr;
     if (h->nHidden < 2) why = "a recurrent net, or no convolutions in front of dense layers";
+    else if (h->convGen) why = "a convolution with padding, two strides, a stride that is no power of two or more than 64 channels";
     else if (!lds) why = "SMARTIES_HIP_GENERIC bit 2";
     else if (!force && r.convPlan) { r.devConv = &r.convArgs; r.devConvRows = &r.convRowsArgs; }
     else {      // (both records are planned on locals and committed together, once nothing refuses the net any more)
@@ -184,7 +186,8 @@ static const ActRoutes& actResolve(hl_learner* h) {
       } else if (actCus(h) < 1) why = "the device does not say its compute units";
       else { r.bandArgs = c; r.panelArgs = a; r.devConv = &r.bandArgs; r.devConvRows = &r.panelArgs; r.devConvBand = bands; r.devConvPanel = panels; }
     }
-    if (why) r.devSeqNo = std::string(": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: ") + why;
+    if (why && h->convGen) r.devSeqNo = std::string(host) + "convolution stacks without padding, with one power-of-two stride and up to 64 channels per layer -- here: " + why;
+    else if (why) r.devSeqNo = std::string(": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: ") + why;
     else { r.devSeq = ACT_DEV_SEQ_CONV; r.devSeqSnap = true; }
   } else if (r.devRows) { r.devSeq = ACT_DEV_SEQ_ROWS; r.devSeqSnap = true; }
   else r.devSeqNo = std::string(host) + "dense nets with input rows up to 8192 and layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: " + why;

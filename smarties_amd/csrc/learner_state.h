@@ -108,6 +108,7 @@ struct hl_learner {
   int extras = 0;      // state variables beyond the first convolution's image: a second input layer behind the conv stack (Approximator.cpp:249-259)
   bool convPrepStale = true;      // the filters' LDS layouts (ConvGeo::Wf, Wx) do not reflect W (conv.hip: conv_prep_kernel)
   ConvGeo cg[HL_MAX_CONV]{}; int convDwBlocks = 0;
+  bool convGen = false;         // a layer of the stack has general geometry (ConvGeo::gen, convg.hip): every layer takes its own launches, acting the training forward launches
   bool convRowsAtari = true;    // the first layer's row-block kernels with the RACER_atari geometry at compile time (SMARTIES_HIP_GENERIC & 16: any-geometry kernels)
   ConvTailPlan convTail{};      // convt.hip: sample-resident kernels for the layers behind the first (on = 0: per-layer launches)
   bool recTm = false; int* tmT = nullptr; int* tmSteps = nullptr; int* tmNext = nullptr;      // wide LSTM / MGU / RNN layers: time-step-major launches (rectm.hip)
@@ -420,6 +421,8 @@ int buildNet(hl_learner* h) {
     g.InC = d.inpFeatures; g.InY = d.inpY; g.InX = d.inpX; g.KnC = d.outFeatures; g.KnY = d.filtery; g.KnX = d.filterx;
     g.S = d.stridex; g.OpY = d.outY; g.OpX = d.outX; g.K = g.InC * g.KnY * g.KnX; g.P = g.OpY * g.OpX;
     g.indW = h->indW[convLayer[j]]; g.indB = h->indB[convLayer[j]];
+    g.Sx = (short)d.stridex; g.Sy = (short)d.stridey; g.Px = (short)d.paddinx; g.Py = (short)d.paddiny;
+    g.gen = convg_needed(d.stridex, d.stridey, d.paddinx, d.paddiny, d.inpFeatures, d.outFeatures) ? 1 : 0;      // (convg.hip's kernels; the others keep conv.hip's)
   }
   if (hOff) {
     const ConvGeo& g = h->cg[c.n_conv - 1];

@@ -459,6 +459,8 @@ int launchFront(hl_learner* h, int parity, hipStream_t s, bool gather) {
         HIPCK(timed(h, "conv_fwd_tail", s, [&] { return launch_conv_fwd_tail(ca, h->convTail, h->convMmax, s); }));
         break;
       }
+      if (ca.L[l].gen) { const int rc = convgForward(h, ca, l, s); if (rc) return rc; }      // general geometry: convg.hip (convg_exec.h)
+      else
       if (ca.L[l].rbRows) HIPCK(timed(h, nm, s, [&] { return launch_conv_forward_rows(ca, l, h->convMmax, s); }));
       else
       HIPCK(timed(h, nm, s, [&] { return launch_conv_forward(ca, l, h->convMmax, s); }));
@@ -606,7 +608,8 @@ int launchBackward(hl_learner* h, int parity, bool fuseAdam, hipStream_t s, bool
     for (int l = 0; l < h->nConv; ++l) if (ca.L[l].rbRows) { ++nRb; lRb = l; }
     // the dense layers' weight-gradient tiles depend on the deltas only, like the filter gradients: with one workgroup per tile and
     // no second rider they join the filter-gradient launch (their Adam pass touches no parameter conv_reduce_adam touches)
-    denseMerged = nRb == 1 && h->convDwBlocks > 0 && h->convDwDense && h->directDw && !h->recurrent && sb.splitMaxMN == 0 && sb.bigDw.empty()
+    // (a stack with a layer of general geometry, convg.hip: per-layer launches, nothing merged, nothing rides)
+    denseMerged = nRb == 1 && !h->convGen && h->convDwBlocks > 0 && h->convDwDense && h->directDw && !h->recurrent && sb.splitMaxMN == 0 && sb.bigDw.empty()
                   && !hyp.push.on && sb.dwBlocks >= h->directDwMinTiles && !sampleC && !(noDx && pex);
     for (int i = 0; denseMerged && i < sb.dwCount; ++i) if (h->hostProbs[sb.dwIdx + i].K > 128) denseMerged = false;      // (the instantiated row batches)
     // ... and the tiles behind the convolution biases' column sums (the table's first nConv problems) need no delta of a
@@ -623,6 +626,7 @@ int launchBackward(hl_learner* h, int parity, bool fuseAdam, hipStream_t s, bool
       HIPCK(timed(h, "conv_back", s, [&] { return launch_conv_back(ca, h->convTail, s); }));
     } else
     for (int l = h->nConv - 1; l >= 1; --l) {
+      if (ca.L[l].gen) { const int rc = convgInputGradient(h, ca, l, s); if (rc) return rc; continue; }      // (convg_exec.h)
       snprintf(nm, sizeof(nm), "conv_dx%d", l);
       DenseRide rd{}; const DenseRide* prd = nullptr;
       if (rideLeft > 0 && conv_dx_rides(ca.L[l])) {
@@ -636,11 +640,12 @@ int launchBackward(hl_learner* h, int parity, bool fuseAdam, hipStream_t s, bool
       HIPCK(timed(h, "conv_dw_dense", s, [&] {
         return launch_conv_dw_dense(ca, lRb, h->convDwBlocks, dwProbs, sb.dwCount, rideT0, hyp, pexF, s); }));
     } else
-    if (nRb == 1 && h->convDwBlocks > 0) {      // the two filter-gradient launches depend on the deltas only: one launch
+    if (nRb == 1 && h->convDwBlocks > 0 && !h->convGen) {      // the two filter-gradient launches depend on the deltas only: one launch
       HIPCK(timed(h, "conv_dw_all", s, [&] { return launch_conv_dw_all(ca, lRb, h->convDwBlocks, s); }));
     } else {
     for (int l = 0; l < h->nConv; ++l) if (ca.L[l].rbRows) HIPCK(timed(h, "conv_dw_rows", s, [&] { return launch_conv_dw_rows(ca, l, s); }));
     if (h->convDwBlocks > 0) HIPCK(timed(h, "conv_dw", s, [&] { return launch_conv_dw(ca, h->convDwBlocks, s); }));
+    if (h->convGen) { const int rc = convgFilterGradients(h, ca, s); if (rc) return rc; }      // (convg_exec.h)
     }
     ca.sc = h->sc;      // (the learning rate of the step)
     HIPCK(timed(h, "conv_reduce_adam", s, [&] { return launch_conv_reduce_adam(ca, hyp, fuseAdam ? 1 : 0, s); }));
