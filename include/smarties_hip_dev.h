@@ -134,11 +134,22 @@ HL_API int hl_select_actions_dev(hl_learner* h, int32_t n, const float* dStates,
  *   a feature row of 2049 .. HL_ACT_DEV_MAX_ROW floats runs act_rows_panel_kernel in place of the row-block kernel (see hl_forward_dev).
  * Both keep the order of every sum of the kernels they stand in for (tests: equal bits on every net both forms can run); hl_forward
  * sends these nets over the training buffers, so the device and the host calls agree to rounding there.
+ * Served, feed-forward nets behind a conv stack with a layer of GENERAL geometry -- zero padding, a stride per axis, a stride that is no
+ * power of two, more than 64 channels (smarties_amd/csrc/actconvg.hip) --: every layer of the stack, the unpadded power-of-two ones
+ * among them, is ONE launch of act_convg_dev_kernel for the agents of a chunk (a workgroup per band of at most 128 outputs of one agent
+ * and up to 64 channels: the band's window staged in LDS with zeros outside the image, the filters read from the source's blob as the
+ * reference lays them out, no prepared copy).  The first layer reads the agents' windows by the mapping above and standardises on
+ * load; the maps between the layers lie in two scratch buffers of the acting source, the agents going in chunks that keep them under
+ * 512 MiB, all chunks enqueued back to back; the last map goes behind the extras of the feature rows, on which the row-block kernel (or
+ * its panelled form beyond 2048 floats) runs as above.  The order of every sum depends on the layer alone: an agent's outputs are the
+ * same bits whatever n, its place among the agents and the chunks.  hl_forward runs these nets over the training buffers: the device
+ * and the host calls agree to rounding.  Served under either acting source.
  *
  * Status: HL_ERR_UNSUPPORTED, with a message naming hl_forward_sequences, for every other recurrent net -- layers beyond 256 cells on
  * narrow inputs (the other time-step-major nets), convolutions in front, encoder_rnn layers: they act on windows in host memory -- and, with
  * a message naming hl_forward and the bound, for feed-forward nets behind convolutions beyond the plans above (a map beyond 160 KB of
- * LDS at any band count; feature rows beyond HL_ACT_DEV_MAX_ROW; dense layers beyond 2048; SMARTIES_HIP_GENERIC bit 2).
+ * LDS at any band count -- with a layer of general geometry: a layer without a band of outputs within 144 KB of LDS --; feature rows
+ * beyond HL_ACT_DEV_MAX_ROW; dense layers beyond 2048; SMARTIES_HIP_GENERIC bit 2).
  * HL_ERR_BAD_ARG for a null handle or array, n < 0 or row_stride < 1.  HL_ERR_STATE between hl_step_begin and hl_step_end.
  * n == 0: HL_OK, nothing is enqueued.  The minibatch buffers and a minibatch drawn ahead are not touched. */
 HL_API int hl_forward_sequences_dev(hl_learner* h, int32_t n, const int64_t* dFirstRow, const int32_t* dNSteps, int64_t row_stride,

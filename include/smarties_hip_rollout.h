@@ -39,7 +39,8 @@ typedef struct hl_rollout_counts {
 /* A rollout of nEnv environments with episodes of at most maxSteps states, owned by the learner h.  `seed` keys the library's action
  * noise (below); episode number k this rollout hands to the replay memory gets the tag tag_base + k, episodes counted in call order
  * and, within a call, in ascending environment index.
- * Served: every net hl_select_actions_sequences_dev serves.  A net that call refuses is refused here, HL_ERR_UNSUPPORTED with that
+ * Served: every net hl_select_actions_sequences_dev serves, conv stacks with padding, a stride per axis or more than 64 channels
+ * among them.  A net that call refuses is refused here, HL_ERR_UNSUPPORTED with that
  * call's message (it names hl_forward_sequences or hl_forward).
  * Status: HL_ERR_BAD_ARG for a null handle or `out`, nEnv < 1, nEnv > 65536 or maxSteps < 2 (checked without a device);
  * HL_ERR_HIP, with the byte count in the message, if the buffer cannot be allocated.

@@ -37,21 +37,13 @@
 //   convg_prep_kernel       VGPR 15   AGPR 0    SGPR 42    scratch 0
 // (the staging loop is unrolled twice, not four times, and the filter gradient walks its (sample, band) pairs in one loop: either of the
 // other forms costs convg_dw_kernel one or two spilled scalar registers)
-#include "dev_common.h"
+#include "convg_band.h"      // cgPad4, CgBand, cgBand, cgSlot, the budget and the band size: shared with actconvg.hip
 
 namespace hl {
 
-__host__ __device__ inline int cgPad4(int k) { return (k + 3) & ~3; }
 __device__ __forceinline__ float cgSoftsign(float x) { return x / (1 + fabsf(x)); }
 __device__ __forceinline__ float cgSoftsignDiff(float x) { const float d = 1 + fabsf(x); return 1 / (d * d); }
 
-// the LDS window of a band: WR rows of WW columns per channel, columns de-interleaved by SX into SX runs of WQ slots, odd row pitch
-struct CgBand { int WR, WW, WQ, pitch, plane; };
-__host__ __device__ inline CgBand cgBand(int RB, int XB, int SY, int SX, int TA, int TB) {
-  CgBand b; b.WR = (RB - 1) * SY + TA; b.WW = (XB - 1) * SX + TB; b.WQ = (b.WW + SX - 1) / SX; b.pitch = (SX * b.WQ) | 1; b.plane = b.WR * b.pitch;
-  return b;
-}
-__host__ __device__ inline int cgSlot(int b, int SX, int WQ) { return (b % SX) * WQ + b / SX; }      // window column b (of output column 0) -> slot
 // one axis of a residue class of the input gradient: T taps, class coordinates j = lo .. lo + n - 1 (input coordinate j S + r - Pd)
 struct CgAxis { int T, lo, n; };
 __host__ __device__ inline CgAxis cgAxis(int r, int S, int Pd, int Kn, int In) {
@@ -64,8 +56,6 @@ __host__ __device__ inline int cgLdg(const ConvGeo& g) { return cgPad4(g.KnC * c
 // floats of dynamic LDS: window of `nc` channels | 64 operand rows of `red` reduction elements (+ 4: pitch = 4 mod 32 where red is a
 // multiple of 32) | a table of `red` offsets
 __host__ __device__ inline size_t cgLdsFloats(const CgBand& bd, int nc, int red) { return (size_t)cgPad4(nc * bd.plane) + (size_t)64 * (cgPad4(red) + 4) + cgPad4(red); }
-constexpr size_t CONVG_LDS_BUDGET = 144 * 1024;
-constexpr int CONVG_BAND_POS = 128;      // positions of a band: 8 tiles of 16, two per wavefront
 constexpr int CONVG_DW_K = 128;          // patch elements of a filter-gradient workgroup: 8 tiles of 16, two per wavefront
 
 bool convg_needed(int sx, int sy, int px, int py, int inC, int knC) {

@@ -477,6 +477,31 @@ hipError_t launch_act_conv_dev(const ActConvArgs& a, int nBlocks, hipStream_t s)
 constexpr int ACT_DEV_MAX_ROW = 8192;     // widest feature / input row of the device calls (HL_ACT_DEV_MAX_ROW of include/smarties_hip_dev.h)
 hipError_t launch_act_conv_band_dev(const ActConvArgs& a, int nBlocks, hipStream_t s);      // 16-byte band loads only where a.bandVec and `in` is 16-byte aligned
 hipError_t launch_act_rows_panel(const ActRowsArgs& a, hipStream_t s);
+// conv stacks of general geometry (actconvg.hip: act_convg_dev_kernel): ONE launch per layer for the agents of a chunk, the maps between
+// the layers in device scratch of the acting source [agents][mapLd], the last one behind the extras of the feature rows
+struct ActConvgLayer {
+  int InC, InY, InX, KnC, KnY, KnX, Sy, Sx, Py, Px, OpY, OpX, K, P; long long indW, indB;
+  // act_convg_plan: a band of RB x XB outputs, ICC reduction channels per chunk, TC x TP tiles of 16 channels x 16 positions per wavefront
+  // (the tile shape: the workgroup owns 16 TC channels), dynamic LDS of the layer's launch
+  int RB, XB, ICC, TC, TP; size_t ldsBytes;
+};
+struct ActConvgArgs {
+  const float* W; const float* stMean; const float* stScale;
+  // the first layer's input: agent i's stacked row read from the states firstRow[i] + max(max(nSteps[i], 1) - 1 - j, 0) * rowStride of `in` [rows][dS]
+  const float* in; const long long* firstRow; const int* nSteps; long long rowStride;
+  const float* src; float* dst;     // the maps of a layer behind the first / of a layer in front of the last: [agents][mapLd]
+  float* feat; int ldF;             // [agents][ldF] feature rows: the extras (first layer's launch), the last map behind them
+  int n, dS, dIn, nL;
+  int img, extras, nF;              // act_convg_plan: floats of the image, state variables beside it, width of a feature row
+  long long mapLd;                  // ... floats of one agent's largest map between two layers (a multiple of 4; 0: one layer)
+  ActConvgLayer L[HL_MAX_CONV];
+};
+// the two maps of an acting source together stay under this many bytes: agents go in chunks of ACT_CONVG_SCRATCH_BYTES / (2 mapLd floats),
+// enqueued back to back.  A memory choice, not a measured one: 256 agents of the 32-channel 84 x 84 stack (1.8 MB per agent) in one chunk
+constexpr size_t ACT_CONVG_SCRATCH_BYTES = (size_t)512 << 20;
+constexpr int ACT_CONVG_MAX_CHUNK = 65535;      // (agents are the grid's second dimension)
+bool act_convg_plan(ActConvgArgs* a);     // host arithmetic only; false: a layer without a band within the LDS budget, a feature row beyond ACT_DEV_MAX_ROW, the geometry
+hipError_t launch_act_convg_dev(const ActConvgArgs& a, int l, hipStream_t s);      // layer l on a.n agents (src / dst / feat / in at the chunk's first agent)
 // rollout inference of recurrent nets for many agents (actseq.hip: act_seq_kernel): a workgroup stages the recurrent stack once and
 // walks its agents' windows; states, window offsets, outputs and per-agent stamps in pinned host memory
 constexpr int ACT_SEQ_CHUNK = 512;      // agents per launch (HL_ACT_SEQ_CHUNK of include/smarties_hip_act.h)

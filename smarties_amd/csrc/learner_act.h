@@ -64,8 +64,18 @@ static ActConvArgs actConvRecord(const hl_learner* h) {
   c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
   c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv; c.recurrent = h->recurrent ? 1 : 0;
   for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
-    // (S = 0: a layer of general geometry, ConvGeo::gen -- every plan declines the net, which then acts through the training forward launches)
+    // (S = 0: a layer of general geometry, ConvGeo::gen -- every plan of the LDS-resident kernels declines the net: actConvgRecord's route serves it)
     c.L[l] = ActConvLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, g.gen ? 0 : g.S, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0}; }
+  return c;
+}
+// a stack with a layer of general geometry, every layer of it (actconvg.hip): the full geometry per layer, filters and biases where the blob has them
+static ActConvgArgs actConvgRecord(const hl_learner* h) {
+  ActConvgArgs c{};
+  c.W = h->W; c.stMean = h->rp.stMean; c.stScale = h->rp.stScale;
+  c.dS = h->dS; c.dIn = h->dIn; c.nL = h->nConv;
+  for (int l = 0; l < h->nConv; ++l) { const ConvGeo& g = h->cg[l];
+    const int sy = g.gen ? g.Sy : g.S, sx = g.gen ? g.Sx : g.S, py = g.gen ? g.Py : 0, px = g.gen ? g.Px : 0;
+    c.L[l] = ActConvgLayer{g.InC, g.InY, g.InX, g.KnC, g.KnY, g.KnX, sy, sx, py, px, g.OpY, g.OpX, g.K, g.P, g.indW, g.indB, 0, 0, 0, 0, 0, 0}; }
   return c;
 }
 // the dense layers hid[first ..]: on raw rows, standardised on load (nF = 0), or on feature rows [extras | last map] of nF columns, standardised already
@@ -161,7 +171,8 @@ static const ActRoutes& actResolve(hl_learner* h) {
   // itself (rectm.hip: lstm_tm_prepare_acts_dev_kernel; live source only: the chain borrows training rows, tmT / tmSteps and the last hidden
   // layer's activations, which a step queued beside it writes), otherwise the batched window kernel of 5.  Dense nets: 8. behind a stacking
   // launch.  Feed-forward nets behind convolutions: the two launches of 3. whatever the row size; beyond that plan act_conv_band_dev_kernel
-  // where the image does not fit beside the maps, act_rows_panel_kernel where the feature row is beyond ACT_ROWS_MAXW
+  // where the image does not fit beside the maps, act_rows_panel_kernel where the feature row is beyond ACT_ROWS_MAXW; a stack
+  // with a layer of general geometry (padding, a stride per axis, beyond 64 channels): act_convg_dev_kernel layer by layer on maps in device scratch
   const char* host = ": this net acts on windows in host memory (hl_forward_sequences); served here: ";
   if (h->recurrent) {
     if (h->wideIn && r.tm && actCus(h) >= 1) r.devSeq = ACT_DEV_SEQ_TM;
@@ -170,7 +181,22 @@ static const ActRoutes& actResolve(hl_learner* h) {
   } else if (h->nConv > 0) {
     why = nullptr;
     if (h->nHidden < 2) why = "a recurrent net, or no convolutions in front of dense layers";
-    else if (h->convGen) why = "a convolution with padding, two strides, a stride that is no power of two or more than 64 channels";
+    else if (h->convGen) {      // every layer through act_convg_dev_kernel, one launch per layer; the dense layers behind as behind every stack
+      ActConvgArgs c = actConvgRecord(h); ActRowsArgs a{}; bool panels = force;
+      auto denseBehind = [&](bool p) { a = actDenseRecord(h, 1, c.nF); panels = p; return p ? act_rows_panel_plan(&a, force ? ACT_DEV_FORCE_PN : 0) : act_rows_plan(&a); };
+      if (!lds) why = "SMARTIES_HIP_GENERIC bit 2";
+      else if (!act_convg_plan(&c) || c.extras != h->extras || c.nF != h->hid[1].nIn) why = "a layer without a band of outputs within 144 KB of LDS, or a feature row beyond HL_ACT_DEV_MAX_ROW = 8192";
+      else if (!denseBehind(force) && !denseBehind(!force)) {
+        why = "the dense layers' activations beyond 160 KB of LDS";
+        for (int j = 1; j < h->nHidden; ++j) if (h->hid[j].size > ACT_ROWS_MAXW) why = "a layer beyond 2048";
+      } else {
+        // agents per chunk: the two maps under ACT_CONVG_SCRATCH_BYTES; SMARTIES_HIP_ACT_CONVG_CHUNK=<agents> (development) overrides it
+        long long chunk = c.mapLd ? (long long)(ACT_CONVG_SCRATCH_BYTES / (2 * sizeof(float))) / c.mapLd : ACT_CONVG_MAX_CHUNK;
+        if (const char* e = getenv("SMARTIES_HIP_ACT_CONVG_CHUNK")) { if (atoll(e) >= 1) chunk = atoll(e); }
+        r.convgArgs = c; r.panelArgs = a; r.devConvRows = &r.panelArgs; r.devConvPanel = panels;
+        r.convgChunk = (int)std::min<long long>(std::max<long long>(chunk, 1), ACT_CONVG_MAX_CHUNK);
+      }
+    }
     else if (!lds) why = "SMARTIES_HIP_GENERIC bit 2";
     else if (!force && r.convPlan) { r.devConv = &r.convArgs; r.devConvRows = &r.convRowsArgs; }
     else {      // (both records are planned on locals and committed together, once nothing refuses the net any more)
@@ -186,7 +212,8 @@ static const ActRoutes& actResolve(hl_learner* h) {
       } else if (actCus(h) < 1) why = "the device does not say its compute units";
       else { r.bandArgs = c; r.panelArgs = a; r.devConv = &r.bandArgs; r.devConvRows = &r.panelArgs; r.devConvBand = bands; r.devConvPanel = panels; }
     }
-    if (why && h->convGen) r.devSeqNo = std::string(host) + "convolution stacks without padding, with one power-of-two stride and up to 64 channels per layer -- here: " + why;
+    if (why && h->convGen) r.devSeqNo = std::string(": this net acts on rows in host memory (hl_forward); served here behind convolutions of general geometry: every layer with a band of outputs within 144 KB of LDS, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: ") + why;
+    else if (h->convGen) { r.devSeq = ACT_DEV_SEQ_CONVG; r.devSeqSnap = true; }
     else if (why) r.devSeqNo = std::string(": this net acts on rows in host memory (hl_forward); served here behind convolutions: every map within 160 KB of LDS beside a band of the image, feature rows up to 8192 and dense layers up to 2048 wide, SMARTIES_HIP_GENERIC bit 2 clear -- here: ") + why;
     else { r.devSeq = ACT_DEV_SEQ_CONV; r.devSeqSnap = true; }
   } else if (r.devRows) { r.devSeq = ACT_DEV_SEQ_ROWS; r.devSeqSnap = true; }

@@ -13,7 +13,7 @@ struct DevCtx {
   const float *W, *stMean, *stScale;
   hipEvent_t *in, *done;
   unsigned* tag; unsigned** stamps;
-  double** out; size_t* outCap; float** rows; size_t* rowsCap; float** feat; size_t* featCap;
+  double** out; size_t* outCap; float** rows; size_t* rowsCap; float** feat; size_t* featCap; float** map; size_t* mapCap;
 };
 static size_t snapMeanOff(const hl_learner* h) { return (size_t)h->nParams; }
 static size_t snapScaleOff(const hl_learner* h) { return (size_t)h->nParams + (size_t)roundUp(h->dS, 4); }
@@ -22,10 +22,10 @@ static DevCtx devCtx(hl_learner* h, int source) {
   if (source == HL_ACT_SNAPSHOT) {
     const float* b = s.snapCur >= 0 ? s.snapBuf[s.snapCur] : nullptr;
     return DevCtx{s.snapStream, true, b, b ? b + snapMeanOff(h) : nullptr, b ? b + snapScaleOff(h) : nullptr, &s.snapIn, &s.snapDone,
-                  &s.snap.tag, &s.snap.stamps, &s.snap.out, &s.snap.outCap, &s.snap.rows, &s.snap.rowsCap, &s.snap.feat, &s.snap.featCap};
+                  &s.snap.tag, &s.snap.stamps, &s.snap.out, &s.snap.outCap, &s.snap.rows, &s.snap.rowsCap, &s.snap.feat, &s.snap.featCap, s.snap.map, s.snap.mapCap};
   }
   return DevCtx{h->stream, false, h->W, h->rp.stMean, h->rp.stScale, &s.devIn, &s.devDone,
-                &s.tag, &s.devStamps, &s.devOut, &s.devOutCap, &s.devRows, &s.devRowsCap, &s.devFeat, &s.devFeatCap};
+                &s.tag, &s.devStamps, &s.devOut, &s.devOutCap, &s.devRows, &s.devRowsCap, &s.devFeat, &s.devFeatCap, s.devMap, s.devMapCap};
 }
 // a cached plan's three pointers into the learner's mutable state, as actFillShared sets them (rows standardised already keep their nullptr)
 template <typename A> static void devSource(const DevCtx& d, A& a) {
@@ -124,7 +124,8 @@ static int devSeqTmForward(hl_learner* h, int n, const int64_t* firstRow, const 
 // n windows of the caller's device arrays, enqueued on the source's stream.  Recurrent nets: ONE launch of the batched window kernel, which
 // gathers and truncates the windows itself (no staging, so no chunks); on wide inputs the chain above.  Behind convolutions: ONE launch of the
 // conv-stack kernel, which reads every agent's stacked row from its window's states, then the row-block kernel on the feature rows per chunk of
-// ACT_ROWS_CHUNK (hl_forward's two launches without the staging).  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
+// ACT_ROWS_CHUNK (hl_forward's two launches without the staging); a stack with a layer of general geometry: one launch of act_convg_dev_kernel
+// per layer and chunk of agents on the source's two scratch maps, then the same row-block kernel.  Dense nets: the agents' stacked rows built by one small launch, then devForward on them
 static int devSeqForward(hl_learner* h, const ActRoutes& r, const DevCtx& d, int n, const DevWindows& w, const float* states, double* out) {
   const long long* firstRow = reinterpret_cast<const long long*>(w.firstRow);
   switch (r.devSeq) {
@@ -140,6 +141,18 @@ static int devSeqForward(hl_learner* h, const ActRoutes& r, const DevCtx& d, int
     c.in = states; c.firstRow = firstRow; c.nSteps = w.nSteps; c.rowStride = w.rowStride; c.feat = *d.feat; c.n = n;
     if (r.devConvBand) HIPCK(timed(h, "act_conv_band_dev", d.st, [&] { return launch_act_conv_band_dev(c, h->act.cus, d.st); }));
     else HIPCK(timed(h, "act_conv_dev", d.st, [&] { return launch_act_conv_dev(c, h->act.cus, d.st); }));
+    return devRows(h, d, *r.devConvRows, r.devConvPanel, n, *d.feat, (size_t)c.nF, out);
+  }
+  case ACT_DEV_SEQ_CONVG: {      // one launch per layer and chunk of agents, all chunks back to back: stream order makes the two maps' reuse safe
+    ActConvgArgs c = r.convgArgs; devSource(d, c);
+    c.in = states; c.rowStride = w.rowStride; c.ldF = c.nF;
+    for (int i0 = 0; i0 < n; i0 += r.convgChunk) {
+      c.n = std::min(r.convgChunk, n - i0); c.firstRow = firstRow + i0; c.nSteps = w.nSteps + i0; c.feat = *d.feat + (size_t)i0 * c.nF;
+      for (int l = 0; l < c.nL; ++l) {
+        c.src = l > 0 ? d.map[(l - 1) & 1] : nullptr; c.dst = l < c.nL - 1 ? d.map[l & 1] : nullptr;
+        HIPCK(timed(h, "act_convg_dev", d.st, [&] { return launch_act_convg_dev(c, l, d.st); }));
+      }
+    }
     return devRows(h, d, *r.devConvRows, r.devConvPanel, n, *d.feat, (size_t)c.nF, out);
   }
   case ACT_DEV_SEQ_ROWS: {
@@ -178,10 +191,15 @@ static int devAct(hl_learner* h, const char* who, int n, const float* in, const 
   if (w && h->act.source == HL_ACT_SNAPSHOT && !r.devSeqSnap) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": recurrent nets on wide inputs act over the training buffers, which cannot run beside a gradient step: they are served by the source HL_ACT_LIVE only");
   { int rc = devSnapEnsure(h, who); if (rc) return rc; }
   const DevCtx d = devCtx(h, h->act.source);
-  if (!w || r.devSeq == ACT_DEV_SEQ_CONV || r.devSeq == ACT_DEV_SEQ_ROWS) { int rc = devStampsEnsure(h, d); if (rc) return rc; }
+  if (!w || r.devSeq == ACT_DEV_SEQ_CONV || r.devSeq == ACT_DEV_SEQ_CONVG || r.devSeq == ACT_DEV_SEQ_ROWS) { int rc = devStampsEnsure(h, d); if (rc) return rc; }
   if (n == 0) return HL_OK;
   if (w && w->rowStride < 1) return fail(h, HL_ERR_BAD_ARG, std::string(who) + ": row_stride below 1");
   if (w && r.devSeq == ACT_DEV_SEQ_CONV) { int rc = devEnsure(h, d.st, d.feat, d.featCap, (size_t)n * r.devConv->nF); if (rc) return rc; }
+  if (w && r.devSeq == ACT_DEV_SEQ_CONVG) {
+    int rc = devEnsure(h, d.st, d.feat, d.featCap, (size_t)n * r.convgArgs.nF); if (rc) return rc;
+    const size_t need = (size_t)std::min(n, r.convgChunk) * (size_t)r.convgArgs.mapLd;      // (one conv layer: no map between layers)
+    for (int b = 0; b < 2 && need; ++b) { rc = devEnsure(h, d.st, &d.map[b], &d.mapCap[b], need); if (rc) return rc; }
+  }
   if (w && r.devSeq == ACT_DEV_SEQ_ROWS) { int rc = devEnsure(h, d.st, d.rows, d.rowsCap, (size_t)n * h->dIn); if (rc) return rc; }
   if (head) { int rc = devEnsure(h, d.st, d.out, d.outCap, (size_t)n * h->nOut); if (rc) return rc; out = *d.out; }
   if (handshake) { int rc = devEnter(h, d, stream); if (rc) return rc; }

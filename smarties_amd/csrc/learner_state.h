@@ -30,12 +30,13 @@ struct ActDevScratch {
   double* out = nullptr; size_t outCap = 0;
   float* rows = nullptr; size_t rowsCap = 0;
   float* feat = nullptr; size_t featCap = 0;
+  float* map[2] = {nullptr, nullptr}; size_t mapCap[2] = {0, 0};      // conv stacks of general geometry: the two maps between the layers' launches, [agents of a chunk][mapLd]
 };
 // What serves a learner's acting calls, resolved ONCE by actResolve (learner_act.h) at the first acting call and read-only from then on: it
 // depends on the net and on SMARTIES_HIP_GENERIC only, never on n or on a call.  The n-dependent choice is made per call by one small
 // function per call family on these facts (actRowsRoute, actWindowsRoute, actDevRowsRoute; the device window calls switch on devSeq).
 // Every argument record is stored once; the device routes point at the resident record wherever they run the resident plan
-enum ActDevSeq { ACT_DEV_SEQ_NONE, ACT_DEV_SEQ_TM, ACT_DEV_SEQ_BATCHED, ACT_DEV_SEQ_CONV, ACT_DEV_SEQ_ROWS };
+enum ActDevSeq { ACT_DEV_SEQ_NONE, ACT_DEV_SEQ_TM, ACT_DEV_SEQ_BATCHED, ACT_DEV_SEQ_CONV, ACT_DEV_SEQ_CONVG, ACT_DEV_SEQ_ROWS };
 struct ActRoutes {
   bool resolved = false;
   // rows in host memory (hl_forward)
@@ -55,6 +56,9 @@ struct ActRoutes {
   const ActConvArgs* devConv = nullptr; const ActRowsArgs* devConvRows = nullptr; bool devConvBand = false, devConvPanel = false;
   // the device routes' own records, filled only where the banded / panelled plan (act_plan.h, actband.hip) serves instead of the resident one
   ActConvArgs bandArgs{}; ActRowsArgs panelArgs{};
+  // a stack with a layer of general geometry (ACT_DEV_SEQ_CONVG; actconvg.hip): one launch per layer on the record below, agents in chunks
+  // of convgChunk, then the dense layers' record devConvRows (panelArgs, under either plan) as behind every conv stack
+  ActConvgArgs convgArgs{}; int convgChunk = 0;
 };
 // rollout inference (learner_act.h)
 struct ActState {
@@ -71,6 +75,7 @@ struct ActState {
   double* devOut = nullptr; size_t devOutCap = 0; double* devSums = nullptr; size_t devSumsCap = 0;
   float* devRows = nullptr; size_t devRowsCap = 0;      // hl_forward_sequences_dev, dense nets with appended observations: the stacked rows
   float* devFeat = nullptr; size_t devFeatCap = 0;      // ... nets behind convolutions: the agents' feature rows [n][nF] between the two launches
+  float* devMap[2] = {nullptr, nullptr}; size_t devMapCap[2] = {0, 0};      // ... stacks of general geometry: the maps between the layers' launches
   // acting on a policy snapshot (learner_dev.h: hl_policy_snapshot, hl_act_dev_source).  source: HL_ACT_LIVE / HL_ACT_SNAPSHOT.  Two
   // buffers [W nParams | stMean | stScale], the small arrays each on a multiple of 4 floats; snapCur the one the acting calls read (-1:
   // none yet).  snapReady[b]: recorded on the learner's stream behind the copy into b; snapRead[b]: recorded on the acting stream behind
@@ -108,7 +113,7 @@ struct hl_learner {
   int extras = 0;      // state variables beyond the first convolution's image: a second input layer behind the conv stack (Approximator.cpp:249-259)
   bool convPrepStale = true;      // the filters' LDS layouts (ConvGeo::Wf, Wx) do not reflect W (conv.hip: conv_prep_kernel)
   ConvGeo cg[HL_MAX_CONV]{}; int convDwBlocks = 0;
-  bool convGen = false;         // a layer of the stack has general geometry (ConvGeo::gen, convg.hip): every layer takes its own launches, acting the training forward launches
+  bool convGen = false;         // a layer of the stack has general geometry (ConvGeo::gen, convg.hip): every layer takes its own launches; acting from device memory: actconvg.hip, hl_forward on host rows: the training forward launches
   bool convRowsAtari = true;    // the first layer's row-block kernels with the RACER_atari geometry at compile time (SMARTIES_HIP_GENERIC & 16: any-geometry kernels)
   ConvTailPlan convTail{};      // convt.hip: sample-resident kernels for the layers behind the first (on = 0: per-layer launches)
   bool recTm = false; int* tmT = nullptr; int* tmSteps = nullptr; int* tmNext = nullptr;      // wide LSTM / MGU / RNN layers: time-step-major launches (rectm.hip)
@@ -340,7 +345,7 @@ void actSnapRelease(hl_learner* h) {
   ActState& s = h->act;
   actSnapSync(h);
   for (hipEvent_t ev : {s.snapIn, s.snapDone, s.snapReady[0], s.snapReady[1], s.snapRead[0], s.snapRead[1]}) if (ev) hipEventDestroy(ev);
-  for (void* q : {(void*)s.snapBuf[0], (void*)s.snapBuf[1], (void*)s.snap.stamps, (void*)s.snap.out, (void*)s.snap.rows, (void*)s.snap.feat}) if (q) hipFree(q);
+  for (void* q : {(void*)s.snapBuf[0], (void*)s.snapBuf[1], (void*)s.snap.stamps, (void*)s.snap.out, (void*)s.snap.rows, (void*)s.snap.feat, (void*)s.snap.map[0], (void*)s.snap.map[1]}) if (q) hipFree(q);
   if (s.snapStream) hipStreamDestroy(s.snapStream);
   s.snapStream = nullptr; s.snapCur = -1; s.snap = ActDevScratch{};
 }
