@@ -24,6 +24,7 @@
 #include "../Math/Gaus_advantage.h"
 #include "../Math/Discrete_advantage.h"
 #include "smarties_hip.h"
+#include "smarties_hip_discrete.h"
 
 #include <mutex>
 #include <sstream>
@@ -170,7 +171,10 @@ class RACER_HIP : public Learner
       if (timing == "one_behind") c.reduction_timing = HL_RDX_ONE_BEHIND;
       else if (timing == "current") c.reduction_timing = HL_RDX_CURRENT;
       else die("SMARTIES_HIP_REDUCTION_TIMING: current or one_behind"); }
-    const int rc = hl_create(&c, &H);
+    // several discrete action variables, or more than 64 labels: the flattened head of hl_create_discrete (smarties_hip_discrete.h)
+    std::vector<int32_t> optValues(M.discreteActionValues.begin(), M.discreteActionValues.end());
+    const bool viaDiscrete = bDiscrete && (optValues.size() > 1 || nA > 64);
+    const int rc = viaDiscrete ? hl_create_discrete(&c, (int32_t) optValues.size(), optValues.data(), &H) : hl_create(&c, &H);
     if (rc) { const std::string msg = H ? hl_last_error(H) : hl_status_string(rc); if (H) hl_destroy(H); H = nullptr; die(msg.c_str()); }
     ck(hl_init_weights(H));
     if (learn_size > 1 && learn_size <= 16 && getenv("SMARTIES_HIP_RCCL") == nullptr) {

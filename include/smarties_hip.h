@@ -191,7 +191,8 @@ typedef struct hl_config {
                                         gives one draw whatever T is (thread 0's, Network/Optimizer.cpp:139) */
   int32_t n_options;                 /* HL_ADV_DISCRETE: number of action options (MDP.maxActionLabel, 2..64) of the ONE
                                         discrete action variable (dimA = 1; actions hold label + 0.1 as in
-                                        Core/StateAction.h:322-341, policies the nOptions probabilities); else 0 */
+                                        Core/StateAction.h:322-341, policies the nOptions probabilities); else 0.
+                                        Several variables, or up to 512 options: hl_create_discrete (smarties_hip_discrete.h) */
   int32_t nn_type;                   /* HL_NN_*: settings nnType of the hidden layers                  */
   int32_t nnBPTTseq;                 /* recurrent nets: steps of truncated BPTT (0 = the default, 16)   */
   int32_t nAppendedObs;              /* MDP.nAppendedObs (Communicator::setNumAppendedPastObservations): the network input is the

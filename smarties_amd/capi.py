@@ -265,6 +265,7 @@ class CApi:
             "restart": (C.c_int, [P, C.c_char_p]),
             "status_string": (C.c_char_p, [C.c_int]),
             "version": (C.c_int, []),
+            "create_discrete": (C.c_int, [C.POINTER(HlConfig), I32, pi32, C.POINTER(P)]),      # include/smarties_hip_discrete.h (product library only)
         }.items():
             if self.has(name):
                 f = self.fn(name)
@@ -286,13 +287,26 @@ def _close_all():
         L.close()
 
 
+def create_discrete(api, values, **kw):
+    """A learner for discrete actions of len(values) variables with values[i] options each (hl_create_discrete): make_config(**kw) with
+    dimA and n_options derived from `values`."""
+    kw.update(dimA=len(values), adv_kind=ADV_DISCRETE, n_options=int(np.prod(values, dtype=np.int64)))
+    return Learner(api, make_config(**kw), values=values)
+
+
 class Learner:
     """Thin object wrapper over one hl_learner handle (names follow include/smarties_hip.h)."""
 
-    def __init__(self, api, cfg):
+    def __init__(self, api, cfg, values=None):
+        """values: the option counts of cfg.dimA discrete action variables (hl_create_discrete); None: hl_create."""
         self.api, self.cfg = api, cfg
         self.h = C.c_void_p()
-        rc = api.fn("create")(C.byref(cfg), C.byref(self.h))
+        if values is None:
+            rc = api.fn("create")(C.byref(cfg), C.byref(self.h))
+        else:
+            v = np.ascontiguousarray(values, dtype=np.int32)
+            rc = api.fn("create_discrete")(C.byref(cfg), len(v), _ptr(v, C.c_int32), C.byref(self.h))
+        self.values = None if values is None else tuple(int(x) for x in values)
         if rc:
             msg = (api.fn("last_error")(self.h) or b"").decode() if self.h else ""
             if self.h:
@@ -304,7 +318,7 @@ class Learner:
         self.nOut = api.fn("num_outputs")(self.h)
         self.dS, self.dA = cfg.dimS, cfg.dimA
         self.dIn = cfg.dimS * (1 + cfg.nAppendedObs)      # network input: the observed state and the appended past ones
-        self.nOptions = cfg.n_options                      # discrete head: options of the one action variable
+        self.nOptions = cfg.n_options                      # discrete head: options (one variable, or the product over hl_create_discrete's)
         self.polDim = cfg.n_options if cfg.n_options else 2 * cfg.dimA
         self.B = max(1, cfg.batchSize // cfg.n_ranks) if cfg.batchSize > 1 else cfg.batchSize
 

@@ -56,7 +56,12 @@ __global__ __launch_bounds__(256) void act_head_kernel(ActHeadArgs a) {
     if (!sample) label = arg;
     else if (label < 0) label = nOpt - 1;        // (u at or beyond the rounded total)
     A = o[1 + label] - expA;
-    a.act[i] = (double)label + 0.1;              // label2actionMessage (StateAction.h:327-341)
+    // label2actionMessage (StateAction.h:327-341): from the last variable down, index = label / shift, label %= shift; one variable: label + 0.1
+    // (constant indices into the argument block)
+    int rest = label;
+#pragma unroll
+    for (int k = DISC_MAX_VARS - 1; k >= 1; --k) if (k < a.dA) { const int sh = a.optShift[k], idx = rest / sh; a.act[(size_t)i * a.dA + k] = (double)idx + 0.1; rest -= idx * sh; }
+    a.act[(size_t)i * a.dA] = (double)rest + 0.1;
   } else {
     // Continuous_policy: outputs [V | nAdv advantage terms | mean x dA | stdev pre-images x dA (ParamLayer)]
     const int dA = a.dA, nAdv = a.nAdv;

@@ -209,6 +209,18 @@ __device__ __forceinline__ float waveSumF(float v) {
   return v;
 }
 
+// discrete head: the label of the action stored at `slot`, as a double whose floor the heads take -- sum_i optShift[i] x floor(message[i])
+// over the dA entries of the message (ActionInfo::actionMessage2label, Core/StateAction.h:304-320); one variable: the message itself.
+// Constant indices into the argument block (a run-time index would put it on the stack)
+__device__ __forceinline__ double discreteLabel(const HeadArgs& a, long long slot) {
+  if (a.dA == 1) return a.rp.A[slot];      // (the one load the heads always issued here)
+  const double* m = a.rp.A + (size_t)slot * a.dA;
+  int label = (int)floor(m[0]);      // (optShift[0] = 1)
+#pragma unroll
+  for (int i = 1; i < DISC_MAX_VARS; ++i) if (i < a.dA) label += (int)a.optShift[i] * (int)floor(m[i]);
+  return (double)label;
+}
+
 __device__ __forceinline__ double scaleNet2V(double x) {   // Learners/RACER_common.cpp:23-27
   return x > 0 ? 100 * (x + 51) - 100 * sqrt(2601 + 100 * x) : 100 * (x - 51) + 100 * sqrt(2601 - 100 * x);
 }

@@ -31,6 +31,7 @@ __global__ __launch_bounds__(256) void head_kernel_t(HeadArgs a, ExtraArgs extra
 }
 
 hipError_t launch_head(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s) {
+  if (a.nOpt > 64) return launch_head_wide(a, maxRows, extra, s);      // options beyond a wavefront's lanes: headw.hip
   ExtraArgs ex{}; if (extra) ex = *extra;
   const int nEx = ex.role ? 1 + ex.helpers : 0;
   const dim3 block(256);

@@ -87,7 +87,7 @@ __device__ __forceinline__ void headBody(const HeadArgs& a, const int row, unsig
   const float bp = lane < a.nSig ? a.params[a.indBp + lane] : 0.f;
   double act = 0, bMean = 0, bStd = 1;
   if (!isNext && a.nOpt) {     // discrete head: lane 0 holds the action message, lane j the behaviour probability of option j
-    if (lane == 0) act = a.rp.A[slot];
+    if (lane == 0) act = discreteLabel(a, slot);      // (one variable: the floor of its message)
     if (lane < a.nOpt) bMean = a.rp.MU[(size_t)slot * a.nOpt + lane];
   } else if (!isNext && lane < dA) {
     act = a.rp.A[(size_t)slot * dA + lane];

@@ -66,7 +66,7 @@ template <int NCH> struct HeadRow {
       }
     }
     actMsg = 0;
-    if (live && nOpt && en == 0) actMsg = a.rp.A[slot];                                 // discrete head: the action message (label + 0.1)
+    if (live && nOpt && en == 0) actMsg = discreteLabel(a, slot);                       // discrete head: the label of the action message (its dA entries through the shifts)
     misc = 0.f;
     if (rowValid) {   // lanes 0..5: RET, DQ, DKL, IMPW, V, ADV of the sampled step; next rows: lanes 6, 7: V, ADV of t+1
       const float* arr = nullptr; long long sl = slot;

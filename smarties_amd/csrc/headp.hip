@@ -230,7 +230,7 @@ bool panel_head_ok(const HeadArgs& a) {
 }
 hipError_t launch_panel_head(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s) {
   ExtraArgs ex{}; if (extra) ex = *extra;
-  unsigned long long mask = 0; for (int c = 0; c < HL_MAX_DIMA && c < 64; ++c) if (a.bounded[c]) mask |= 1ull << c;
+  unsigned long long mask = 0; for (int c = 0; c < HL_MAX_DIMA && c < 64 && !a.nOpt; ++c) if (a.bounded[c]) mask |= 1ull << c;      // (discrete head: those bytes hold the label shifts)
   switch (a.H) {
     case 32: return panelHeadLaunch<32>(a, mask, maxRows, ex, s);
     case 64: return panelHeadLaunch<64>(a, mask, maxRows, ex, s);

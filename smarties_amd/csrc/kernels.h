@@ -41,6 +41,7 @@ struct SampleArgs {
   float eta0; double epsAnneal;
 };
 
+constexpr int DISC_MAX_VARS = 9, DISC_MAX_OPT = 512;      // HL_DISCRETE_MAX_VARS / HL_DISCRETE_MAX_OPTIONS of include/smarties_hip_discrete.h
 struct HeadArgs {
   DevScalars* sc; DevReplay rp; DevBatch bt;
   int B, dA, nDense, nOut, H;       // H = width of the last hidden block
@@ -53,7 +54,9 @@ struct HeadArgs {
   long long indWo, indBo, indBp; int ldWo;   // output dense W/b, ParamLayer bias
   float* dOut; int ldDo;            // [B][ldDo] output-layer deltas (f32)
   float* Dres; float* D; int ldD;   // gradient wrt last hidden block output / after act'
-  unsigned char bounded[HL_MAX_DIMA];
+  // discrete head (nOpt > 0; `bounded` is not read there): the label shifts of the dA action variables, label = sum_i optShift[i] x
+  // floor(message[i]) (ActionInfo::actionMessage2label); one variable: optShift[0] = 1.  In the same bytes: the kernels' argument blocks keep their size
+  union { unsigned char bounded[HL_MAX_DIMA]; unsigned short optShift[DISC_MAX_VARS]; };
   int parity;
   int outFunc;                      // activation of the output layer (settings nnOutputFunc)
 };
@@ -340,6 +343,8 @@ hipError_t launch_dw_wide(const GemmProblem* dProbs, int nProbs, int nTiles, int
 hipError_t launch_splitk_reduce(const GemmProblem* dProbs, int nProbs, int maxMN, const DevScalars* sc, const AdamHyper& hyp, hipStream_t s,
                                 const PostArgs* farBeta = nullptr);      // farBeta: a rider workgroup runs farBetaPhase (tail_dev.h)
 hipError_t launch_head(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
+// the head launch beyond 64 options (headw.hip: head_wide_kernel); launch_head hands them over
+hipError_t launch_head_wide(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
 hipError_t launch_fused(const FusedArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
 size_t fused_lds_bytes(int dS, int H);
 // the same step for two-hidden-layer nets with wide states (first layer streamed in slabs) and any head of head_rows.h (fusedw.hip)
@@ -380,6 +385,7 @@ struct ActHeadArgs {
   double* act; double* mu; float* V; float* ADV;
   int n, dA, nOut, nDense, nAdv, nOpt;       // nAdv: 1 + 2 dA under the Gaussian advantage, else 0; nOpt > 0: the discrete head
   unsigned long long bounded;                // bit i: action component i is bounded (dA <= HL_MAX_DIMA = 64)
+  unsigned short optShift[DISC_MAX_VARS];    // discrete head: the label shifts of the dA action variables (HeadArgs::optShift)
 };
 hipError_t launch_act_head(const ActHeadArgs& a, hipStream_t s);
 // hl_policy_snapshot (actdev.hip: policy_snapshot_kernel): what the acting kernels read of the learner's mutable state -- the blob W [nW]

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "../../include/smarties_hip_discrete.h"
 
 using namespace hl;
 
@@ -53,7 +54,10 @@ const char* hl_status_string(int s) {
 }
 const char* hl_last_error(const hl_learner* h) { return h ? h->err.c_str() : "null handle"; }
 
-int hl_create(const hl_config* cfgIn, hl_learner** out) {
+}  // extern "C"
+// the body of hl_create and hl_create_discrete (include/smarties_hip_discrete.h).  discN == 0: hl_create -- one discrete action variable of
+// up to 64 options; discN > 0: the caller's variables, checked here against dimA and n_options
+static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* discValues, hl_learner** out) {
   if (!cfgIn || !out) return HL_ERR_BAD_ARG;
   // the previous layout (no reduction_timing): copied into a zeroed struct, the missing field reads as HL_RDX_CURRENT
   hl_config cfgV1;
@@ -69,7 +73,15 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       cfg->n_hidden > HL_MAX_HIDDEN || cfg->batchSize <= 0 || cfg->n_ranks < 1) return HL_ERR_BAD_ARG;
   if (cfg->n_ranks > 256) return HL_ERR_UNSUPPORTED;   // the replica counters travel as 16-bit chunks in fp32 (tail_dev.h: encodeCounters)
   if (cfg->adv_kind != HL_ADV_ZERO && cfg->adv_kind != HL_ADV_GAUSSIAN && cfg->adv_kind != HL_ADV_DISCRETE) return HL_ERR_UNSUPPORTED;
-  if (cfg->adv_kind == HL_ADV_DISCRETE && (cfg->dimA != 1 || cfg->n_options < 2 || cfg->n_options > 64)) return HL_ERR_BAD_ARG;   // head launch: one option per lane of the sample's wavefront, 1 + 2 x 64 staged deltas (above 32 options: not the panel / fused heads)
+  if (!discN && cfg->adv_kind == HL_ADV_DISCRETE && (cfg->dimA != 1 || cfg->n_options < 2 || cfg->n_options > 64)) return HL_ERR_BAD_ARG;   // head launch: one option per lane of the sample's wavefront, 1 + 2 x 64 staged deltas (above 32 options: not the panel / fused heads)
+  if (discN) {      // several variables flattened to one label (MDPdescriptor::discreteActionValues / maxActionLabel, Core/StateAction.cpp:134-156)
+    if (cfg->adv_kind != HL_ADV_DISCRETE || !discValues || discN != cfg->dimA) return HL_ERR_BAD_ARG;
+    long long prod = 1;
+    for (int i = 0; i < discN; ++i) { if (discValues[i] < 2) return HL_ERR_BAD_ARG; prod = std::min<long long>(prod * discValues[i], 1ll << 40); }
+    if (prod != cfg->n_options) return HL_ERR_BAD_ARG;
+    // beyond 64 options: head_wide_kernel (headw.hip) -- at most eight options per lane, 1 + 2 x 512 outputs and staged deltas per wavefront in LDS
+    if (prod > DISC_MAX_OPT) return refuse(out, "discrete actions: more than 512 options (the product of the variables' counts); the head launch holds 1 + 2 x 512 outputs per sample (headw.hip)");
+  }
   if (cfg->nnFunc < HL_FUNC_LINEAR || cfg->nnFunc > HL_FUNC_EXP) return HL_ERR_UNSUPPORTED;   // the ten names of makeFunction (Functions.h:643-668)
   if (cfg->episode_order != HL_ORDER_STABLE) return HL_ERR_UNSUPPORTED;   // reference permutation: oracle only
   if (cfg->nn_type < HL_NN_FFNN || cfg->nn_type > HL_NN_RNN) return HL_ERR_UNSUPPORTED;
@@ -155,6 +167,10 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   }
   HIPCK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   h->dS = cfg->dimS; h->dA = cfg->dimA;
+  if (cfg->adv_kind == HL_ADV_DISCRETE) {      // discreteActionShifts: shifts[0] = 1, shifts[i] = shifts[i-1] * values[i-1]
+    h->discChecked = discN > 0;
+    for (int i = 0, sh = 1; i < cfg->dimA; ++i) { h->discValues[i] = discN ? discValues[i] : cfg->n_options; h->discShift[i] = sh; sh *= h->discValues[i]; }
+  }
   const double nL = cfg->n_ranks;
   h->Bglobal = cfg->batchSize > 1 ? (int)(std::ceil(cfg->batchSize / nL) * nL) : cfg->batchSize;
   h->B = cfg->batchSize > 1 ? h->Bglobal / cfg->n_ranks : h->Bglobal;
@@ -411,7 +427,8 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
       // long-reduction kernel (256 < units <= 640), one replica's gradient or a pushed one alike (launchWeightGrad)
       bool sc = h->nConv == 0 && !(h->generic & 512) && HT <= 32;      // (<= 512 units: a panel's group fits its XCD at one workgroup per CU, the kernel's registers at their worst)
       for (int j = 1; j < h->nHidden; ++j) sc = sc && !gemm_oneshot_ok(GEMM_X, h->hid[j].size);
-      h->stepChainOk = sc;
+      // (beyond 64 options the head is the head launch's alone -- headw.hip: the forward chain, that launch and the input-gradient launches go out on their own)
+      h->stepChainOk = sc && h->nOpt <= 64;
     }
   }
   h->ldDo = (int)roundUp(h->nDense, 16);
@@ -464,6 +481,13 @@ int hl_create(const hl_config* cfgIn, hl_learner** out) {
   if (const char* e = getenv("SMARTIES_HIP_NO_GRAPH")) { if (e[0] == '1') h->useGraph = false; }
   if (const char* e = getenv("SMARTIES_HIP_XCHG_TIMEOUT_MS")) h->xchgTimeoutTicks = std::max(1LL, atoll(e)) * 100000LL;
   return HL_OK;
+}
+
+extern "C" {
+int hl_create(const hl_config* cfg, hl_learner** out) { return createLearner(cfg, 0, nullptr, out); }
+int hl_create_discrete(const hl_config* cfg, int32_t n_vars, const int32_t* values, hl_learner** out) {
+  if (n_vars < 1 || n_vars > HL_MAX_DIMA) return HL_ERR_BAD_ARG;
+  return createLearner(cfg, n_vars, values, out);
 }
 
 int hl_destroy(hl_learner* h) {
@@ -684,6 +708,11 @@ int hl_append_episode(hl_learner* h, int32_t N, const float* states, const doubl
   HL_LOCK(h);
   if (N < 2) return fail(h, HL_ERR_BAD_ARG, "Episode must at least have s0 and sT");
   const int dS = h->dS, dA = h->dA, pD = h->polDim;
+  if (h->discChecked)      // hl_create_discrete: every entry of a message against its variable's count (actionMessage2label's asserts); the last step carries no action
+    for (int t = 0; t + 1 < N; ++t) for (int i = 0; i < dA; ++i) {
+      const double v = std::floor(actions[(size_t)t * dA + i]);
+      if (!(v >= 0 && v < h->discValues[i])) return fail(h, HL_ERR_BAD_ARG, "discrete action: step " + std::to_string(t) + ", variable " + std::to_string(i) + " is outside its " + std::to_string(h->discValues[i]) + " options");
+    }
   long long off = 0; int eid = 0; int rc = appendAlloc(h, N, &off, &eid); if (rc) return rc;
   const size_t nf = (size_t)N;
   auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };

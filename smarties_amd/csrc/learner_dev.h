@@ -172,6 +172,7 @@ static int devHead(hl_learner* h, const DevCtx& d, int n, const double* O, const
   a.O = O; a.noise = io.noise; a.act = io.act; a.mu = io.mu; a.V = io.V; a.ADV = io.ADV;
   a.n = n; a.dA = h->dA; a.nOut = h->nOut; a.nDense = h->nDense; a.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; a.nOpt = h->nOpt;
   for (int i = 0; i < h->dA; ++i) if (h->cfg.bounded[i]) a.bounded |= 1ull << i;
+  for (int i = 0; i < h->dA && h->nOpt; ++i) a.optShift[i] = (unsigned short)h->discShift[i];
   HIPCK(timed(h, "act_head_kernel", d.st, [&] { return launch_act_head(a, d.st); }));
   return HL_OK;
 }

@@ -139,6 +139,9 @@ struct hl_learner {
   long long* winSlot = nullptr; int* winT = nullptr; int* winNextSrc = nullptr; hl::DevScalars* scW = nullptr;
   RecLayer rec[HL_MAX_HIDDEN]{};
   int nOpt = 0, polDim = 0, nSig = 0;      // discrete head: options; entries of a stored policy (2 dA | nOpt); sigma ParamLayer size (dA | 0)
+  // discrete head: options and label shift per action variable (hl_create: the one variable, shift 1; hl_create_discrete: dA of them);
+  // discChecked: hl_append_episode holds every entry to its variable's count (hl_create_discrete only: hl_create's learners take what they took)
+  int discValues[hl::DISC_MAX_VARS]{}, discShift[hl::DISC_MAX_VARS]{}; bool discChecked = false;
   long long maxObsLocal = 0, maxObsGlobal = 0, minObsLocal = 0;
   // parameter blob layout (Parameters::_computeNParams, Layers/Parameters.h:159-176)
   std::vector<long long> indW, nW, indB, nB;

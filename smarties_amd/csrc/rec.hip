@@ -1799,7 +1799,7 @@ bool rec_step_fused_ok(const RecArgs& a, const HeadArgs& ha) {
 hipError_t launch_rec_step_fused(const RecArgs& a, const HeadArgs& ha, const ExtraArgs* extra, hipStream_t s) {
   if (!rec_step_fused_ok(a, ha)) return hipErrorInvalidValue;
   ExtraArgs ex{}; if (extra) ex = *extra;
-  unsigned long long mask = 0; for (int c = 0; c < HL_MAX_DIMA && c < 64; ++c) if (ha.bounded[c]) mask |= 1ull << c;
+  unsigned long long mask = 0; for (int c = 0; c < HL_MAX_DIMA && c < 64 && !ha.nOpt; ++c) if (ha.bounded[c]) mask |= 1ull << c;      // (discrete head: those bytes hold the label shifts)
   const dim3 grid(a.B + (ex.role ? 1 : 0)), block(ex.role ? 256 : 128);
   if (a.gates == 2) return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(mgu32_step_wave_kernel<decltype(in0)::value>, grid, block, 0, s, a, ha, mask, ex); });
   return launchWave32(a, [&](auto in0) { hipLaunchKernelGGL(lstm32_step_wave_kernel<decltype(in0)::value>, grid, block, 0, s, a, ha, mask, ex); });

@@ -280,7 +280,8 @@ HeadArgs headArgs(hl_learner* h, int parity) {
   ha.nOut = h->nOut; ha.H = q.size; ha.Yin = q.hasRes ? q.Rr : q.Y; ha.ldY = q.ldA; ha.Xlast = q.X; ha.Ylast = q.Y;
   ha.func = q.func; ha.params = h->W; ha.indWo = h->indWo; ha.indBo = h->indBo; ha.indBp = h->indBp; ha.ldWo = h->ldWo;
   ha.dOut = h->dOut; ha.ldDo = h->ldDo; ha.Dres = q.Dres; ha.D = q.D; ha.ldD = q.ldA; ha.parity = parity; ha.outFunc = h->cfg.nnOutputFunc;
-  for (int i = 0; i < h->dA; ++i) ha.bounded[i] = h->cfg.bounded[i];
+  if (h->nOpt) for (int i = 0; i < h->dA; ++i) ha.optShift[i] = (unsigned short)h->discShift[i];      // (in the bytes of `bounded`, which the discrete head does not read)
+  else for (int i = 0; i < h->dA; ++i) ha.bounded[i] = h->cfg.bounded[i];
   return ha;
 }
 

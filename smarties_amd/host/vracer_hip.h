@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <limits>
 #include "../../include/smarties_hip.h"
+#include "../../include/smarties_hip_discrete.h"
 
 namespace smarties_amd {
 
@@ -88,6 +89,7 @@ class VRACER {
   bool bTrain = true, bInit = false;
   bool recurrent = false;
   int nOut = 0, nDense = 0, nAdv = 0, nOpt = 0;      // nAdv: advantage outputs between V and the policy; nOpt: discrete options
+  std::vector<Uint> optShifts; std::vector<int32_t> optValues;      // discrete actions: label shift and option count per action variable
   // one in-progress episode per agent: MemoryBuffer::inProgress (ReplayMemory/MemoryBuffer.h)
   struct InProgress { Fvec states; Rvec actions, policies, rewards; Fvec values, advantages; int64_t tag = 0; };
   std::vector<InProgress> inProgress;
@@ -147,8 +149,11 @@ class VRACER {
     if (c.returnsEstimator < 0) die("returnsEstimator " + hp.returnsEstimator + " not recognized");
     // AlgoFactory.cpp:78-152: discrete action spaces always get RACER<Discrete_advantage, Discrete_policy, Uint>
     if (M.bDiscreteActions()) {
-      if (M.dimAction != 1 || M.discreteActionValues.size() != 1) die("one discrete action variable is served");
-      c.adv_kind = HL_ADV_DISCRETE; c.n_options = (int32_t)M.discreteActionValues[0]; nOpt = c.n_options;
+      // several variables are flattened to one label (discreteActionShifts / maxActionLabel, Core/StateAction.cpp:134-156): hl_create_discrete
+      if (M.discreteActionValues.size() != M.dimAction) die("discreteActionValues must hold one count per action variable");
+      Uint prod = 1; optShifts.clear(); optValues.clear();
+      for (Uint i = 0; i < M.dimAction; ++i) { optShifts.push_back(prod); optValues.push_back((int32_t)M.discreteActionValues[i]); prod *= M.discreteActionValues[i]; }
+      c.adv_kind = HL_ADV_DISCRETE; c.n_options = (int32_t)prod; nOpt = c.n_options;
     } else if (hp.learner == "VRACER") c.adv_kind = HL_ADV_ZERO;
     else if (hp.learner == "RACER") c.adv_kind = HL_ADV_GAUSSIAN;
     else die("learner " + hp.learner + " is not served by the HIP library");
@@ -164,7 +169,8 @@ class VRACER {
     c.epsAnneal = hp.epsAnneal; c.learnrate = hp.learnrate; c.nnLambda = hp.nnLambda; c.explNoise = hp.explNoise;
     c.outWeightsPrefac = hp.outWeightsPrefac; c.randSeed = hp.randSeed;
     c.n_ranks = nLearners; c.rank = learnerRank; c.device_id = deviceID; c.ref_threads = 1;
-    const int rc = hl_create(&c, &H);
+    const bool viaDiscrete = nOpt && (optValues.size() > 1 || nOpt > 64);      // (one variable of up to 64 options: hl_create, as before)
+    const int rc = viaDiscrete ? hl_create_discrete(&c, (int32_t)optValues.size(), optValues.data(), &H) : hl_create(&c, &H);
     if (rc) {       // (hl_create may hand back a handle that only carries the message)
       const std::string msg = std::string("hl_create: ") + hl_status_string(rc) + ": " + hl_last_error(H);
       if (H) { hl_destroy(H); H = nullptr; }
@@ -219,9 +225,10 @@ class VRACER {
         Real expA = 0; for (int j = 0; j < nOpt; ++j) expA += probs[j] * output[(Uint)(1 + j)];
         const Real V = scaleNet2V(output[0]), A = output[1 + label] - expA;
         EP.values.push_back((Fval)V); EP.advantages.push_back((Fval)((Fval)(V + A) - (Fval)V));
-        agent.action = Rvec(1, (Real)label + 0.1);                                              // label2actionMessage (StateAction.h:327-341)
+        agent.action = Rvec(dA);                                                                // label2actionMessage (StateAction.h:327-341)
+        for (Uint i = dA, rest = label; i > 0; --i) { agent.action[i - 1] = (Real)(rest / optShifts[i - 1]) + 0.1; rest %= optShifts[i - 1]; }
         agent.policyVector = probs;
-        EP.actions.push_back(agent.action[0]);
+        EP.actions.insert(EP.actions.end(), agent.action.begin(), agent.action.end());
         EP.policies.insert(EP.policies.end(), probs.begin(), probs.end());
         return;
       }
