@@ -47,7 +47,7 @@ import ctypes as C
 from smarties_amd import capi
 from test_convg_cpu import NETS, REFUSED
 api = capi.load_hip()
-for name, kw in [(n, v[0]) for n, v in NETS.items()] + [(n, v[0]) for n, v in REFUSED.items()]:
+for name, kw in [(n, v[0]) for n, v in NETS.items()] + [(n, v[0]) for n, v in REFUSED.items()] + %r:
     cfg = capi.make_config(**kw)
     if name == "outY-off-the-formula": cfg.conv[0].outY += 1
     h = C.c_void_p()
@@ -57,15 +57,20 @@ for name, kw in [(n, v[0]) for n, v in NETS.items()] + [(n, v[0]) for n, v in RE
 
 
 def test_hl_create_admits_general_convolution_geometry():
-    """One child process without a device for all cases: the status, and no handle left behind by any of them."""
+    """One child process without a device for all cases: the status, and no handle left behind by any of them.  Beside NETS, the nets
+    tests/blocks.py states for the per-block comparison (column segments, residue classes without a tap, strides up to 8, a padding of
+    K - 1, 65 and 256 channels, a 1 x 1 filter): all admitted."""
+    import blocks      # (imports this module: not at the top)
+    more = [(n, blocks.SHAPES[n]["kw"]) for n in blocks.CONVG_NEW]
+    assert len(more) == 5, more
     env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="")
-    out = subprocess.run([sys.executable, "-c", _CODE % (ROOT, os.path.join(ROOT, "tests"))], capture_output=True, text=True, env=env)
+    out = subprocess.run([sys.executable, "-c", _CODE % (ROOT, os.path.join(ROOT, "tests"), more)], capture_output=True, text=True, env=env)
     got = {}
     for line in out.stdout.splitlines():
         if line.startswith("CASE|"):
             _, name, rc, msg = line.split("|", 3)
             got[name] = (int(rc), msg)
-    want = dict({n: 2 for n in NETS}, **{n: v[1] for n, v in REFUSED.items()})
+    want = dict({n: 2 for n in list(NETS) + [n for n, _ in more]}, **{n: v[1] for n, v in REFUSED.items()})
     assert sorted(got) == sorted(want), out.stdout + out.stderr
     for name, rc in want.items():
         assert got[name] == (rc, ""), (name, got[name])

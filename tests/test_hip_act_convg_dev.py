@@ -1,6 +1,6 @@
 """Acting from device memory for conv stacks of general geometry (smarties_amd/csrc/actconvg.hip: act_convg_dev_kernel, one launch per conv
 layer on maps in device scratch; learner_act.h / learner_dev.h: the route ACT_DEV_SEQ_CONVG), on the GPU: the six small nets of
-tests/test_convg_cpu.py against the fp64 build of the CPU restatement, the bits across layouts, permutations, n and chunks of agents, the
+tests/test_convg_cpu.py and the five general-geometry nets of tests/blocks.py against the fp64 build of the CPU restatement, the bits across layouts, permutations, n and chunks of agents, the
 head and the snapshot source, training left untouched, the rollout buffer, the refusals that remain.
 (On the commit before the feature every device window call on these nets returns HL_ERR_UNSUPPORTED.)"""
 import numpy as np
@@ -12,10 +12,15 @@ from acting import (N_AGENTS, TOL32, _bare, _call_dev, _check_heads, _columns, _
 from oracle_api import synth_cfg
 from parity import assert_columns, relinf, twin64
 from smarties_amd import capi
-from test_convg_cpu import NETS
+import blocks
+from test_convg_cpu import NETS as CPU_NETS
 
 pytestmark = pytest.mark.gpu
 NAMES = ["same-3x3", "stride3", "aniso", "general-then-classic", "wide-channels", "frames-extras"]
+# the geometries tests/blocks.py states for the training kernels' per-block comparison, here under the acting kernel's own band plan (it
+# prefers 72 KB) and staging (quads inside an image row, single loads at its ends, a slot table): rows of 132, a stride of 8, a padding of K - 1
+NAMES_BLOCKS = list(blocks.CONVG_NEW)
+NETS = dict(CPU_NETS, **{n: (blocks.SHAPES[n]["kw"], blocks.SHAPES[n]["sc"], blocks.SHAPES[n]["n_eps"]) for n in NAMES_BLOCKS})
 CPU_BAR = ()      # nets whose fp32 restatement loses more than TOL32 / 3 row-wise on these rows: none (the docstring of the first test)
 QUIET = ("act_conv_dev", "act_conv_band_dev", "conv_fwd0", "conv_fwd1", "convg_fwd0", "convg_fwd1")
 
@@ -37,10 +42,12 @@ def _learner(hip_api, name, monkeypatch, chunk=None):
     return _synth_learner(hip_api, kw, sc_kw, n_eps)
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + NAMES_BLOCKS)
 def test_general_conv_stacks_act_from_device_windows(hip_api, name, monkeypatch):
     """The fp32 restatement against its fp64 build on these 37 rows after three steps (CPU), worst row-wise relinf: 2.1e-7 same-3x3, 1.7e-7 stride3,
-    1.4e-7 aniso, 4.1e-7 general-then-classic, 6.1e-7 wide-channels, 3.7e-7 frames-extras -- every net within TOL32 / 3 = 3.3e-6, so every net is held to TOL32 row by row."""
+    1.4e-7 aniso, 4.1e-7 general-then-classic, 6.1e-7 wide-channels, 3.7e-7 frames-extras; of NAMES_BLOCKS 2.9e-7 convg-wide-rows-132x2-b16,
+    1.4e-7 convg-no-tap-classes-b8, 2.6e-7 convg-stride8x5-k9x8-b8, 2.8e-7 convg-stride7x5-k8x6-b8, 2.6e-7 convg-65-256-1x1-b41 -- every net
+    within TOL32 / 3 = 3.3e-6, so every net is held to TOL32 row by row."""
     import torch
     kw, sc_kw, n_eps = NETS[name]
     monkeypatch.delenv("SMARTIES_HIP_GENERIC", raising=False)
