@@ -93,7 +93,11 @@ class RolloutStageCounts(C.Structure):      # hl_rollout_stage_counts (include/s
                 ("stalls", C.c_int64)]
 
 
-ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2     # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
+class NafConfig(C.Structure):      # hl_naf_config (include/smarties_hip_naf.h)
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("targetDelay", C.c_double)]
+
+
+ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2    # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
 ROLLOUT_MAX_ENV = 65536
 
 
@@ -266,6 +270,10 @@ class CApi:
             "status_string": (C.c_char_p, [C.c_int]),
             "version": (C.c_int, []),
             "create_discrete": (C.c_int, [C.POINTER(HlConfig), I32, pi32, C.POINTER(P)]),      # include/smarties_hip_discrete.h (product library only)
+            # include/smarties_hip_naf.h (product library only)
+            "create_naf": (C.c_int, [C.POINTER(HlConfig), C.POINTER(NafConfig), C.POINTER(P)]),
+            "naf_get_target": (C.c_int, [P, pf]),
+            "naf_set_target": (C.c_int, [P, pf]),
         }.items():
             if self.has(name):
                 f = self.fn(name)
@@ -287,6 +295,14 @@ def _close_all():
         L.close()
 
 
+NAF_MAX_DIMA = 17      # HL_NAF_MAX_DIMA
+
+
+def create_naf(api, targetDelay, **kw):
+    """A NAF learner (hl_create_naf, include/smarties_hip_naf.h): make_config(**kw) and the reference's targetDelay setting."""
+    return Learner(api, make_config(**kw), naf=NafConfig(C.sizeof(NafConfig), 0, float(targetDelay)))
+
+
 def create_discrete(api, values, **kw):
     """A learner for discrete actions of len(values) variables with values[i] options each (hl_create_discrete): make_config(**kw) with
     dimA and n_options derived from `values`."""
@@ -297,11 +313,14 @@ def create_discrete(api, values, **kw):
 class Learner:
     """Thin object wrapper over one hl_learner handle (names follow include/smarties_hip.h)."""
 
-    def __init__(self, api, cfg, values=None):
-        """values: the option counts of cfg.dimA discrete action variables (hl_create_discrete); None: hl_create."""
+    def __init__(self, api, cfg, values=None, naf=None):
+        """values: the option counts of cfg.dimA discrete action variables (hl_create_discrete); naf: a NafConfig (hl_create_naf);
+        neither: hl_create."""
         self.api, self.cfg = api, cfg
         self.h = C.c_void_p()
-        if values is None:
+        if naf is not None:
+            rc = api.fn("create_naf")(C.byref(cfg), C.byref(naf), C.byref(self.h))
+        elif values is None:
             rc = api.fn("create")(C.byref(cfg), C.byref(self.h))
         else:
             v = np.ascontiguousarray(values, dtype=np.int32)
@@ -354,6 +373,16 @@ class Learner:
         for a in (w, m1, m2):
             assert a is None or a.size == self.nParams
         self._ck(self.api.fn("set_params")(self.h, _ptr(w, C.c_float), _ptr(m1, C.c_float), _ptr(m2, C.c_float)))
+
+    def naf_get_target(self):
+        w = np.zeros(self.nParams, np.float32)
+        self._ck(self.api.fn("naf_get_target")(self.h, _ptr(w, C.c_float)))
+        return w
+
+    def naf_set_target(self, w):
+        w = _f32(w)
+        assert w.size == self.nParams
+        self._ck(self.api.fn("naf_set_target")(self.h, _ptr(w, C.c_float)))
 
     def get_params(self):
         w, m1, m2 = [np.zeros(self.nParams, np.float32) for _ in range(3)]

@@ -343,6 +343,21 @@ hipError_t launch_dw_wide(const GemmProblem* dProbs, int nProbs, int nTiles, int
 hipError_t launch_splitk_reduce(const GemmProblem* dProbs, int nProbs, int maxMN, const DevScalars* sc, const AdamHyper& hyp, hipStream_t s,
                                 const PostArgs* farBeta = nullptr);      // farBeta: a rider workgroup runs farBetaPhase (tail_dev.h)
 hipError_t launch_head(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
+// NAF learners (headq.hip; include/smarties_hip_naf.h): the head with the triangular-matrix advantage, a workgroup per sample, and the
+// launches of the target path -- the gather of the next states' rows, V_tgt of each row from the target net's last hidden block, Adam
+// with the target weights' update behind it
+constexpr int NAF_MAX_DIMA = 17, NAF_MAX_NL = NAF_MAX_DIMA * (NAF_MAX_DIMA + 1) / 2;
+struct NafHeadArgs {
+  HeadArgs h; int nL;               // h.nAdv = nL: the policy mean at 1 + nL
+  int retNone;                      // returnsEstimator "none": target r_t + gamma V_tgt(s_{t+1}); else the stored return estimate
+  double gamma, explNoise;
+  const float* vTgt;                // [B] V_tgt(s_{t+1}) (retNone)
+};
+hipError_t launch_head_naf(const NafHeadArgs& a, int maxRows, hipStream_t s);
+hipError_t launch_naf_next_gather(const DevReplay& rp, const long long* slot, float* X1, int ldX, int dS, int B, hipStream_t s);
+hipError_t launch_naf_vtgt(const float* Y, int ldY, int H, const float* Wo, int ldWo, const float* bo, int outFunc, float* vTgt, int B, hipStream_t s);
+enum { NAF_TGT_KEEP = 0, NAF_TGT_POLYAK = 1, NAF_TGT_COPY = 2 };
+hipError_t launch_naf_adam_target(const AdamArgs& a, float* T, int mode, double alpha, hipStream_t s);
 // the head launch beyond 64 options (headw.hip: head_wide_kernel); launch_head hands them over
 hipError_t launch_head_wide(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
 hipError_t launch_fused(const FusedArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);

@@ -352,11 +352,12 @@ static void unpackBlob(const hl_learner* h, const std::vector<float>& in, std::v
 int hl_save(hl_learner* h, const char* base) {
   if (!h || !base) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
-  std::vector<float> P[3]; for (auto& v : P) v.resize((size_t)h->nParams);
+  std::vector<float> P[4]; for (auto& v : P) v.resize((size_t)h->nParams);
   int rc = hl_get_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
-  const char* suf[3] = {"_weights", "_1stMom", "_2ndMom"};
+  if (h->naf) { rc = hl_naf_get_target(h, P[3].data()); if (rc) return rc; }      // AdamOptimizer::save: the target weights beside the weights (Optimizer.cpp:188-189)
+  const char* suf[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
   std::vector<float> buf;
-  for (int b = 0; b < 3; ++b) {
+  for (int b = 0; b < (h->naf ? 4 : 3); ++b) {
     packBlob(h, P[b], buf);
     // like Network::save: write <name>_backup.raw first, then copy it over <name>.raw
     const std::string name = std::string(base) + suf[b] + ".raw", back = std::string(base) + suf[b] + "_backup.raw";
@@ -373,14 +374,15 @@ int hl_save(hl_learner* h, const char* base) {
 int hl_restart(hl_learner* h, const char* base) {
   if (!h || !base) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
-  std::vector<float> P[3]; for (auto& v : P) v.resize((size_t)h->nParams);
+  std::vector<float> P[4]; for (auto& v : P) v.resize((size_t)h->nParams);
   int rc = hl_get_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+  bool tgtRead = false;
   size_t n = 0;
   for (const auto& l : h->lay) n += l.type == 1 ? (size_t)l.size * (l.nIn + 1) : (l.type == 2 ? 2 * (size_t)l.size :
                                   (l.type == 4 || l.type == 5 ? (size_t)l.ld * (l.nIn + l.size + 1) :
                                    (l.type == 6 ? (size_t)l.nIn + l.size : (size_t)l.size)));
-  const char* suf[3] = {"_weights", "_1stMom", "_2ndMom"};
-  for (int b = 0; b < 3; ++b) {
+  const char* suf[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
+  for (int b = 0; b < (h->naf ? 4 : 3); ++b) {
     const std::string name = std::string(base) + suf[b] + ".raw";
     FILE* f = fopen(name.c_str(), "rb");
     if (!f) { if (b == 0) return fail(h, HL_ERR_IO, "Parameters restart file " + name + " not found."); continue; }
@@ -388,8 +390,11 @@ int hl_restart(hl_learner* h, const char* base) {
     const size_t got = fread(buf.data(), sizeof(float), n + 1, f); fclose(f);
     if (got != n) return fail(h, HL_ERR_IO, "Mismatch in restarted file " + name);
     buf.resize(n); unpackBlob(h, buf, P[b]);
+    if (b == 3) tgtRead = true;
   }
-  return hl_set_params(h, P[0].data(), P[1].data(), P[2].data());
+  rc = hl_set_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+  if (h->naf) return hl_naf_set_target(h, tgtRead ? P[3].data() : P[0].data());      // a missing file: a copy of the weights (Optimizer.cpp:207-209)
+  return HL_OK;
 }
 
 // rollout inference: Approximator::forward(agent) for n states (RACER.cpp:30-59)

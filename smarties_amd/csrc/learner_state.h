@@ -147,6 +147,12 @@ struct hl_learner {
   std::vector<long long> indW, nW, indB, nB;
   long long nParams = 0;
   float *W = nullptr, *M1 = nullptr, *M2 = nullptr, *G = nullptr;
+  // NAF learners (hl_create_naf, include/smarties_hip_naf.h): the target weights (layout of W), the optimiser's copy counter
+  // (Optimizer.h: cntUpdateDelay), and -- returnsEstimator "none" -- the next states' rows, the target net's activations and V_tgt per row
+  bool naf = false; double tgtDelay = 0; long long tgtCnt = 0;
+  float *Wtgt = nullptr, *nafX1 = nullptr, *nafVtgt = nullptr;
+  float *tgtX[HL_MAX_HIDDEN]{}, *tgtY[HL_MAX_HIDDEN]{}, *tgtR[HL_MAX_HIDDEN]{};
+  std::vector<int> tgtFwdIdx, tgtFwdBlocks;
   DevScalars* sc = nullptr;
   DevReplay rp{};
   StepBuf buf[2];                          // double-buffered minibatch workspace (see step_exec.h)
@@ -411,6 +417,7 @@ int buildNet(hl_learner* h) {
   const bool discrete = c.adv_kind == HL_ADV_DISCRETE;
   h->nOpt = discrete ? c.n_options : 0; h->polDim = discrete ? c.n_options : 2 * c.dimA; h->nSig = discrete ? 0 : c.dimA;
   h->nAdv = c.adv_kind == HL_ADV_GAUSSIAN ? 1 + 2 * c.dimA : (discrete ? c.n_options : 0);
+  if (h->naf) h->nAdv = c.dimA * (c.dimA + 1) / 2;      // NAF: [V, l x nL, mean] (NAF.cpp:47), the triangle where the Gaussian advantage has its outputs
   h->nDense = 1 + h->nAdv + (discrete ? c.n_options : c.dimA); h->nOut = h->nDense + h->nSig;
   const int outLayer = (int)lw.size();
   lw.push_back(roundUp(h->nDense, 8) * prev); lb.push_back(h->nDense);

@@ -234,6 +234,20 @@ int buildProblems(hl_learner* h) {
       for (int i = 0; i < sb.dwCount; ++i) { sb.dwTable.p[i] = P[sb.dwIdx + i]; sb.dwTableAdam.p[i] = P[sb.dwAdamIdx + i]; }
     }
   }
+  // NAF learners, returnsEstimator "none": the forward chain once more, on the target weights and the next states' rows, into
+  // activation arrays of its own (the live ones feed the backward pass); B rows, the same for both minibatch buffers
+  h->tgtFwdIdx.clear(); h->tgtFwdBlocks.clear();
+  for (int j = 0; j < nH && h->nafX1; ++j) {
+    const DevHidden& d = h->hid[j];
+    GemmProblem p{}; p.flavor = GEMM_F; p.epi = EPI_FWD; p.M = B; p.N = d.size; p.K = d.nIn; p.dynRows = 0;
+    if (j == 0) { p.A = h->nafX1; p.lda = h->ldX0; }
+    else { const DevHidden& q = h->hid[j - 1]; p.A = q.hasRes ? h->tgtR[j - 1] : h->tgtY[j - 1]; p.lda = q.ldA; }
+    p.B = h->Wtgt + d.indW; p.ldb = d.ldW; p.bias = h->Wtgt + d.indB;
+    p.C = h->tgtX[j]; p.C2 = h->tgtY[j]; p.C3 = d.hasRes ? h->tgtR[j] : nullptr; p.ldc = d.ldA; p.func = d.func;
+    if (d.hasRes) { p.resW = h->Wtgt + d.indWr; p.resB = h->Wtgt + d.indBr; p.resIn = p.A; p.ldRes = p.lda; p.resN = d.resW; }
+    int cur = 0; setTiles(p, cur);
+    h->tgtFwdIdx.push_back((int)P.size()); h->tgtFwdBlocks.push_back(cur); P.push_back(p);
+  }
   if (h->dProbs) hipFree(h->dProbs);
   h->dProbs = nullptr;
   HIPCK(devAlloc(&h->dProbs, P.size()));
@@ -276,7 +290,7 @@ PostArgs postArgs(hl_learner* h, int parity, int mode) {
 }
 HeadArgs headArgs(hl_learner* h, int parity) {
   const DevHidden& q = h->hid[h->nHidden - 1];
-  HeadArgs ha{}; ha.sc = h->sc; ha.rp = h->rp; ha.bt = h->buf[parity].bt; ha.B = h->B; ha.dA = h->dA; ha.nDense = h->nDense; ha.nAdv = h->cfg.adv_kind == HL_ADV_GAUSSIAN ? h->nAdv : 0; ha.nOpt = h->nOpt; ha.nSig = h->nSig;
+  HeadArgs ha{}; ha.sc = h->sc; ha.rp = h->rp; ha.bt = h->buf[parity].bt; ha.B = h->B; ha.dA = h->dA; ha.nDense = h->nDense; ha.nAdv = (h->cfg.adv_kind == HL_ADV_GAUSSIAN || h->naf) ? h->nAdv : 0; ha.nOpt = h->nOpt; ha.nSig = h->nSig;
   ha.nOut = h->nOut; ha.H = q.size; ha.Yin = q.hasRes ? q.Rr : q.Y; ha.ldY = q.ldA; ha.Xlast = q.X; ha.Ylast = q.Y;
   ha.func = q.func; ha.params = h->W; ha.indWo = h->indWo; ha.indBo = h->indBo; ha.indBp = h->indBp; ha.ldWo = h->ldWo;
   ha.dOut = h->dOut; ha.ldDo = h->ldDo; ha.Dres = q.Dres; ha.D = q.D; ha.ldD = q.ldA; ha.parity = parity; ha.outFunc = h->cfg.nnOutputFunc;
@@ -508,6 +522,10 @@ int launchForward(hl_learner* h, int parity, hipStream_t s, bool nextSample = fa
 }
 int launchHead(hl_learner* h, int parity, hipStream_t s, bool nextSample = false) {
   const HeadArgs ha = headArgs(h, parity);
+  if (h->naf) {      // headq.hip through naf_exec.h: eager steps, no riders
+    if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the NAF head launch");
+    return nafHead(h, ha, parity, adamHyper(h, parity), s);
+  }
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   // (recurrent nets have no forward GEMM launches: the whole sampler of the next step rides along the head kernel)
   if (nextSample) {
@@ -687,6 +705,7 @@ int launchAdam(hl_learner* h, int parity) {
   AdamArgs aa{}; aa.sc = h->sc; aa.W = h->W; aa.M1 = h->M1; aa.M2 = h->M2; aa.G = h->G; aa.n = h->nParams;
   aa.eta0 = (float)h->cfg.learnrate; aa.lambda = (float)h->cfg.nnLambda; aa.fac = (float)(1.0 / h->Bglobal);
   aa.epsAnneal = h->cfg.epsAnneal; aa.parity = parity;
+  if (h->naf) return nafAdam(h, aa);      // Adam and the target weights in one launch (naf_exec.h)
   HIPCK(timed(h, "adam_kernel", h->stream, [&] { return launch_adam(aa, h->stream); }));
   return HL_OK;
 }
@@ -950,7 +969,8 @@ int stepEager(hl_learner* h, const long long* dFlat) {
     HIPCK(hipEventRecord(h->evSide, h->sideStream));
     h->preValid = true; h->preParity = p ^ 1; h->sidePending = true;
   }
-  rc = launchMlp(h, p, !exch, s); if (rc) return rc;
+  rc = launchMlp(h, p, !exch && !h->naf, s); if (rc) return rc;
+  if (h->naf) { rc = launchAdam(h, p); if (rc) return rc; }      // (NAF: Adam with the target weights' update, its own launch behind the weight gradients)
   h->lastParity = p;
   if (!periodic && !evict && !exch) return launchPost(h, p, POST_AGG | POST_BETA, s);
   rc = launchPost(h, p, POST_AGG, s); if (rc) return rc;
