@@ -97,6 +97,10 @@ class NafConfig(C.Structure):      # hl_naf_config (include/smarties_hip_naf.h)
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("targetDelay", C.c_double)]
 
 
+class DqnConfig(C.Structure):      # hl_dqn_config (include/smarties_hip_dqn.h)
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("targetDelay", C.c_double)]
+
+
 ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2    # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
 ROLLOUT_MAX_ENV = 65536
 
@@ -274,6 +278,10 @@ class CApi:
             "create_naf": (C.c_int, [C.POINTER(HlConfig), C.POINTER(NafConfig), C.POINTER(P)]),
             "naf_get_target": (C.c_int, [P, pf]),
             "naf_set_target": (C.c_int, [P, pf]),
+            # include/smarties_hip_dqn.h (product library only)
+            "create_dqn": (C.c_int, [C.POINTER(HlConfig), C.POINTER(DqnConfig), pi32, C.POINTER(P)]),
+            "dqn_get_target": (C.c_int, [P, pf]),
+            "dqn_set_target": (C.c_int, [P, pf]),
         }.items():
             if self.has(name):
                 f = self.fn(name)
@@ -303,6 +311,13 @@ def create_naf(api, targetDelay, **kw):
     return Learner(api, make_config(**kw), naf=NafConfig(C.sizeof(NafConfig), 0, float(targetDelay)))
 
 
+def create_dqn(api, targetDelay, values, **kw):
+    """A DQN learner (hl_create_dqn, include/smarties_hip_dqn.h): create_discrete's variables and the reference's targetDelay setting
+    (<= 0: no target net)."""
+    kw.update(dimA=len(values), adv_kind=ADV_DISCRETE, n_options=int(np.prod(values, dtype=np.int64)))
+    return Learner(api, make_config(**kw), values=values, dqn=DqnConfig(C.sizeof(DqnConfig), 0, float(targetDelay)))
+
+
 def create_discrete(api, values, **kw):
     """A learner for discrete actions of len(values) variables with values[i] options each (hl_create_discrete): make_config(**kw) with
     dimA and n_options derived from `values`."""
@@ -313,13 +328,16 @@ def create_discrete(api, values, **kw):
 class Learner:
     """Thin object wrapper over one hl_learner handle (names follow include/smarties_hip.h)."""
 
-    def __init__(self, api, cfg, values=None, naf=None):
+    def __init__(self, api, cfg, values=None, naf=None, dqn=None):
         """values: the option counts of cfg.dimA discrete action variables (hl_create_discrete); naf: a NafConfig (hl_create_naf);
-        neither: hl_create."""
+        neither: hl_create.  dqn: a DqnConfig beside `values` (hl_create_dqn)."""
         self.api, self.cfg = api, cfg
         self.h = C.c_void_p()
         if naf is not None:
             rc = api.fn("create_naf")(C.byref(cfg), C.byref(naf), C.byref(self.h))
+        elif dqn is not None:
+            v = np.ascontiguousarray(values, dtype=np.int32)
+            rc = api.fn("create_dqn")(C.byref(cfg), C.byref(dqn), _ptr(v, C.c_int32), C.byref(self.h))
         elif values is None:
             rc = api.fn("create")(C.byref(cfg), C.byref(self.h))
         else:
@@ -383,6 +401,16 @@ class Learner:
         w = _f32(w)
         assert w.size == self.nParams
         self._ck(self.api.fn("naf_set_target")(self.h, _ptr(w, C.c_float)))
+
+    def dqn_get_target(self):
+        w = np.zeros(self.nParams, np.float32)
+        self._ck(self.api.fn("dqn_get_target")(self.h, _ptr(w, C.c_float)))
+        return w
+
+    def dqn_set_target(self, w):
+        w = _f32(w)
+        assert w.size == self.nParams
+        self._ck(self.api.fn("dqn_set_target")(self.h, _ptr(w, C.c_float)))
 
     def get_params(self):
         w, m1, m2 = [np.zeros(self.nParams, np.float32) for _ in range(3)]

@@ -358,6 +358,18 @@ hipError_t launch_naf_next_gather(const DevReplay& rp, const long long* slot, fl
 hipError_t launch_naf_vtgt(const float* Y, int ldY, int H, const float* Wo, int ldWo, const float* bo, int outFunc, float* vTgt, int B, hipStream_t s);
 enum { NAF_TGT_KEEP = 0, NAF_TGT_POLYAK = 1, NAF_TGT_COPY = 2 };
 hipError_t launch_naf_adam_target(const AdamArgs& a, float* T, int mode, double alpha, hipStream_t s);
+// DQN learners (headdq.hip; include/smarties_hip_dqn.h): output layer, head and the output layer's backward for 16 minibatch rows per
+// workgroup on the MFMA.  h.nDense = h.nOut = h.nOpt: the outputs are the Q values
+struct DqnHeadArgs {
+  HeadArgs h;
+  int retNone;                      // returnsEstimator "none": target r_t + gamma sum_i p^_i Q~_i; else the stored return estimate
+  int hasTgt;                       // ... with Q~ from the target net (targetDelay > 0); 0: the live net's own Q values on s_{t+1}
+  double gamma;
+  const float* Ynxt;                // [B][h.ldY] last hidden block of the live net on s_{t+1} (retNone)
+  const float* Ytgt;                // [B][h.ldY] ... of the target net (hasTgt)
+  const float* tgtParams;           // the target blob, layout of h.params (hasTgt)
+};
+hipError_t launch_head_dqn(const DqnHeadArgs& a, int maxRows, hipStream_t s);
 // the head launch beyond 64 options (headw.hip: head_wide_kernel); launch_head hands them over
 hipError_t launch_head_wide(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
 hipError_t launch_fused(const FusedArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);

@@ -34,12 +34,14 @@
 #include "kernels.h"
 #include "../../include/smarties_hip_discrete.h"
 #include "../../include/smarties_hip_naf.h"
+#include "../../include/smarties_hip_dqn.h"
 
 using namespace hl;
 
 #include "learner_state.h"
 #include "convg_exec.h"
 #include "naf_exec.h"
+#include "dqn_exec.h"
 #include "step_exec.h"
 
 // =================================================================================================
@@ -62,9 +64,14 @@ const char* hl_last_error(const hl_learner* h) { return h ? h->err.c_str() : "nu
 // naf != nullptr: hl_create_naf (include/smarties_hip_naf.h) -- the caller's adv_kind is ignored, the head is headq.hip's
 constexpr int HL_ADV_QUADRATIC = 3;      // internal: Quadratic_advantage (no value of the public enumeration)
 static_assert(HL_NAF_MAX_DIMA == NAF_MAX_DIMA, "the header's cap is the head kernel's");
-static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* discValues, hl_learner** out, const hl_naf_config* naf = nullptr) {
+// dqn != nullptr: hl_create_dqn (include/smarties_hip_dqn.h) -- hl_create_discrete's variables, the caller's adv_kind is ignored, the head is headdq.hip's
+static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* discValues, hl_learner** out, const hl_naf_config* naf = nullptr, const hl_dqn_config* dqn = nullptr) {
   if (!cfgIn || !out) return HL_ERR_BAD_ARG;
   hl_config cfgNaf;
+  if (dqn) {
+    if (dqn->struct_size != (int32_t)sizeof(hl_dqn_config) || cfgIn->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
+    cfgNaf = *cfgIn; cfgNaf.adv_kind = HL_ADV_DISCRETE; cfgIn = &cfgNaf;      // (checked below as the discrete-action configuration it is)
+  }
   if (naf) {
     if (naf->struct_size != (int32_t)sizeof(hl_naf_config) || cfgIn->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
     cfgNaf = *cfgIn; cfgNaf.adv_kind = HL_ADV_ZERO; cfgIn = &cfgNaf;      // (checked below as the continuous-action configuration it is)
@@ -90,6 +97,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     for (int i = 0; i < discN; ++i) { if (discValues[i] < 2) return HL_ERR_BAD_ARG; prod = std::min<long long>(prod * discValues[i], 1ll << 40); }
     if (prod != cfg->n_options) return HL_ERR_BAD_ARG;
     // beyond 64 options: head_wide_kernel (headw.hip) -- at most eight options per lane, 1 + 2 x 512 outputs and staged deltas per wavefront in LDS
+    if (prod > DISC_MAX_OPT && dqn) return refuse(out, "DQN: more than 512 options (the product of the variables' counts); the head holds 16 rows of 512 Q values per row set in LDS (headdq.hip)");
     if (prod > DISC_MAX_OPT) return refuse(out, "discrete actions: more than 512 options (the product of the variables' counts); the head launch holds 1 + 2 x 512 outputs per sample (headw.hip)");
   }
   if (cfg->nnFunc < HL_FUNC_LINEAR || cfg->nnFunc > HL_FUNC_EXP) return HL_ERR_UNSUPPORTED;   // the ten names of makeFunction (Functions.h:643-668)
@@ -126,6 +134,12 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     if (cfg->n_ranks > 1) return refuse(out, "NAF: one replica only (the target weights have no exchange)");
     if (cfg->dimA > HL_NAF_MAX_DIMA) return refuse(out, "NAF: dimA beyond 17 (the head holds 1 + 153 + 17 dense outputs in three register slots per lane, headq.hip)");
     if (cfg->nAppendedObs > 0 || cfg->dimS > 512 || cfg->batchSize > 1024) return refuse(out, "NAF: appended observations, states beyond 512 components and batches beyond 1024 are not served (the next states' rows are gathered beside the sampler's)");
+  }
+  if (dqn) {      // what the DQN step is wired for (include/smarties_hip_dqn.h)
+    if (cfg->nn_type != HL_NN_FFNN || cfg->encoder_rnn) return refuse(out, "DQN: recurrent layers are not served (feed-forward dense nets only)");
+    if (cfg->n_conv > 0) return refuse(out, "DQN: convolutions are not served (feed-forward dense nets only)");
+    if (cfg->n_ranks > 1) return refuse(out, "DQN: one replica only (the target weights have no exchange)");
+    if (cfg->nAppendedObs > 0 || cfg->dimS > 512 || cfg->batchSize > 1024) return refuse(out, "DQN: appended observations, states beyond 512 components and batches beyond 1024 are not served (the next states' rows are gathered beside the sampler's)");
   }
   if (cfg->encoder_rnn && cfg->nn_type != HL_NN_MGU) return HL_ERR_BAD_ARG;      // (the one mix the reference builds: Approximator.cpp:221-223, 264-270)
   if (cfg->ERoldSeqFilter < HL_ER_OLDEST || cfg->ERoldSeqFilter > HL_ER_MINERROR) return HL_ERR_BAD_ARG;
@@ -168,6 +182,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
   hl_learner* h = new hl_learner();
   h->cfg = *cfg;
   if (naf) { h->naf = true; h->tgtDelay = naf->targetDelay; h->cfg.adv_kind = HL_ADV_QUADRATIC; h->useGraph = false; }      // (eager steps: the target path has no riders)
+  if (dqn) { h->dqn = true; h->tgtDelay = dqn->targetDelay; h->useGraph = false; }      // (adv_kind stays HL_ADV_DISCRETE: labels, stored policies and their checks are hl_create_discrete's)
   if (cfg->n_encoder > 0) {     // createEncoder: the encoder layers are the first hidden layers of the one network (Learner_approximator.cpp:149-166)
     int n = 0;
     for (int j = 0; j < cfg->n_encoder; ++j) if (cfg->encoder[j] > 0) h->cfg.hidden[n++] = cfg->encoder[j];
@@ -285,16 +300,22 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
   HIPCK(devAlloc(&h->M2, (size_t)h->nParams + PARAM_TAIL)); HIPCK(devAlloc(&h->G, (size_t)h->nParams + PARAM_TAIL));
   HIPCK(devAlloc(&h->sc, 1));
   h->ldX0 = (int)roundUp(h->dIn, 16);
-  if (h->naf) {
+  if (hasTargetNet(h)) {
     HIPCK(devAlloc(&h->Wtgt, (size_t)h->nParams + PARAM_TAIL));
     HIPCK(hipMemset(h->Wtgt, 0, ((size_t)h->nParams + PARAM_TAIL) * sizeof(float)));
     if (cfg->returnsEstimator == HL_RET_NONE) {      // the next states' rows, the target net's activations, V_tgt per row
       HIPCK(devAlloc(&h->nafX1, (size_t)h->Mmax * h->ldX0)); HIPCK(hipMemset(h->nafX1, 0, (size_t)h->Mmax * h->ldX0 * sizeof(float)));
-      HIPCK(devAlloc(&h->nafVtgt, (size_t)B));
+      if (h->naf) HIPCK(devAlloc(&h->nafVtgt, (size_t)B));
       for (int j = 0; j < h->nHidden; ++j) {
         const size_t n = (size_t)h->Mmax * h->hid[j].ldA;
-        HIPCK(devAlloc(&h->tgtX[j], n)); HIPCK(devAlloc(&h->tgtY[j], n));
-        if (h->hid[j].hasRes) HIPCK(devAlloc(&h->tgtR[j], n));
+        if (h->naf || h->tgtDelay > 0) {      // (DQN with targetDelay <= 0: no target chain)
+          HIPCK(devAlloc(&h->tgtX[j], n)); HIPCK(devAlloc(&h->tgtY[j], n));
+          if (h->hid[j].hasRes) HIPCK(devAlloc(&h->tgtR[j], n));
+        }
+        if (h->dqn) {      // DQN: the live net on the next states' rows
+          HIPCK(devAlloc(&h->nxtX[j], n)); HIPCK(devAlloc(&h->nxtY[j], n));
+          if (h->hid[j].hasRes) HIPCK(devAlloc(&h->nxtR[j], n));
+        }
       }
     }
   }
@@ -378,7 +399,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     }
   }
   {   // fused forward + head + dX kernel: two equal hidden blocks of width H <= 256, small state / action spaces
-    const bool off = (h->generic & 1) != 0 || h->naf;      // (NAF: the generic launch sequence with headq.hip's head)
+    const bool off = (h->generic & 1) != 0 || hasTargetNet(h);      // (NAF, DQN: the generic launch sequence with a head of their own)
     if (!off && h->nHidden == 2 && !h->recurrent && !h->preproc) {
       const DevHidden& d0 = h->hid[0]; const DevHidden& d1 = h->hid[1];
       h->fusedOk = cfg->nnOutputFunc == HL_FUNC_LINEAR && d0.size == d1.size && d1.size >= 16 && d1.size <= 256 && (d1.size & (d1.size - 1)) == 0 && h->dS <= 32 && h->nAdv == 0 && h->nDense <= 8 && h->ldWo == 8 &&
@@ -405,7 +426,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
       HIPCK(hipStreamSynchronize(nullptr));
     }
   }
-  if (!h->fusedOk && (h->nHidden == 2 || h->nHidden == 3) && !h->recurrent && !h->preproc && !(h->generic & 1) && !h->naf) {
+  if (!h->fusedOk && (h->nHidden == 2 || h->nHidden == 3) && !h->recurrent && !h->preproc && !(h->generic & 1) && !hasTargetNet(h)) {
     // the wide variant of the fused kernel (fusedw.hip): same placement, same probe; also for THREE equal hidden blocks (settings/RACER_glider.json)
     const DevHidden& d0 = h->hid[0]; const DevHidden& d1 = h->hid[1];
     const int comps = h->nOpt ? h->nOpt : h->dA, nLH = h->nHidden;
@@ -459,7 +480,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
       bool sc = h->nConv == 0 && !(h->generic & 512) && HT <= 32;      // (<= 512 units: a panel's group fits its XCD at one workgroup per CU, the kernel's registers at their worst)
       for (int j = 1; j < h->nHidden; ++j) sc = sc && !gemm_oneshot_ok(GEMM_X, h->hid[j].size);
       // (beyond 64 options the head is the head launch's alone -- headw.hip: the forward chain, that launch and the input-gradient launches go out on their own)
-      h->stepChainOk = sc && h->nOpt <= 64 && !h->naf;
+      h->stepChainOk = sc && h->nOpt <= 64 && !hasTargetNet(h);
     }
   }
   h->ldDo = (int)roundUp(h->nDense, 16);
@@ -524,20 +545,29 @@ int hl_create_naf(const hl_config* cfg, const hl_naf_config* naf, hl_learner** o
   if (!naf) return HL_ERR_BAD_ARG;
   return createLearner(cfg, 0, nullptr, out, naf);
 }
-int hl_naf_get_target(hl_learner* h, float* w) {
-  if (!h || !w || !h->naf || !h->Wtgt) return HL_ERR_BAD_ARG;
+int hl_create_dqn(const hl_config* cfg, const hl_dqn_config* dqn, const int32_t* values, hl_learner** out) {
+  if (!cfg || !dqn || !values || cfg->dimA < 1 || cfg->dimA > HL_MAX_DIMA) return HL_ERR_BAD_ARG;
+  return createLearner(cfg, cfg->dimA, values, out, nullptr, dqn);
+}
+// the body of hl_naf_get_target / hl_dqn_get_target and of the two set calls (`mine`: the handle is of the caller's kind)
+static int targetGet(hl_learner* h, bool mine, float* w) {
+  if (!h || !w || !mine || !h->Wtgt) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   HIPCK(hipMemcpyAsync(w, h->Wtgt, (size_t)h->nParams * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   return HL_OK;
 }
-int hl_naf_set_target(hl_learner* h, const float* w) {
-  if (!h || !w || !h->naf || !h->Wtgt) return HL_ERR_BAD_ARG;
+static int targetSet(hl_learner* h, bool mine, const float* w) {
+  if (!h || !w || !mine || !h->Wtgt) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   HIPCK(hipMemcpyAsync(h->Wtgt, w, (size_t)h->nParams * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   return HL_OK;
 }
+int hl_naf_get_target(hl_learner* h, float* w) { return targetGet(h, h && h->naf, w); }
+int hl_naf_set_target(hl_learner* h, const float* w) { return targetSet(h, h && h->naf, w); }
+int hl_dqn_get_target(hl_learner* h, float* w) { return targetGet(h, h && h->dqn, w); }
+int hl_dqn_set_target(hl_learner* h, const float* w) { return targetSet(h, h && h->dqn, w); }
 
 int hl_destroy(hl_learner* h) {
   if (!h) return HL_OK;
@@ -575,7 +605,7 @@ int hl_destroy(hl_learner* h) {
   for (void* q : {(void*)h->tmT, (void*)h->tmSteps, (void*)h->tmNext, (void*)h->tmCtr, (void*)h->tmP}) if (q) hipFree(q);
   for (void* p : ptrs) if (p) hipFree(p);
   for (float* q : {h->Wtgt, h->nafX1, h->nafVtgt}) if (q) hipFree(q);
-  for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* q : {h->tgtX[j], h->tgtY[j], h->tgtR[j]}) if (q) hipFree(q);
+  for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* q : {h->tgtX[j], h->tgtY[j], h->tgtR[j], h->nxtX[j], h->nxtY[j], h->nxtR[j]}) if (q) hipFree(q);
   for (int l = 0; l < h->nConv; ++l) { ConvGeo& g = h->cg[l];
     if (l != h->nConv - 1) for (float* p : {g.X, g.Y, g.D}) if (p) hipFree(p);
     for (float* p : {g.part, g.Wf, g.Wx, g.Wg}) if (p) hipFree(p); }
@@ -673,7 +703,7 @@ int hl_init_weights(hl_learner* h) {
     for (int o = 0; o < h->nSig; ++o) W[h->indBp + o] = (float)((S * S - 0.25) / S);   // SoftPlus::_inv (Functions.h:564-568)
   }
   HIPCK(hipMemcpyAsync(h->W, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (h->naf) { HIPCK(hipMemcpyAsync(h->Wtgt, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream)); h->tgtCnt = 0; }      // (Optimizer.cpp:233: the target weights start as a copy)
+  if (hasTargetNet(h)) { HIPCK(hipMemcpyAsync(h->Wtgt, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream)); h->tgtCnt = 0; }      // (Optimizer.cpp:233: the target weights start as a copy)
   h->convPrepStale = true;
   std::memcpy(s.rng, g.x, sizeof(g.x)); s.rngPos = g.p;
   HIPCK(hipMemcpyAsync(&h->sc->rng[0], s.rng, sizeof(s.rng), hipMemcpyHostToDevice, h->stream));

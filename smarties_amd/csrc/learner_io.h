@@ -354,10 +354,10 @@ int hl_save(hl_learner* h, const char* base) {
   HL_LOCK(h);
   std::vector<float> P[4]; for (auto& v : P) v.resize((size_t)h->nParams);
   int rc = hl_get_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
-  if (h->naf) { rc = hl_naf_get_target(h, P[3].data()); if (rc) return rc; }      // AdamOptimizer::save: the target weights beside the weights (Optimizer.cpp:188-189)
+  if (hasTargetNet(h)) { rc = h->naf ? hl_naf_get_target(h, P[3].data()) : hl_dqn_get_target(h, P[3].data()); if (rc) return rc; }      // AdamOptimizer::save: the target weights beside the weights (Optimizer.cpp:188-189)
   const char* suf[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
   std::vector<float> buf;
-  for (int b = 0; b < (h->naf ? 4 : 3); ++b) {
+  for (int b = 0; b < (hasTargetNet(h) ? 4 : 3); ++b) {
     packBlob(h, P[b], buf);
     // like Network::save: write <name>_backup.raw first, then copy it over <name>.raw
     const std::string name = std::string(base) + suf[b] + ".raw", back = std::string(base) + suf[b] + "_backup.raw";
@@ -382,7 +382,7 @@ int hl_restart(hl_learner* h, const char* base) {
                                   (l.type == 4 || l.type == 5 ? (size_t)l.ld * (l.nIn + l.size + 1) :
                                    (l.type == 6 ? (size_t)l.nIn + l.size : (size_t)l.size)));
   const char* suf[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
-  for (int b = 0; b < (h->naf ? 4 : 3); ++b) {
+  for (int b = 0; b < (hasTargetNet(h) ? 4 : 3); ++b) {
     const std::string name = std::string(base) + suf[b] + ".raw";
     FILE* f = fopen(name.c_str(), "rb");
     if (!f) { if (b == 0) return fail(h, HL_ERR_IO, "Parameters restart file " + name + " not found."); continue; }
@@ -393,7 +393,7 @@ int hl_restart(hl_learner* h, const char* base) {
     if (b == 3) tgtRead = true;
   }
   rc = hl_set_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
-  if (h->naf) return hl_naf_set_target(h, tgtRead ? P[3].data() : P[0].data());      // a missing file: a copy of the weights (Optimizer.cpp:207-209)
+  if (hasTargetNet(h)) { const float* t = tgtRead ? P[3].data() : P[0].data(); return h->naf ? hl_naf_set_target(h, t) : hl_dqn_set_target(h, t); }      // a missing file: a copy of the weights (Optimizer.cpp:207-209)
   return HL_OK;
 }
 

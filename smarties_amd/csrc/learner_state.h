@@ -153,6 +153,12 @@ struct hl_learner {
   float *Wtgt = nullptr, *nafX1 = nullptr, *nafVtgt = nullptr;
   float *tgtX[HL_MAX_HIDDEN]{}, *tgtY[HL_MAX_HIDDEN]{}, *tgtR[HL_MAX_HIDDEN]{};
   std::vector<int> tgtFwdIdx, tgtFwdBlocks;
+  // DQN learners (hl_create_dqn, include/smarties_hip_dqn.h) share all of it -- Wtgt always, nafX1 with returnsEstimator "none", the
+  // target net's activations with targetDelay > 0 as well -- and run the LIVE net on the next states' rows too: activations and forward
+  // problem records of their own
+  bool dqn = false;
+  float *nxtX[HL_MAX_HIDDEN]{}, *nxtY[HL_MAX_HIDDEN]{}, *nxtR[HL_MAX_HIDDEN]{};
+  std::vector<int> nxtFwdIdx, nxtFwdBlocks;
   DevScalars* sc = nullptr;
   DevReplay rp{};
   StepBuf buf[2];                          // double-buffered minibatch workspace (see step_exec.h)
@@ -259,6 +265,9 @@ struct hl_learner {
 };
 
 namespace {
+
+// learners that keep target weights (NAF, DQN): the generic launch sequence, eager, Adam with the target update as a launch of its own
+inline bool hasTargetNet(const hl_learner* h) { return h->naf || h->dqn; }
 
 // Exchange windows (hl_xchg_export) are UNCACHED device memory, and uncached memory must never go back to the allocator: on this
 // runtime (ROCm 7.2, gfx950) memory freed after a life as hipDeviceMallocUncached and handed out again by hipMalloc made kernels of
@@ -419,6 +428,7 @@ int buildNet(hl_learner* h) {
   h->nAdv = c.adv_kind == HL_ADV_GAUSSIAN ? 1 + 2 * c.dimA : (discrete ? c.n_options : 0);
   if (h->naf) h->nAdv = c.dimA * (c.dimA + 1) / 2;      // NAF: [V, l x nL, mean] (NAF.cpp:47), the triangle where the Gaussian advantage has its outputs
   h->nDense = 1 + h->nAdv + (discrete ? c.n_options : c.dimA); h->nOut = h->nDense + h->nSig;
+  if (h->dqn) { h->nAdv = 0; h->nDense = h->nOut = c.n_options; }      // DQN: the Q values alone (DQN.cpp:52), no value column
   const int outLayer = (int)lw.size();
   lw.push_back(roundUp(h->nDense, 8) * prev); lb.push_back(h->nDense);
   const int paramLayer = h->nSig ? (int)lw.size() : -1;

@@ -236,18 +236,24 @@ int buildProblems(hl_learner* h) {
   }
   // NAF learners, returnsEstimator "none": the forward chain once more, on the target weights and the next states' rows, into
   // activation arrays of its own (the live ones feed the backward pass); B rows, the same for both minibatch buffers
-  h->tgtFwdIdx.clear(); h->tgtFwdBlocks.clear();
-  for (int j = 0; j < nH && h->nafX1; ++j) {
-    const DevHidden& d = h->hid[j];
-    GemmProblem p{}; p.flavor = GEMM_F; p.epi = EPI_FWD; p.M = B; p.N = d.size; p.K = d.nIn; p.dynRows = 0;
-    if (j == 0) { p.A = h->nafX1; p.lda = h->ldX0; }
-    else { const DevHidden& q = h->hid[j - 1]; p.A = q.hasRes ? h->tgtR[j - 1] : h->tgtY[j - 1]; p.lda = q.ldA; }
-    p.B = h->Wtgt + d.indW; p.ldb = d.ldW; p.bias = h->Wtgt + d.indB;
-    p.C = h->tgtX[j]; p.C2 = h->tgtY[j]; p.C3 = d.hasRes ? h->tgtR[j] : nullptr; p.ldc = d.ldA; p.func = d.func;
-    if (d.hasRes) { p.resW = h->Wtgt + d.indWr; p.resB = h->Wtgt + d.indBr; p.resIn = p.A; p.ldRes = p.lda; p.resN = d.resW; }
-    int cur = 0; setTiles(p, cur);
-    h->tgtFwdIdx.push_back((int)P.size()); h->tgtFwdBlocks.push_back(cur); P.push_back(p);
-  }
+  // DQN learners: the same records for the target chain where there is a target net (targetDelay > 0), and a third set -- the LIVE
+  // weights on the next states' rows, activation arrays of their own again
+  auto nextChain = [&](const float* Wb, float** X, float** Y, float** R, std::vector<int>& idx, std::vector<int>& blocks) {
+    idx.clear(); blocks.clear();
+    for (int j = 0; j < nH && h->nafX1 && Y[0]; ++j) {
+      const DevHidden& d = h->hid[j];
+      GemmProblem p{}; p.flavor = GEMM_F; p.epi = EPI_FWD; p.M = B; p.N = d.size; p.K = d.nIn; p.dynRows = 0;
+      if (j == 0) { p.A = h->nafX1; p.lda = h->ldX0; }
+      else { const DevHidden& q = h->hid[j - 1]; p.A = q.hasRes ? R[j - 1] : Y[j - 1]; p.lda = q.ldA; }
+      p.B = Wb + d.indW; p.ldb = d.ldW; p.bias = Wb + d.indB;
+      p.C = X[j]; p.C2 = Y[j]; p.C3 = d.hasRes ? R[j] : nullptr; p.ldc = d.ldA; p.func = d.func;
+      if (d.hasRes) { p.resW = Wb + d.indWr; p.resB = Wb + d.indBr; p.resIn = p.A; p.ldRes = p.lda; p.resN = d.resW; }
+      int cur = 0; setTiles(p, cur);
+      idx.push_back((int)P.size()); blocks.push_back(cur); P.push_back(p);
+    }
+  };
+  nextChain(h->Wtgt, h->tgtX, h->tgtY, h->tgtR, h->tgtFwdIdx, h->tgtFwdBlocks);
+  nextChain(h->W, h->nxtX, h->nxtY, h->nxtR, h->nxtFwdIdx, h->nxtFwdBlocks);
   if (h->dProbs) hipFree(h->dProbs);
   h->dProbs = nullptr;
   HIPCK(devAlloc(&h->dProbs, P.size()));
@@ -526,6 +532,10 @@ int launchHead(hl_learner* h, int parity, hipStream_t s, bool nextSample = false
     if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the NAF head launch");
     return nafHead(h, ha, parity, adamHyper(h, parity), s);
   }
+  if (h->dqn) {      // headdq.hip through dqn_exec.h: eager steps, no riders
+    if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the DQN head launch");
+    return dqnHead(h, ha, parity, adamHyper(h, parity), s);
+  }
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   // (recurrent nets have no forward GEMM launches: the whole sampler of the next step rides along the head kernel)
   if (nextSample) {
@@ -706,6 +716,7 @@ int launchAdam(hl_learner* h, int parity) {
   aa.eta0 = (float)h->cfg.learnrate; aa.lambda = (float)h->cfg.nnLambda; aa.fac = (float)(1.0 / h->Bglobal);
   aa.epsAnneal = h->cfg.epsAnneal; aa.parity = parity;
   if (h->naf) return nafAdam(h, aa);      // Adam and the target weights in one launch (naf_exec.h)
+  if (h->dqn) return dqnAdam(h, aa);      // ... (dqn_exec.h)
   HIPCK(timed(h, "adam_kernel", h->stream, [&] { return launch_adam(aa, h->stream); }));
   return HL_OK;
 }
@@ -969,8 +980,8 @@ int stepEager(hl_learner* h, const long long* dFlat) {
     HIPCK(hipEventRecord(h->evSide, h->sideStream));
     h->preValid = true; h->preParity = p ^ 1; h->sidePending = true;
   }
-  rc = launchMlp(h, p, !exch && !h->naf, s); if (rc) return rc;
-  if (h->naf) { rc = launchAdam(h, p); if (rc) return rc; }      // (NAF: Adam with the target weights' update, its own launch behind the weight gradients)
+  rc = launchMlp(h, p, !exch && !hasTargetNet(h), s); if (rc) return rc;
+  if (hasTargetNet(h)) { rc = launchAdam(h, p); if (rc) return rc; }      // (NAF, DQN: Adam with the target weights' update, its own launch behind the weight gradients)
   h->lastParity = p;
   if (!periodic && !evict && !exch) return launchPost(h, p, POST_AGG | POST_BETA, s);
   rc = launchPost(h, p, POST_AGG, s); if (rc) return rc;
