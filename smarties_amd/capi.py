@@ -101,6 +101,10 @@ class DqnConfig(C.Structure):      # hl_dqn_config (include/smarties_hip_dqn.h)
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("targetDelay", C.c_double)]
 
 
+class DpgConfig(C.Structure):      # hl_dpg_config (include/smarties_hip_dpg.h)
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("targetDelay", C.c_double)]
+
+
 ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2    # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
 ROLLOUT_MAX_ENV = 65536
 
@@ -282,6 +286,14 @@ class CApi:
             "create_dqn": (C.c_int, [C.POINTER(HlConfig), C.POINTER(DqnConfig), pi32, C.POINTER(P)]),
             "dqn_get_target": (C.c_int, [P, pf]),
             "dqn_set_target": (C.c_int, [P, pf]),
+            # include/smarties_hip_dpg.h (product library only)
+            "create_dpg": (C.c_int, [C.POINTER(HlConfig), C.POINTER(DpgConfig), C.POINTER(P)]),
+            "dpg_critic_num_params": (C.c_int64, [P]),
+            "dpg_get_critic": (C.c_int, [P, pf, pf, pf]),
+            "dpg_set_critic": (C.c_int, [P, pf, pf, pf]),
+            "dpg_get_target": (C.c_int, [P, C.c_int32, pf]),
+            "dpg_set_target": (C.c_int, [P, C.c_int32, pf]),
+            "dpg_readback": (C.c_int, [P, C.c_int32, C.POINTER(C.c_double), C.c_int64]),
         }.items():
             if self.has(name):
                 f = self.fn(name)
@@ -318,6 +330,14 @@ def create_dqn(api, targetDelay, values, **kw):
     return Learner(api, make_config(**kw), values=values, dqn=DqnConfig(C.sizeof(DqnConfig), 0, float(targetDelay)))
 
 
+DPG_MAX_DIMA = 16      # HL_DPG_MAX_DIMA
+
+
+def create_dpg(api, targetDelay, **kw):
+    """A DPG learner (hl_create_dpg, include/smarties_hip_dpg.h): make_config(**kw) and the reference's targetDelay setting, for both nets."""
+    return Learner(api, make_config(**kw), dpg=DpgConfig(C.sizeof(DpgConfig), 0, float(targetDelay)))
+
+
 def create_discrete(api, values, **kw):
     """A learner for discrete actions of len(values) variables with values[i] options each (hl_create_discrete): make_config(**kw) with
     dimA and n_options derived from `values`."""
@@ -328,13 +348,15 @@ def create_discrete(api, values, **kw):
 class Learner:
     """Thin object wrapper over one hl_learner handle (names follow include/smarties_hip.h)."""
 
-    def __init__(self, api, cfg, values=None, naf=None, dqn=None):
+    def __init__(self, api, cfg, values=None, naf=None, dqn=None, dpg=None):
         """values: the option counts of cfg.dimA discrete action variables (hl_create_discrete); naf: a NafConfig (hl_create_naf);
-        neither: hl_create.  dqn: a DqnConfig beside `values` (hl_create_dqn)."""
+        neither: hl_create.  dqn: a DqnConfig beside `values` (hl_create_dqn); dpg: a DpgConfig (hl_create_dpg)."""
         self.api, self.cfg = api, cfg
         self.h = C.c_void_p()
         if naf is not None:
             rc = api.fn("create_naf")(C.byref(cfg), C.byref(naf), C.byref(self.h))
+        elif dpg is not None:
+            rc = api.fn("create_dpg")(C.byref(cfg), C.byref(dpg), C.byref(self.h))
         elif dqn is not None:
             v = np.ascontiguousarray(values, dtype=np.int32)
             rc = api.fn("create_dqn")(C.byref(cfg), C.byref(dqn), _ptr(v, C.c_int32), C.byref(self.h))
@@ -353,6 +375,7 @@ class Learner:
         _LIVE.add(self)
         self.nParams = api.fn("num_params")(self.h)
         self.nOut = api.fn("num_outputs")(self.h)
+        self.nCritic = api.fn("dpg_critic_num_params")(self.h) if dpg is not None else 0      # the critic's padded blob (hl_create_dpg)
         self.dS, self.dA = cfg.dimS, cfg.dimA
         self.dIn = cfg.dimS * (1 + cfg.nAppendedObs)      # network input: the observed state and the appended past ones
         self.nOptions = cfg.n_options                      # discrete head: options (one variable, or the product over hl_create_discrete's)
@@ -411,6 +434,33 @@ class Learner:
         w = _f32(w)
         assert w.size == self.nParams
         self._ck(self.api.fn("dqn_set_target")(self.h, _ptr(w, C.c_float)))
+
+    def dpg_get_critic(self):
+        w, m1, m2 = [np.zeros(self.nCritic, np.float32) for _ in range(3)]
+        self._ck(self.api.fn("dpg_get_critic")(self.h, _ptr(w, C.c_float), _ptr(m1, C.c_float), _ptr(m2, C.c_float)))
+        return w, m1, m2
+
+    def dpg_set_critic(self, w=None, m1=None, m2=None):
+        w, m1, m2 = [None if a is None else _f32(a) for a in (w, m1, m2)]
+        for a in (w, m1, m2):
+            assert a is None or a.size == self.nCritic
+        self._ck(self.api.fn("dpg_set_critic")(self.h, _ptr(w, C.c_float), _ptr(m1, C.c_float), _ptr(m2, C.c_float)))
+
+    def dpg_get_target(self, which):
+        w = np.zeros(self.nCritic if which else self.nParams, np.float32)
+        self._ck(self.api.fn("dpg_get_target")(self.h, which, _ptr(w, C.c_float)))
+        return w
+
+    def dpg_set_target(self, which, w):
+        w = _f32(w)
+        assert w.size == (self.nCritic if which else self.nParams)
+        self._ck(self.api.fn("dpg_set_target")(self.h, which, _ptr(w, C.c_float)))
+
+    def dpg_readback(self, what):
+        """hl_dpg_readback: 0 Q~_t, 1 Q~_next, 2 dQ~/da [B][dA], 3 q, 4 the critic's output gradient, 5 its summed weight gradient"""
+        out = np.zeros(self.B * self.dA if what == 2 else (self.nCritic if what == 5 else self.B), np.float64)
+        self._ck(self.api.fn("dpg_readback")(self.h, what, _ptr(out, C.c_double), out.size))
+        return out.reshape(self.B, self.dA) if what == 2 else out
 
     def get_params(self):
         w, m1, m2 = [np.zeros(self.nParams, np.float32) for _ in range(3)]

@@ -370,6 +370,35 @@ struct DqnHeadArgs {
   const float* tgtParams;           // the target blob, layout of h.params (hasTgt)
 };
 hipError_t launch_head_dqn(const DqnHeadArgs& a, int maxRows, hipStream_t s);
+// DPG learners (dpgt.hip; include/smarties_hip_dpg.h): the target chain Q~(s, mu~(s)) of both target nets on s_t and s_{t+1} with the
+// gradient of Q~_t with respect to the action input as ONE launch, the head on the live nets' last hidden blocks, the gather of the
+// critic's input rows, and Adam with the target update over both nets
+constexpr int DPG_MAX_DIMA = 16, DPG_MAX_WIDTH = 512;
+struct DpgLayer { int nIn, size, ldW, hasRes, resW; long long indW, indB, indWr, indBr; };
+struct DpgNetDesc { int nHidden, func, ldWo; long long indWo, indBo; DpgLayer L[HL_MAX_HIDDEN]; };
+struct DpgTargetArgs {
+  DevReplay rp; const long long* slot;      // the minibatch's slot table
+  int B, dS, dA, outFuncA;
+  const float* Wa; const float* Wc;         // the TARGET blobs of the actor and of the critic
+  DpgNetDesc actor, critic;
+  int ld;                                   // pitch of the two activation tiles in LDS
+  float* qT; float* qN; float* dQda;        // [B], [B], [B][DPG_MAX_DIMA]
+};
+size_t dpg_target_lds(const DpgTargetArgs& a);      // bytes of LDS the launch needs (hl_create_dpg refuses what exceeds 160 KB)
+hipError_t launch_dpg_target(const DpgTargetArgs& a, hipStream_t s);
+struct DpgHeadArgs {
+  HeadArgs h;                               // the actor: nDense = dA outputs, nOut = 2 dA
+  const float* cYin; const float* cX; const float* cY; int cH, cLd, cFunc;      // the critic's last hidden block
+  const float* cW; long long cIndWo, cIndBo; int cLdWo;
+  float* cDOut; int cLdDo; float* cDres; float* cD;
+  const float* qT; const float* qN; const float* dQda;
+  double* cQ; double* cG;                   // [B] q and the critic's output gradient (hl_dpg_readback)
+  double gamma, explNoise;
+};
+hipError_t launch_head_dpg(const DpgHeadArgs& a, hipStream_t s);
+hipError_t launch_dpg_critic_gather(const DevReplay& rp, const long long* slot, const float* X0, int ldX0, float* Xc, int ldXc, int dS, int dA, int B, hipStream_t s);
+struct DpgAdamArgs { AdamArgs a[2]; float* T[2]; float etaMul[2]; int mode; double alpha; };      // [0] actor, [1] critic
+hipError_t launch_dpg_adam_target(const DpgAdamArgs& a, hipStream_t s);
 // the head launch beyond 64 options (headw.hip: head_wide_kernel); launch_head hands them over
 hipError_t launch_head_wide(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
 hipError_t launch_fused(const FusedArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);

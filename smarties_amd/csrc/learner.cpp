@@ -35,6 +35,7 @@
 #include "../../include/smarties_hip_discrete.h"
 #include "../../include/smarties_hip_naf.h"
 #include "../../include/smarties_hip_dqn.h"
+#include "../../include/smarties_hip_dpg.h"
 
 using namespace hl;
 
@@ -42,6 +43,7 @@ using namespace hl;
 #include "convg_exec.h"
 #include "naf_exec.h"
 #include "dqn_exec.h"
+#include "dpg_exec.h"
 #include "step_exec.h"
 
 // =================================================================================================
@@ -65,9 +67,16 @@ const char* hl_last_error(const hl_learner* h) { return h ? h->err.c_str() : "nu
 constexpr int HL_ADV_QUADRATIC = 3;      // internal: Quadratic_advantage (no value of the public enumeration)
 static_assert(HL_NAF_MAX_DIMA == NAF_MAX_DIMA, "the header's cap is the head kernel's");
 // dqn != nullptr: hl_create_dqn (include/smarties_hip_dqn.h) -- hl_create_discrete's variables, the caller's adv_kind is ignored, the head is headdq.hip's
-static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* discValues, hl_learner** out, const hl_naf_config* naf = nullptr, const hl_dqn_config* dqn = nullptr) {
+// dpg != nullptr: hl_create_dpg (include/smarties_hip_dpg.h) -- the caller's adv_kind is ignored, the handle's network is the actor, the critic is dpg_exec.h's
+static_assert(HL_DPG_MAX_DIMA == DPG_MAX_DIMA, "the header's cap is the target kernel's");
+static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* discValues, hl_learner** out, const hl_naf_config* naf = nullptr, const hl_dqn_config* dqn = nullptr,
+                         const hl_dpg_config* dpg = nullptr) {
   if (!cfgIn || !out) return HL_ERR_BAD_ARG;
   hl_config cfgNaf;
+  if (dpg) {
+    if (dpg->struct_size != (int32_t)sizeof(hl_dpg_config) || cfgIn->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
+    cfgNaf = *cfgIn; cfgNaf.adv_kind = HL_ADV_ZERO; cfgIn = &cfgNaf;      // (checked below as the continuous-action configuration it is)
+  }
   if (dqn) {
     if (dqn->struct_size != (int32_t)sizeof(hl_dqn_config) || cfgIn->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
     cfgNaf = *cfgIn; cfgNaf.adv_kind = HL_ADV_DISCRETE; cfgIn = &cfgNaf;      // (checked below as the discrete-action configuration it is)
@@ -135,6 +144,19 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     if (cfg->dimA > HL_NAF_MAX_DIMA) return refuse(out, "NAF: dimA beyond 17 (the head holds 1 + 153 + 17 dense outputs in three register slots per lane, headq.hip)");
     if (cfg->nAppendedObs > 0 || cfg->dimS > 512 || cfg->batchSize > 1024) return refuse(out, "NAF: appended observations, states beyond 512 components and batches beyond 1024 are not served (the next states' rows are gathered beside the sampler's)");
   }
+  if (dpg) {      // what the DPG step is wired for (include/smarties_hip_dpg.h)
+    if (cfg->returnsEstimator != HL_RET_NONE) return refuse(out, "DPG: return estimators other than \"none\" are not served (the target is r + gamma Q~(s', mu~(s')) of the target launch)");
+    if (cfg->nn_type != HL_NN_FFNN || cfg->encoder_rnn) return refuse(out, "DPG: recurrent layers are not served (feed-forward dense nets only)");
+    if (cfg->n_conv > 0) return refuse(out, "DPG: convolutions are not served (feed-forward dense nets only)");
+    if (cfg->n_ranks > 1) return refuse(out, "DPG: one replica only (the critic and the target weights have no exchange)");
+    if (cfg->dimA > HL_DPG_MAX_DIMA) return refuse(out, "DPG: dimA beyond 16 (the mean is one 16-column tile behind the state in the target launch, dpgt.hip)");
+    if (cfg->nAppendedObs > 0 || cfg->dimS > 512 || cfg->batchSize > 1024) return refuse(out, "DPG: appended observations, states beyond 512 components and batches beyond 1024 are not served (the target launch gathers its rows from the replay)");
+    for (int j = 0; j < cfg->n_hidden; ++j) if (cfg->hidden[j] > DPG_MAX_WIDTH) return refuse(out, "DPG: hidden layers beyond 512 units are not served (the target launch holds a layer's 16 rows in LDS, dpgt.hip)");
+    // (the reference builds ONE encoder under both nets -- createEncoder, Learner_approximator.cpp:149-166 --: the critic's input is
+    //  encoder(s) | action and both nets' gradients meet in its weights; a private copy per net would train another model)
+    if (cfg->n_encoder > 0) return refuse(out, "DPG: encoder layers are not served (the reference shares one encoder between the actor and the critic; the two nets here have no common layers)");
+    if (dpgTargetLdsOf(*cfg) > 160 * 1024) return refuse(out, "DPG: the critic layers' activation derivatives of 16 rows do not fit the target launch's 160 KB of LDS (dpgt.hip: two 512-wide layers, six 256-wide ones)");
+  }
   if (dqn) {      // what the DQN step is wired for (include/smarties_hip_dqn.h)
     if (cfg->nn_type != HL_NN_FFNN || cfg->encoder_rnn) return refuse(out, "DQN: recurrent layers are not served (feed-forward dense nets only)");
     if (cfg->n_conv > 0) return refuse(out, "DQN: convolutions are not served (feed-forward dense nets only)");
@@ -183,6 +205,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
   h->cfg = *cfg;
   if (naf) { h->naf = true; h->tgtDelay = naf->targetDelay; h->cfg.adv_kind = HL_ADV_QUADRATIC; h->useGraph = false; }      // (eager steps: the target path has no riders)
   if (dqn) { h->dqn = true; h->tgtDelay = dqn->targetDelay; h->useGraph = false; }      // (adv_kind stays HL_ADV_DISCRETE: labels, stored policies and their checks are hl_create_discrete's)
+  if (dpg) { h->dpg = true; h->tgtDelay = dpg->targetDelay; h->useGraph = false; }      // (adv_kind HL_ADV_ZERO: a continuous policy without advantage outputs; buildNet drops the value column)
   if (cfg->n_encoder > 0) {     // createEncoder: the encoder layers are the first hidden layers of the one network (Learner_approximator.cpp:149-166)
     int n = 0;
     for (int j = 0; j < cfg->n_encoder; ++j) if (cfg->encoder[j] > 0) h->cfg.hidden[n++] = cfg->encoder[j];
@@ -303,6 +326,16 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
   if (hasTargetNet(h)) {
     HIPCK(devAlloc(&h->Wtgt, (size_t)h->nParams + PARAM_TAIL));
     HIPCK(hipMemset(h->Wtgt, 0, ((size_t)h->nParams + PARAM_TAIL) * sizeof(float)));
+    if (h->dpg) {      // the critic; the target launch gathers its own rows and keeps its activations in LDS (dpgt.hip)
+      const int rc2 = dpgBuildCritic(h); if (rc2) return rc2;
+      hl_learner::DpgCritic& c = h->critic;
+      c.tgt = DpgTargetArgs{}; c.tgt.dS = h->dS; c.tgt.dA = h->dA; c.tgt.outFuncA = h->cfg.nnOutputFunc;
+      c.tgt.actor = dpgDesc(h->hid, h->nHidden, h->indWo, h->indBo, h->ldWo); c.tgt.critic = dpgDesc(c.hid, c.nHidden, c.indWo, c.indBo, c.ldWo);
+      int need = std::max(h->dS + 16, h->dS + h->dA);
+      for (int j = 0; j < h->nHidden; ++j) need = std::max(need, h->hid[j].size);
+      c.tgt.ld = (int)roundUp(need, 16) + 4;
+      if (dpg_target_lds(c.tgt) > 160 * 1024) return fail(h, HL_ERR_UNSUPPORTED, "DPG: the critic layers' activation derivatives of 16 rows do not fit the target launch's 160 KB of LDS (dpgt.hip)");
+    } else
     if (cfg->returnsEstimator == HL_RET_NONE) {      // the next states' rows, the target net's activations, V_tgt per row
       HIPCK(devAlloc(&h->nafX1, (size_t)h->Mmax * h->ldX0)); HIPCK(hipMemset(h->nafX1, 0, (size_t)h->Mmax * h->ldX0 * sizeof(float)));
       if (h->naf) HIPCK(devAlloc(&h->nafVtgt, (size_t)B));
@@ -569,6 +602,58 @@ int hl_naf_set_target(hl_learner* h, const float* w) { return targetSet(h, h && 
 int hl_dqn_get_target(hl_learner* h, float* w) { return targetGet(h, h && h->dqn, w); }
 int hl_dqn_set_target(hl_learner* h, const float* w) { return targetSet(h, h && h->dqn, w); }
 
+int hl_create_dpg(const hl_config* cfg, const hl_dpg_config* dpg, hl_learner** out) {
+  if (!dpg) return HL_ERR_BAD_ARG;
+  return createLearner(cfg, 0, nullptr, out, nullptr, nullptr, dpg);
+}
+int64_t hl_dpg_critic_num_params(const hl_learner* h) { return h && h->dpg && h->critic.W ? h->critic.nParams : -1; }
+// copies between the caller's arrays and the critic's (NULL = skip); toHost: get
+static int dpgCriticCopy(hl_learner* h, float* const host[3], bool toHost) {
+  if (!h || !h->dpg || !h->critic.W) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  float* dev[3] = {h->critic.W, h->critic.M1, h->critic.M2};
+  const size_t n = (size_t)h->critic.nParams * sizeof(float);
+  for (int i = 0; i < 3; ++i) if (host[i]) {
+    if (toHost) HIPCK(hipMemcpyAsync(host[i], dev[i], n, hipMemcpyDeviceToHost, h->stream));
+    else HIPCK(hipMemcpyAsync(dev[i], host[i], n, hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCK(hipStreamSynchronize(h->stream));
+  return HL_OK;
+}
+int hl_dpg_get_critic(hl_learner* h, float* w, float* m1, float* m2) { float* const p[3] = {w, m1, m2}; return dpgCriticCopy(h, p, true); }
+int hl_dpg_set_critic(hl_learner* h, const float* w, const float* m1, const float* m2) {
+  float* const p[3] = {const_cast<float*>(w), const_cast<float*>(m1), const_cast<float*>(m2)}; return dpgCriticCopy(h, p, false);
+}
+int hl_dpg_get_target(hl_learner* h, int32_t which, float* w) {
+  if (!h || !w || !h->dpg || !h->Wtgt || !h->critic.Wtgt || which < 0 || which > 1) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  HIPCK(hipMemcpyAsync(w, which ? h->critic.Wtgt : h->Wtgt, (size_t)(which ? h->critic.nParams : h->nParams) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return HL_OK;
+}
+int hl_dpg_set_target(hl_learner* h, int32_t which, const float* w) {
+  if (!h || !w || !h->dpg || !h->Wtgt || !h->critic.Wtgt || which < 0 || which > 1) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  HIPCK(hipMemcpyAsync(which ? h->critic.Wtgt : h->Wtgt, w, (size_t)(which ? h->critic.nParams : h->nParams) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return HL_OK;
+}
+int hl_dpg_readback(hl_learner* h, int32_t what, double* dst, int64_t cap) {
+  if (!h || !dst || !h->dpg || !h->critic.W || what < 0 || what > 5) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  const hl_learner::DpgCritic& c = h->critic; const int B = h->B;
+  const int64_t n = what == 2 ? (int64_t)B * h->dA : (what == 5 ? c.nParams : B);
+  if (cap < n) return HL_ERR_BAD_ARG;
+  HIPCK(hipStreamSynchronize(h->stream));
+  if (what == 3 || what == 4) { HIPCK(hipMemcpy(dst, what == 3 ? c.q : c.gOut, (size_t)B * sizeof(double), hipMemcpyDeviceToHost)); return HL_OK; }
+  const float* src = what == 0 ? c.qT : (what == 1 ? c.qN : (what == 2 ? c.dQda : c.G));
+  std::vector<float> buf(what == 2 ? (size_t)B * DPG_MAX_DIMA : (size_t)n);
+  HIPCK(hipMemcpy(buf.data(), src, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
+  if (what == 2) { for (int b = 0; b < B; ++b) for (int i = 0; i < h->dA; ++i) dst[(size_t)b * h->dA + i] = buf[(size_t)b * DPG_MAX_DIMA + i]; }
+  else for (int64_t i = 0; i < n; ++i) dst[i] = buf[(size_t)i];
+  return HL_OK;
+}
+
 int hl_destroy(hl_learner* h) {
   if (!h) return HL_OK;
   h->mu.lock();      // (released before the handle goes away; no other thread may still be using it)
@@ -605,6 +690,7 @@ int hl_destroy(hl_learner* h) {
   for (void* q : {(void*)h->tmT, (void*)h->tmSteps, (void*)h->tmNext, (void*)h->tmCtr, (void*)h->tmP}) if (q) hipFree(q);
   for (void* p : ptrs) if (p) hipFree(p);
   for (float* q : {h->Wtgt, h->nafX1, h->nafVtgt}) if (q) hipFree(q);
+  if (h->dpg) dpgFreeCritic(h);
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* q : {h->tgtX[j], h->tgtY[j], h->tgtR[j], h->nxtX[j], h->nxtY[j], h->nxtR[j]}) if (q) hipFree(q);
   for (int l = 0; l < h->nConv; ++l) { ConvGeo& g = h->cg[l];
     if (l != h->nConv - 1) for (float* p : {g.X, g.Y, g.D}) if (p) hipFree(p);
@@ -704,6 +790,21 @@ int hl_init_weights(hl_learner* h) {
   }
   HIPCK(hipMemcpyAsync(h->W, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (hasTargetNet(h)) { HIPCK(hipMemcpyAsync(h->Wtgt, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream)); h->tgtCnt = 0; }      // (Optimizer.cpp:233: the target weights start as a copy)
+  if (h->dpg) {      // the critic, built and initialised behind the actor (the DPG constructor): the same rules, Linear output, biases zero
+    hl_learner::DpgCritic& c = h->critic;
+    std::vector<float> Wc((size_t)c.nParams, 0.f);
+    for (int j = 0; j < c.nHidden; ++j) {
+      const DevHidden& d = c.hid[j]; const float init = (float)initFactor(d.func, d.nIn, d.size);
+      for (int i = 0; i < d.nIn; ++i) for (int o = 0; o < d.size; ++o) Wc[d.indW + o + (long long)d.ldW * i] = uni(-init, init);
+      if (d.hasRes) for (int o = 0; o < d.size; ++o) { Wc[d.indWr + o] = 1.f; Wc[d.indBr + o] = 0.f; }
+    }
+    const int Hc = c.hid[c.nHidden - 1].size; const double iFac = h->cfg.outWeightsPrefac;
+    const float init = (float)((iFac > 0 ? iFac : 1) * initFactor(HL_FUNC_LINEAR, Hc, 1));
+    for (int i = 0; i < Hc; ++i) Wc[c.indWo + (long long)c.ldWo * i] = uni(-init, init);
+    HIPCK(hipMemcpyAsync(c.W, Wc.data(), Wc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipMemcpyAsync(c.Wtgt, Wc.data(), Wc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));      // (Wc goes out of scope)
+  }
   h->convPrepStale = true;
   std::memcpy(s.rng, g.x, sizeof(g.x)); s.rngPos = g.p;
   HIPCK(hipMemcpyAsync(&h->sc->rng[0], s.rng, sizeof(s.rng), hipMemcpyHostToDevice, h->stream));

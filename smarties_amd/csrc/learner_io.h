@@ -311,9 +311,9 @@ int hl_restart_memory(hl_learner* h, const char* base, int32_t rank) {
 }
 
 // ---- checkpoint in the reference's format (Network::save / restart, Network/Network.cpp:22-68) ----
-static void packBlob(const hl_learner* h, const std::vector<float>& P, std::vector<float>& out) {
+static void packBlob(const std::vector<hl_learner::LayDesc>& lay, const std::vector<float>& P, std::vector<float>& out) {
   out.clear();
-  for (const auto& l : h->lay) {
+  for (const auto& l : lay) {
     const float* W = P.data() + l.indW; const float* Bv = P.data() + l.indB;
     if (l.type == 1) {
       for (int i = 0; i < l.nIn; ++i) for (int o = 0; o < l.size; ++o) out.push_back(W[o + (long long)l.ld * i]);
@@ -330,9 +330,9 @@ static void packBlob(const hl_learner* h, const std::vector<float>& P, std::vect
     } else for (int o = 0; o < l.size; ++o) out.push_back(Bv[o]);
   }
 }
-static void unpackBlob(const hl_learner* h, const std::vector<float>& in, std::vector<float>& P) {
+static void unpackBlob(const std::vector<hl_learner::LayDesc>& lay, const std::vector<float>& in, std::vector<float>& P) {
   size_t k = 0;
-  for (const auto& l : h->lay) {
+  for (const auto& l : lay) {
     float* W = P.data() + l.indW; float* Bv = P.data() + l.indB;
     if (l.type == 1) {
       for (int i = 0; i < l.nIn; ++i) for (int o = 0; o < l.size; ++o) W[o + (long long)l.ld * i] = in[k++];
@@ -349,18 +349,14 @@ static void unpackBlob(const hl_learner* h, const std::vector<float>& in, std::v
     } else for (int o = 0; o < l.size; ++o) Bv[o] = in[k++];
   }
 }
-int hl_save(hl_learner* h, const char* base) {
-  if (!h || !base) return HL_ERR_BAD_ARG;
-  HL_LOCK(h);
-  std::vector<float> P[4]; for (auto& v : P) v.resize((size_t)h->nParams);
-  int rc = hl_get_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
-  if (hasTargetNet(h)) { rc = h->naf ? hl_naf_get_target(h, P[3].data()) : hl_dqn_get_target(h, P[3].data()); if (rc) return rc; }      // AdamOptimizer::save: the target weights beside the weights (Optimizer.cpp:188-189)
-  const char* suf[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
+// the blobs of one network: <base>_weights, _1stMom, _2ndMom and -- nBlobs = 4 -- _tgt_weights
+static const char* const BLOB_SUFFIX[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
+static int saveBlobs(hl_learner* h, const std::vector<hl_learner::LayDesc>& lay, const std::string& base, const std::vector<float>* P, int nBlobs) {
   std::vector<float> buf;
-  for (int b = 0; b < (hasTargetNet(h) ? 4 : 3); ++b) {
-    packBlob(h, P[b], buf);
+  for (int b = 0; b < nBlobs; ++b) {
+    packBlob(lay, P[b], buf);
     // like Network::save: write <name>_backup.raw first, then copy it over <name>.raw
-    const std::string name = std::string(base) + suf[b] + ".raw", back = std::string(base) + suf[b] + "_backup.raw";
+    const std::string name = base + BLOB_SUFFIX[b] + ".raw", back = base + BLOB_SUFFIX[b] + "_backup.raw";
     for (const std::string& fn : {back, name}) {
       FILE* f = fopen(fn.c_str(), "wb");
       if (!f) return fail(h, HL_ERR_IO, "Unable to save into file " + fn);
@@ -371,29 +367,58 @@ int hl_save(hl_learner* h, const char* base) {
   }
   return HL_OK;
 }
+// ... read into P (files that are missing leave their array as it is; the weights' file must exist); *tgtRead: the fourth was there
+static int loadBlobs(hl_learner* h, const std::vector<hl_learner::LayDesc>& lay, const std::string& base, std::vector<float>* P, int nBlobs, bool* tgtRead) {
+  size_t n = 0;
+  for (const auto& l : lay) n += l.type == 1 ? (size_t)l.size * (l.nIn + 1) : (l.type == 2 ? 2 * (size_t)l.size :
+                                  (l.type == 4 || l.type == 5 ? (size_t)l.ld * (l.nIn + l.size + 1) :
+                                   (l.type == 6 ? (size_t)l.nIn + l.size : (size_t)l.size)));
+  for (int b = 0; b < nBlobs; ++b) {
+    const std::string name = base + BLOB_SUFFIX[b] + ".raw";
+    FILE* f = fopen(name.c_str(), "rb");
+    if (!f) { if (b == 0) return fail(h, HL_ERR_IO, "Parameters restart file " + name + " not found."); continue; }
+    std::vector<float> buf(n + 1);
+    const size_t got = fread(buf.data(), sizeof(float), n + 1, f); fclose(f);
+    if (got != n) return fail(h, HL_ERR_IO, "Mismatch in restarted file " + name);
+    buf.resize(n); unpackBlob(lay, buf, P[b]);
+    if (b == 3) *tgtRead = true;
+  }
+  return HL_OK;
+}
+int hl_save(hl_learner* h, const char* base) {
+  if (!h || !base) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  std::vector<float> P[4]; for (auto& v : P) v.resize((size_t)h->nParams);
+  int rc = hl_get_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+  if (h->naf || h->dqn) { rc = h->naf ? hl_naf_get_target(h, P[3].data()) : hl_dqn_get_target(h, P[3].data()); if (rc) return rc; }      // AdamOptimizer::save: the target weights beside the weights (Optimizer.cpp:188-189)
+  if (h->dpg) { rc = hl_dpg_get_target(h, 0, P[3].data()); if (rc) return rc; }
+  rc = saveBlobs(h, h->lay, base, P, hasTargetNet(h) ? 4 : 3); if (rc) return rc;
+  if (h->dpg) {      // the critic's four blobs beside the actor's: <base>_critic_weights ...
+    for (auto& v : P) v.assign((size_t)h->critic.nParams, 0.f);
+    rc = hl_dpg_get_critic(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+    rc = hl_dpg_get_target(h, 1, P[3].data()); if (rc) return rc;
+    return saveBlobs(h, h->criticLay, std::string(base) + "_critic", P, 4);
+  }
+  return HL_OK;
+}
 int hl_restart(hl_learner* h, const char* base) {
   if (!h || !base) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   std::vector<float> P[4]; for (auto& v : P) v.resize((size_t)h->nParams);
   int rc = hl_get_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
   bool tgtRead = false;
-  size_t n = 0;
-  for (const auto& l : h->lay) n += l.type == 1 ? (size_t)l.size * (l.nIn + 1) : (l.type == 2 ? 2 * (size_t)l.size :
-                                  (l.type == 4 || l.type == 5 ? (size_t)l.ld * (l.nIn + l.size + 1) :
-                                   (l.type == 6 ? (size_t)l.nIn + l.size : (size_t)l.size)));
-  const char* suf[4] = {"_weights", "_1stMom", "_2ndMom", "_tgt_weights"};
-  for (int b = 0; b < (hasTargetNet(h) ? 4 : 3); ++b) {
-    const std::string name = std::string(base) + suf[b] + ".raw";
-    FILE* f = fopen(name.c_str(), "rb");
-    if (!f) { if (b == 0) return fail(h, HL_ERR_IO, "Parameters restart file " + name + " not found."); continue; }
-    std::vector<float> buf(n + 1);
-    const size_t got = fread(buf.data(), sizeof(float), n + 1, f); fclose(f);
-    if (got != n) return fail(h, HL_ERR_IO, "Mismatch in restarted file " + name);
-    buf.resize(n); unpackBlob(h, buf, P[b]);
-    if (b == 3) tgtRead = true;
-  }
+  rc = loadBlobs(h, h->lay, base, P, hasTargetNet(h) ? 4 : 3, &tgtRead); if (rc) return rc;
   rc = hl_set_params(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
-  if (hasTargetNet(h)) { const float* t = tgtRead ? P[3].data() : P[0].data(); return h->naf ? hl_naf_set_target(h, t) : hl_dqn_set_target(h, t); }      // a missing file: a copy of the weights (Optimizer.cpp:207-209)
+  if (h->naf || h->dqn) { const float* t = tgtRead ? P[3].data() : P[0].data(); return h->naf ? hl_naf_set_target(h, t) : hl_dqn_set_target(h, t); }      // a missing file: a copy of the weights (Optimizer.cpp:207-209)
+  if (h->dpg) {      // the same rule for both nets; the critic's files at <base>_critic
+    rc = hl_dpg_set_target(h, 0, tgtRead ? P[3].data() : P[0].data()); if (rc) return rc;
+    for (auto& v : P) v.assign((size_t)h->critic.nParams, 0.f);
+    rc = hl_dpg_get_critic(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+    tgtRead = false;
+    rc = loadBlobs(h, h->criticLay, std::string(base) + "_critic", P, 4, &tgtRead); if (rc) return rc;
+    rc = hl_dpg_set_critic(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+    return hl_dpg_set_target(h, 1, tgtRead ? P[3].data() : P[0].data());
+  }
   return HL_OK;
 }
 

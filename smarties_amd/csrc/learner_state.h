@@ -159,6 +159,19 @@ struct hl_learner {
   bool dqn = false;
   float *nxtX[HL_MAX_HIDDEN]{}, *nxtY[HL_MAX_HIDDEN]{}, *nxtR[HL_MAX_HIDDEN]{};
   std::vector<int> nxtFwdIdx, nxtFwdBlocks;
+  // DPG learners (hl_create_dpg, include/smarties_hip_dpg.h): the handle's network is the actor (Wtgt its target weights); the critic is
+  // a second net -- blob, moments, gradient, target weights, activations and problem records of its own (dpg_exec.h).  One set of
+  // records: its input rows are gathered per step from the minibatch buffer in use
+  bool dpg = false;
+  struct DpgCritic {
+    int nHidden = 0, dIn = 0, ldX0 = 0, ldWo = 8, ldDo = 16;
+    DevHidden hid[HL_MAX_HIDDEN]{};
+    long long nParams = 0, indWo = 0, indBo = 0;
+    float *W = nullptr, *M1 = nullptr, *M2 = nullptr, *G = nullptr, *Wtgt = nullptr, *X0 = nullptr, *dOut = nullptr;
+    float *qT = nullptr, *qN = nullptr, *dQda = nullptr; double *q = nullptr, *gOut = nullptr;      // the target launch's outputs; q and the output gradient of the last step
+    std::vector<int> fwdIdx, fwdBlocks, dxIdx, dxBlocks; int dwIdx = 0, dwCount = 0, dwBlocks = 0;
+    hl::DpgTargetArgs tgt{};      // the target launch's record (slot table and B set per step)
+  } critic;
   DevScalars* sc = nullptr;
   DevReplay rp{};
   StepBuf buf[2];                          // double-buffered minibatch workspace (see step_exec.h)
@@ -235,6 +248,7 @@ struct hl_learner {
   long long nCollectives = 0;              // RCCL calls issued or captured so far (tests: every path speaks the same wire protocol)
   struct LayDesc { int type, nIn, size, ld; long long indW, indB; };   // 1 dense, 2 parametric residual, 3 ParamLayer, 4 LSTM, 5 MGU (ld = gates x cells), 6 convolution (nIn = filter floats, size = biases)
   std::vector<LayDesc> lay;       // trainable layers in network order (checkpoint packing, Network::save)
+  std::vector<LayDesc> criticLay; // ... of a DPG learner's critic
   bool exchGraph = true;     // replica exchanges may be captured into the replayed graphs (cleared if a capture fails)
   bool xcdSafe = false;      // fused kernel: panel exchange through agent-scope accesses (workgroup b was NOT found on XCD b % 8, or forced)
   bool fusedOk = false; unsigned* panelCtr = nullptr;   // fused forward/head/dX kernel (fused.hip) usable for this network
@@ -266,8 +280,8 @@ struct hl_learner {
 
 namespace {
 
-// learners that keep target weights (NAF, DQN): the generic launch sequence, eager, Adam with the target update as a launch of its own
-inline bool hasTargetNet(const hl_learner* h) { return h->naf || h->dqn; }
+// learners that keep target weights (NAF, DQN, DPG): the generic launch sequence, eager, Adam with the target update as a launch of its own
+inline bool hasTargetNet(const hl_learner* h) { return h->naf || h->dqn || h->dpg; }
 
 // Exchange windows (hl_xchg_export) are UNCACHED device memory, and uncached memory must never go back to the allocator: on this
 // runtime (ROCm 7.2, gfx950) memory freed after a life as hipDeviceMallocUncached and handed out again by hipMalloc made kernels of
@@ -429,6 +443,7 @@ int buildNet(hl_learner* h) {
   if (h->naf) h->nAdv = c.dimA * (c.dimA + 1) / 2;      // NAF: [V, l x nL, mean] (NAF.cpp:47), the triangle where the Gaussian advantage has its outputs
   h->nDense = 1 + h->nAdv + (discrete ? c.n_options : c.dimA); h->nOut = h->nDense + h->nSig;
   if (h->dqn) { h->nAdv = 0; h->nDense = h->nOut = c.n_options; }      // DQN: the Q values alone (DQN.cpp:52), no value column
+  if (h->dpg) { h->nAdv = 0; h->nDense = c.dimA; h->nOut = 2 * c.dimA; }      // DPG's actor: the mean and the ParamLayer (DPG.cpp:188-191), no value column
   const int outLayer = (int)lw.size();
   lw.push_back(roundUp(h->nDense, 8) * prev); lb.push_back(h->nDense);
   const int paramLayer = h->nSig ? (int)lw.size() : -1;

@@ -254,6 +254,7 @@ int buildProblems(hl_learner* h) {
   };
   nextChain(h->Wtgt, h->tgtX, h->tgtY, h->tgtR, h->tgtFwdIdx, h->tgtFwdBlocks);
   nextChain(h->W, h->nxtX, h->nxtY, h->nxtR, h->nxtFwdIdx, h->nxtFwdBlocks);
+  if (h->dpg) dpgProblems(h, P);      // DPG learners: the critic's forward, input-gradient and weight-gradient records (dpg_exec.h)
   if (h->dProbs) hipFree(h->dProbs);
   h->dProbs = nullptr;
   HIPCK(devAlloc(&h->dProbs, P.size()));
@@ -289,7 +290,7 @@ PostArgs postArgs(hl_learner* h, int parity, int mode) {
   PostArgs pa{}; pa.sc = h->sc; pa.rp = h->rp; pa.bt = h->buf[parity].bt; pa.B = h->B; pa.mode = mode;
   pa.clipImpWeight = h->cfg.clipImpWeight; pa.epsAnneal = h->cfg.epsAnneal; pa.penalTol = h->cfg.penalTol;
   pa.maxObsGlobal = (double)h->maxObsGlobal; pa.batchGlobal = (double)h->Bglobal; pa.nRanks = exchanging(h) ? 2 : 1;   // > 1: use the exchanged counters
-  pa.parity = parity; pa.eta0 = (float)h->cfg.learnrate; pa.aggStaged = h->fusedOk ? 1 : 0; pa.hasAdv = h->nAdv > 0 ? 1 : 0;
+  pa.parity = parity; pa.eta0 = (float)h->cfg.learnrate; pa.aggStaged = h->fusedOk ? 1 : 0; pa.hasAdv = (h->nAdv > 0 || h->dpg) ? 1 : 0;      // (DPG: Q = q of the critic beside V = p)
   pa.cntMsg = wired(h) ? h->G + h->nParams + CNT_MSG_OFFSET : nullptr;
   pa.behind = oneBehind(h) ? 1 : 0;
   return pa;
@@ -536,6 +537,10 @@ int launchHead(hl_learner* h, int parity, hipStream_t s, bool nextSample = false
     if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the DQN head launch");
     return dqnHead(h, ha, parity, adamHyper(h, parity), s);
   }
+  if (h->dpg) {      // dpgt.hip through dpg_exec.h: the critic's launches, the target launch and the head; eager steps, no riders
+    if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the DPG head launch");
+    return dpgHead(h, ha, parity, adamHyper(h, parity), s);
+  }
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   // (recurrent nets have no forward GEMM launches: the whole sampler of the next step rides along the head kernel)
   if (nextSample) {
@@ -717,6 +722,7 @@ int launchAdam(hl_learner* h, int parity) {
   aa.epsAnneal = h->cfg.epsAnneal; aa.parity = parity;
   if (h->naf) return nafAdam(h, aa);      // Adam and the target weights in one launch (naf_exec.h)
   if (h->dqn) return dqnAdam(h, aa);      // ... (dqn_exec.h)
+  if (h->dpg) return dpgAdam(h, aa);      // ... of both nets (dpg_exec.h)
   HIPCK(timed(h, "adam_kernel", h->stream, [&] { return launch_adam(aa, h->stream); }));
   return HL_OK;
 }
@@ -745,6 +751,9 @@ int launchMoments(hl_learner* h) {
 int launchMomentsApply(hl_learner* h, bool bInit, double rRateFac, double* moments = nullptr) {
   MomentsArgs ma{}; ma.sc = h->sc; ma.rp = h->rp; ma.dS = h->dS; ma.moments = moments ? moments : h->dMoments;
   ma.bInit = bInit ? 1 : 0; ma.learnrate = h->cfg.learnrate; ma.epsAnneal = h->cfg.epsAnneal; ma.rRateFac = rRateFac;
+  // DPG: the constructor's `settings.learnrate *= 10` (DPG.cpp:201) is never undone, and the replay reads the same settings object
+  // (Learner.cpp:21-22; MemoryProcessing.cpp:102): the statistics move with ten times the configured rate
+  if (h->dpg) ma.learnrate *= (double)DPG_CRITIC_ETA;
   HIPCK(launch_moments_apply(ma, h->stream));
   return HL_OK;
 }
