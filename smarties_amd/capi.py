@@ -105,6 +105,14 @@ class DpgConfig(C.Structure):      # hl_dpg_config (include/smarties_hip_dpg.h)
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("targetDelay", C.c_double)]
 
 
+class PpoConfig(C.Structure):      # hl_ppo_config (include/smarties_hip_ppo.h)
+    _fields_ = [("struct_size", C.c_int32), ("nEpochs", C.c_int32), ("klDivConstraint", C.c_double), ("n_vars", C.c_int32), ("values", C.c_int32 * 9)]
+
+
+class PpoState(C.Structure):       # hl_ppo_state
+    _fields_ = [("penalCoef", C.c_double), ("DKL_target", C.c_double), ("cntBatch", C.c_int64), ("cntEpoch", C.c_int64), ("stepsLeft", C.c_int64)]
+
+
 ROLLOUT_EVALUATE, ROLLOUT_NO_STORE = 1, 2    # HL_ROLLOUT_EVALUATE, HL_ROLLOUT_NO_STORE: flags of hl_rollout_step
 ROLLOUT_MAX_ENV = 65536
 
@@ -294,6 +302,15 @@ class CApi:
             "dpg_get_target": (C.c_int, [P, C.c_int32, pf]),
             "dpg_set_target": (C.c_int, [P, C.c_int32, pf]),
             "dpg_readback": (C.c_int, [P, C.c_int32, C.POINTER(C.c_double), C.c_int64]),
+            # include/smarties_hip_ppo.h (product library only)
+            "create_ppo": (C.c_int, [C.POINTER(HlConfig), C.POINTER(PpoConfig), C.POINTER(P)]),
+            "ppo_values": (C.c_int, [P, C.c_int32, pf, C.POINTER(C.c_double)]),
+            "ppo_critic_num_params": (C.c_int64, [P]),
+            "ppo_get_critic": (C.c_int, [P, pf, pf, pf]),
+            "ppo_set_critic": (C.c_int, [P, pf, pf, pf]),
+            "ppo_get_state": (C.c_int, [P, C.POINTER(PpoState)]),
+            "ppo_set_state": (C.c_int, [P, C.POINTER(PpoState)]),
+            "ppo_readback": (C.c_int, [P, C.c_int32, C.POINTER(C.c_double), C.c_int64]),
         }.items():
             if self.has(name):
                 f = self.fn(name)
@@ -338,6 +355,21 @@ def create_dpg(api, targetDelay, **kw):
     return Learner(api, make_config(**kw), dpg=DpgConfig(C.sizeof(DpgConfig), 0, float(targetDelay)))
 
 
+PPO_MAX_DIMA = 16      # HL_PPO_MAX_DIMA
+
+
+def create_ppo(api, klDivConstraint, nEpochs, values=None, **kw):
+    """A PPO learner (hl_create_ppo, include/smarties_hip_ppo.h): make_config(**kw), the initial DKL_target, the epochs over a horizon of
+    maxTotObsNum steps and, for discrete actions, the option counts of the action variables."""
+    ppo = PpoConfig(C.sizeof(PpoConfig), int(nEpochs), float(klDivConstraint), 0)
+    if values is not None:
+        kw.update(dimA=len(values), adv_kind=ADV_DISCRETE, n_options=int(np.prod(values, dtype=np.int64)))
+        ppo.n_vars = len(values)
+        for i, v in enumerate(values):
+            ppo.values[i] = int(v)
+    return Learner(api, make_config(**kw), ppo=ppo)
+
+
 def create_discrete(api, values, **kw):
     """A learner for discrete actions of len(values) variables with values[i] options each (hl_create_discrete): make_config(**kw) with
     dimA and n_options derived from `values`."""
@@ -348,15 +380,18 @@ def create_discrete(api, values, **kw):
 class Learner:
     """Thin object wrapper over one hl_learner handle (names follow include/smarties_hip.h)."""
 
-    def __init__(self, api, cfg, values=None, naf=None, dqn=None, dpg=None):
+    def __init__(self, api, cfg, values=None, naf=None, dqn=None, dpg=None, ppo=None):
         """values: the option counts of cfg.dimA discrete action variables (hl_create_discrete); naf: a NafConfig (hl_create_naf);
-        neither: hl_create.  dqn: a DqnConfig beside `values` (hl_create_dqn); dpg: a DpgConfig (hl_create_dpg)."""
+        neither: hl_create.  dqn: a DqnConfig beside `values` (hl_create_dqn); dpg: a DpgConfig (hl_create_dpg);
+        ppo: a PpoConfig (hl_create_ppo)."""
         self.api, self.cfg = api, cfg
         self.h = C.c_void_p()
         if naf is not None:
             rc = api.fn("create_naf")(C.byref(cfg), C.byref(naf), C.byref(self.h))
         elif dpg is not None:
             rc = api.fn("create_dpg")(C.byref(cfg), C.byref(dpg), C.byref(self.h))
+        elif ppo is not None:
+            rc = api.fn("create_ppo")(C.byref(cfg), C.byref(ppo), C.byref(self.h))
         elif dqn is not None:
             v = np.ascontiguousarray(values, dtype=np.int32)
             rc = api.fn("create_dqn")(C.byref(cfg), C.byref(dqn), _ptr(v, C.c_int32), C.byref(self.h))
@@ -376,6 +411,8 @@ class Learner:
         self.nParams = api.fn("num_params")(self.h)
         self.nOut = api.fn("num_outputs")(self.h)
         self.nCritic = api.fn("dpg_critic_num_params")(self.h) if dpg is not None else 0      # the critic's padded blob (hl_create_dpg)
+        if ppo is not None:
+            self.nCritic = api.fn("ppo_critic_num_params")(self.h)
         self.dS, self.dA = cfg.dimS, cfg.dimA
         self.dIn = cfg.dimS * (1 + cfg.nAppendedObs)      # network input: the observed state and the appended past ones
         self.nOptions = cfg.n_options                      # discrete head: options (one variable, or the product over hl_create_discrete's)
@@ -461,6 +498,37 @@ class Learner:
         out = np.zeros(self.B * self.dA if what == 2 else (self.nCritic if what == 5 else self.B), np.float64)
         self._ck(self.api.fn("dpg_readback")(self.h, what, _ptr(out, C.c_double), out.size))
         return out.reshape(self.B, self.dA) if what == 2 else out
+
+    def ppo_get_critic(self):
+        w, m1, m2 = [np.zeros(self.nCritic, np.float32) for _ in range(3)]
+        self._ck(self.api.fn("ppo_get_critic")(self.h, _ptr(w, C.c_float), _ptr(m1, C.c_float), _ptr(m2, C.c_float)))
+        return w, m1, m2
+
+    def ppo_set_critic(self, w=None, m1=None, m2=None):
+        w, m1, m2 = [None if a is None else _f32(a) for a in (w, m1, m2)]
+        for a in (w, m1, m2):
+            assert a is None or a.size == self.nCritic
+        self._ck(self.api.fn("ppo_set_critic")(self.h, _ptr(w, C.c_float), _ptr(m1, C.c_float), _ptr(m2, C.c_float)))
+
+    def ppo_values(self, states):
+        s = _f32(states).reshape(-1, self.dS); out = np.zeros(len(s), np.float64)
+        self._ck(self.api.fn("ppo_values")(self.h, len(s), _ptr(s, C.c_float), _ptr(out, C.c_double)))
+        return out
+
+    def ppo_state(self):
+        st = PpoState()
+        self._ck(self.api.fn("ppo_get_state")(self.h, C.byref(st)))
+        return st
+
+    def ppo_set_state(self, penalCoef, DKL_target, cntBatch=0, cntEpoch=0):
+        st = PpoState(float(penalCoef), float(DKL_target), int(cntBatch), int(cntEpoch), 0)
+        self._ck(self.api.fn("ppo_set_state")(self.h, C.byref(st)))
+
+    def ppo_readback(self, what):
+        """hl_ppo_readback: 0 rho, 1 D_KL, 2 isOff, 3 gain, 4 V, 5 the critic's output gradient, 6 its summed weight gradient"""
+        out = np.zeros(self.nCritic if what == 6 else self.B, np.float64)
+        self._ck(self.api.fn("ppo_readback")(self.h, what, _ptr(out, C.c_double), out.size))
+        return out
 
     def get_params(self):
         w, m1, m2 = [np.zeros(self.nParams, np.float32) for _ in range(3)]

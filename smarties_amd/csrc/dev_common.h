@@ -312,4 +312,20 @@ __device__ __forceinline__ void adamStep(const AdamCoef& c, float g, float& w, f
   w = w + c.eta * (ret + penal);
 }
 
+// element e of Adam over two nets' parameter ranges -- [0] then [1], each with its own learning-rate factor and nnLambda -- and, behind
+// it on the same element, the target weights' update (NAF_TGT_KEEP: none, T is not read): dpg_adam_target_kernel and ppo_adam_kernel
+__device__ __forceinline__ void twoNetAdamElement(const DpgAdamArgs& q, long long e) {
+  const long long n0 = q.a[0].n;
+  const int net = e >= n0 ? 1 : 0; const long long i = e - (net ? n0 : 0);
+  const AdamArgs& a = q.a[net];
+  AdamCoef c; c.eta = a.sc->etaEff[a.parity] * q.etaMul[net]; c.lambda = a.lambda; c.fac = a.fac;
+  float w = a.W[i], m1 = a.M1[i], m2 = a.M2[i];
+  adamStep(c, a.G[i], w, m1, m2);
+  a.W[i] = w; a.M1[i] = m1; a.M2[i] = m2;
+  if (q.mode == NAF_TGT_KEEP) return;
+  float* T = q.T[net];
+  if (q.mode == NAF_TGT_COPY) T[i] = w;
+  else { const float t = T[i]; T[i] = (float)((double)t + q.alpha * (double)(w - t)); }
+}
+
 }  // namespace hl

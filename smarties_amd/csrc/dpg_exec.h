@@ -11,11 +11,12 @@ void setTiles(GemmProblem& p, int& cursor, bool maySplit);      // (step_exec.h)
 
 constexpr float DPG_CRITIC_ETA = 10.f, DPG_CRITIC_LAMBDA = 1e-4f;      // the DPG constructor: learnrate x 10, nnLambda 1e-4 for the critic
 
-// the critic's description by the Builder's rules (buildNet's, for dense layers): the actor's hidden layers on dimS + dimA inputs, one
-// Linear output; the blob's blocks on multiples of 8 floats.  Then its arrays
-int dpgBuildCritic(hl_learner* h) {
+// a critic's description by the Builder's rules (buildNet's, for dense layers): the actor's hidden layers on dIn inputs -- DPG: dimS + dimA,
+// PPO (ppo_exec.h): dimS --, one Linear output; the blob's blocks on multiples of 8 floats.  Then its arrays; withTarget: the target copy
+// and the target launch's outputs (DPG)
+int buildCritic(hl_learner* h, int dIn, bool withTarget) {
   hl_learner::DpgCritic& c = h->critic;
-  c.nHidden = h->nHidden; c.dIn = h->dS + h->dA; c.ldX0 = (int)roundUp(c.dIn, 16);
+  c.nHidden = h->nHidden; c.dIn = dIn; c.ldX0 = (int)roundUp(c.dIn, 16);
   long long tot = 0; int prev = c.dIn;
   auto block = [&](long long n) { const long long at = tot; tot += roundUp(n, 8); return at; };
   h->criticLay.clear();
@@ -32,9 +33,9 @@ int dpgBuildCritic(hl_learner* h) {
   h->criticLay.push_back({1, prev, 1, c.ldWo, c.indWo, c.indBo});
   c.nParams = tot;
   const size_t n = (size_t)c.nParams + PARAM_TAIL; const int B = h->B;
-  for (float** p : {&c.W, &c.M1, &c.M2, &c.G, &c.Wtgt}) HIPCK(devAlloc(p, n));
+  for (float** p : {&c.W, &c.M1, &c.M2, &c.G}) HIPCK(devAlloc(p, n));
   HIPCK(devAlloc(&c.X0, (size_t)B * c.ldX0)); HIPCK(devAlloc(&c.dOut, (size_t)B * c.ldDo));
-  HIPCK(devAlloc(&c.qT, (size_t)B)); HIPCK(devAlloc(&c.qN, (size_t)B)); HIPCK(devAlloc(&c.dQda, (size_t)B * DPG_MAX_DIMA));
+  if (withTarget) { HIPCK(devAlloc(&c.Wtgt, n)); HIPCK(devAlloc(&c.qT, (size_t)B)); HIPCK(devAlloc(&c.qN, (size_t)B)); HIPCK(devAlloc(&c.dQda, (size_t)B * DPG_MAX_DIMA)); }
   HIPCK(devAlloc(&c.q, (size_t)B)); HIPCK(devAlloc(&c.gOut, (size_t)B));
   for (int j = 0; j < c.nHidden; ++j) {
     DevHidden& d = c.hid[j]; const size_t m = (size_t)B * d.ldA;
@@ -43,7 +44,7 @@ int dpgBuildCritic(hl_learner* h) {
   }
   return HL_OK;
 }
-void dpgFreeCritic(hl_learner* h) {
+void freeCritic(hl_learner* h) {
   hl_learner::DpgCritic& c = h->critic;
   for (void* p : {(void*)c.W, (void*)c.M1, (void*)c.M2, (void*)c.G, (void*)c.Wtgt, (void*)c.X0, (void*)c.dOut, (void*)c.qT, (void*)c.qN, (void*)c.dQda, (void*)c.q, (void*)c.gOut}) if (p) hipFree(p);
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* p : {c.hid[j].X, c.hid[j].Y, c.hid[j].Rr, c.hid[j].D, c.hid[j].Dres}) if (p) hipFree(p);

@@ -381,18 +381,8 @@ hipError_t launch_dpg_critic_gather(const DevReplay& rp, const long long* slot, 
 // Adam and the target update (naf_adam_target_kernel's element) over the actor's range, then the critic's: each with its own
 // learning-rate factor and nnLambda
 __global__ __launch_bounds__(256) void dpg_adam_target_kernel(DpgAdamArgs q) {
-  const long long n0 = q.a[0].n, n = n0 + q.a[1].n;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-    const int net = e >= n0 ? 1 : 0; const long long i = e - (net ? n0 : 0);
-    const AdamArgs& a = q.a[net];
-    AdamCoef c; c.eta = a.sc->etaEff[a.parity] * q.etaMul[net]; c.lambda = a.lambda; c.fac = a.fac;
-    float w = a.W[i], m1 = a.M1[i], m2 = a.M2[i];
-    adamStep(c, a.G[i], w, m1, m2);
-    a.W[i] = w; a.M1[i] = m1; a.M2[i] = m2;
-    float* T = q.T[net];
-    if (q.mode == NAF_TGT_COPY) T[i] = w;
-    else if (q.mode == NAF_TGT_POLYAK) { const float t = T[i]; T[i] = (float)((double)t + q.alpha * (double)(w - t)); }
-  }
+  const long long n = q.a[0].n + q.a[1].n;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) twoNetAdamElement(q, e);
 }
 hipError_t launch_dpg_adam_target(const DpgAdamArgs& a, hipStream_t s) {
   const long long n = a.a[0].n + a.a[1].n;

@@ -399,6 +399,22 @@ hipError_t launch_head_dpg(const DpgHeadArgs& a, hipStream_t s);
 hipError_t launch_dpg_critic_gather(const DevReplay& rp, const long long* slot, const float* X0, int ldX0, float* Xc, int ldXc, int dS, int dA, int B, hipStream_t s);
 struct DpgAdamArgs { AdamArgs a[2]; float* T[2]; float etaMul[2]; int mode; double alpha; };      // [0] actor, [1] critic
 hipError_t launch_dpg_adam_target(const DpgAdamArgs& a, hipStream_t s);
+// PPO learners (headppo.hip; include/smarties_hip_ppo.h): both output layers, the fp64 head of PPO::Train and both output layers' backward
+// as ONE launch with 16 minibatch rows per workgroup; Adam over both nets with the serial penalty / DKL_target chain in a workgroup of its own
+struct PpoHeadArgs {
+  HeadArgs h;                               // the actor: nDense = dA (continuous, nOut = 2 dA) or nOpt (discrete, nOut = nOpt) outputs
+  const float* cYin; const float* cX; const float* cY; int cH, cLd, cFunc;      // the critic's last hidden block
+  const float* cW; long long cIndWo, cIndBo; int cLdWo;
+  float* cDOut; int cLdDo; float* cDres; float* cD;
+  double* cV; double* cG; double* gain;     // [B] V, the critic's output gradient, gain (hl_ppo_readback)
+  double* rowStat;                          // [3][B] rho, D_KL, isOff of the rows: what the scalar chain of ppo_adam_kernel walks
+  const double* pen;                        // device: {penalCoef, DKL_target, penalUpdateCount, penalUpdateDelta}
+  double Cpol;                              // CmaxPol = clipImpWeight < 1
+};
+size_t ppo_head_lds(int nq);                // bytes of LDS of ppo_head_kernel<nq>
+hipError_t launch_head_ppo(const PpoHeadArgs& a, hipStream_t s);
+struct PpoAdamArgs { const double* rowStat; double* pen; int B; };      // beside a DpgAdamArgs without target weights
+hipError_t launch_ppo_adam(const DpgAdamArgs& a, const PpoAdamArgs& p, hipStream_t s);
 // the head launch beyond 64 options (headw.hip: head_wide_kernel); launch_head hands them over
 hipError_t launch_head_wide(const HeadArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);
 hipError_t launch_fused(const FusedArgs& a, int maxRows, const ExtraArgs* extra, hipStream_t s);

@@ -36,6 +36,7 @@
 #include "../../include/smarties_hip_naf.h"
 #include "../../include/smarties_hip_dqn.h"
 #include "../../include/smarties_hip_dpg.h"
+#include "../../include/smarties_hip_ppo.h"
 
 using namespace hl;
 
@@ -44,6 +45,7 @@ using namespace hl;
 #include "naf_exec.h"
 #include "dqn_exec.h"
 #include "dpg_exec.h"
+#include "ppo_exec.h"
 #include "step_exec.h"
 
 // =================================================================================================
@@ -70,9 +72,15 @@ static_assert(HL_NAF_MAX_DIMA == NAF_MAX_DIMA, "the header's cap is the head ker
 // dpg != nullptr: hl_create_dpg (include/smarties_hip_dpg.h) -- the caller's adv_kind is ignored, the handle's network is the actor, the critic is dpg_exec.h's
 static_assert(HL_DPG_MAX_DIMA == DPG_MAX_DIMA, "the header's cap is the target kernel's");
 static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* discValues, hl_learner** out, const hl_naf_config* naf = nullptr, const hl_dqn_config* dqn = nullptr,
-                         const hl_dpg_config* dpg = nullptr) {
+                         const hl_dpg_config* dpg = nullptr, const hl_ppo_config* ppo = nullptr) {
   if (!cfgIn || !out) return HL_ERR_BAD_ARG;
   hl_config cfgNaf;
+  // ppo != nullptr: hl_create_ppo (include/smarties_hip_ppo.h) -- the caller's adv_kind is ignored, the handle's network is the actor (continuous: DPG's
+  // layout; discrete: hl_create_discrete's variables, the options alone as outputs), the critic is ppo_exec.h's
+  if (ppo) {
+    if (ppo->struct_size != (int32_t)sizeof(hl_ppo_config) || cfgIn->struct_size != sizeof(hl_config) || ppo->n_vars < 0 || ppo->n_vars > HL_DISCRETE_MAX_VARS) return HL_ERR_BAD_ARG;
+    cfgNaf = *cfgIn; cfgNaf.adv_kind = ppo->n_vars > 0 ? HL_ADV_DISCRETE : HL_ADV_ZERO; cfgIn = &cfgNaf;
+  }
   if (dpg) {
     if (dpg->struct_size != (int32_t)sizeof(hl_dpg_config) || cfgIn->struct_size != sizeof(hl_config)) return HL_ERR_BAD_ARG;
     cfgNaf = *cfgIn; cfgNaf.adv_kind = HL_ADV_ZERO; cfgIn = &cfgNaf;      // (checked below as the continuous-action configuration it is)
@@ -106,6 +114,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     for (int i = 0; i < discN; ++i) { if (discValues[i] < 2) return HL_ERR_BAD_ARG; prod = std::min<long long>(prod * discValues[i], 1ll << 40); }
     if (prod != cfg->n_options) return HL_ERR_BAD_ARG;
     // beyond 64 options: head_wide_kernel (headw.hip) -- at most eight options per lane, 1 + 2 x 512 outputs and staged deltas per wavefront in LDS
+    if (prod > DISC_MAX_OPT && ppo) return refuse(out, "PPO: more than 512 options (the product of the variables' counts); the head holds 16 rows of 512 policy outputs in LDS (headppo.hip)");
     if (prod > DISC_MAX_OPT && dqn) return refuse(out, "DQN: more than 512 options (the product of the variables' counts); the head holds 16 rows of 512 Q values per row set in LDS (headdq.hip)");
     if (prod > DISC_MAX_OPT) return refuse(out, "discrete actions: more than 512 options (the product of the variables' counts); the head launch holds 1 + 2 x 512 outputs per sample (headw.hip)");
   }
@@ -157,6 +166,17 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     if (cfg->n_encoder > 0) return refuse(out, "DPG: encoder layers are not served (the reference shares one encoder between the actor and the critic; the two nets here have no common layers)");
     if (dpgTargetLdsOf(*cfg) > 160 * 1024) return refuse(out, "DPG: the critic layers' activation derivatives of 16 rows do not fit the target launch's 160 KB of LDS (dpgt.hip: two 512-wide layers, six 256-wide ones)");
   }
+  if (ppo) {      // what the PPO step is wired for (include/smarties_hip_ppo.h)
+    if (cfg->nn_type != HL_NN_FFNN || cfg->encoder_rnn) return refuse(out, "PPO: recurrent layers are not served (feed-forward dense nets only)");
+    if (cfg->n_conv > 0) return refuse(out, "PPO: convolutions are not served (feed-forward dense nets only)");
+    if (cfg->n_ranks > 1) return refuse(out, "PPO: one replica only (the critic and the penalty coefficient have no exchange)");
+    if (!ppo->n_vars && cfg->dimA > HL_PPO_MAX_DIMA) return refuse(out, "PPO: dimA beyond 16 (the means are one 16-column tile of the head launch, headppo.hip)");
+    if (cfg->nAppendedObs > 0 || cfg->dimS > 512 || cfg->batchSize > 1024) return refuse(out, "PPO: appended observations, states beyond 512 components and batches beyond 1024 are not served (the critic reads the sampler's state rows)");
+    // (the reference builds ONE encoder under both nets, PPO_common.cpp:48-54: both nets' gradients meet in its weights)
+    if (cfg->n_encoder > 0) return refuse(out, "PPO: encoder layers are not served (the reference shares one encoder between the actor and the critic; the two nets here have no common layers)");
+    if (!(cfg->clipImpWeight < 1)) return refuse(out, "PPO: clipImpWeight is CmaxPol and must be below 1 (isFarPolicyPPO, Episode.h:22-27)");
+    if (ppo->nEpochs < 1) return refuse(out, "PPO: nEpochs (batchSize / obsPerStep) must be at least 1");
+  }
   if (dqn) {      // what the DQN step is wired for (include/smarties_hip_dqn.h)
     if (cfg->nn_type != HL_NN_FFNN || cfg->encoder_rnn) return refuse(out, "DQN: recurrent layers are not served (feed-forward dense nets only)");
     if (cfg->n_conv > 0) return refuse(out, "DQN: convolutions are not served (feed-forward dense nets only)");
@@ -206,6 +226,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
   if (naf) { h->naf = true; h->tgtDelay = naf->targetDelay; h->cfg.adv_kind = HL_ADV_QUADRATIC; h->useGraph = false; }      // (eager steps: the target path has no riders)
   if (dqn) { h->dqn = true; h->tgtDelay = dqn->targetDelay; h->useGraph = false; }      // (adv_kind stays HL_ADV_DISCRETE: labels, stored policies and their checks are hl_create_discrete's)
   if (dpg) { h->dpg = true; h->tgtDelay = dpg->targetDelay; h->useGraph = false; }      // (adv_kind HL_ADV_ZERO: a continuous policy without advantage outputs; buildNet drops the value column)
+  if (ppo) { h->ppo = true; h->ppoSt.nEpochs = ppo->nEpochs; h->ppoSt.klInit = ppo->klDivConstraint; h->useGraph = false; }      // (eager steps; buildNet drops the value column)
   if (cfg->n_encoder > 0) {     // createEncoder: the encoder layers are the first hidden layers of the one network (Learner_approximator.cpp:149-166)
     int n = 0;
     for (int j = 0; j < cfg->n_encoder; ++j) if (cfg->encoder[j] > 0) h->cfg.hidden[n++] = cfg->encoder[j];
@@ -327,7 +348,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     HIPCK(devAlloc(&h->Wtgt, (size_t)h->nParams + PARAM_TAIL));
     HIPCK(hipMemset(h->Wtgt, 0, ((size_t)h->nParams + PARAM_TAIL) * sizeof(float)));
     if (h->dpg) {      // the critic; the target launch gathers its own rows and keeps its activations in LDS (dpgt.hip)
-      const int rc2 = dpgBuildCritic(h); if (rc2) return rc2;
+      const int rc2 = buildCritic(h, h->dS + h->dA, true); if (rc2) return rc2;
       hl_learner::DpgCritic& c = h->critic;
       c.tgt = DpgTargetArgs{}; c.tgt.dS = h->dS; c.tgt.dA = h->dA; c.tgt.outFuncA = h->cfg.nnOutputFunc;
       c.tgt.actor = dpgDesc(h->hid, h->nHidden, h->indWo, h->indBo, h->ldWo); c.tgt.critic = dpgDesc(c.hid, c.nHidden, c.indWo, c.indBo, c.ldWo);
@@ -351,6 +372,12 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
         }
       }
     }
+  }
+  if (h->ppo) {      // the critic on the state rows; penalCoef = 1 (PPO.h:35), DKL_target = klDivConstraint, the accumulators 0
+    const int rc2 = buildCritic(h, h->dS, false); if (rc2) return rc2;
+    HIPCK(devAlloc(&h->ppoSt.pen, 4)); HIPCK(devAlloc(&h->ppoSt.rowStat, (size_t)3 * B)); HIPCK(devAlloc(&h->ppoSt.gain, (size_t)B));
+    const double pen0[4] = {1.0, h->ppoSt.klInit, 0.0, 0.0};
+    HIPCK(hipMemcpy(h->ppoSt.pen, pen0, sizeof(pen0), hipMemcpyHostToDevice));
   }
   for (int j = 0; j < h->nHidden; ++j) {
     DevHidden& d = h->hid[j];
@@ -432,7 +459,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
     }
   }
   {   // fused forward + head + dX kernel: two equal hidden blocks of width H <= 256, small state / action spaces
-    const bool off = (h->generic & 1) != 0 || hasTargetNet(h);      // (NAF, DQN: the generic launch sequence with a head of their own)
+    const bool off = (h->generic & 1) != 0 || ownAdamLaunch(h);      // (NAF, DQN: the generic launch sequence with a head of their own)
     if (!off && h->nHidden == 2 && !h->recurrent && !h->preproc) {
       const DevHidden& d0 = h->hid[0]; const DevHidden& d1 = h->hid[1];
       h->fusedOk = cfg->nnOutputFunc == HL_FUNC_LINEAR && d0.size == d1.size && d1.size >= 16 && d1.size <= 256 && (d1.size & (d1.size - 1)) == 0 && h->dS <= 32 && h->nAdv == 0 && h->nDense <= 8 && h->ldWo == 8 &&
@@ -459,7 +486,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
       HIPCK(hipStreamSynchronize(nullptr));
     }
   }
-  if (!h->fusedOk && (h->nHidden == 2 || h->nHidden == 3) && !h->recurrent && !h->preproc && !(h->generic & 1) && !hasTargetNet(h)) {
+  if (!h->fusedOk && (h->nHidden == 2 || h->nHidden == 3) && !h->recurrent && !h->preproc && !(h->generic & 1) && !ownAdamLaunch(h)) {
     // the wide variant of the fused kernel (fusedw.hip): same placement, same probe; also for THREE equal hidden blocks (settings/RACER_glider.json)
     const DevHidden& d0 = h->hid[0]; const DevHidden& d1 = h->hid[1];
     const int comps = h->nOpt ? h->nOpt : h->dA, nLH = h->nHidden;
@@ -513,7 +540,7 @@ static int createLearner(const hl_config* cfgIn, int32_t discN, const int32_t* d
       bool sc = h->nConv == 0 && !(h->generic & 512) && HT <= 32;      // (<= 512 units: a panel's group fits its XCD at one workgroup per CU, the kernel's registers at their worst)
       for (int j = 1; j < h->nHidden; ++j) sc = sc && !gemm_oneshot_ok(GEMM_X, h->hid[j].size);
       // (beyond 64 options the head is the head launch's alone -- headw.hip: the forward chain, that launch and the input-gradient launches go out on their own)
-      h->stepChainOk = sc && h->nOpt <= 64 && !hasTargetNet(h);
+      h->stepChainOk = sc && h->nOpt <= 64 && !ownAdamLaunch(h);
     }
   }
   h->ldDo = (int)roundUp(h->nDense, 16);
@@ -608,8 +635,8 @@ int hl_create_dpg(const hl_config* cfg, const hl_dpg_config* dpg, hl_learner** o
 }
 int64_t hl_dpg_critic_num_params(const hl_learner* h) { return h && h->dpg && h->critic.W ? h->critic.nParams : -1; }
 // copies between the caller's arrays and the critic's (NULL = skip); toHost: get
-static int dpgCriticCopy(hl_learner* h, float* const host[3], bool toHost) {
-  if (!h || !h->dpg || !h->critic.W) return HL_ERR_BAD_ARG;
+static int criticCopy(hl_learner* h, bool mine, float* const host[3], bool toHost) {
+  if (!h || !mine || !h->critic.W) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   float* dev[3] = {h->critic.W, h->critic.M1, h->critic.M2};
   const size_t n = (size_t)h->critic.nParams * sizeof(float);
@@ -620,9 +647,9 @@ static int dpgCriticCopy(hl_learner* h, float* const host[3], bool toHost) {
   HIPCK(hipStreamSynchronize(h->stream));
   return HL_OK;
 }
-int hl_dpg_get_critic(hl_learner* h, float* w, float* m1, float* m2) { float* const p[3] = {w, m1, m2}; return dpgCriticCopy(h, p, true); }
+int hl_dpg_get_critic(hl_learner* h, float* w, float* m1, float* m2) { float* const p[3] = {w, m1, m2}; return criticCopy(h, h && h->dpg, p, true); }
 int hl_dpg_set_critic(hl_learner* h, const float* w, const float* m1, const float* m2) {
-  float* const p[3] = {const_cast<float*>(w), const_cast<float*>(m1), const_cast<float*>(m2)}; return dpgCriticCopy(h, p, false);
+  float* const p[3] = {const_cast<float*>(w), const_cast<float*>(m1), const_cast<float*>(m2)}; return criticCopy(h, h && h->dpg, p, false);
 }
 int hl_dpg_get_target(hl_learner* h, int32_t which, float* w) {
   if (!h || !w || !h->dpg || !h->Wtgt || !h->critic.Wtgt || which < 0 || which > 1) return HL_ERR_BAD_ARG;
@@ -651,6 +678,57 @@ int hl_dpg_readback(hl_learner* h, int32_t what, double* dst, int64_t cap) {
   HIPCK(hipMemcpy(buf.data(), src, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
   if (what == 2) { for (int b = 0; b < B; ++b) for (int i = 0; i < h->dA; ++i) dst[(size_t)b * h->dA + i] = buf[(size_t)b * DPG_MAX_DIMA + i]; }
   else for (int64_t i = 0; i < n; ++i) dst[i] = buf[(size_t)i];
+  return HL_OK;
+}
+
+// ---- PPO learners (include/smarties_hip_ppo.h) ----
+int hl_create_ppo(const hl_config* cfg, const hl_ppo_config* ppo, hl_learner** out) {
+  if (!ppo || ppo->struct_size != (int32_t)sizeof(hl_ppo_config)) return HL_ERR_BAD_ARG;      // (before any field behind it is read)
+  return createLearner(cfg, ppo->n_vars > 0 ? ppo->n_vars : 0, ppo->n_vars > 0 ? ppo->values : nullptr, out, nullptr, nullptr, nullptr, ppo);
+}
+int64_t hl_ppo_critic_num_params(const hl_learner* h) { return h && h->ppo && h->critic.W ? h->critic.nParams : -1; }
+int hl_ppo_get_critic(hl_learner* h, float* w, float* m1, float* m2) { float* const p[3] = {w, m1, m2}; return criticCopy(h, h && h->ppo, p, true); }
+int hl_ppo_set_critic(hl_learner* h, const float* w, const float* m1, const float* m2) {
+  float* const p[3] = {const_cast<float*>(w), const_cast<float*>(m1), const_cast<float*>(m2)}; return criticCopy(h, h && h->ppo, p, false);
+}
+// gradient steps before the clear: what is left of this epoch, then the whole epochs behind it
+static long long ppoStepsLeft(const hl_learner* h) {
+  const long long H = h->cfg.maxTotObsNum, B = h->cfg.batchSize, perEpoch = (H + B - 1) / B;
+  return (H - h->ppoSt.cntBatch + B - 1) / B + (h->ppoSt.nEpochs - 1 - h->ppoSt.cntEpoch) * perEpoch;
+}
+int hl_ppo_get_state(hl_learner* h, hl_ppo_state* st) {
+  if (!h || !st || !h->ppo || !h->ppoSt.pen) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  double pen[4];
+  HIPCK(hipMemcpyAsync(pen, h->ppoSt.pen, sizeof(pen), hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  st->penalCoef = pen[0]; st->DKL_target = pen[1]; st->cntBatch = h->ppoSt.cntBatch; st->cntEpoch = h->ppoSt.cntEpoch; st->stepsLeft = ppoStepsLeft(h);
+  return HL_OK;
+}
+int hl_ppo_set_state(hl_learner* h, const hl_ppo_state* st) {
+  if (!h || !st || !h->ppo || !h->ppoSt.pen || st->cntBatch < 0 || st->cntEpoch < 0 || st->cntEpoch >= h->ppoSt.nEpochs || st->cntBatch >= h->cfg.maxTotObsNum) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  const double pen[2] = {st->penalCoef, st->DKL_target};
+  HIPCK(hipMemcpyAsync(h->ppoSt.pen, pen, sizeof(pen), hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  h->ppoSt.cntBatch = st->cntBatch; h->ppoSt.cntEpoch = st->cntEpoch;
+  return HL_OK;
+}
+int hl_ppo_readback(hl_learner* h, int32_t what, double* dst, int64_t cap) {
+  if (!h || !dst || !h->ppo || !h->critic.W || what < 0 || what > 6) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  const hl_learner::DpgCritic& c = h->critic; const int B = h->B;
+  const int64_t n = what == 6 ? c.nParams : B;
+  if (cap < n) return HL_ERR_BAD_ARG;
+  HIPCK(hipStreamSynchronize(h->stream));
+  if (what == 6) {
+    std::vector<float> buf((size_t)n);
+    HIPCK(hipMemcpy(buf.data(), c.G, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) dst[i] = buf[(size_t)i];
+    return HL_OK;
+  }
+  const double* src = what < 3 ? h->ppoSt.rowStat + (size_t)what * B : (what == 3 ? h->ppoSt.gain : (what == 4 ? c.q : c.gOut));
+  HIPCK(hipMemcpy(dst, src, (size_t)B * sizeof(double), hipMemcpyDeviceToHost));
   return HL_OK;
 }
 
@@ -690,7 +768,9 @@ int hl_destroy(hl_learner* h) {
   for (void* q : {(void*)h->tmT, (void*)h->tmSteps, (void*)h->tmNext, (void*)h->tmCtr, (void*)h->tmP}) if (q) hipFree(q);
   for (void* p : ptrs) if (p) hipFree(p);
   for (float* q : {h->Wtgt, h->nafX1, h->nafVtgt}) if (q) hipFree(q);
-  if (h->dpg) dpgFreeCritic(h);
+  if (h->dpg || h->ppo) freeCritic(h);
+  for (double* q : {h->ppoSt.pen, h->ppoSt.rowStat, h->ppoSt.gain}) if (q) hipFree(q);
+  if (h->ppoSt.valPin) hipHostFree(h->ppoSt.valPin);
   for (int j = 0; j < HL_MAX_HIDDEN; ++j) for (float* q : {h->tgtX[j], h->tgtY[j], h->tgtR[j], h->nxtX[j], h->nxtY[j], h->nxtR[j]}) if (q) hipFree(q);
   for (int l = 0; l < h->nConv; ++l) { ConvGeo& g = h->cg[l];
     if (l != h->nConv - 1) for (float* p : {g.X, g.Y, g.D}) if (p) hipFree(p);
@@ -790,7 +870,7 @@ int hl_init_weights(hl_learner* h) {
   }
   HIPCK(hipMemcpyAsync(h->W, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (hasTargetNet(h)) { HIPCK(hipMemcpyAsync(h->Wtgt, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, h->stream)); h->tgtCnt = 0; }      // (Optimizer.cpp:233: the target weights start as a copy)
-  if (h->dpg) {      // the critic, built and initialised behind the actor (the DPG constructor): the same rules, Linear output, biases zero
+  if (h->dpg || h->ppo) {      // the critic, built and initialised behind the actor (the DPG constructor, PPO's setupNet): the same rules, Linear output, biases zero
     hl_learner::DpgCritic& c = h->critic;
     std::vector<float> Wc((size_t)c.nParams, 0.f);
     for (int j = 0; j < c.nHidden; ++j) {
@@ -802,7 +882,7 @@ int hl_init_weights(hl_learner* h) {
     const float init = (float)((iFac > 0 ? iFac : 1) * initFactor(HL_FUNC_LINEAR, Hc, 1));
     for (int i = 0; i < Hc; ++i) Wc[c.indWo + (long long)c.ldWo * i] = uni(-init, init);
     HIPCK(hipMemcpyAsync(c.W, Wc.data(), Wc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipMemcpyAsync(c.Wtgt, Wc.data(), Wc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (c.Wtgt) HIPCK(hipMemcpyAsync(c.Wtgt, Wc.data(), Wc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));      // (Wc goes out of scope)
   }
   h->convPrepStale = true;
@@ -1090,6 +1170,10 @@ int hl_step(hl_learner* h, int32_t n, const int64_t* flat) {
   if (!h || n < 0) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
   int s = 0;
+  if (h->ppo) {      // PPO::blockGradientUpdates; the steps left before clearAll (in front of everything a refused call could change)
+    if (h->nTransitions < h->cfg.maxTotObsNum) return fail(h, HL_ERR_STATE, "PPO: fewer than nHorizon = maxTotObsNum steps are stored (blockGradientUpdates)");
+    if (n > ppoStepsLeft(h)) return fail(h, HL_ERR_STATE, "PPO: more steps than are left before the buffer is cleared");
+  }
   if (n == h->lastCallN) { if (++h->sameCallN == 3 && !flat && n > h->eagerChain && n < 1000) { int rc = prepareExact(h, n); if (rc) return rc; } }
   else { h->lastCallN = n; h->sameCallN = 1; }
   while (s < n) {
@@ -1119,6 +1203,22 @@ int hl_step(hl_learner* h, int32_t n, const int64_t* flat) {
     if (logStep) { rc = appendGradStats(h); if (rc) return rc; }
     h->gsCalls += 1;
     h->nGradSteps += 1; s += 1;
+    if (h->ppo) {      // PPO::setupTasks, stepComplete: the epoch counters, updateRewardsStats per pass over the data, clearAll after nEpochs
+      hl_learner::Ppo& pp = h->ppoSt;
+      pp.cntBatch += h->cfg.batchSize;
+      if (pp.cntBatch >= h->cfg.maxTotObsNum) {
+        rc = launchMoments(h); if (rc) return rc;
+        rc = launchMomentsApply(h, false, 1); if (rc) return rc;
+        pp.cntBatch = 0; pp.cntEpoch += 1;
+      }
+      if (pp.cntEpoch >= pp.nEpochs) {      // every episode goes, as the removal rules drop theirs; nSeen* stay
+        rc = refreshInsertionStats(h); if (rc) return rc;
+        for (const EpMeta& e : h->order) h->freeEids.push_back(e.eid);
+        h->order.clear(); h->nTransitions = 0; h->minLenAtN = -1; h->tableDirty = true; h->countsDirty = true;
+        rc = flushPending(h); if (rc) return rc;
+        pp.cntEpoch = 0; pp.cntBatch = 0;
+      }
+    }
   }
   return HL_OK;
 }
@@ -1127,6 +1227,8 @@ int hl_step(hl_learner* h, int32_t n, const int64_t* flat) {
 int hl_step_begin(hl_learner* h, const int64_t* flat) {
   if (!h) return HL_ERR_BAD_ARG;
   HL_LOCK(h);
+  // (the on-policy life cycle -- the nHorizon block, the epoch counters, the statistics per pass, the clear -- lives in hl_step alone)
+  if (h->ppo) return fail(h, HL_ERR_UNSUPPORTED, "hl_step_begin: the split step is not wired for PPO learners (one replica, no host-side exchange; hl_step runs the on-policy life cycle)");
   int rc = preStepChecks(h); if (rc) return rc;
   h->statsFresh = false; h->anyStep = true;
   rc = dropPresample(h); if (rc) return rc;
@@ -1198,6 +1300,38 @@ int hl_step_end(hl_learner* h) {
 #include "learner_act.h"
 #include "learner_dev.h"
 #include "learner_rollout.h"
+
+// V(s) of a PPO learner's critic: the row-block acting launch of hl_forward (actrows.hip) on the critic's description and blob, rows and
+// values through a pinned stage of its own; neither the minibatch buffers nor a minibatch drawn ahead are touched
+int hl_ppo_values(hl_learner* h, int32_t n, const float* states, double* v) {
+  if (!h || !h->ppo || !h->critic.W || n < 0 || (n > 0 && (!states || !v))) return HL_ERR_BAD_ARG;
+  HL_LOCK(h);
+  if (h->inStep) return fail(h, HL_ERR_STATE, "hl_ppo_values between hl_step_begin and hl_step_end");
+  hl_learner::Ppo& pp = h->ppoSt; const hl_learner::DpgCritic& c = h->critic;
+  if (!pp.valuesOk) {
+    ActRowsArgs a{}; a.W = c.W; a.stMean = h->rp.stMean; a.stScale = h->rp.stScale;
+    a.nDense = 1; a.nSig = 0; a.nOut = 1; a.ldWo = c.ldWo; a.indWo = c.indWo; a.indBo = c.indBo; a.indBp = 0; a.outFunc = HL_FUNC_LINEAR;
+    a.dS = h->dS; a.dIn = h->dS; a.nL = c.nHidden;
+    for (int j = 0; j < c.nHidden; ++j) { const DevHidden& d = c.hid[j]; a.L[j] = ActLayer{d.nIn, d.size, d.ldW, d.func, d.hasRes, d.resW, d.indW, d.indB, d.indWr, d.indBr}; }
+    if (!act_rows_plan(&a)) return fail(h, HL_ERR_UNSUPPORTED, "PPO: the critic does not fit the row-block acting launch");
+    pp.values = a; pp.valuesOk = true;
+  }
+  // the stage: [ACT_ROWS_CHUNK][dS] floats | values as doubles | one stamp per row block
+  const size_t inBytes = ((size_t)ACT_ROWS_CHUNK * h->dS * sizeof(float) + 255) & ~(size_t)255, outBytes = (size_t)ACT_ROWS_CHUNK * sizeof(double);
+  if (!pp.valPin) HIPCK(actPinAlloc(&pp.valPin, inBytes + outBytes + (size_t)act_rows_blocks(ACT_ROWS_CHUNK) * sizeof(unsigned)));
+  float* in = reinterpret_cast<float*>(pp.valPin); double* out = reinterpret_cast<double*>(pp.valPin + inBytes);
+  volatile unsigned* done = reinterpret_cast<volatile unsigned*>(pp.valPin + inBytes + outBytes);
+  for (int r0 = 0; r0 < n; r0 += ACT_ROWS_CHUNK) {
+    const int m = std::min(ACT_ROWS_CHUNK, n - r0);
+    std::memcpy(in, states + (size_t)r0 * h->dS, (size_t)m * h->dS * sizeof(float));
+    const unsigned tag = actNextTag(h);
+    ActRowsArgs a = pp.values; a.in = in; a.out = out; a.done = done; a.n = m; a.tag = tag;
+    { int rc = ppoValuesLaunch(h, a); if (rc) return rc; }
+    { int rc = actWait(h, done, act_rows_blocks(m), tag); if (rc) return rc; }
+    std::memcpy(v + r0, out, (size_t)m * sizeof(double));
+  }
+  return HL_OK;
+}
 
 int hl_sync(hl_learner* h) {
   if (!h) return HL_ERR_BAD_ARG;

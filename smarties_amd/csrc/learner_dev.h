@@ -189,6 +189,7 @@ static int devAct(hl_learner* h, const char* who, int n, const float* in, const 
   if (h->naf) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": acting from device memory is not wired for NAF learners (the policy mean sits behind the triangle, at 1 + nL); hl_forward serves them");
   if (h->dqn) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": acting from device memory is not wired for DQN learners (the outputs are Q values, the acting heads read [V | A | logits]); hl_forward serves them");
   if (h->dpg) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": acting from device memory is not wired for DPG learners (the actor's outputs are [mean | sigma] without a value column); hl_forward serves them");
+  if (h->ppo) return fail(h, HL_ERR_UNSUPPORTED, std::string(who) + ": acting from device memory is not wired for PPO learners (the actor has no value column, V is the critic's); hl_forward and hl_ppo_values serve them");
   if (h->inStep) return fail(h, HL_ERR_STATE, std::string(who) + " between hl_step_begin and hl_step_end");
   const ActRoutes& r = actResolve(h);
   if (w ? r.devSeq == ACT_DEV_SEQ_NONE : !r.devRows) return fail(h, HL_ERR_UNSUPPORTED, who + (w ? r.devSeqNo : r.devRowsNo));
@@ -262,6 +263,7 @@ int hl_act_dev_source(hl_learner* h, int32_t source) {
   if (h->naf && source == HL_ACT_SNAPSHOT) return fail(h, HL_ERR_UNSUPPORTED, "hl_act_dev_source: the snapshot source is not wired for NAF learners");
   if (h->dqn && source == HL_ACT_SNAPSHOT) return fail(h, HL_ERR_UNSUPPORTED, "hl_act_dev_source: the snapshot source is not wired for DQN learners");
   if (h->dpg && source == HL_ACT_SNAPSHOT) return fail(h, HL_ERR_UNSUPPORTED, "hl_act_dev_source: the snapshot source is not wired for DPG learners");
+  if (h->ppo && source == HL_ACT_SNAPSHOT) return fail(h, HL_ERR_UNSUPPORTED, "hl_act_dev_source: the snapshot source is not wired for PPO learners");
   h->act.source = source;
   return HL_OK;
 }
@@ -272,6 +274,7 @@ int hl_policy_snapshot(hl_learner* h) {
   if (h->naf) return fail(h, HL_ERR_UNSUPPORTED, "hl_policy_snapshot: the snapshot source is not wired for NAF learners");
   if (h->dqn) return fail(h, HL_ERR_UNSUPPORTED, "hl_policy_snapshot: the snapshot source is not wired for DQN learners");
   if (h->dpg) return fail(h, HL_ERR_UNSUPPORTED, "hl_policy_snapshot: the snapshot source is not wired for DPG learners");
+  if (h->ppo) return fail(h, HL_ERR_UNSUPPORTED, "hl_policy_snapshot: the snapshot source is not wired for PPO learners");
   ActState& s = h->act;
   if (!s.snapBuf[0]) {      // the two buffers and their events, once
     if (h->nParams % 8) return fail(h, HL_ERR_STATE, "hl_policy_snapshot: the blob is no multiple of 8 floats");

@@ -399,6 +399,11 @@ int hl_save(hl_learner* h, const char* base) {
     rc = hl_dpg_get_target(h, 1, P[3].data()); if (rc) return rc;
     return saveBlobs(h, h->criticLay, std::string(base) + "_critic", P, 4);
   }
+  if (h->ppo) {      // PPO's critic: three blobs at <base>_critic
+    for (auto& v : P) v.assign((size_t)h->critic.nParams, 0.f);
+    rc = hl_ppo_get_critic(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+    return saveBlobs(h, h->criticLay, std::string(base) + "_critic", P, 3);
+  }
   return HL_OK;
 }
 int hl_restart(hl_learner* h, const char* base) {
@@ -418,6 +423,12 @@ int hl_restart(hl_learner* h, const char* base) {
     rc = loadBlobs(h, h->criticLay, std::string(base) + "_critic", P, 4, &tgtRead); if (rc) return rc;
     rc = hl_dpg_set_critic(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
     return hl_dpg_set_target(h, 1, tgtRead ? P[3].data() : P[0].data());
+  }
+  if (h->ppo) {
+    for (auto& v : P) v.assign((size_t)h->critic.nParams, 0.f);
+    rc = hl_ppo_get_critic(h, P[0].data(), P[1].data(), P[2].data()); if (rc) return rc;
+    rc = loadBlobs(h, h->criticLay, std::string(base) + "_critic", P, 3, &tgtRead); if (rc) return rc;
+    return hl_ppo_set_critic(h, P[0].data(), P[1].data(), P[2].data());
   }
   return HL_OK;
 }

@@ -113,6 +113,7 @@ int hl_rollout_create(hl_learner* h, int32_t nEnv, int32_t maxSteps, uint64_t se
   if (h->naf) return fail(h, HL_ERR_UNSUPPORTED, "hl_rollout_create: the rollout buffer is not wired for NAF learners (its acting launch reads the policy mean where NAF keeps the triangle)");
   if (h->dqn) return fail(h, HL_ERR_UNSUPPORTED, "hl_rollout_create: the rollout buffer is not wired for DQN learners (its acting launch reads [V | A | logits] where DQN keeps the Q values)");
   if (h->dpg) return fail(h, HL_ERR_UNSUPPORTED, "hl_rollout_create: the rollout buffer is not wired for DPG learners (its acting launch reads a value column the actor does not have)");
+  if (h->ppo) return fail(h, HL_ERR_UNSUPPORTED, "hl_rollout_create: the rollout buffer is not wired for PPO learners (its acting launch reads a value column the actor does not have)");
   const ActRoutes& rt = actResolve(h);
   if (rt.devSeq == ACT_DEV_SEQ_NONE) return fail(h, HL_ERR_UNSUPPORTED, "hl_rollout_create" + rt.devSeqNo);
   hl_rollout* r = new hl_rollout();

@@ -172,6 +172,18 @@ struct hl_learner {
     std::vector<int> fwdIdx, fwdBlocks, dxIdx, dxBlocks; int dwIdx = 0, dwCount = 0, dwBlocks = 0;
     hl::DpgTargetArgs tgt{};      // the target launch's record (slot table and B set per step)
   } critic;
+  // PPO learners (hl_create_ppo, include/smarties_hip_ppo.h): the handle's network is the actor, `critic` the value net on the state rows
+  // (no target weights; q = V, gOut = its output gradient).  Epoch counters on the host (PPO.cpp: setupTasks); penalCoef, DKL_target and
+  // the two accumulators of the penalty update in device memory (headppo.hip)
+  bool ppo = false;
+  struct Ppo {
+    int nEpochs = 1; long long cntBatch = 0, cntEpoch = 0; double klInit = 0;
+    double* pen = nullptr;          // device: {penalCoef, DKL_target, penalUpdateCount, penalUpdateDelta}
+    double* rowStat = nullptr;      // device [3][B]: rho, D_KL, isOff of the last step's rows
+    double* gain = nullptr;         // device [B]
+    hl::ActRowsArgs values{}; bool valuesOk = false;      // hl_ppo_values: the row-block acting launch on the critic's description and blob
+    unsigned char* valPin = nullptr;
+  } ppoSt;
   DevScalars* sc = nullptr;
   DevReplay rp{};
   StepBuf buf[2];                          // double-buffered minibatch workspace (see step_exec.h)
@@ -282,6 +294,8 @@ namespace {
 
 // learners that keep target weights (NAF, DQN, DPG): the generic launch sequence, eager, Adam with the target update as a launch of its own
 inline bool hasTargetNet(const hl_learner* h) { return h->naf || h->dqn || h->dpg; }
+// ... and PPO learners, which keep none: the same launch sequence
+inline bool ownAdamLaunch(const hl_learner* h) { return hasTargetNet(h) || h->ppo; }
 
 // Exchange windows (hl_xchg_export) are UNCACHED device memory, and uncached memory must never go back to the allocator: on this
 // runtime (ROCm 7.2, gfx950) memory freed after a life as hipDeviceMallocUncached and handed out again by hipMalloc made kernels of
@@ -444,6 +458,7 @@ int buildNet(hl_learner* h) {
   h->nDense = 1 + h->nAdv + (discrete ? c.n_options : c.dimA); h->nOut = h->nDense + h->nSig;
   if (h->dqn) { h->nAdv = 0; h->nDense = h->nOut = c.n_options; }      // DQN: the Q values alone (DQN.cpp:52), no value column
   if (h->dpg) { h->nAdv = 0; h->nDense = c.dimA; h->nOut = 2 * c.dimA; }      // DPG's actor: the mean and the ParamLayer (DPG.cpp:188-191), no value column
+  if (h->ppo) { h->nAdv = 0; h->nDense = discrete ? c.n_options : c.dimA; h->nOut = h->nDense + h->nSig; }      // PPO's actor: nA outputs and, continuous, the ParamLayer (PPO_common.cpp:58-63), no value column
   const int outLayer = (int)lw.size();
   lw.push_back(roundUp(h->nDense, 8) * prev); lb.push_back(h->nDense);
   const int paramLayer = h->nSig ? (int)lw.size() : -1;

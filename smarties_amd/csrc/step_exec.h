@@ -254,7 +254,7 @@ int buildProblems(hl_learner* h) {
   };
   nextChain(h->Wtgt, h->tgtX, h->tgtY, h->tgtR, h->tgtFwdIdx, h->tgtFwdBlocks);
   nextChain(h->W, h->nxtX, h->nxtY, h->nxtR, h->nxtFwdIdx, h->nxtFwdBlocks);
-  if (h->dpg) dpgProblems(h, P);      // DPG learners: the critic's forward, input-gradient and weight-gradient records (dpg_exec.h)
+  if (h->dpg || h->ppo) dpgProblems(h, P);      // DPG and PPO learners: the critic's forward, input-gradient and weight-gradient records (dpg_exec.h)
   if (h->dProbs) hipFree(h->dProbs);
   h->dProbs = nullptr;
   HIPCK(devAlloc(&h->dProbs, P.size()));
@@ -541,6 +541,10 @@ int launchHead(hl_learner* h, int parity, hipStream_t s, bool nextSample = false
     if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the DPG head launch");
     return dpgHead(h, ha, parity, adamHyper(h, parity), s);
   }
+  if (h->ppo) {      // headppo.hip through ppo_exec.h: the critic's launches and the head; eager steps, no riders
+    if (nextSample) return fail(h, HL_ERR_STATE, "no rider slot on the PPO head launch");
+    return ppoHead(h, ha, parity, adamHyper(h, parity), s);
+  }
   ExtraArgs ex{}; const ExtraArgs* pex = nullptr;
   // (recurrent nets have no forward GEMM launches: the whole sampler of the next step rides along the head kernel)
   if (nextSample) {
@@ -723,6 +727,7 @@ int launchAdam(hl_learner* h, int parity) {
   if (h->naf) return nafAdam(h, aa);      // Adam and the target weights in one launch (naf_exec.h)
   if (h->dqn) return dqnAdam(h, aa);      // ... (dqn_exec.h)
   if (h->dpg) return dpgAdam(h, aa);      // ... of both nets (dpg_exec.h)
+  if (h->ppo) return ppoAdam(h, aa);      // both nets and the penalty chain, no target weights (ppo_exec.h)
   HIPCK(timed(h, "adam_kernel", h->stream, [&] { return launch_adam(aa, h->stream); }));
   return HL_OK;
 }
@@ -754,6 +759,7 @@ int launchMomentsApply(hl_learner* h, bool bInit, double rRateFac, double* momen
   // DPG: the constructor's `settings.learnrate *= 10` (DPG.cpp:201) is never undone, and the replay reads the same settings object
   // (Learner.cpp:21-22; MemoryProcessing.cpp:102): the statistics move with ten times the configured rate
   if (h->dpg) ma.learnrate *= (double)DPG_CRITIC_ETA;
+  if (h->ppo) ma.learnrate *= (double)PPO_CRITIC_ETA;      // PPO_common.cpp:71, the same way: x 3
   HIPCK(launch_moments_apply(ma, h->stream));
   return HL_OK;
 }
@@ -978,7 +984,7 @@ int stepEager(hl_learner* h, const long long* dFlat) {
     if (h->sidePending) { HIPCK(hipStreamWaitEvent(s, h->evSide, 0)); h->sidePending = false; }
   }
   else { rc = dropPresample(h); if (rc) return rc; rc = launchSample(h, 0, dFlat, true, s); if (rc) return rc; }
-  const bool evict = evictionDue(h);
+  const bool evict = evictionDue(h) && !h->ppo;      // (PPO never runs applyEpisodesRemovalAlgo: the buffer is cleared after nEpochs, hl_step)
   if (h->bigBatch && !dFlat && !exch && !periodic && !evict && ((k + 1) % 1000) != 0 && h->cfg.dataSamplingAlgo == HL_SAMPLE_UNIFORM) {      // (the prioritised samplers' table follows this step's errors)
     // large batches: the sampler of the NEXT step (one workgroup, hundreds of microseconds) runs beside this step's launches; it
     // starts behind everything queued so far (the buffer it fills was the previous step's) and keeps the generator's state for
@@ -989,13 +995,14 @@ int stepEager(hl_learner* h, const long long* dFlat) {
     HIPCK(hipEventRecord(h->evSide, h->sideStream));
     h->preValid = true; h->preParity = p ^ 1; h->sidePending = true;
   }
-  rc = launchMlp(h, p, !exch && !hasTargetNet(h), s); if (rc) return rc;
-  if (hasTargetNet(h)) { rc = launchAdam(h, p); if (rc) return rc; }      // (NAF, DQN: Adam with the target weights' update, its own launch behind the weight gradients)
+  rc = launchMlp(h, p, !exch && !ownAdamLaunch(h), s); if (rc) return rc;
+  if (ownAdamLaunch(h)) { rc = launchAdam(h, p); if (rc) return rc; }      // (NAF, DQN, DPG, PPO: Adam as its own launch behind the weight gradients)
   h->lastParity = p;
   if (!periodic && !evict && !exch) return launchPost(h, p, POST_AGG | POST_BETA, s);
   rc = launchPost(h, p, POST_AGG, s); if (rc) return rc;
   if (periodic) {
     rc = launchPeriodicSweep(h); if (rc) return rc;
+    if (h->ppo) return launchPost(h, p, POST_BETA, s);      // (updateTrainingStatistics alone: PPO's updateRewardsStats follows the epoch counters, hl_step)
     rc = launchMoments(h); if (rc) return rc;
     rc = allreduceMoments(h); if (rc) return rc;
     if (oneBehind(h)) { rc = applyMomentsOneBehind(h); if (rc) return rc; }
